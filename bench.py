@@ -1,22 +1,28 @@
 #!/usr/bin/env python3
 """bench.py -- env steps/sec of the batched AC power-flow env.step() on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--workload ieee123_b8192|ieee13_b4096|ieee8500_3ph_b1024]
-                    [--solver nr|fbs] [--batch B] [--no-cpu-baseline] [--no-also]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ieee123_b8192|ieee13_b4096|ieee8500_3ph_b1024]
+                    [--solver nr|fbs] [--batch B] [--dump-outputs DIR]
+                    [--full [--repeats R] [--no-cpu-baseline] [--no-also] [--no-secondary]]
 
 One "step" = one batched env.step(): actions -> batteries/curtailment -> weather -> injections
 -> AC load flow -> line flows -> frequency -> reward/flags -> observation block, for every
 instance of the batch, with the K action batches already resident in HBM.  The default
 workload is the configuration BASELINE.json's target is quoted on (configs[2]): the 123-bus radial
 feeder, 8192 instances per GPU, forward/backward-sweep load flow, reference defaults for stochastic
-loads and weather.  Protocol: W warm-up steps, then R regions of exactly K
-steps, each bracketed by a barrier + device synchronisation on both sides; per region the maximum
-over the ranks' clocks; `value` / `ms_per_step` are the MEDIAN region, p10 / p90 beside them.
+loads and weather.  Protocol: the GPU's clocks are brought up by SETTLE_S seconds of steps (the
+state is then restored, so they change no output), then W warm-up steps, then ONE timed region of
+exactly K steps bracketed by a barrier + device synchronisation on both sides (the maximum over the
+ranks' clocks); `value` / `ms_per_step` are that region's rate / milliseconds per step.
+--dump-outputs DIR writes what the last timed step returned (observations, reward, flags, info
+arrays) as DIR/<name>.npy, float64, for output-for-output comparisons of two builds.
 
-The same line carries (N = 1): the Newton-Raphson measurement and BASELINE configs 2 and 5 ("also",
-each with its own roofline), the device-resident rollout collector and the host-inclusive rate of
-plain env.step() ("rollout", "with_host_io"), the accuracy of the GPU voltages / angles / flows
-against the CPU oracle's Newton-Raphson, and the CPU baselines (all cores and one core).
+A plain run prints that headline alone.  --full adds (N = 1): R regions of K steps each with their
+median / p10 / p90 ("regions"), the Newton-Raphson measurement and BASELINE
+configs 2 and 5 ("also", each with its own roofline), the device-resident rollout collector and the
+host-inclusive rate of plain env.step() ("rollout", "with_host_io"), the accuracy of the GPU
+voltages / angles / flows against the CPU oracle's Newton-Raphson, and the CPU baselines (all cores
+and one core).
 
 For N > 1 the driver launches one process per GPU (torch.distributed.run); each rank owns a
 contiguous block of instances (weak scaling, per-GPU batch fixed).  `value` is BASELINE config 4 as
@@ -42,6 +48,10 @@ import grid_fed_rl_gym_amd as P  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # vendor figure for MI355X FP64 vector
+# The GPU's clocks take ~20-40 ms to come up under this load (a region right behind 5 warm-up steps read 5-10 % low): the
+# headline steps this long before its warm-up, whatever --warmup is
+SETTLE_S = 0.2
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all, file headers included
 
 WORKLOADS = {
     "ieee123_b8192": dict(feeder="ieee123_like", batch=8192, solver="fbs"),       # BASELINE.json config 3 (and 4 for N > 1)
@@ -138,6 +148,22 @@ def quantiles(xs):
     return float(np.median(a)), float(np.quantile(a, 0.1)), float(np.quantile(a, 0.9))
 
 
+def write_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: every array as out_dir/<name><suffix>.npy in float64.  The arrays share a leading instance axis; when
+    they would exceed DUMP_LIMIT_BYTES together, the same fixed, seeded sample of instances is written from each of them,
+    and its indices as `instance`."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if v is not None}
+    n = next(iter(arrays.values())).shape[0]
+    per_instance = sum(8 * (a.size // n) for a in arrays.values())
+    headers = 256 * (len(arrays) + 1)                       # .npy headers (128 bytes each here), the index file's among them
+    if per_instance * n + headers > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=(DUMP_LIMIT_BYTES - headers) // (per_instance + 8), replace=False))
+        arrays = dict({k: a[idx] for k, a in arrays.items()}, instance=idx)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def cpu_baseline(fs, env_kwargs, budget_s=15.0, threads=None):
     """The oracle timed on this box's host cores on a bounded sample of the same workload.
     Prefers the C/OpenMP port (oracle/liboracle_cpu.so) when it has been built, else the NumPy
@@ -168,7 +194,7 @@ def cpu_baseline(fs, env_kwargs, budget_s=15.0, threads=None):
             "sample": f"NumPy oracle, {b} instances x 4 steps of the same workload in {dt:.1f} s"}
 
 
-def measure_unbalanced(args, device, with_cpu):
+def measure_unbalanced(args, device, with_cpu, settle=False, dump_dir=""):
     """BASELINE.json config 5: 8500-node three-phase unbalanced FBS, batch 1024 -- load-flow solves/s.
     A "step" is one batched solve from a flat start; injections resident in HBM."""
     from grid_fed_rl_gym_amd.unbalanced import UnbalancedPowerFlow, ieee8500_like
@@ -178,6 +204,11 @@ def measure_unbalanced(args, device, with_cpu):
     Pb, Qb = lam[:, None, None] * Pn[None], lam[:, None, None] * Qn[None]
     s = UnbalancedPowerFlow(tolerance=args.tolerance, max_iterations=args.max_iterations or 100, device=device)
     s.upload(spec, Pb, Qb)
+    t_end = time.perf_counter() + (SETTLE_S if settle else 0.0)
+    while time.perf_counter() < t_end:                  # every solve starts flat from the same injections: nothing to restore
+        for _ in range(8):
+            s.solve_device()
+        s.synchronize()
     for _ in range(args.warmup):
         s.solve_device()
     s.synchronize(); s.timing_read()
@@ -192,6 +223,9 @@ def measure_unbalanced(args, device, with_cpu):
         ms, cnt = s.timing_read()
         total_ms += ms; launches += cnt
     sol = s.download()
+    if dump_dir:
+        write_outputs(dump_dir, {"voltages_re": sol.voltages.real, "voltages_im": sol.voltages.imag, "converged": sol.converged,
+                                 "iterations": sol.iterations, "losses": sol.losses, "max_mismatch": sol.max_mismatch})
     desc = s.describe()
     avg_ms = total_ms / max(launches, 1)
     mean_it = float(sol.iterations.mean())
@@ -257,26 +291,29 @@ def measure_unbalanced(args, device, with_cpu):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=500,
-                    help="untimed steps before the first timed region (default 500 = 20 ms: the GPU's clocks take that long to settle "
-                         "under this load -- with 5 warm-up steps the median over the regions reads 5 %% low and the p10 10 %% low)")
+    ap.add_argument("--steps", type=int, default=50, help="timed steps of the headline (one region)")
+    ap.add_argument("--warmup", type=int, default=500, help="untimed steps right before the timed region (after the clock settle, SETTLE_S)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64; a fixed, seeded sample of the instances "
+                         "when everything together would exceed 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: timed regions with their spread, the other solver, BASELINE configs 2, 4 (loopback) "
+                         "and 5, meshed feeders, rollout, host I/O, post-step checks, accuracy against the CPU oracle, CPU baselines")
     ap.add_argument("--repeats", type=int, default=120,
-                    help="timed regions of exactly --steps steps each, every one bracketed by barrier + device synchronisation; median / p10 / p90 "
-                         "are reported, and the median of the FIRST 40 regions beside them (`value_first_40_regions`: rounds 2-3's statistic).  "
-                         "120 regions = 0.1 s of GPU time at the driver's `--steps 20 --warmup 5`: the GPU's clocks take ~20 ms to settle under "
-                         "this load, so ten regions of 0.9 ms (round 2) all fell into the ramp and read 10 %% below the sustained rate, forty "
-                         "(round 3) had their median at its end (5 %% below); with 120 the median is the sustained rate and the p10 shows the ramp")
+                    help="--full: timed regions of exactly --steps steps each, every one bracketed by barrier + device synchronisation; median / "
+                         "p10 / p90 are reported (`regions`), and the median of the FIRST 40 regions beside them.  The GPU's clocks take ~20 ms "
+                         "to settle under this load: ten regions of 0.9 ms all fell into the ramp and read 10 %% below the sustained rate, "
+                         "forty had their median at its end (5 %% below); with 120 the median is the sustained rate and the p10 shows the ramp")
     ap.add_argument("--workload", default="ieee123_b8192", choices=sorted(WORKLOADS))
     ap.add_argument("--solver", default="", choices=["", "nr", "fbs"],
                     help="fbs = BASELINE.json config 3 (DistributionPowerFlow); nr = the reference's Newton-Raphson; default: the workload's")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the second measurement with the other solver")
-    ap.add_argument("--no-also", action="store_true", help="skip BASELINE configs 2 and 5, the rollout and the host-inclusive measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the second measurement with the other solver")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip BASELINE configs 2 and 5, the rollout and the host-inclusive measurements")
     ap.add_argument("--batch", type=int, default=0, help="instances per GPU (default: the workload's)")
     ap.add_argument("--waves", type=int, default=0, help="wavefronts per 64-instance group (0 = auto)")
     ap.add_argument("--tolerance", type=float, default=1e-6, help="ablation only; the headline uses 1e-6")
     ap.add_argument("--max-iterations", type=int, default=0, help="ablation only; 0 = 50 (nr) / 100 (fbs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the accuracy and CPU baseline legs")
     ap.add_argument("--no-allgather", action="store_true")
     args = ap.parse_args()
 
@@ -300,7 +337,15 @@ def main():
         if world != 1:
             print("[bench] the 3-phase workload is a single-GPU measurement", file=sys.stderr)
             sys.exit(2)
-        print(json.dumps(measure_unbalanced(args, device, not args.no_cpu_baseline)), flush=True)
+        one = argparse.Namespace(**vars(args)); one.repeats = 1
+        result = measure_unbalanced(one, device, False, settle=True, dump_dir=args.dump_outputs)
+        for k in ("repeats", "ms_per_step_p10_p90"):
+            result.pop(k)
+        if args.full:
+            full = measure_unbalanced(args, device, not args.no_cpu_baseline)
+            result["regions"] = {k: full[k] for k in ("value", "ms_per_step", "ms_per_step_p10_p90", "repeats", "steps", "warmup")}
+            result.update({k: full[k] for k in ("roofline", "accuracy", "cpu_baseline") if k in full})
+        print(json.dumps(result), flush=True)
         return
     wl = WORKLOADS[args.workload]
     solver0 = args.solver or wl["solver"]
@@ -315,8 +360,9 @@ def main():
         return dict(stochastic_loads=True, weather_variation=True, solver=solver, tolerance=args.tolerance,
                     max_iterations=args.max_iterations or (50 if solver == "nr" else 100))
 
-    def measure(fs, B, solver, use_gather, repeats, extras=False, warmup=None, steps=None, linear_solver=None):
-        """W untimed + R x K timed batched steps of one solver; returns the measurement as a dict."""
+    def measure(fs, B, solver, use_gather, repeats, extras=False, warmup=None, steps=None, linear_solver=None, settle=False, dump_dir=""):
+        """W untimed + R x K timed batched steps of one solver; returns the measurement as a dict.  settle: SETTLE_S seconds of
+        steps first, then the state is restored; dump_dir: the last timed step's outputs are written there."""
         warmup = args.warmup if warmup is None else warmup
         steps = args.steps if steps is None else steps
         more = {} if linear_solver is None else {"linear_solver": linear_solver}
@@ -332,6 +378,15 @@ def main():
         st = env.get_state()
         st[:, env.state_column("time")] = 11.5 * 3600.0          # midday: loads near peak, PV producing
         env.set_state(st)
+        if settle:
+            # no exchange in here: the ranks' step counts differ, and the collectives must pair up
+            t_end = time.perf_counter() + SETTLE_S
+            k = 0
+            while time.perf_counter() < t_end:
+                for _ in range(8):
+                    h.step_device(k % n_act); k += 1
+                h.synchronize()
+            env.set_state(st)                                   # the warm-up starts from the same state as without the settle
         if use_gather:
             uid = rz.broadcast_bytes(_lib.Handle.comm_unique_id() if rank == 0 else None)
             h.comm_init(uid, rank, world)
@@ -365,13 +420,15 @@ def main():
                 elapsed = rz.all_reduce_max(elapsed)
             regions.append(elapsed)
             kernel_ms += timing["solve"]["total_ms"]; kernel_launches += timing["solve"]["launches"]
-        out = h.download_step(want_obs=False)                    # sanity of the timed work: every instance solved
+        out = h.download_step(want_obs=bool(dump_dir))           # sanity of the timed work: every instance solved
+        if dump_dir:
+            write_outputs(dump_dir, out, f".rank{rank}" if world > 1 else "")
         m = dict(solver=solver, regions=regions, kernel_ms=kernel_ms, kernel_launches=kernel_launches, desc=desc, B=B, fs=fs, steps=steps,
                  converged_fraction=float(out["power_flow_converged"].mean()),
                  mean_iterations=float(out["iterations"].mean()))
         if extras and rank == 0:
             m.update(side_measurements(env, fs, B, actions, solver))
-        if desc.get("step_launches", 1) > 1 and rank == 0 and not use_gather:
+        if args.full and desc.get("step_launches", 1) > 1 and rank == 0 and not use_gather:
             # how long ONE of the step's two dispatches runs (what rocprofv3 --kernel-trace reports per dispatch), from the
             # workgroups' own start / end stamps on the GPU's 100 MHz clock; armed only now, after everything that is timed
             try:
@@ -699,7 +756,7 @@ def main():
     B = args.batch or wl["batch"]
     if rehearsal:
         if rank == 0:
-            m = measure_loopback(fs, B, solver0, world, max(3, args.repeats // 2), min(args.warmup, 50), args.steps)
+            m = measure_loopback(fs, B, solver0, world, max(3, args.repeats // 2) if args.full else 1, min(args.warmup, 50), args.steps)
             lb = loopback_summary(fs, B, world, m, args.steps)
             result = {"metric": "env steps/sec (batched feeders)", "value": lb["value"], "unit": "env_steps/s", "n_gpus": world,
                       "steps": args.steps, "warmup": min(args.warmup, 50), "ms_per_step": lb["ms_per_step"], "higher_is_better": True,
@@ -712,7 +769,7 @@ def main():
         rz.barrier()
         rz.close()
         return
-    main_m = measure(fs, B, solver0, False, args.repeats, extras=(world == 1))
+    main_m = measure(fs, B, solver0, False, 1, settle=True, dump_dir=args.dump_outputs)
     # The exchange is the one part of an N-rank run no box of this pool could rehearse over real links: if setting it up fails the same
     # way on every rank (no librccl, a communicator that cannot be formed), the line still goes out -- the sharded steps without the
     # exchange, flagged -- instead of nothing.  The ranks agree on that through fixed-name rendezvous entries (not the sequence-numbered
@@ -720,7 +777,7 @@ def main():
     gather_m, gather_error = None, None
     if want_gather:
         try:
-            gather_m = measure(fs, B, solver0, True, args.repeats)
+            gather_m = measure(fs, B, solver0, True, 1, settle=True)
         except Exception as e:                                   # noqa: BLE001 -- reported in the line
             gather_error = f"{type(e).__name__}: {e}"[:300]
         try:
@@ -731,8 +788,10 @@ def main():
         bad = [f"rank {r}: {st}" for r, st in enumerate(states) if st != "ok"]
         if bad:
             gather_m, gather_error = None, "; ".join(bad)[:600]
+    # --full: the regions protocol and the side measurements, on an environment of their own
+    regions_m = measure(fs, B, solver0, False, args.repeats, extras=(world == 1)) if args.full else None
     other = None
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         other = measure(fs, B, "nr" if solver0 == "fbs" else "fbs", False, max(3, args.repeats // 2))
 
     if rank == 0:
@@ -742,11 +801,9 @@ def main():
         solver_text = {"nr": "Newton-Raphson (exact Jacobian)", "fbs": "forward/backward sweep (DistributionPowerFlow)"}
         result = {
             "metric": "env steps/sec (batched feeders)", "value": head["value"], "unit": "env_steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
-            "ms_per_step": head["ms_per_step"], "value_p10_p90": head["value_p10_p90"], "ms_per_step_p10_p90": head["ms_per_step_p10_p90"],
-            "value_first_40_regions": head["value_first_40_regions"], "value_first_region": head["value_first_region"],
-            "statistic": "median over the timed regions of --steps steps each (max over ranks per region); value_first_40_regions: the median of the "
-                         "first 40 of them (the GPU's clocks are still ramping there), value_first_region: the first region alone",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
+            "statistic": f"one timed region of exactly --steps steps behind {SETTLE_S:g} s of clock settle and --warmup steps, bracketed by "
+                         "barrier + device synchronisation (max over ranks)",
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{fs.name}, batch={B} per GPU, {solver_text[solver0]}, "
@@ -757,13 +814,23 @@ def main():
                        "instances_per_workgroup": desc.get("instances_per_workgroup", 64), "workgroups": desc.get("workgroups", desc["groups"]),
                        "tree_levels": desc["levels"], "obs_allgather_in_value": gather_m is not None,
                        "parallelism": f"batch-sharded x{world}"},
-            "roofline": roofline_of(main_m, plain, args.workload),
             "converged_fraction": head_m["converged_fraction"],
             "host": host_description(),
         }
-        for k in ("post_step_checks", "rollout", "with_host_io", "with_host_io_fresh_arrays", "with_host_io_pinned", "with_host_io_float32_observations"):
-            if k in main_m:
-                result[k] = main_m[k]
+        if regions_m is None:
+            result["roofline"] = roofline_of(main_m, plain, args.workload)
+        else:
+            r = summarize(regions_m, world)
+            result["regions"] = {"value": r["value"], "value_p10_p90": r["value_p10_p90"], "ms_per_step": r["ms_per_step"],
+                                 "ms_per_step_p10_p90": r["ms_per_step_p10_p90"], "value_first_40_regions": r["value_first_40_regions"],
+                                 "value_first_region": r["value_first_region"], "repeats": args.repeats, "steps": args.steps, "warmup": args.warmup,
+                                 "statistic": "median over the timed regions of --steps steps each (max over ranks per region; no exchange); "
+                                              "value_first_40_regions: the median of the first 40 of them (the GPU's clocks are still ramping "
+                                              "there), value_first_region: the first region alone"}
+            result["roofline"] = roofline_of(regions_m, r, args.workload)
+            for k in ("post_step_checks", "rollout", "with_host_io", "with_host_io_fresh_arrays", "with_host_io_pinned", "with_host_io_float32_observations"):
+                if k in regions_m:
+                    result[k] = regions_m[k]
         if world > 1 and want_gather and gather_m is None:
             result["obs_allgather_error"] = gather_error
             result["gather_verified"] = False
@@ -790,7 +857,7 @@ def main():
                               "value": o["value"], "unit": "env_steps/s", "ms_per_step": o["ms_per_step"], "value_p10_p90": o["value_p10_p90"],
                               "value_first_40_regions": o["value_first_40_regions"], "avg_launch_ms": o["avg_launch_ms"], "mean_iterations": other["mean_iterations"],
                               "converged_fraction": other["converged_fraction"], "roofline": roofline_of(other, o, args.workload)}
-        if world == 1 and not args.no_also and args.workload == "ieee123_b8192":
+        if args.full and world == 1 and not args.no_also and args.workload == "ieee123_b8192":
             # BASELINE configs 2 and 5 in the same line, each with its own roofline
             try:
                 w2 = WORKLOADS["ieee13_b4096"]
@@ -828,7 +895,7 @@ def main():
                 result["also_config5"] = {k: r5[k] for k in ("metric", "value", "unit", "ms_per_step", "config", "roofline", "converged_fraction")}
             except Exception as e:
                 result["also_config5"] = {"error": str(e)}
-        if world == 1 and not args.no_also and args.workload == "ieee123_b8192":
+        if args.full and world == 1 and not args.no_also and args.workload == "ieee123_b8192":
             # Meshed feeders: Newton-Raphson with a sparse block LU (north_star: "Jacobian build, sparse LU/Cholesky solve";
             # the reference solves them densely, power_flow.py:186-190).  Two graphs of the reference's own generators' kind:
             # 123 buses with 26 loops (IEEE123Bus's cycle count, feeders/ieee_feeders.py:236-330) and the ScalableFeeder(123)
@@ -902,7 +969,7 @@ def main():
                     result["also_config4_loopback"][f"world_{W}"] = loopback_summary(fs, B, W, m4, min(args.steps, 20))
             except Exception as e:
                 result["also_config4_loopback"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["accuracy"] = accuracy(fs, solver0)
             # the reference's CPU path is dense Newton-Raphson: that port is THE baseline; the CPU port of
             # the solver the GPU ran is reported next to it when it differs; and the same on ONE core

@@ -3,9 +3,10 @@
 
     python tools/collect_profile.py TAG OUT_PREFIX [--traffic-key ieee123_b8192:fbs --kernel gs_k_step_fbs_flow2]
 
-reads   gpurun_out/TAG_trace/**/_kernel_stats.csv            (rocprofv3 --kernel-trace --stats)
-        gpurun_out/TAG_pmc_FETCH_SIZE/**/_counter_collection.csv, gpurun_out/TAG_pmc_WRITE_SIZE/**  (separate --pmc passes)
-        gpurun_out/TAG_bench.log                             (the un-profiled bench line of the same build)
+reads   OUT/TAG_trace/**/_kernel_stats.csv            (rocprofv3 --kernel-trace --stats)
+        OUT/TAG_pmc_FETCH_SIZE/**/_counter_collection.csv, OUT/TAG_pmc_WRITE_SIZE/**  (separate --pmc passes)
+        OUT/TAG_bench.log                             (the un-profiled bench line of the same build)
+        where OUT = $PROFILE_OUT, default profile_out/ (as in tools/profile.sh)
 writes  profiles/OUT_PREFIX_kernel_stats.csv  (rows of the gs_* kernels), profiles/OUT_PREFIX_pmc.csv (kernel, counter, value_kb
         per dispatch), profiles/OUT_PREFIX_bench.json, and -- with --traffic-key -- the entry of profiles/hbm_traffic.json that
         bench.py reads for roofline.traffic: fabric-side bytes per launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024, FETCH_SIZE
@@ -19,10 +20,11 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("PROFILE_OUT") or os.path.join(ROOT, "profile_out")
 
 
 def find(tag_dir, suffix):
-    hits = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", tag_dir, "**", "*" + suffix), recursive=True))
+    hits = sorted(glob.glob(os.path.join(OUT, tag_dir, "**", "*" + suffix), recursive=True))
     return hits[-1] if hits else None
 
 
@@ -63,7 +65,7 @@ def main():
     if len(out_rows) > 1:
         with open(os.path.join(prof, a.out_prefix + "_pmc.csv"), "w", newline="") as f:
             csv.writer(f).writerows(out_rows)
-    bench = os.path.join(ROOT, "gpurun_out", a.tag + "_bench.log")
+    bench = os.path.join(OUT, a.tag + "_bench.log")
     if os.path.exists(bench):
         for line in open(bench):
             if line.startswith("{"):
