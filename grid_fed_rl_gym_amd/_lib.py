@@ -90,6 +90,7 @@ SYMBOLS = [
     ("gs_destroy", None, [_H]),
     ("gs_dims", C.c_int, [_H, _ip, _ip, _ip, _ip, _ip, _ip]),
     ("gs_describe", C.c_int, [_H, C.c_char_p, C.c_int32]),
+    ("gs_plan_describe", C.c_int, [C.POINTER(gs_topology), C.POINTER(gs_config), C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     ("gs_synchronize", C.c_int, [_H]),
     ("gs_solve", C.c_int, [_H, _dp, _dp, C.POINTER(gs_solution_view)]),
     ("gs_upload_injections", C.c_int, [_H, _dp, _dp]),
@@ -296,6 +297,18 @@ def flat_newton_map(spec, zero_z="open") -> np.ndarray:
     if rc != GS_OK:
         raise PowerFlowError(f"gs_flat_newton_map_dump failed ({rc}): {lib.gs_last_error(None).decode()}")
     return out
+
+
+def plan_describe(spec: FeederSpec, cfg: gs_config, batch: int, cus: int = 256) -> dict:
+    """gs_plan_describe: what Handle(spec, cfg, batch).describe() returns on a device with ``cus`` compute units, planned on the host
+    (no device needed)."""
+    lib = load()
+    t, keep = _topology_of(spec)
+    buf = C.create_string_buffer(4096)
+    rc = lib.gs_plan_describe(C.byref(t), C.byref(cfg), int(batch), int(cus), buf, 4096)
+    if rc != GS_OK:
+        raise PowerFlowError(f"gs_plan_describe failed ({rc}): {lib.gs_last_error(None).decode()}")
+    return json.loads(buf.value.decode())
 
 
 def mesh_schedule(spec: FeederSpec, nw: int = 4, ni: int = 10, acc_cap: int = 4, region_base: int = 0, slot_bytes: int = 144,

@@ -15,7 +15,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -24,6 +23,7 @@
 #include "kernels.h"
 #include "topology.h"
 #include "mesh_schedule.h"
+#include "plan.h"
 
 namespace {
 
@@ -76,46 +76,25 @@ constexpr size_t GS_CHECKS_MAX_EVENTS = 4096;
 
 }  // namespace
 
-struct gs_handle {
+// A handle is its plan (plan.h: members, rows, launch shapes, host tables) and the device state built from it.
+struct gs_handle : GsPlan {
   int device = 0;
   hipStream_t stream = nullptr;
-  int B = 0, Bp = 0, groups = 0, W = 1;
-  int n = 0, m = 0, obs_dim = 0, action_dim = 0, state_dim = 0;
-  int n_loads = 0, n_gens = 0, n_bats = 0;
   gs_config cfg{};
   HostTopology topo;
   GsTables T{};
-  GsRows R{};
-  GsSolveCfg SC{};
-  GsEnvCfg EC{};
-  double total_load = 0.0;
   struct gs_checks* fused = nullptr;      // checks evaluated inside the step kernel's epilogue (gs_checks_set_fused)
-  int solve_kernel = 0;     // 0 tree, 1 lu, 2 fbs, 3 dense, 4 tree with LDS messages, 5 fbs with LDS messages, 6 fbs as a dataflow over LDS
-  size_t dyn_lds = 0;
-  // the env step of a handle whose solver is the dataflow sweep runs the second-generation kernel (kernels_flow2.hip:
-  // 32 instances per workgroup, half-waves on different buses) when the feeder fits its tables; gs_solve keeps kernel 6
-  bool flow2 = false; GsF2Tables F2{}; std::string flow2_why;
-  bool f2_small = false, f2_half = false, f2_wide = false; int f2_iw = 32, f2_nw = 16, f2_npos = 0;
-  // A step of the 16-instance sweep kernel goes out as TWO launches, each half of the workgroups, on two streams: consecutive
-  // steps of one half need nothing from the other half, so the second stream's kernels slide into the launch gaps and the
-  // uneven tails of the first's (two handles of 4096 instances on two streams: 205 M env-steps/s against 186 M for one of
-  // 8192).  `forked`: stream2 holds step launches the main stream has not waited for yet; every entry point other than the
-  // step itself joins first (GS_ENTER).
-  bool split_ok = false, forked = false;
-  hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_peer = nullptr, ev_peer2 = nullptr;     // which member of the family (8 instances per workgroup for small feeders)
+  // A step of the second-generation kernels goes out as TWO launches, each half of the workgroups, on two streams
+  // (GsPlan::split_ok): consecutive steps of one half need nothing from the other half, so the second stream's kernels slide
+  // into the launch gaps and the uneven tails of the first's (two handles of 4096 instances on two streams: 205 M env-steps/s
+  // against 186 M for one of 8192).  `forked`: stream2 holds step launches the main stream has not waited for yet; every entry
+  // point other than the step itself joins first (GS_ENTER).
+  bool forked = false;
+  hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_peer = nullptr, ev_peer2 = nullptr;
   // The second-generation step kernels do not write the (|V|, angle) / (flow, |P| / rating) row pairs: those are the first
   // 2 n + 2 m columns of the observation block the step writes anyway.  `rows_stale`: the rows lag behind `last_obs`, the block
   // of the last step; every entry point that reads or partly rewrites them restores them first (ensure_rows).
-  bool lean = false, rows_stale = false; const double* last_obs = nullptr;
-  // solve_kernel 7: Newton-Raphson with the dense block LU on the matrix cores (kernels_dense.hip), a launch of its own between
-  // the two halves of the step / solve
-  GsDenseArgs DA{}; int dense_grid = 0; size_t dense_lds = 0; bool dense_blockrow = true;
-  // solve_kernel 8: Newton-Raphson with the sparse block LU of an instance in the LDS of a one-wave workgroup (kernels_sparse.hip),
-  // launched the same way
-  GsSparseArgs SA{}; int sparse_grid = 0; size_t sparse_lds = 0;
-  bool nr2 = false;         // ... and likewise the Newton-Raphson step of a radial all-PQ feeder (gs_k_step_nr_flow2) instead of kernel 4
-  bool nrm = false;         // ... and of a meshed all-PQ feeder whose block LU stays narrow (gs_k_step_nr_mesh2, mesh_schedule.h) instead of kernel 1
-  std::string mesh_why; int mesh_levels = 0, mesh_rows = 0, mesh_units = 0, mesh_messages = 0, mesh_accs = 0;
+  bool rows_stale = false; const double* last_obs = nullptr;
   unsigned long long* d_stamps = nullptr;
   bool was_reset = false;
   std::vector<void*> allocs;
@@ -127,7 +106,6 @@ struct gs_handle {
   // every step -- so that the all-gather of step k (on its own stream) can run while step k + 1 computes
   double* d_obs2[2] = {nullptr, nullptr}; int obs_cur = 0;
   hipStream_t comm_stream = nullptr; hipEvent_t ev_step = nullptr, ev_gather[2] = {nullptr, nullptr}; bool gather_pending[2] = {false, false};
-  int obs_skip0 = 0, obs_skip1 = 0;   // the block of per-instance constants inside an observation
   // host observation arrays whose constant columns are in place (gs_host_obs_bind): gs_step / gs_download_step copy only the
   // changing columns into these -- two strided copies instead of one whole block, 36 % fewer bytes over PCIe on the 123-bus feeder
   std::vector<const double*> bound_obs;
@@ -170,10 +148,6 @@ struct gs_handle {
 };
 
 namespace {
-
-enum { SF_REWARD = 0, SF_VMAX, SF_VMIN, SF_LOSSES, SF_EPREW, SF_MAXMIS, SF_COUNT };
-enum { SI_VIOL = 0, SI_STEP, SI_ITERS, SI_STATUS, SI_COUNT };
-enum { SU_TERM = 0, SU_TRUNC, SU_CONV, SU_VF0, SU_VF1, SU_VF2, SU_VF3, SU_COUNT };
 
 int fail(gs_handle* h, int code, const char* fmt, ...) {
   char buf[512];
@@ -322,38 +296,42 @@ int fetch_scalars(gs_handle* h, bool sync = true) {
   return GS_OK;
 }
 
+void launch_dense(gs_handle* h, int grid, const GsDenseArgs& args, double* slab, int nb) {
 #if defined(GS_BUILD_EXPERIMENTS)
-#define GS_DENSE_PANEL_LAUNCH(h, grid, args, nb) hipLaunchKernelGGL(gs_k_nr_dense_mfma, dim3(grid), dim3(256), (h)->dense_lds, (h)->stream, args, (h)->slab, nb)
-#else
-#define GS_DENSE_PANEL_LAUNCH(h, grid, args, nb) ((void)0)
+  if (!h->dense_blockrow) { hipLaunchKernelGGL(gs_k_nr_dense_mfma, dim3(grid), dim3(256), h->dense_lds, h->stream, args, slab, nb); return; }
 #endif
-#define GS_DENSE_LAUNCH(h, grid, args, nb)                                                                                          \
-  do {                                                                                                                              \
-    if ((h)->dense_blockrow) hipLaunchKernelGGL(gs_k_nr_dense_mfma2, dim3(grid), dim3(256), (h)->dense_lds, (h)->stream, args, (h)->slab, nb); \
-    else GS_DENSE_PANEL_LAUNCH(h, grid, args, nb);                                                                                 \
-  } while (0)
+  hipLaunchKernelGGL(gs_k_nr_dense_mfma2, dim3(grid), dim3(256), h->dense_lds, h->stream, args, slab, nb);
+}
+
+// the linear solve of nr_dense_mfma / nr_sparse_lds: a launch of its own between the two halves of the step / solve
+void launch_linear(gs_handle* h) {
+#if defined(GS_BUILD_EXPERIMENTS)
+  if (h->solve == SolveMember::nr_sparse_lds) {
+    hipLaunchKernelGGL(gs_k_nr_sparse_lds, dim3(h->sparse_grid), dim3(64 * h->SA.waves), h->sparse_lds, h->stream, h->SA, h->slab, h->B);
+    return;
+  }
+#endif
+  launch_dense(h, h->dense_grid, h->DA, h->slab, h->B);
+}
 
 int launch_solve(gs_handle* h) {
   LaunchTimer lt(h, GS_K_SOLVE);
   dim3 grid(h->groups), block(64 * h->W);
 #define GS_SOLVE(k) hipLaunchKernelGGL(k, grid, block, h->dyn_lds, h->stream, h->T, h->R, h->SC, h->slab, h->B)
-  if (h->solve_kernel == 0) GS_SOLVE(gs_k_nr_tree);
-  else if (h->solve_kernel == 4) GS_SOLVE(gs_k_nr_tree_lds);
-  else if (h->solve_kernel == 1) GS_SOLVE(gs_k_nr_lu);
-  else if (h->solve_kernel == 3) GS_SOLVE(gs_k_nr_dense);
-  else if (h->solve_kernel == 7) {
-    GS_DENSE_LAUNCH(h, h->dense_grid, h->DA, h->B);
-    hipLaunchKernelGGL(gs_k_posts_nr_dmfma, grid, block, h->dyn_lds, h->stream, h->T, h->R, h->SC, h->slab, h->B);
+  switch (h->solve) {
+    case SolveMember::nr_tree: GS_SOLVE(gs_k_nr_tree); break;
+    case SolveMember::nr_tree_lds: GS_SOLVE(gs_k_nr_tree_lds); break;
+    case SolveMember::nr_sparse_lu: GS_SOLVE(gs_k_nr_lu); break;
+    case SolveMember::nr_dense_pivot: GS_SOLVE(gs_k_nr_dense); break;
+    case SolveMember::fbs: GS_SOLVE(gs_k_fbs); break;
+    case SolveMember::fbs_lds: GS_SOLVE(gs_k_fbs_lds); break;
+    case SolveMember::fbs_flow: GS_SOLVE(gs_k_fbs_flow); break;
+    case SolveMember::nr_dense_mfma:
+    case SolveMember::nr_sparse_lds:
+      launch_linear(h);
+      GS_SOLVE(gs_k_posts_nr_dmfma);
+      break;
   }
-#if defined(GS_BUILD_EXPERIMENTS)
-  else if (h->solve_kernel == 8) {
-    hipLaunchKernelGGL(gs_k_nr_sparse_lds, dim3(h->sparse_grid), dim3(64 * h->SA.waves), h->sparse_lds, h->stream, h->SA, h->slab, h->B);
-    hipLaunchKernelGGL(gs_k_posts_nr_dmfma, grid, block, h->dyn_lds, h->stream, h->T, h->R, h->SC, h->slab, h->B);
-  }
-#endif
-  else if (h->solve_kernel == 5) GS_SOLVE(gs_k_fbs_lds);
-  else if (h->solve_kernel == 6) GS_SOLVE(gs_k_fbs_flow);
-  else GS_SOLVE(gs_k_fbs);
 #undef GS_SOLVE
   HIPCHK(h, hipGetLastError());
   return GS_OK;
@@ -385,10 +363,10 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
     if (h->lean) { h->rows_stale = true; h->last_obs = obs_out; }
     const GsFusedChecks fc = fused_checks_args(h);
     const GsRolloutStep rsv = rs ? *rs : GsRolloutStep{};
-    if (h->nr2 || h->flow2 || h->nrm) {        // 64 / IW workgroups per 64-instance slab group, each with its own IW instances
+    if (h->second_gen()) {        // 64 / IW workgroups per 64-instance slab group, each with its own IW instances
       const int per_group = 64 / h->f2_iw, n_wg = h->groups * per_group;
       const dim3 b2(64 * h->f2_nw);
-      // (two half-grid launches on two streams, see gs_handle::split_ok; the halves are whole 64-instance slab groups)
+      // (two half-grid launches on two streams, see gs_handle::forked; the halves are whole 64-instance slab groups)
       // (per-launch event pairs, gs_timing_enable(1), bracket ONE launch on the main stream: the step stays whole then)
       const bool split = h->split_ok && !h->timing;
       const int n_first = split ? (h->groups / 2) * per_group : n_wg;
@@ -401,52 +379,42 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
       f2a.wg_offset = 0; f2b.wg_offset = n_first;
 #define GS_F2(k) do { hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv); \
                       if (n_first < n_wg) hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv); } while (0)
-      if (h->nrm) { if (fc.enabled) GS_F2(gs_k_stepc_nr_mesh2); else GS_F2(gs_k_step_nr_mesh2); }
-      else if (h->nr2) {
-        if (h->f2_small) { if (fc.enabled) GS_F2(gs_k_stepc_nr_flow2s); else GS_F2(gs_k_step_nr_flow2s); }
-        else { if (fc.enabled) GS_F2(gs_k_stepc_nr_flow2); else GS_F2(gs_k_step_nr_flow2); }
-      } else {
-        if (h->f2_small) { if (fc.enabled) GS_F2(gs_k_stepc_fbs_flow2s); else GS_F2(gs_k_step_fbs_flow2s); }
-        else if (h->f2_wide) { if (fc.enabled) GS_F2(gs_k_stepc_fbs_flow2x); else GS_F2(gs_k_step_fbs_flow2x); }
-        else if (h->f2_half) { if (fc.enabled) GS_F2(gs_k_stepc_fbs_flow2h); else GS_F2(gs_k_step_fbs_flow2h); }
+#define GS_F2_PAIR(kc, k) do { if (fc.enabled) GS_F2(kc); else GS_F2(k); } while (0)
+      switch (h->step) {
+        case StepMember::fbs_flow2s: GS_F2_PAIR(gs_k_stepc_fbs_flow2s, gs_k_step_fbs_flow2s); break;
+        case StepMember::fbs_flow2h: GS_F2_PAIR(gs_k_stepc_fbs_flow2h, gs_k_step_fbs_flow2h); break;
+        case StepMember::fbs_flow2x: GS_F2_PAIR(gs_k_stepc_fbs_flow2x, gs_k_step_fbs_flow2x); break;
 #if defined(GS_BUILD_EXPERIMENTS)
-        else { if (fc.enabled) GS_F2(gs_k_stepc_fbs_flow2); else GS_F2(gs_k_step_fbs_flow2); }
+        case StepMember::fbs_flow2: GS_F2_PAIR(gs_k_stepc_fbs_flow2, gs_k_step_fbs_flow2); break;
 #endif
+        case StepMember::nr_flow2s: GS_F2_PAIR(gs_k_stepc_nr_flow2s, gs_k_step_nr_flow2s); break;
+        case StepMember::nr_flow2: GS_F2_PAIR(gs_k_stepc_nr_flow2, gs_k_step_nr_flow2); break;
+        case StepMember::nr_mesh2: GS_F2_PAIR(gs_k_stepc_nr_mesh2, gs_k_step_nr_mesh2); break;
+        case StepMember::none: break;
       }
+#undef GS_F2_PAIR
 #undef GS_F2
       HIPCHK(h, hipGetLastError());
       return GS_OK;
     }
 #define GS_STEP(k) hipLaunchKernelGGL(k, grid, block, h->dyn_lds, h->stream, h->T, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc)
-    if (h->solve_kernel == 7) {      // prologue | dense Newton-Raphson, one workgroup per instance | epilogue + observation pack
-      GS_STEP(gs_k_pre_nr_dmfma);
-      GS_DENSE_LAUNCH(h, h->dense_grid, h->DA, h->B);
-      if (fc.enabled) GS_STEP(gs_k_postc_nr_dmfma); else GS_STEP(gs_k_post_nr_dmfma);
-    } else
-#if defined(GS_BUILD_EXPERIMENTS)
-    if (h->solve_kernel == 8) {      // prologue | sparse LU in LDS, one wavefront per instance | epilogue + observation pack
-      GS_STEP(gs_k_pre_nr_dmfma);
-      hipLaunchKernelGGL(gs_k_nr_sparse_lds, dim3(h->sparse_grid), dim3(64 * h->SA.waves), h->sparse_lds, h->stream, h->SA, h->slab, h->B);
-      if (fc.enabled) GS_STEP(gs_k_postc_nr_dmfma); else GS_STEP(gs_k_post_nr_dmfma);
-    } else
-#endif
-    if (fc.enabled) {
-      if (h->solve_kernel == 0) GS_STEP(gs_k_stepc_nr_tree);
-      else if (h->solve_kernel == 4) GS_STEP(gs_k_stepc_nr_tree_lds);
-      else if (h->solve_kernel == 1) GS_STEP(gs_k_stepc_nr_lu);
-      else if (h->solve_kernel == 3) GS_STEP(gs_k_stepc_nr_dense);
-      else if (h->solve_kernel == 5) GS_STEP(gs_k_stepc_fbs_lds);
-      else if (h->solve_kernel == 6) GS_STEP(gs_k_stepc_fbs_flow);
-      else GS_STEP(gs_k_stepc_fbs);
-    } else {
-      if (h->solve_kernel == 0) GS_STEP(gs_k_step_nr_tree);
-      else if (h->solve_kernel == 4) GS_STEP(gs_k_step_nr_tree_lds);
-      else if (h->solve_kernel == 1) GS_STEP(gs_k_step_nr_lu);
-      else if (h->solve_kernel == 3) GS_STEP(gs_k_step_nr_dense);
-      else if (h->solve_kernel == 5) GS_STEP(gs_k_step_fbs_lds);
-      else if (h->solve_kernel == 6) GS_STEP(gs_k_step_fbs_flow);
-      else GS_STEP(gs_k_step_fbs);
+#define GS_STEP_PAIR(kc, k) do { if (fc.enabled) GS_STEP(kc); else GS_STEP(k); } while (0)
+    switch (h->solve) {
+      case SolveMember::nr_tree: GS_STEP_PAIR(gs_k_stepc_nr_tree, gs_k_step_nr_tree); break;
+      case SolveMember::nr_tree_lds: GS_STEP_PAIR(gs_k_stepc_nr_tree_lds, gs_k_step_nr_tree_lds); break;
+      case SolveMember::nr_sparse_lu: GS_STEP_PAIR(gs_k_stepc_nr_lu, gs_k_step_nr_lu); break;
+      case SolveMember::nr_dense_pivot: GS_STEP_PAIR(gs_k_stepc_nr_dense, gs_k_step_nr_dense); break;
+      case SolveMember::fbs: GS_STEP_PAIR(gs_k_stepc_fbs, gs_k_step_fbs); break;
+      case SolveMember::fbs_lds: GS_STEP_PAIR(gs_k_stepc_fbs_lds, gs_k_step_fbs_lds); break;
+      case SolveMember::fbs_flow: GS_STEP_PAIR(gs_k_stepc_fbs_flow, gs_k_step_fbs_flow); break;
+      case SolveMember::nr_dense_mfma:      // prologue | the linear solve, one workgroup / wavefront per instance | epilogue + observation pack
+      case SolveMember::nr_sparse_lds:
+        GS_STEP(gs_k_pre_nr_dmfma);
+        launch_linear(h);
+        GS_STEP_PAIR(gs_k_postc_nr_dmfma, gs_k_post_nr_dmfma);
+        break;
     }
+#undef GS_STEP_PAIR
 #undef GS_STEP
     HIPCHK(h, hipGetLastError()); }
   return GS_OK;     // the observation block was written by the step kernel itself
@@ -472,74 +440,107 @@ void copy_info(gs_handle* h, double* reward, uint8_t* term, uint8_t* trunc, cons
 }
 
 
-// The first Newton step from the flat start as a constant linear map of the injections (GsF2Tables::mesh_w): for a network whose
-// buses other than the slack are all PQ buses,  x = J0^-1 (S_spec - S_calc(flat)) = W [P_spec; 1]  with Q_spec = 0 -- W = the
-// angle-equation columns of J0^-1 and the constant term, (2 (n - 1)) x n.  J0: the exact Jacobian (power_flow.py:243-287) at |V| = 1,
-// angle 0 (the slack at its set point), inverted by Gauss-Jordan with partial pivoting.  Output in the operand order of
-// v_mfma_f64_16x16x4: [tiles row tiles][steps k-steps][64 lanes], A[row = lane & 15][k = lane >> 4], zero-padded.  false: J0 singular
-// or the sizes do not fit.
-static bool flat_newton_map(const HostTopology& ht, int tiles, int steps, std::vector<double>& wt) {
-  const int n_ = ht.n, sl = ht.slack, na = n_ - 1, N2 = 2 * na, K = na + 1;
-  if (na < 1 || N2 > 16 * tiles || K > 4 * steps) return false;
-  std::vector<double> v0(n_, 1.0);
-  if (ht.fixed_v[sl]) v0[sl] = ht.v_set[sl];
-  auto act = [&](int i) { return i < sl ? i : i - 1; };
-  std::vector<double> Pc(n_, 0.0), Qc(n_, 0.0), J((size_t)N2 * N2, 0.0);
-  for (int i = 0; i < n_; ++i)
-    for (int q = ht.row_ptr[i]; q < ht.row_ptr[i + 1]; ++q) {
-      const int j = ht.col[q];
-      const double g = i == j ? ht.Gd[i] : ht.G[q], bq = i == j ? ht.Bd[i] : ht.B[q];
-      Pc[i] += v0[i] * v0[j] * g; Qc[i] -= v0[i] * v0[j] * bq;
-    }
-  for (int i = 0; i < n_; ++i) {
-    if (i == sl) continue;
-    const int a = act(i);
-    const double vi = v0[i];
-    J[(size_t)(2 * a) * N2 + 2 * a] = -Qc[i] - vi * vi * ht.Bd[i];
-    J[(size_t)(2 * a) * N2 + 2 * a + 1] = Pc[i] / vi + vi * ht.Gd[i];
-    J[(size_t)(2 * a + 1) * N2 + 2 * a] = Pc[i] - vi * vi * ht.Gd[i];
-    J[(size_t)(2 * a + 1) * N2 + 2 * a + 1] = Qc[i] / vi - vi * ht.Bd[i];
-    for (int q = ht.row_ptr[i]; q < ht.row_ptr[i + 1]; ++q) {
-      const int j = ht.col[q];
-      if (j == i || j == sl) continue;
-      const int aj = act(j);
-      const double aa = vi * v0[j], gs_bc = -ht.B[q] * aa, gc_bs = ht.G[q] * aa;
-      J[(size_t)(2 * a) * N2 + 2 * aj] += gs_bc; J[(size_t)(2 * a) * N2 + 2 * aj + 1] += gc_bs / v0[j];
-      J[(size_t)(2 * a + 1) * N2 + 2 * aj] += -gc_bs; J[(size_t)(2 * a + 1) * N2 + 2 * aj + 1] += gs_bc / v0[j];
-    }
+// argument checks of gs_create and gs_plan_describe
+int check_args(const gs_topology* topo, const gs_config* cfg, int32_t batch) {
+  if (!topo || !cfg) return fail(nullptr, GS_E_INVALID, "topology / config is NULL");
+  if (topo->struct_size != (int32_t)sizeof(gs_topology) || cfg->struct_size != (int32_t)sizeof(gs_config))
+    return fail(nullptr, GS_E_INVALID, "struct_size mismatch (ABI %d): topology %d vs %zu, config %d vs %zu",
+                GS_ABI_VERSION, topo->struct_size, sizeof(gs_topology), cfg->struct_size, sizeof(gs_config));
+  if (batch <= 0) return fail(nullptr, GS_E_INVALID, "batch must be > 0");
+  if (cfg->max_iterations < 1) return fail(nullptr, GS_E_INVALID, "max_iterations must be >= 1");
+  if (!(cfg->power_base > 0.0)) return fail(nullptr, GS_E_INVALID, "power_base must be > 0");
+  if (!(cfg->timestep > 0.0)) return fail(nullptr, GS_E_INVALID, "timestep must be > 0");
+  return GS_OK;
+}
+
+// the topology compiled and the handle planned (host only), or the rejection as the library's error
+int plan_handle(const gs_topology& topo, const gs_config& cfg, int32_t batch, int cus, HostTopology& ht, GsPlan& p) {
+  std::string why = gs_compile_topology(topo, cfg.zero_z_mode, cfg.linear_solver == GS_LINSOLVE_SPARSE_LU,
+                                        cfg.solver_kind == GS_SOLVER_NR && cfg.jacobian_mode == GS_JACOBIAN_AS_CODED &&
+                                            (cfg.linear_solver == GS_LINSOLVE_AUTO || cfg.linear_solver == GS_LINSOLVE_DENSE_PIVOT),
+                                        ht);
+  if (!why.empty()) return fail(nullptr, GS_E_INVALID, "topology: %s", why.c_str());
+  why = gs_plan(topo, cfg, ht, batch, cus, p);
+  if (!why.empty()) return fail(nullptr, p.err_code, "%s", why.c_str());
+  return GS_OK;
+}
+
+// The flat-start captures.  Iteration 0 of every solve starts from the flat start, where the Jacobian is the same for every
+// instance: what it computes from it is computed once here, by the solver kernels themselves (bit-identical: the same blocks,
+// the same operations), and kept as a table that iteration 0 then reads.
+int flat_start_captures(gs_handle* h) {
+  const HostTopology& ht = h->topo;
+  const GsRows& R = h->R;
+  int rc = 0;
+  // dense block LU: the block factors, by one workgroup of the solver kernel in mode 1 (gs_create allocated DA.flat)
+  if (h->DA.flat) {
+    GsDenseArgs once = h->DA;
+    once.jinv_t = nullptr; once.mode = 1; once.max_it = 1;
+    launch_dense(h, 1, once, nullptr, 1);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+      return fail(nullptr, GS_E_HIP, "dense_mfma: factorisation of the flat-start Jacobian failed");
   }
-  std::vector<double> Ji((size_t)N2 * N2, 0.0);
-  for (int u = 0; u < N2; ++u) Ji[(size_t)u * N2 + u] = 1.0;
-  for (int c = 0; c < N2; ++c) {
-    int pr = c;
-    for (int r = c + 1; r < N2; ++r) if (std::fabs(J[(size_t)r * N2 + c]) > std::fabs(J[(size_t)pr * N2 + c])) pr = r;
-    const double pv = J[(size_t)pr * N2 + c];
-    if (!(pv != 0.0) || !std::isfinite(pv)) return false;
-    if (pr != c)
-      for (int k = 0; k < N2; ++k) { std::swap(J[(size_t)pr * N2 + k], J[(size_t)c * N2 + k]); std::swap(Ji[(size_t)pr * N2 + k], Ji[(size_t)c * N2 + k]); }
-    const double ip = 1.0 / pv;
-    for (int k = 0; k < N2; ++k) { J[(size_t)c * N2 + k] *= ip; Ji[(size_t)c * N2 + k] *= ip; }
-    for (int r = 0; r < N2; ++r) {
-      if (r == c) continue;
-      const double f = J[(size_t)r * N2 + c];
-      if (f == 0.0) continue;
-      for (int k = 0; k < N2; ++k) { J[(size_t)r * N2 + k] -= f * J[(size_t)c * N2 + k]; Ji[(size_t)r * N2 + k] -= f * Ji[(size_t)c * N2 + k]; }
-    }
+#if defined(GS_BUILD_EXPERIMENTS)
+  // sparse block LU in LDS: the factors, by one workgroup of the solver kernel in mode 1 (GS_LU_NO_FLAT=1: off)
+  if (h->solve == SolveMember::nr_sparse_lds && !getenv("GS_LU_NO_FLAT")) {
+    double* flat = nullptr;
+    if ((rc = dev_alloc(h, &flat, (size_t)4 * (ht.lu_n_slots + ht.n) + 4))) return rc;
+    GsSparseArgs once = h->SA;
+    once.flat_out = flat; once.mode = 1; once.max_it = 1;
+    hipLaunchKernelGGL(gs_k_nr_sparse_lds, dim3(1), dim3(64 * h->SA.waves), h->sparse_lds, h->stream, once, h->slab, 1);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+      return fail(nullptr, GS_E_HIP, "sparse_lds: factorisation of the flat-start Jacobian failed");
+    h->SA.flat = flat;
   }
-  std::vector<double> cst(N2, 0.0);
-  for (int u = 0; u < N2; ++u)
-    for (int a2 = 0; a2 < na; ++a2) {
-      const int bus = a2 < sl ? a2 : a2 + 1;
-      cst[u] -= Ji[(size_t)u * N2 + 2 * a2] * Pc[bus] + Ji[(size_t)u * N2 + 2 * a2 + 1] * Qc[bus];
-    }
-  wt.assign((size_t)tiles * steps * 64, 0.0);
-  for (int t = 0; t < tiles; ++t)
-    for (int s2 = 0; s2 < steps; ++s2)
-      for (int ln = 0; ln < 64; ++ln) {
-        const int u = 16 * t + (ln & 15), k = 4 * s2 + (ln >> 4);
-        if (u < N2 && k < K) wt[((size_t)t * steps + s2) * 64 + ln] = k < na ? Ji[(size_t)u * N2 + 2 * k] : cst[u];
-      }
-  return true;
+#endif
+  // Sparse block LU (GsTables::lu_flat): one ordinary solve of group 0, capped at one iteration, leaves the factors in the rows
+  // of lane 0; they are kept as a table of wave-uniform scalars and iteration 0 then only carries its right-hand side through
+  // (kernels_solve.hip, linsolve_lu_flat).  GS_LU_NO_FLAT=1: off.
+  if (h->solve == SolveMember::nr_sparse_lu && ht.lu_n_piv > 0 && !getenv("GS_LU_NO_FLAT")) {
+    double* tab = nullptr;
+    const int nblk = ht.lu_n_slots + ht.n;
+    if ((rc = dev_alloc(h, &tab, (size_t)4 * nblk + 4))) return rc;
+    hipLaunchKernelGGL(gs_k_fill_rows, dim3(1), dim3(64), 0, h->stream, R.P.base, 2, ht.n, R.total, h->slab, -0.01);
+    hipLaunchKernelGGL(gs_k_fill_rows, dim3(1), dim3(64), 0, h->stream, R.Q.base, 2, ht.n, R.total, h->slab, 0.0);
+    GsSolveCfg once = h->SC; once.max_iterations = 1; once.stamps = nullptr;
+    hipLaunchKernelGGL(gs_k_nr_lu, dim3(1), dim3(64 * h->W), h->dyn_lds, h->stream, h->T, h->R, once, h->slab, 1);
+    if (ht.lu_n_slots > 0)
+      hipLaunchKernelGGL(gs_k_gather_lane, dim3((4 * ht.lu_n_slots + 255) / 256), dim3(256), 0, h->stream, R.LU, 4 * ht.lu_n_slots, 0, h->slab, tab);
+    hipLaunchKernelGGL(gs_k_gather_lane, dim3((4 * ht.n + 255) / 256), dim3(256), 0, h->stream, R.LUD, 4 * ht.n, 0, h->slab, tab + (size_t)4 * ht.lu_n_slots);
+    double status = 0.0;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(&status, h->slab + GS_ELEM(R.STATUS, 0), sizeof status, hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(nullptr, GS_E_HIP, "sparse LU: factorisation of the flat-start Jacobian failed");
+    const double flag = status == (double)GS_STATUS_SINGULAR ? 1.0 : 0.0;
+    if (hipMemcpy(tab + (size_t)4 * nblk, &flag, sizeof flag, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(h->slab, 0, (size_t)R.total * GS_LANES * sizeof(double)) != hipSuccess)      // group 0 as gs_create leaves every group
+      return fail(nullptr, GS_E_HIP, "sparse LU: flat-start table");
+    h->T.lu_flat = tab;
+  }
+  // Newton-Raphson on the second-generation frame: the constants of the flat-start elimination (GsF2Tables::nrflat), written by
+  // ONE workgroup of the step kernel itself on the zeroed state of group 0, then group 0 is cleared again.  GS_NR_NO_FLAT=1: off.
+  const bool nr2 = h->step == StepMember::nr_flow2s || h->step == StepMember::nr_flow2 || h->step == StepMember::nr_mesh2;
+  if (nr2 && h->f2_npos > 0 && !getenv("GS_NR_NO_FLAT")) {
+    double* tab = nullptr;
+    if ((rc = dev_alloc(h, &tab, (size_t)h->f2_npos * 16))) return rc;
+    if (hipMemset(tab, 0, (size_t)h->f2_npos * 16 * sizeof(double)) != hipSuccess ||
+        hipMemset(h->d_in, 0, h->in_doubles * sizeof(double)) != hipSuccess) return fail(nullptr, GS_E_HIP, "hipMemset failed");      // (d_in: zero actions for the capture step)
+    GsF2Tables cap = h->F2; cap.nrflat = tab; cap.nrflat_mode = 1; cap.wg_offset = 0;
+    GsPackArgs pa{}; GsFusedChecks fc{}; GsRolloutStep rsv{};
+    GsSolveCfg sc = h->SC; sc.stamps = nullptr;
+    const dim3 b2(64 * h->f2_nw);
+    const int Bc = std::min(h->B, h->f2_iw);
+#define GS_CAPTURE(k) hipLaunchKernelGGL(k, dim3(1), b2, h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc, h->EC, h->slab, Bc, h->d_in, h->total_load, pa, fc, rsv)
+    if (h->step == StepMember::nr_mesh2) GS_CAPTURE(gs_k_step_nr_mesh2);
+    else if (h->step == StepMember::nr_flow2s) GS_CAPTURE(gs_k_step_nr_flow2s);
+    else GS_CAPTURE(gs_k_step_nr_flow2);
+#undef GS_CAPTURE
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemset(h->slab, 0, (size_t)R.total * GS_LANES * sizeof(double)) != hipSuccess)
+      return fail(nullptr, GS_E_HIP, "Newton-Raphson: flat-start table");
+    h->F2.nrflat = tab; h->F2.nrflat_mode = 2;
+  }
+  return GS_OK;
 }
 
 }  // namespace
@@ -569,92 +570,22 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
               int64_t first_instance, gs_handle** out) {
   if (!out) return fail(nullptr, GS_E_INVALID, "out is NULL");
   *out = nullptr;
-  if (!topo || !cfg) return fail(nullptr, GS_E_INVALID, "topology / config is NULL");
-  if (topo->struct_size != (int32_t)sizeof(gs_topology) || cfg->struct_size != (int32_t)sizeof(gs_config))
-    return fail(nullptr, GS_E_INVALID, "struct_size mismatch (ABI %d): topology %d vs %zu, config %d vs %zu",
-                GS_ABI_VERSION, topo->struct_size, sizeof(gs_topology), cfg->struct_size, sizeof(gs_config));
-  if (batch <= 0) return fail(nullptr, GS_E_INVALID, "batch must be > 0");
-  if (cfg->max_iterations < 1) return fail(nullptr, GS_E_INVALID, "max_iterations must be >= 1");
-  if (!(cfg->power_base > 0.0)) return fail(nullptr, GS_E_INVALID, "power_base must be > 0");
-  if (!(cfg->timestep > 0.0)) return fail(nullptr, GS_E_INVALID, "timestep must be > 0");
+  int rc = check_args(topo, cfg, batch);
+  if (rc) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, GS_E_NO_DEVICE, "no HIP device visible: libgridstep has no CPU fallback");
   if (device < 0 || device >= ndev) return fail(nullptr, GS_E_NO_DEVICE, "device %d out of range (0..%d)", device, ndev - 1);
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
 
   gs_handle* h = new gs_handle();
   h->device = device;
   h->cfg = *cfg;
-  std::string why = gs_compile_topology(*topo, cfg->zero_z_mode, cfg->linear_solver == GS_LINSOLVE_SPARSE_LU,
-                                        cfg->solver_kind == GS_SOLVER_NR && cfg->jacobian_mode == GS_JACOBIAN_AS_CODED &&
-                                            (cfg->linear_solver == GS_LINSOLVE_AUTO || cfg->linear_solver == GS_LINSOLVE_DENSE_PIVOT),
-                                        h->topo);
-  if (!why.empty()) { int rc = fail(nullptr, GS_E_INVALID, "topology: %s", why.c_str()); delete h; return rc; }
+  if ((rc = plan_handle(*topo, *cfg, batch, cus, h->topo, *h))) { delete h; return rc; }
   const HostTopology& ht = h->topo;
+  h->EC.first_instance = first_instance;
   h->line_x.assign(topo->x, topo->x + topo->m);
-  h->B = batch; h->Bp = (batch + 63) / 64 * 64; h->groups = h->Bp / 64;
-  int W = cfg->waves_per_group;
-  if (const char* e = getenv("GS_WAVES")) W = atoi(e);
-  const bool auto_w = W <= 0;
-  if (W <= 0) { W = 1; while (W < 16 && h->groups * W * 2 <= 2048) W *= 2; }
-  if (W > GS_MAX_WAVES) W = GS_MAX_WAVES;
-  h->W = W;
-  if (cfg->solver_kind == GS_SOLVER_FBS) {
-    if (!ht.fbs_ok) { int rc = fail(nullptr, GS_E_TOPOLOGY, "FBS: %s", ht.fbs_why.c_str()); delete h; return rc; }
-    h->solve_kernel = 2;
-    const size_t msg_bytes = (size_t)2 * ht.max_level_width * 6 * GS_LANES * sizeof(double);
-    if (msg_bytes + 24576 <= 160 * 1024 && !GS_EXPERIMENT_ENV("GS_NO_LDS_TREE")) { h->solve_kernel = 5; h->dyn_lds = msg_bytes; }
-    // dataflow sweeps: one 16-byte-per-lane message slot and one flag word per bus in LDS, at most 8 buses per wave
-    // (their state lives in registers); flat start only
-    const size_t flow_bytes = (size_t)ht.n * 2 * GS_LANES * sizeof(double) + (size_t)ht.n * sizeof(int32_t);
-    const int n_items = ht.is_forest ? ht.lvl_ptr[ht.n_levels] : 0;
-    // its LDS footprint allows one group per CU whatever W is, so a batch of any size runs it with all 16 waves
-    if (auto_w && n_items > 8 * W && n_items <= 8 * GS_MAX_WAVES) { W = GS_MAX_WAVES; h->W = W; }
-    if (!cfg->fbs_warm_start && flow_bytes + 24576 <= 160 * 1024 && (n_items + W - 1) / W <= 8 &&
-        !getenv("GS_NO_FLOW")) {
-      h->solve_kernel = 6; h->dyn_lds = flow_bytes; }
-  } else if (cfg->solver_kind == GS_SOLVER_NR) {
-    if (cfg->linear_solver == GS_LINSOLVE_TREE && !ht.is_forest) {
-      int rc = fail(nullptr, GS_E_TOPOLOGY, "tree elimination requested but the active network has loops"); delete h; return rc; }
-    int ls = cfg->linear_solver;
-    if (ls == GS_LINSOLVE_AUTO)
-      ls = (cfg->jacobian_mode == GS_JACOBIAN_AS_CODED) ? GS_LINSOLVE_DENSE_PIVOT
-                                                       : (ht.is_forest ? GS_LINSOLVE_TREE : GS_LINSOLVE_SPARSE_LU);
-    // meshed network whose sparse block LU would fill in (more than a quarter of all blocks): dense LU on the matrix cores
-    const int na_ = ht.n_active;
-    const bool mfma_fits = cfg->jacobian_mode == GS_JACOBIAN_EXACT && na_ >= 1 && 2 * na_ <= 256 && !GS_EXPERIMENT_ENV("GS_NO_DENSE_MFMA");
-    if (ls == GS_LINSOLVE_DENSE_MFMA && !mfma_fits) {
-      int rc = fail(nullptr, GS_E_TOPOLOGY, "dense_mfma needs the exact Jacobian and at most 128 non-slack buses (have %d)", na_); delete h; return rc; }
-    if (cfg->linear_solver == GS_LINSOLVE_AUTO && ls == GS_LINSOLVE_SPARSE_LU && mfma_fits && (long long)ht.lu_n_slots * 4 > (long long)na_ * na_)
-      ls = GS_LINSOLVE_DENSE_MFMA;
-    // meshed network with few loops: the sparse block LU of an instance in LDS, when its blocks fit beside a second workgroup's
-    // (one instance: its blocks + 7 doubles per bus; the shared schedule is about 2.5 x the blocks in bytes: two instances at least)
-    const size_t sparse_need = ((size_t)4 * (ht.lu_n_slots + ht.n) + (size_t)7 * ht.n) * sizeof(double);
-    const bool sparse_fits = ht.has_lu && !ht.is_forest && ht.lu_n_piv > 0 && ht.n <= 256 && sparse_need <= 32 * 1024;
-#if !defined(GS_BUILD_EXPERIMENTS)
-    if (ls == GS_LINSOLVE_SPARSE_LDS) {
-      int rc = fail(nullptr, GS_E_INVALID, "linear_solver sparse_lds is an experiment (measured, never AUTO's choice): build the library with `make EXPERIMENTS=1`"); delete h; return rc; }
-#endif
-    if (ls == GS_LINSOLVE_SPARSE_LDS && !sparse_fits) {
-      int rc = fail(nullptr, GS_E_TOPOLOGY, "sparse_lds needs a meshed network of at most 256 buses whose block LU fits 32 KB of LDS (%zu bytes here)", sparse_need); delete h; return rc; }
-    // (AUTO does not take it: measured on the 123-bus feeder with 26 loops it reaches 12.9 M env-steps/s against the slab-row
-    // kernel's 17.7 M -- four instances per CU, each a chain of 7-to-40-lane steps, lose to 64 instances per workgroup on full
-    // lanes, bytes or not; DESIGN.md section 7.  GS_SPARSE_LDS_AUTO=1 makes AUTO take it, for measurements.)
-    if (cfg->linear_solver == GS_LINSOLVE_AUTO && ls == GS_LINSOLVE_SPARSE_LU && sparse_fits && GS_EXPERIMENT_ENV("GS_SPARSE_LDS_AUTO"))
-      ls = GS_LINSOLVE_SPARSE_LDS;
-    h->solve_kernel = (ls == GS_LINSOLVE_TREE) ? 0 : (ls == GS_LINSOLVE_SPARSE_LU) ? 1 : (ls == GS_LINSOLVE_DENSE_MFMA) ? 7 : (ls == GS_LINSOLVE_SPARSE_LDS) ? 8 : 3;
-    // forest sweeps through LDS messages when two adjacent levels fit next to the 24 KB static block
-    const size_t msg_bytes = (size_t)2 * ht.max_level_width * 6 * GS_LANES * sizeof(double);
-    if (h->solve_kernel == 0 && msg_bytes + 24576 <= 160 * 1024 && !GS_EXPERIMENT_ENV("GS_NO_LDS_TREE")) h->solve_kernel = 4;
-    if (h->solve_kernel == 4) h->dyn_lds = msg_bytes;
-  } else { int rc = fail(nullptr, GS_E_INVALID, "unknown solver_kind %d", cfg->solver_kind); delete h; return rc; }
-  // the epilogue's cross-wave partials need 48 KB; the observation pack stages two or three 64-column tiles behind them
-  h->dyn_lds = std::max<size_t>(49152 + 2 * 64 * 65 * sizeof(double), h->dyn_lds);
-
-  h->n = ht.n; h->m = ht.m; h->n_loads = topo->n_loads; h->n_gens = topo->n_gens; h->n_bats = topo->n_bats;
-  h->obs_dim = 2 * h->n + 2 * h->m + 1 + 2 * h->n_loads + h->n_gens + 2 * h->n_bats;     // grid_env.py:307-314
-  h->action_dim = h->n_bats + h->n_gens;                                                    // grid_env.py:351
-  h->state_dim = 12 + 2 * h->n_bats + h->n_gens + 2 * h->n + 2 * h->m;
   auto bail = [&](int rc) { gs_destroy(h); return rc; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipSetDevice failed"));
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
@@ -678,7 +609,7 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
         return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", max_dyn));
     for (const void* f : {
 #if defined(GS_BUILD_EXPERIMENTS)
-                          (const void*)gs_k_step_fbs_flow2, (const void*)gs_k_stepc_fbs_flow2,
+                          (const void*)gs_k_step_fbs_flow2, (const void*)gs_k_stepc_fbs_flow2, (const void*)gs_k_nr_sparse_lds,
 #endif
                           (const void*)gs_k_step_nr_flow2,
                           (const void*)gs_k_stepc_nr_flow2, (const void*)gs_k_step_fbs_flow2s, (const void*)gs_k_stepc_fbs_flow2s,
@@ -687,9 +618,6 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
                           (const void*)gs_k_step_nr_mesh2, (const void*)gs_k_stepc_nr_mesh2})      // no static LDS in these
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
         return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", 160 * 1024));
-  }
-
-  {
     hipError_t e = hipFuncSetAttribute((const void*)gs_k_nr_dense_mfma2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
 #if defined(GS_BUILD_EXPERIMENTS)
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gs_k_nr_dense_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
@@ -697,483 +625,13 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     if (e != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(gs_k_nr_dense_mfma): %s", hipGetErrorString(e)));
   }
 
-  // ---- rows ----
-  GsRows& R = h->R;
-  int r = 0;
-  auto take = [&](int count) { int at = r; r += count; return at; };
-  auto take_even = [&](int count) { r = (r + 1) & ~1; return take(count); };          // blocks whose entries pair up
-  auto take_pair = [&](GsFam2& a, GsFam2& b2, int count) { r = (r + 1) & ~1; a.base = r; b2.base = r + 1; r += 2 * count; };
-  const int n = h->n, m = h->m;
-  take_pair(R.P, R.Q, n); take_pair(R.VM, R.VA, n); take_pair(R.FLOW, R.ENVLOAD, m); R.LOAD = take(m);
-  R.LOSSES = take(1); R.MAXMIS = take(1); R.ITERS = take(1); R.CONV = take(1); R.STATUS = take(1);
-  // scratch rows are allocated only for the kernel that uses them: the slab is what the step
-  // streams through L2 / Infinity Cache, so every unused row costs residency
-  const int sk = h->solve_kernel;
-  const bool k_tree = sk == 0, k_lu = sk == 1, k_fbs = sk == 2 || sk == 5 || sk == 6, k_dense = sk == 3, k_tree_lds = sk == 4;
-  const bool k_rhs = k_tree || k_lu || k_dense;
-  take_pair(R.E, R.F, n); take_pair(R.PC, R.QC, n);
-  take_pair(R.R0, R.R1, k_rhs ? n : 0); take_pair(R.X0, R.X1, k_rhs ? n : 0);
-  R.RVM = take(n);
-  R.SV = take_even(k_tree || k_tree_lds ? 2 * n : 0); R.QV = take_even(k_tree ? 2 * n : 0);
-  R.TB = take_even(k_tree || k_tree_lds ? 4 * n : 0); R.CB = take_even(k_tree ? 4 * n : 0);
-  take_pair(R.JR, R.JI, k_fbs ? n : 0);
-  R.LU = take_even(h->solve_kernel == 1 ? 4 * ht.lu_n_slots : 0);
-  R.LUD = take_even(h->solve_kernel == 1 ? 4 * n : 0);
-  const int dnN = ht.dn_N;
-  R.DA = take(h->solve_kernel == 3 ? dnN * dnN : 0);
-  R.DB = take(h->solve_kernel == 3 ? dnN : 0); R.DX = take(h->solve_kernel == 3 ? dnN : 0);
-  R.DPERM = take(h->solve_kernel == 3 ? dnN : 0);
-  R.TIME = take(1); R.STEP = take(1); R.VIOL = take(1); R.TOTLOSS = take(1); R.EPREW = take(1); R.FREQ = take(1);
-  R.IRR = take(1); R.WIND = take(1); R.TEMP = take(1); R.CLOUD = take(1); R.SEEDLO = take(1); R.SEEDHI = take(1);
-  R.SOC = take(h->n_bats); R.BATP = take(h->n_bats); R.CURT = take(h->n_gens); R.GENP = take(h->n_gens);
-  R.REWARD = take(1); R.TERM = take(1); R.TRUNC = take(1); R.VMAX = take(1); R.VMIN = take(1); R.VFLAGS = take(4);
-  R.ACT = take(h->action_dim); R.LOADP = take_even(h->n_loads + 1);   // written in pairs by the load-noise draws
-  R.total = (r + 1) & ~1;        // rows are stored in pairs (GS_ELEM)
-
-  // ---- per-wave work lists of the forest sweeps (records in the order each wave meets them) ----
-  std::vector<GsItemRec> witems;
-  std::vector<int32_t> wl_ptr(h->W + 1, 0), ovf_slot;
-  if (ht.is_forest) {
-    const int maxw = ht.max_level_width;
-    const bool flow = h->solve_kernel == 6;      // messages by bus index, items dealt for equal item counts per wave
-    std::vector<int> owner(ht.lvl_ptr[ht.n_levels], 0);
-    {
-      std::vector<int> load(h->W, 0);
-      for (int lv = 0; lv < ht.n_levels; ++lv)
-        for (int t = ht.lvl_ptr[lv]; t < ht.lvl_ptr[lv + 1]; ++t) {
-          int w = (t - ht.lvl_ptr[lv]) % h->W;
-          if (flow) { w = 0; for (int v = 1; v < h->W; ++v) if (load[v] < load[w]) w = v; }
-          owner[t] = w; ++load[w];
-        }
-    }
-    for (int w = 0; w < h->W; ++w) {
-      wl_ptr[w] = (int)witems.size();
-      for (int lv = 0; lv < ht.n_levels; ++lv)
-        for (int t = ht.lvl_ptr[lv]; t < ht.lvl_ptr[lv + 1]; ++t) {
-          if (owner[t] != w) continue;
-          GsItemRec r{};
-          const int i = ht.lvl_bus[t], p = ht.parent[i];
-          r.bus = i; r.parent = p; r.level = lv;
-          r.slot = (lv & 1) * maxw + (t - ht.lvl_ptr[lv]);
-          r.parent_slot = p >= 0 ? ((lv + 1) & 1) * maxw + ht.lvl_pos[p] : 0;
-          r.flags = (ht.th_free[i] ? 1 : 0) | (ht.vm_free[i] ? 2 : 0) |
-                    (p >= 0 && ht.th_free[p] ? 4 : 0) | (p >= 0 && ht.vm_free[p] ? 8 : 0);
-          r.n_children = ht.child_ptr[i + 1] - ht.child_ptr[i];
-          r.ovf0 = (int)ovf_slot.size();
-          for (int q = 0; q < r.n_children; ++q) {
-            const int ch = ht.child_idx[ht.child_ptr[i] + q];
-            const int cs = flow ? ch : ((lv - 1) & 1) * maxw + ht.lvl_pos[ch];
-            if (q < GS_ITEM_CHILDREN) r.child_slot[q] = cs; else ovf_slot.push_back(cs);
-          }
-          if (p >= 0) { r.g = ht.G[ht.parent_pos[i]]; r.b = ht.B[ht.parent_pos[i]]; }
-          r.gd = ht.Gd[i]; r.bd = ht.Bd[i];
-          if (h->solve_kernel == 5 || flow) {       // FBS flavour: parent includes the slack, (g, b) := z = 1 / y
-            const int fp = ht.fbs_parent[i], pos = ht.fbs_parent_pos[i];
-            const double yr = -ht.G[pos], yi = -ht.B[pos], yd = yr * yr + yi * yi;
-            r.g = yr / yd; r.b = -yi / yd;
-            r.gd = yr; r.bd = yi;
-            if (p < 0) { r.parent = fp; r.flags |= 16; }
-          }
-          witems.push_back(r);
-        }
-    }
-    wl_ptr[h->W] = (int)witems.size();
-  }
-
-  std::vector<GsInjRec> winj;
-  std::vector<int32_t> wi_ptr(h->W + 1, 0);
-  for (int w = 0; w < h->W; ++w) {
-    wi_ptr[w] = (int)winj.size();
-    // dataflow sweep kernel: a wave builds the injections of the buses it solves, in item order, straight into the
-    // solver's registers (a bus that is nobody's item -- the slack -- needs no injection there)
-    std::vector<int> mine;
-    if (h->solve_kernel == 6) for (int k = wl_ptr[w]; k < wl_ptr[w + 1]; ++k) mine.push_back(witems[k].bus);
-    else for (int i = w; i < ht.n; i += h->W) mine.push_back(i);
-    for (int i : mine) {
-      GsInjRec r{};
-      r.bus = i;
-      r.nl = ht.bl_ptr[i + 1] - ht.bl_ptr[i]; r.ng = ht.bg_ptr[i + 1] - ht.bg_ptr[i]; r.nb = ht.bb_ptr[i + 1] - ht.bb_ptr[i];
-      r.generic = (r.nl > 2 || r.ng > 2 || r.nb > 2) ? 1 : 0;
-      if (r.nl > 0) r.l0 = ht.bl_idx[ht.bl_ptr[i]];
-      if (r.nl > 1) r.l1 = ht.bl_idx[ht.bl_ptr[i] + 1];
-      if (r.ng > 0) r.g0 = ht.bg_idx[ht.bg_ptr[i]];
-      if (r.ng > 1) r.g1 = ht.bg_idx[ht.bg_ptr[i] + 1];
-      if (r.nb > 0) r.b0 = ht.bb_idx[ht.bb_ptr[i]];
-      if (r.nb > 1) r.b1 = ht.bb_idx[ht.bb_ptr[i] + 1];
-      winj.push_back(r);
-    }
-  }
-  wi_ptr[h->W] = (int)winj.size();
-
-  // mismatch records: each bus' Ybus row in chunks of GS_ELL_K entries (same entry order as the
-  // CSR row); buses are dealt to the waves longest row first so that every wave gets about the
-  // same number of records
-  std::vector<GsBusRec> wbus;
-  std::vector<int32_t> wb_ptr(h->W + 1, 0);
-  {
-    std::vector<int> order(ht.n), nrec(ht.n);
-    for (int i = 0; i < ht.n; ++i) { order[i] = i; nrec[i] = std::max(1, (ht.row_ptr[i + 1] - ht.row_ptr[i] + GS_ELL_K - 1) / GS_ELL_K); }
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return nrec[a] > nrec[b2]; });
-    std::vector<std::vector<int>> mine(h->W);
-    std::vector<int> load(h->W, 0);
-    for (int i : order) {
-      int best = 0;
-      for (int w = 1; w < h->W; ++w) if (load[w] < load[best]) best = w;
-      mine[best].push_back(i); load[best] += nrec[i];
-    }
-    for (int w = 0; w < h->W; ++w) {
-      wb_ptr[w] = (int)wbus.size();
-      std::sort(mine[w].begin(), mine[w].end());
-      for (int i : mine[w]) {
-        const int p0 = ht.row_ptr[i], p1 = ht.row_ptr[i + 1];
-        for (int c0 = 0; c0 < nrec[i]; ++c0) {
-          GsBusRec r{};
-          r.bus = i;
-          r.flags = (ht.th_free[i] ? 1 : 0) | (ht.vm_free[i] ? 2 : 0) | (c0 + 1 < nrec[i] ? 4 : 0) | (c0 > 0 ? 8 : 0);
-          for (int k = 0; k < GS_ELL_K; ++k) {
-            const int p = p0 + c0 * GS_ELL_K + k;
-            if (p < p1) { r.col[k] = ht.col[p]; r.G[k] = ht.G[p]; r.B[k] = ht.B[p]; }
-            else { r.col[k] = i; r.G[k] = 0.0; r.B[k] = 0.0; }
-          }
-          wbus.push_back(r);
-        }
-      }
-    }
-    wb_ptr[h->W] = (int)wbus.size();
-  }
-
-  // ---- second-generation step kernels (kernels_flow2.hip): IW instances per workgroup, NW waves, NI buses per sub-group ----
-  std::vector<GsF2Rec> f2recs; std::vector<int32_t> f2anc; std::vector<double> f2z;
-  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  // LDS carve-up shared by the members of the family; returns the total
-  auto f2_layout = [&](GsF2Tables& F, int NW, int IW, size_t second_region_min, size_t n_table_ints, int zcols, size_t z_bytes = 0) {
-    const int nsl = ht.n + 3;
-    const size_t SB = (size_t)(IW + 1) * 16;
-    size_t off = up16((size_t)nsl * SB);
-    F.off_tile = (int32_t)off;
-    off += up16(std::max<size_t>({(size_t)nsl * SB, second_region_min, (size_t)ht.m * SB, (size_t)(topo->n_loads + 4) * IW * sizeof(double)}));
-    F.off_anc = (int32_t)off; off += up16(n_table_ints * 4);
-    F.off_z = (int32_t)off; off += up16(std::max((size_t)nsl * zcols * 8, z_bytes));
-    F.off_prof = (int32_t)off; off += up16(24 * sizeof(double));
-    F.env_genp = 0; F.env_curt = topo->n_gens; F.env_batp = 2 * topo->n_gens; F.env_soc = 2 * topo->n_gens + topo->n_bats;
-    F.off_env = (int32_t)off; off += up16((size_t)(2 * topo->n_gens + 2 * topo->n_bats + 1) * IW * sizeof(double));
-    F.off_red = (int32_t)off; off += 2 * (size_t)NW * IW * sizeof(double);
-    F.off_atom = (int32_t)off; off += 8 * (size_t)IW * sizeof(unsigned long long) + 16 * (size_t)IW * sizeof(uint32_t);
-    F.lds_bytes = (int32_t)off; F.n_slots = nsl; F.slack = ht.slack;
-    return off;
-  };
-  auto f2_devices = [&](GsF2Rec& r, int i) {
-    r.nl = ht.bl_ptr[i + 1] - ht.bl_ptr[i]; r.ng = ht.bg_ptr[i + 1] - ht.bg_ptr[i]; r.nb = ht.bb_ptr[i + 1] - ht.bb_ptr[i];
-    if (r.nl > 0) r.l0 = ht.bl_idx[ht.bl_ptr[i]];
-    if (r.nl > 1) r.l1 = ht.bl_idx[ht.bl_ptr[i] + 1];
-    if (r.ng > 0) r.g0 = ht.bg_idx[ht.bg_ptr[i]];
-    if (r.ng > 1) r.g1 = ht.bg_idx[ht.bg_ptr[i] + 1];
-    if (r.nb > 0) r.b0 = ht.bb_idx[ht.bb_ptr[i]];
-    if (r.nb > 1) r.b1 = ht.bb_idx[ht.bb_ptr[i] + 1];
-  };
-  int max_dev = 0, max_ch = 0;
-  for (int i = 0; i < ht.n; ++i) {
-    max_dev = std::max({max_dev, ht.bl_ptr[i + 1] - ht.bl_ptr[i], ht.bg_ptr[i + 1] - ht.bg_ptr[i], ht.bb_ptr[i + 1] - ht.bb_ptr[i]});
-    if (ht.is_forest) max_ch = std::max(max_ch, ht.child_ptr[i + 1] - ht.child_ptr[i]);
-  }
-  const int SL_ZERO = ht.n, SL_ONE = ht.n + 1, SL_DUMMY = ht.n + 2, nsl = ht.n + 3;
-
-  // -- sweep solver: one record per position of the preorder of the tree below the slack
-  // (eligible wherever the first-generation dataflow kernel is, and -- with the number of waves left to the library -- for
-  // feeders beyond its 128 buses)
-  if (h->solve_kernel == 6 || (cfg->solver_kind == GS_SOLVER_FBS && auto_w && !cfg->fbs_warm_start && ht.is_forest && ht.fbs_ok &&
-                               ht.lvl_ptr[ht.n_levels] > 8 * GS_MAX_WAVES && !getenv("GS_NO_FLOW"))) {
-    std::string& why = h->flow2_why;
-    std::vector<int> order, size(ht.n, 1), depth(ht.n, 0);
-    {
-      std::vector<std::vector<int>> kids(ht.n);
-      std::vector<int> roots;
-      for (int lv = ht.n_levels - 1; lv >= 0; --lv)
-        for (int t = ht.lvl_ptr[lv]; t < ht.lvl_ptr[lv + 1]; ++t) {
-          const int i = ht.lvl_bus[t], fp = ht.fbs_parent[i];
-          if (fp == ht.slack) roots.push_back(i); else kids[fp].push_back(i);
-        }
-      std::sort(roots.begin(), roots.end());
-      for (auto& k : kids) std::sort(k.begin(), k.end());
-      std::vector<std::pair<int, int>> stack;
-      for (int ri = (int)roots.size() - 1; ri >= 0; --ri) stack.push_back({roots[ri], 1});
-      while (!stack.empty()) {
-        auto [i, d] = stack.back(); stack.pop_back();
-        order.push_back(i); depth[i] = d;
-        for (int q = (int)kids[i].size() - 1; q >= 0; --q) stack.push_back({kids[i][q], d + 1});
-      }
-      for (int p = (int)order.size() - 1; p >= 0; --p) { const int i = order[p], fp = ht.fbs_parent[i]; if (fp != ht.slack) size[fp] += size[i]; }
-    }
-    const int N = (int)order.size();
-    int max_depth = 1;
-    for (int i : order) max_depth = std::max(max_depth, depth[i]);
-    // forward sweep by pointer jumping, radix 4: round r adds the partial sums of the ancestors 4^r, 2 * 4^r and 3 * 4^r up
-    int n_jump = 0;
-    while ((1 << (2 * n_jump)) < max_depth) ++n_jump;
-    n_jump = std::max(2, (n_jump + 1) & ~1);                         // even: the last round then reads the second buffer
-    // small feeders: 8 instances per workgroup, the eight sub-groups of a wavefront on eight buses
-    const bool small = N <= GS_F2S_WAVES * (64 / GS_F2S_IW) * GS_F2S_ITEMS && !getenv("GS_NO_FLOW2_SMALL");
-    // default: 16 instances per workgroup, two workgroups per CU (GS_FLOW2_IW=32 asks for the 32-instance member, one per CU)
-    const bool wide = !small && N > GS_F2_WAVES * 2 * GS_F2_ITEMS;          // 129 ... 256 buses: eight buses per sub-group
-    const bool half = !small && !wide && !(GS_EXPERIMENT_ENV("GS_FLOW2_IW") && atoi(GS_EXPERIMENT_ENV("GS_FLOW2_IW")) == 32);
-    const int NW = small ? GS_F2S_WAVES : wide ? GS_F2X_WAVES : half ? GS_F2H_WAVES : GS_F2_WAVES,
-              NI = small ? GS_F2S_ITEMS : wide ? GS_F2X_ITEMS : half ? GS_F2H_ITEMS : GS_F2_ITEMS,
-              IW = small ? GS_F2S_IW : (wide || half) ? GS_F2H_IW : 32;
-    const int NPOS = NW * (64 / IW) * NI;
-    GsF2Tables& F = h->F2;
-    const size_t off = f2_layout(F, NW, IW, 0, (size_t)n_jump * nsl * 4, 2);
-    F.n_jump = n_jump;
-    if (getenv("GS_NO_FLOW2")) why = "disabled by GS_NO_FLOW2";
-    else if (N > NPOS) why = "more than " + std::to_string(NPOS) + " buses below the slack";
-    // (the second-generation sweeps hold their stopping criterion, the summed mismatch, in 2^-44 pu fixed point: below ~1e-10 the
-    // threshold is a handful of units and every lane's rounding shows; the first-generation kernels compare in double precision)
-    else if (!(cfg->tolerance >= 1e-10)) why = "tolerance below 1e-10";
-    else if (N != ht.lvl_ptr[ht.n_levels]) why = "part of the forest does not hang off the slack bus";
-    else if (max_dev > 2) why = "more than two devices of a kind at one bus";
-    else if (off > 160 * 1024) why = "LDS tables do not fit";
-    else if (ht.n < 2 || ht.m < 1 || N < 1) why = "trivial network";
-    if (why.empty()) {
-      h->flow2 = true; h->f2_small = small; h->f2_half = half; h->f2_wide = wide; h->f2_iw = IW; h->f2_nw = NW;
-      GsF2Rec idle{}; idle.bus = SL_DUMMY; idle.parent = SL_ONE; idle.last = SL_DUMMY;
-      f2recs.assign((size_t)NPOS, idle);
-      f2z.assign((size_t)nsl * 2, 0.0);
-      f2anc.assign((size_t)n_jump * nsl * 4, SL_ZERO);            // [round][slot][4]: the slot's ancestors 1, 2, 3 steps of 4^round up (no ancestor: ZERO)
-      std::vector<int> up1((size_t)nsl, SL_ZERO);                    // parent slot of every slot (the slack's children: ZERO)
-      for (int p = 0; p < N; ++p) {
-        GsF2Rec& r = f2recs[p];
-        const int i = order[p];
-        const int fp = ht.fbs_parent[i], pos = ht.fbs_parent_pos[i];
-        const double yr = -ht.G[pos], yi = -ht.B[pos], yd = yr * yr + yi * yi;      // branch admittance = -Y_ip; z = 1 / y
-        r.bus = i; r.parent = fp; r.flags = 1 | (fp == ht.slack ? 2 : 0); r.last = order[p + size[i] - 1]; r.level = depth[i];
-        r.zr = yr / yd; r.zi = -yi / yd; r.yr = yr; r.yi = yi;
-        f2z[2 * (size_t)i] = r.zr; f2z[2 * (size_t)i + 1] = r.zi;
-        up1[i] = fp == ht.slack ? SL_ZERO : fp;
-        f2_devices(r, i);
-      }
-      {
-        std::vector<int> step = up1;                                 // ancestor 4^round steps up
-        for (int r = 0; r < n_jump; ++r) {
-          for (int sidx = 0; sidx < nsl; ++sidx) {
-            int a = sidx;
-            for (int k = 0; k < 3; ++k) { a = step[a]; f2anc[((size_t)r * nsl + sidx) * 4 + k] = a; }
-          }
-          std::vector<int> nxt((size_t)nsl);
-          for (int sidx = 0; sidx < nsl; ++sidx) nxt[sidx] = step[step[step[step[sidx]]]];
-          step.swap(nxt);
-        }
-      }
-    }
-  }
-
-  // -- Newton-Raphson: every (wave, item) holds a group of HV = 64 / IW buses of ONE level of the tree
-  if (h->solve_kernel == 4 && ht.fbs_ok) {
-    std::string& why = h->flow2_why;
-    bool all_pq = true, off_slack = true;
-    for (int i = 0; i < ht.n; ++i) {
-      if (i != ht.slack && ht.lvl_pos[i] >= 0 && !(ht.th_free[i] && ht.vm_free[i])) all_pq = false;
-      if (i != ht.slack && ht.lvl_pos[i] < 0) off_slack = false;                       // a bus outside the forest
-      if (ht.lvl_pos[i] >= 0 && ht.parent[i] < 0 && ht.fbs_parent[i] != ht.slack) off_slack = false;
-    }
-    auto deal = [&](int NW, int HV, std::vector<std::vector<std::vector<int>>>& mine, std::vector<std::vector<int>>& mine_lv) {
-      mine.assign(NW, {}); mine_lv.assign(NW, {});
-      for (int lv = 0; lv < ht.n_levels; ++lv)
-        for (int t = ht.lvl_ptr[lv]; t < ht.lvl_ptr[lv + 1]; t += HV) {
-          int w = 0;
-          for (int v = 1; v < NW; ++v) if (mine[v].size() < mine[w].size()) w = v;
-          std::vector<int> grp;
-          for (int q = 0; q < HV; ++q) grp.push_back(t + q < ht.lvl_ptr[lv + 1] ? ht.lvl_bus[t + q] : -1);
-          mine[w].push_back(grp); mine_lv[w].push_back(lv);
-        }
-      int mx = 0;
-      for (auto& v : mine) mx = std::max<int>(mx, (int)v.size());
-      return mx;
-    };
-    std::vector<std::vector<std::vector<int>>> mine; std::vector<std::vector<int>> mine_lv;
-    bool small = !getenv("GS_NO_FLOW2_SMALL") && deal(GS_F2NS_WAVES, 64 / GS_F2S_IW, mine, mine_lv) <= GS_F2NS_ITEMS;
-    const int NW = small ? GS_F2NS_WAVES : GS_F2N_WAVES, NI = small ? GS_F2NS_ITEMS : GS_F2N_ITEMS, IW = small ? GS_F2S_IW : 32, HV = 64 / IW;
-    const int max_items = deal(NW, HV, mine, mine_lv);
-    const int NPOS = NW * HV * NI, maxw = ht.max_level_width;
-    h->f2_npos = NPOS;
-    GsF2Tables& F = h->F2;
-    // the ring's zero entry: behind the ring's two parities and behind the K slots that share the region
-    const size_t ring_entry = (size_t)3 * IW * 16;
-    const int ring_zero = (int)std::max<size_t>((size_t)2 * maxw, ((size_t)nsl * (IW + 1) * 16 + ring_entry - 1) / ring_entry);
-    const size_t ring_bytes = (size_t)(ring_zero + 1) * ring_entry;
-    const int pos_off = (2 * (ht.n + 1) * GS_F2_CHILDREN + nsl + 3) & ~3;
-    const int n_ints = pos_off + NPOS * 4;
-    const size_t off = f2_layout(F, NW, IW, ring_bytes, (size_t)n_ints, 4);
-    F.n_jump = 0; F.n_levels = ht.n_levels; F.pos_off = pos_off; F.n_anc_ints = n_ints; F.ring_zero = ring_zero;
-    if (getenv("GS_NO_FLOW2")) why = "disabled by GS_NO_FLOW2";
-    else if (!h->SC.jacobian_exact && cfg->jacobian_mode != GS_JACOBIAN_EXACT) why = "as-coded Jacobian";
-    else if (!all_pq) why = "a bus below the slack is not a PQ bus";
-    else if (!off_slack) why = "part of the network does not hang off the slack bus";
-    else if (max_items > NI) why = "more than " + std::to_string(NI) + " bus groups per wave";
-    else if (max_ch > GS_F2_CHILDREN) why = "a bus has more than " + std::to_string(GS_F2_CHILDREN) + " children";
-    else if (max_dev > 2) why = "more than two devices of a kind at one bus";
-    else if (off > 160 * 1024) why = "LDS tables do not fit";
-    else if (ht.n < 2 || ht.m < 1) why = "trivial network";
-    if (why.empty()) {
-      h->nr2 = true; h->f2_small = small; h->f2_iw = IW; h->f2_nw = NW;
-      GsF2Rec idle{}; idle.bus = SL_DUMMY; idle.parent = SL_ONE; idle.last = SL_DUMMY; idle.level = -1;
-      f2recs.assign((size_t)NPOS, idle);
-      f2z.assign((size_t)nsl * 4, 0.0);
-      f2anc.assign((size_t)n_ints, 0);
-      // rows of n + 1 buses (row n: idle positions); entries beyond a bus's children name the ZERO slot / the ring's zero entry
-      int32_t* child_bus = f2anc.data(); int32_t* child_ring = child_bus + (ht.n + 1) * GS_F2_CHILDREN; int32_t* nch = child_ring + (ht.n + 1) * GS_F2_CHILDREN;
-      std::fill(child_bus, child_bus + (ht.n + 1) * GS_F2_CHILDREN, SL_ZERO);
-      std::fill(child_ring, child_ring + (ht.n + 1) * GS_F2_CHILDREN, ring_zero);
-      int32_t* pos_tab = f2anc.data() + pos_off;
-      std::vector<int> level_of(ht.n, 0);
-      for (int lv = 0; lv < ht.n_levels; ++lv) for (int t = ht.lvl_ptr[lv]; t < ht.lvl_ptr[lv + 1]; ++t) level_of[ht.lvl_bus[t]] = lv;
-      auto ring_of = [&](int i) { return (level_of[i] & 1) * maxw + ht.lvl_pos[i]; };
-      for (int i = 0; i < ht.n; ++i) {
-        nch[i] = ht.child_ptr[i + 1] - ht.child_ptr[i];
-        for (int q = ht.child_ptr[i]; q < ht.child_ptr[i + 1]; ++q) {
-          const int c = ht.child_idx[q];
-          child_bus[i * GS_F2_CHILDREN + (q - ht.child_ptr[i])] = c; child_ring[i * GS_F2_CHILDREN + (q - ht.child_ptr[i])] = ring_of(c);
-        }
-        if (ht.lvl_pos[i] >= 0) {
-          const int pos = ht.fbs_parent_pos[i];
-          f2z[4 * (size_t)i] = ht.G[pos]; f2z[4 * (size_t)i + 1] = ht.B[pos]; f2z[4 * (size_t)i + 2] = ht.Gd[i]; f2z[4 * (size_t)i + 3] = ht.Bd[i];
-        }
-      }
-      for (int p = 0; p < NPOS; ++p) { pos_tab[4 * p] = SL_DUMMY; pos_tab[4 * p + 1] = SL_ONE; pos_tab[4 * p + 2] = 0; pos_tab[4 * p + 3] = 0; }
-      for (int w = 0; w < NW; ++w)
-        for (int j = 0; j < (int)mine[w].size(); ++j) {
-          int grp_maxch = 0;
-          for (int i : mine[w][j]) if (i >= 0) grp_maxch = std::max(grp_maxch, ht.child_ptr[i + 1] - ht.child_ptr[i]);
-          for (int hh = 0; hh < HV; ++hh) {
-            const int p = (w * HV + hh) * NI + j;
-            GsF2Rec& r = f2recs[p];
-            r.level = mine_lv[w][j]; r.pad1 = grp_maxch;        // most children of the group's buses
-            const int i = mine[w][j][hh];
-            if (i < 0) continue;
-            const int fp = ht.fbs_parent[i];
-            r.bus = i; r.parent = fp; r.flags = 1 | (fp == ht.slack ? 2 : 0); r.last = i;
-            pos_tab[4 * p] = i; pos_tab[4 * p + 1] = fp; pos_tab[4 * p + 2] = ring_of(i); pos_tab[4 * p + 3] = fp == ht.slack ? 0 : ring_of(fp);
-            f2_devices(r, i);
-          }
-        }
-    }
-  }
-
-  // -- Newton-Raphson on a meshed feeder: the block LU as rows of lane items (mesh_schedule.h), 8 instances per workgroup
-  std::vector<int32_t> mesh_items, mesh_rowinfo;
-  if (h->solve_kernel == 1 && !ht.is_forest) {
-    std::string& why = h->mesh_why;
-    const int NW = GS_F2M_WAVES, NI = GS_F2M_ITEMS, IW = GS_F2S_IW, HV = 64 / IW;
-    bool all_pq = true;
-    for (int i = 0; i < ht.n; ++i) if (i != ht.slack && !(ht.th_free[i] && ht.vm_free[i])) all_pq = false;
-    GsF2Tables& F = h->F2;
-    MeshSchedule S;
-    if (getenv("GS_NO_FLOW2") || getenv("GS_NO_MESH2")) why = "disabled by GS_NO_FLOW2 / GS_NO_MESH2";
-    else if (cfg->jacobian_mode != GS_JACOBIAN_EXACT) why = "as-coded Jacobian";
-    else if (!all_pq) why = "a bus other than the slack is not a PQ bus";
-    else if (ht.fixed_v[ht.slack] == 0) why = "no typed slack bus";
-    else if (max_dev > 2) why = "more than two devices of a kind at one bus";
-    else if (ht.n < 2 || ht.m < 1) why = "trivial network";
-    else {
-      const int off_tile = (int)up16((size_t)nsl * (IW + 1) * 16);          // where f2_layout puts the region (below)
-      // message units that leave room for a second workgroup on the CU: 80 KB less everything else the workgroup keeps in LDS
-      // (an estimate: the Ybus tables' size is known only from the schedule; f2_layout below decides)
-      const size_t fixed = up16((size_t)nsl * (IW + 1) * 16) + (size_t)6 * 16 * IW + (size_t)NW * 16 * 16 * IW + (size_t)nsl * IW * 8 +
-                           (size_t)(ht.nnz + 8) * 8 + (size_t)(ht.nnz + nsl + 4) * 16 + 4096;
-      const int unit_budget = fixed < 80 * 1024 ? (int)((80 * 1024 - fixed) / (16 * IW)) : 1;
-      gs_mesh_schedule(ht, NW, NI, IW, off_tile, (IW + 1) * 16, GS_MESH_ACC, unit_budget, S);
-      if (!S.ok) why = S.why;
-    }
-    if (why.empty()) {
-      // ints staged at off_anc: every bus's neighbour list; doubles at off_z: the Ybus entries of the pairs, then of the diagonal per slot
-      size_t off = f2_layout(F, NW, IW, (size_t)S.region_bytes, S.adj_ent.size(), 0, S.ytab.size() * sizeof(double));
-      F.off_scr = (int32_t)off; off += (size_t)NW * 16 * 16 * IW;           // exchange scratch: 16 units per wave
-      F.mesh_off_p = (int32_t)off; off += (size_t)nsl * IW * sizeof(double);   // P_spec by voltage slot
-      F.lds_bytes = (int32_t)off;
-      if (off > 160 * 1024) why = "LDS tables do not fit";
-    }
-    if (why.empty()) {
-      h->nrm = true; h->f2_small = false; h->f2_iw = IW; h->f2_nw = NW; h->f2_npos = NW * HV * NI;
-      // ---- iteration 0 as a matrix product (GsF2Tables::mesh_w): the flat-start Jacobian, inverted once on the host
-      if (!getenv("GS_NR_NO_FLAT") && ht.n <= 128) {
-        std::vector<double> wt;
-        if (flat_newton_map(ht, 16, 32, wt)) {
-          { const int rcw = dev_upload(h, &F.mesh_w, wt); if (rcw) return bail(rcw); }
-          F.mesh_w_steps = 32; F.mesh_slack = ht.slack;
-        }
-      }
-      h->mesh_levels = S.n_levels; h->mesh_rows = S.n_rows; h->mesh_units = S.msg_units; h->mesh_messages = S.n_messages; h->mesh_accs = S.n_accumulators;
-      F.n_jump = 0; F.n_levels = S.n_levels; F.pos_off = 0; F.n_anc_ints = (int32_t)S.adj_ent.size(); F.ring_zero = 0;
-      F.mesh_nz = (int32_t)S.ytab.size(); F.mesh_pairs = S.n_pairs;
-      f2anc = S.adj_ent; f2z = S.ytab;
-      GsF2Rec idle{}; idle.bus = SL_DUMMY; idle.parent = SL_ONE; idle.last = SL_DUMMY; idle.level = -1;
-      f2recs.assign((size_t)NW * HV * NI, idle);
-      for (int w = 0; w < NW; ++w) for (int j = 0; j < NI; ++j) for (int hh = 0; hh < HV; ++hh) {
-        const GsMeshItem& it = S.items[((size_t)w * NI + j) * HV + hh];
-        if (!(it.flags & GS_MESH_F_PIVOT)) continue;
-        GsF2Rec& r = f2recs[((size_t)w * HV + hh) * NI + j];        // position of (wave, sub-group, row) in the frame's numbering
-        r.bus = it.bus; r.parent = SL_ONE; r.flags = 1; r.last = it.bus; r.level = S.rowinfo[((size_t)w * NI + j) * 4];
-        f2_devices(r, it.bus);
-      }
-      mesh_items = S.packed; mesh_rowinfo = S.rowinfo_packed;
-    }
-  }
-
-  // ---- level schedule of the sparse block LU for this handle's W waves (kernels_solve.hip, linsolve_lu) ----
-  std::vector<int32_t> lu_a_ptr, lu_a, lu_b_ptr, lu_b, lu_c_ptr, lu_c, lu_r_ptr, lu_r;
-  if (ht.has_lu) {
-    const int NL = ht.lu_n_levels, Wn = h->W;
-    std::vector<std::vector<std::vector<int32_t>>> A(Wn, std::vector<std::vector<int32_t>>(NL)), Bs(Wn, std::vector<std::vector<int32_t>>(NL)),
-        Cs(Wn, std::vector<std::vector<int32_t>>(NL)), Rs(Wn, std::vector<std::vector<int32_t>>(NL));
-    for (int L = 0; L < NL; ++L) {
-      // phase A: one item per (pivot, neighbour), plus one per pivot for the singularity test; dealt round-robin
-      int turn = 0;
-      std::map<int32_t, std::vector<std::pair<int32_t, int32_t>>> tgt;        // target code -> updates
-      for (int t = 0; t < ht.lu_n_piv; ++t) {
-        if (ht.lu_piv_level[t] != L) continue;
-        const int k = ht.lu_piv_bus[t];
-        { auto& a = A[turn++ % Wn][L]; a.push_back(k); a.push_back(-1); }
-        for (int q = ht.lu_nb_ptr[t]; q < ht.lu_nb_ptr[t + 1]; ++q) {
-          auto& a = A[turn++ % Wn][L]; a.push_back(k); a.push_back(ht.lu_nb_jk[q]);
-          tgt[-(1 + ht.n + ht.lu_nb_bus[q])].push_back({ht.lu_nb_jk[q], k});          // r_i -= (A_ik D_k^-1) r_k
-        }
-        for (int q = ht.lu_pair_ptr[t]; q < ht.lu_pair_ptr[t + 1]; ++q) tgt[ht.lu_pair_ij[q]].push_back({ht.lu_pair_ik[q], ht.lu_pair_kj[q]});
-      }
-      // phase B: targets dealt to the wave with the fewest updates so far in this level
-      std::vector<int> load(Wn, 0);
-      std::vector<std::pair<int32_t, std::vector<std::pair<int32_t, int32_t>>>> order(tgt.begin(), tgt.end());
-      std::stable_sort(order.begin(), order.end(), [](const auto& x, const auto& y) { return x.second.size() > y.second.size(); });
-      for (auto& e : order) {
-        int w = 0;
-        for (int v = 1; v < Wn; ++v) if (load[v] < load[w]) w = v;
-        load[w] += (int)e.second.size() + 1;
-        auto& b = Bs[w][L];
-        b.push_back(e.first); b.push_back((int32_t)e.second.size());
-        for (auto& u : e.second) { b.push_back(u.first); b.push_back(u.second); }
-        if (e.first < -ht.n) {      // the right-hand-side records alone: all iteration 0 needs (GsTables::lu_flat)
-          auto& rr = Rs[w][L];
-          rr.push_back(e.first); rr.push_back((int32_t)e.second.size());
-          for (auto& u : e.second) { rr.push_back(u.first); rr.push_back(u.second); }
-        }
-      }
-      // phase C: the level's pivots, round-robin
-      int tc = 0;
-      for (int t = 0; t < ht.lu_n_piv; ++t) if (ht.lu_piv_level[t] == L) Cs[tc++ % Wn][L].push_back(t);
-    }
-    auto flatten = [&](std::vector<std::vector<std::vector<int32_t>>>& X, std::vector<int32_t>& ptr, std::vector<int32_t>& flat, int unit) {
-      for (int w = 0; w < Wn; ++w) {
-        for (int L = 0; L < NL; ++L) { ptr.push_back((int32_t)flat.size() / unit); flat.insert(flat.end(), X[w][L].begin(), X[w][L].end()); }
-        ptr.push_back((int32_t)flat.size() / unit);
-      }
-    };
-    flatten(A, lu_a_ptr, lu_a, 2); flatten(Bs, lu_b_ptr, lu_b, 1); flatten(Cs, lu_c_ptr, lu_c, 1); flatten(Rs, lu_r_ptr, lu_r, 1);
-  }
-
-  // ---- tables ----
+  // ---- uploads (the table arena packs them in this order) ----
+  if (!h->mesh_w.empty() && (rc = dev_upload(h, &h->F2.mesh_w, h->mesh_w))) return bail(rc);
   GsTables& T = h->T;
-  T.n = n; T.m = m; T.nnz = ht.nnz; T.n_levels = ht.n_levels;
+  T.n = h->n; T.m = h->m; T.nnz = ht.nnz; T.n_levels = ht.n_levels;
   T.n_loads = h->n_loads; T.n_gens = h->n_gens; T.n_bats = h->n_bats;
   T.lu_n_piv = ht.lu_n_piv; T.lu_n_slots = ht.lu_n_slots; T.lu_n_orig = ht.lu_n_orig; T.lu_n_levels = ht.lu_n_levels;
   T.dn_N = ht.dn_N;
-  int rc = 0;
 #define UP(field, vec) if ((rc = dev_upload(h, &T.field, ht.vec))) return bail(rc)
   UP(ell_col, ell_col); UP(ell_G, ell_G); UP(ell_B, ell_B); UP(rem_ptr, rem_ptr); UP(rem_col, rem_col);
   UP(rem_G, rem_G); UP(rem_B, rem_B);
@@ -1181,9 +639,9 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
   UP(th_free, th_free); UP(vm_free, vm_free); UP(v_set, v_set); UP(fixed_v, fixed_v);
   UP(lvl_ptr, lvl_ptr); UP(lvl_bus, lvl_bus); UP(parent, parent); UP(parent_pos, parent_pos);
   UP(child_ptr, child_ptr); UP(child_idx, child_idx); UP(lvl_pos, lvl_pos);
-  if ((rc = dev_upload(h, &T.winj, winj)) || (rc = dev_upload(h, &T.wi_ptr, wi_ptr))) return bail(rc);
-  if ((rc = dev_upload(h, &T.wbus, wbus)) || (rc = dev_upload(h, &T.wb_ptr, wb_ptr))) return bail(rc);
-  if ((rc = dev_upload(h, &T.witems, witems)) || (rc = dev_upload(h, &T.wl_ptr, wl_ptr)) || (rc = dev_upload(h, &T.ovf_slot, ovf_slot))) return bail(rc);
+  if ((rc = dev_upload(h, &T.winj, h->winj)) || (rc = dev_upload(h, &T.wi_ptr, h->wi_ptr))) return bail(rc);
+  if ((rc = dev_upload(h, &T.wbus, h->wbus)) || (rc = dev_upload(h, &T.wb_ptr, h->wb_ptr))) return bail(rc);
+  if ((rc = dev_upload(h, &T.witems, h->witems)) || (rc = dev_upload(h, &T.wl_ptr, h->wl_ptr)) || (rc = dev_upload(h, &T.ovf_slot, h->ovf_slot))) return bail(rc);
   T.max_level_width = ht.max_level_width;
   UP(fbs_parent, fbs_parent); UP(fbs_parent_pos, fbs_parent_pos);
   UP(lfrom, lfrom); UP(lto, lto); UP(lyr, lyr); UP(lyi, lyi); UP(lrating, lrating); UP(lrating_inv, lrating_inv);
@@ -1191,228 +649,41 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
   UP(lu_nb_jk, lu_nb_jk); UP(lu_pair_ptr, lu_pair_ptr); UP(lu_pair_ik, lu_pair_ik); UP(lu_pair_kj, lu_pair_kj);
   UP(lu_pair_ij, lu_pair_ij); UP(lu_orig_slot, lu_orig_slot); UP(lu_orig_i, lu_orig_i); UP(lu_orig_j, lu_orig_j);
   UP(lu_orig_pos, lu_orig_pos);
-  if ((rc = dev_upload(h, &T.lu_a_ptr, lu_a_ptr)) || (rc = dev_upload(h, &T.lu_a, lu_a)) || (rc = dev_upload(h, &T.lu_b_ptr, lu_b_ptr)) ||
-      (rc = dev_upload(h, &T.lu_b, lu_b)) || (rc = dev_upload(h, &T.lu_c_ptr, lu_c_ptr)) || (rc = dev_upload(h, &T.lu_c, lu_c)) ||
-      (rc = dev_upload(h, &T.lu_r_ptr, lu_r_ptr)) || (rc = dev_upload(h, &T.lu_r, lu_r))) return bail(rc);
+  if ((rc = dev_upload(h, &T.lu_a_ptr, h->lu_a_ptr)) || (rc = dev_upload(h, &T.lu_a, h->lu_a)) || (rc = dev_upload(h, &T.lu_b_ptr, h->lu_b_ptr)) ||
+      (rc = dev_upload(h, &T.lu_b, h->lu_b)) || (rc = dev_upload(h, &T.lu_c_ptr, h->lu_c_ptr)) || (rc = dev_upload(h, &T.lu_c, h->lu_c)) ||
+      (rc = dev_upload(h, &T.lu_r_ptr, h->lu_r_ptr)) || (rc = dev_upload(h, &T.lu_r, h->lu_r))) return bail(rc);
   UP(dn_th_idx, dn_th_idx); UP(dn_vm_idx, dn_vm_idx);
   UP(bl_ptr, bl_ptr); UP(bl_idx, bl_idx); UP(bg_ptr, bg_ptr); UP(bg_idx, bg_idx); UP(bb_ptr, bb_ptr); UP(bb_idx, bb_idx);
   UP(load_base, load_base); UP(load_q, load_q); UP(gen_kind, gen_kind); UP(gen_cap, gen_cap); UP(gen_p0, gen_p0);
   UP(gen_p1, gen_p1); UP(gen_p2, gen_p2); UP(bat_cap, bat_cap); UP(bat_rating, bat_rating); UP(bat_eff, bat_eff);
 #undef UP
-  // ---- dense block LU on the matrix cores (kernels_dense.hip): unknown numbering, Jacobian blocks by column panel, scratch ----
-  if (h->solve_kernel == 7) {
+  if (h->solve == SolveMember::nr_dense_mfma) {
     GsDenseArgs& D = h->DA;
-    std::vector<int32_t> act_bus, act_of(ht.n, -1);
-    for (int i = 0; i < ht.n; ++i) if (ht.th_free[i] || ht.vm_free[i]) { act_of[i] = (int32_t)act_bus.size(); act_bus.push_back(i); }
-    const int na = (int)act_bus.size(), NB = (2 * na + 63) / 64;
-    // (panel by panel, block row by block row inside a panel: the panel form reads a panel's range, the block-row form a block's)
-    std::vector<int32_t> ent_ptr(NB + 1, 0), bent_ptr((size_t)NB * NB + 1, 0), ent;
-    std::vector<GsDenseEntry> bent;
-    for (int pnl = 0; pnl < NB; ++pnl) {
-      ent_ptr[pnl] = (int32_t)ent.size() / 3;
-      for (int blk = 0; blk < NB; ++blk) {
-        bent_ptr[(size_t)pnl * NB + blk] = (int32_t)ent.size() / 3;
-        for (int i = 0; i < ht.n; ++i) {
-          if (act_of[i] < 0 || (2 * act_of[i]) / 64 != blk) continue;
-          for (int q = ht.row_ptr[i]; q < ht.row_ptr[i + 1]; ++q) {
-            const int j = ht.col[q];
-            if (act_of[j] < 0 || (2 * act_of[j]) / 64 != pnl) continue;
-            ent.push_back(i); ent.push_back(j); ent.push_back(q);
-            GsDenseEntry e{};
-            e.ib = i; e.jb = j;
-            e.dst = ((2 * act_of[i] - 64 * blk) * 66 + (2 * act_of[j] - 64 * pnl)) | (ht.th_free[i] ? 1 << 16 : 0) | (ht.vm_free[i] ? 1 << 17 : 0) |
-                    (ht.th_free[j] ? 1 << 18 : 0) | (ht.vm_free[j] ? 1 << 19 : 0);
-            e.g = i == j ? ht.Gd[i] : ht.G[q]; e.b = i == j ? ht.Bd[i] : ht.B[q];
-            bent.push_back(e);
-          }
-        }
-      }
-    }
-    if (bent.empty()) bent.push_back(GsDenseEntry{});
-    ent_ptr[NB] = bent_ptr[(size_t)NB * NB] = (int32_t)ent.size() / 3;
-    D.n = ht.n; D.na = na; D.NB = NB; D.max_it = cfg->max_iterations; D.jacobian_exact = 1; D.rows_total = h->R.total;
-    D.tol = cfg->tolerance; D.alpha = cfg->acceleration_factor;
-    if ((rc = dev_upload(h, &D.act_bus, act_bus)) || (rc = dev_upload(h, &D.act_of, act_of)) || (rc = dev_upload(h, &D.ent_ptr, ent_ptr)) ||
-        (rc = dev_upload(h, &D.ent, ent)) || (rc = dev_upload(h, &D.bent_ptr, bent_ptr)) || (rc = dev_upload(h, &D.bent, bent))) return bail(rc);
+    if ((rc = dev_upload(h, &D.act_bus, h->act_bus)) || (rc = dev_upload(h, &D.act_of, h->act_of)) || (rc = dev_upload(h, &D.ent_ptr, h->ent_ptr)) ||
+        (rc = dev_upload(h, &D.ent, h->ent)) || (rc = dev_upload(h, &D.bent_ptr, h->bent_ptr)) || (rc = dev_upload(h, &D.bent, h->bent))) return bail(rc);
     D.row_ptr = T.row_ptr; D.col = T.col; D.G = T.G; D.Bv = T.Bv; D.Gd = T.Gd; D.Bd = T.Bd;
     D.th_free = T.th_free; D.vm_free = T.vm_free; D.fixed_v = T.fixed_v; D.v_set = T.v_set;
-    D.R = h->R;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    // persistent grid, instances strided over it.  Block-row form: two block buffers in LDS, two workgroups per CU; panel form (GS_DENSE_PANEL=1
-    // in a build with the experiments): the whole 64-column panel in LDS, one workgroup per CU
-    const size_t NP = (size_t)64 * NB;
-    h->dense_blockrow = !GS_EXPERIMENT_ENV("GS_DENSE_PANEL");
-    if (h->dense_blockrow) {
-      h->dense_grid = std::max(1, std::min(h->B, 2 * cus));
-      h->dense_lds = ((size_t)2 * 64 * 66 + NP + (size_t)8 * ((ht.n + 1) & ~1) + 8) * sizeof(double);
-    } else {
-      h->dense_grid = std::max(1, std::min(h->B, cus));
-      h->dense_lds = (NP * 66 + NP + (size_t)8 * ((ht.n + 1) & ~1) + 2 * 528 + 8) * sizeof(double);
-    }
-    if (h->dense_lds > 160 * 1024 - 256) return bail(fail(nullptr, GS_E_TOPOLOGY, "dense_mfma: %zu bytes of LDS needed", h->dense_lds));
-    double* scratch = nullptr;
-    if ((rc = dev_alloc(h, &scratch, (size_t)h->dense_grid * NB * NB * 64 * 64))) return bail(rc);
-    D.scratch = scratch;
-    // the flat-start Jacobian is the same for every instance: factor it once, here, with the solver kernel itself
-    // (bit-identical to what iteration 0 of every solve would compute; GS_DENSE_NO_FLAT=1 keeps it per solve)
-    if (!getenv("GS_DENSE_NO_FLAT")) {
-      double* flat = nullptr;
-      if ((rc = dev_alloc(h, &flat, (size_t)NB * NB * 64 * 64 + 8))) return bail(rc);
-      GsDenseArgs once = D;
-      once.flat = flat; once.mode = 1; once.max_it = 1;
-      GS_DENSE_LAUNCH(h, 1, once, 1);
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
-        return bail(fail(nullptr, GS_E_HIP, "dense_mfma: factorisation of the flat-start Jacobian failed"));
-      D.flat = flat;
-      // ---- and its inverse, for iteration 0 as one product (GsDenseArgs::jinv_t): the same entries as the kernel's assembly
-      // (power_flow.py:243-287, exact sign; fixed components and padding unknowns: identity rows and columns), flat start
-      if (h->dense_blockrow) {
-        const int n_ = ht.n, NPd = 64 * NB;
-        std::vector<double> v0(n_, 1.0), Pc(n_, 0.0), Qc(n_, 0.0), Jm((size_t)NPd * NPd, 0.0), Ji((size_t)NPd * NPd, 0.0);
-        for (int i = 0; i < n_; ++i) if (ht.fixed_v[i]) v0[i] = ht.v_set[i];
-        for (int i = 0; i < n_; ++i)
-          for (int q = ht.row_ptr[i]; q < ht.row_ptr[i + 1]; ++q) {
-            const int j = ht.col[q];
-            Pc[i] += v0[i] * v0[j] * ht.G[q]; Qc[i] -= v0[i] * v0[j] * ht.B[q];
-          }
-        for (int u = 0; u < NPd; ++u) Jm[(size_t)u * NPd + u] = 1.0;              // padding / fixed components
-        for (int i = 0; i < n_; ++i) {
-          const int a = act_of[i];
-          if (a < 0) continue;
-          const bool thi = ht.th_free[i] != 0, vfi = ht.vm_free[i] != 0;
-          const double vi = v0[i], vvb = vi * vi * ht.Bd[i];
-          Jm[(size_t)(2 * a) * NPd + 2 * a] = thi ? (-Qc[i] - vvb) : 1.0;
-          Jm[(size_t)(2 * a) * NPd + 2 * a + 1] = (thi && vfi) ? (Pc[i] / vi + vi * ht.Gd[i]) : 0.0;
-          Jm[(size_t)(2 * a + 1) * NPd + 2 * a] = (thi && vfi) ? (Pc[i] - vi * vi * ht.Gd[i]) : 0.0;
-          Jm[(size_t)(2 * a + 1) * NPd + 2 * a + 1] = vfi ? (Qc[i] / vi - vi * ht.Bd[i]) : 1.0;
-          for (int q = ht.row_ptr[i]; q < ht.row_ptr[i + 1]; ++q) {
-            const int j = ht.col[q];
-            if (j == i || act_of[j] < 0) continue;
-            const int aj = act_of[j];
-            const bool thj = ht.th_free[j] != 0, vfj = ht.vm_free[j] != 0;
-            const double aa = vi * v0[j], gs_bc = -ht.B[q] * aa, gc_bs = ht.G[q] * aa;
-            if (thi && thj) Jm[(size_t)(2 * a) * NPd + 2 * aj] = gs_bc;
-            if (thi && vfj) Jm[(size_t)(2 * a) * NPd + 2 * aj + 1] = gc_bs / v0[j];
-            if (vfi && thj) Jm[(size_t)(2 * a + 1) * NPd + 2 * aj] = -gc_bs;
-            if (vfi && vfj) Jm[(size_t)(2 * a + 1) * NPd + 2 * aj + 1] = gs_bc / v0[j];
-          }
-        }
-        for (int u = 0; u < NPd; ++u) Ji[(size_t)u * NPd + u] = 1.0;
-        bool ok = true;
-        for (int c = 0; c < NPd && ok; ++c) {
-          int pr = c;
-          for (int r = c + 1; r < NPd; ++r) if (std::fabs(Jm[(size_t)r * NPd + c]) > std::fabs(Jm[(size_t)pr * NPd + c])) pr = r;
-          const double pv = Jm[(size_t)pr * NPd + c];
-          if (!(pv != 0.0) || !std::isfinite(pv)) { ok = false; break; }
-          if (pr != c)
-            for (int k = 0; k < NPd; ++k) { std::swap(Jm[(size_t)pr * NPd + k], Jm[(size_t)c * NPd + k]); std::swap(Ji[(size_t)pr * NPd + k], Ji[(size_t)c * NPd + k]); }
-          const double ip = 1.0 / pv;
-          for (int k = 0; k < NPd; ++k) { Jm[(size_t)c * NPd + k] *= ip; Ji[(size_t)c * NPd + k] *= ip; }
-          for (int r = 0; r < NPd; ++r) {
-            if (r == c) continue;
-            const double f = Jm[(size_t)r * NPd + c];
-            if (f == 0.0) continue;
-            for (int k = 0; k < NPd; ++k) { Jm[(size_t)r * NPd + k] -= f * Jm[(size_t)c * NPd + k]; Ji[(size_t)r * NPd + k] -= f * Ji[(size_t)c * NPd + k]; }
-          }
-        }
-        if (ok) {
-          std::vector<double> jt((size_t)NPd * NPd);
-          for (int u = 0; u < NPd; ++u)
-            for (int c = 0; c < NPd; ++c) jt[(size_t)c * NPd + u] = Ji[(size_t)u * NPd + c];
-          if ((rc = dev_upload(h, &D.jinv_t, jt))) return bail(rc);
-        }
-      }
-    }
+    const size_t blocks = (size_t)D.NB * D.NB * 64 * 64;
+    if ((rc = dev_alloc(h, &D.scratch, (size_t)h->dense_grid * blocks)) || (h->dense_flat && (rc = dev_alloc(h, &D.flat, blocks + 8))) ||
+        (!h->jinv_t.empty() && (rc = dev_upload(h, &D.jinv_t, h->jinv_t)))) return bail(rc);
   }
-  // a step as two half-grid launches on two streams: only where each half still gives every CU a workgroup
-  h->lean = (h->flow2 || h->nr2 || h->nrm) && !getenv("GS_EAGER_ROWS");
-  if ((h->flow2 || h->nr2 || h->nrm) && 2 * (size_t)h->F2.lds_bytes <= 160 * 1024 && !getenv("GS_NO_SPLIT") && h->groups * (64 / h->f2_iw) >= 512 &&
-      h->groups >= 2) {
-    if (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess)
-      return bail(fail(nullptr, GS_E_HIP, "second step stream: hipStreamCreate / hipEventCreate failed"));
-    h->split_ok = true;
-  }
-
-  if (h->nrm) {
-    if ((rc = dev_upload(h, &h->F2.mesh_items, mesh_items)) || (rc = dev_upload(h, &h->F2.mesh_rowinfo, mesh_rowinfo))) return bail(rc);
-  }
-  if (h->flow2 || h->nr2 || h->nrm) {
-    // buses with a voltage set point, for the kernels' flat start (the slack; the first entry travels inside the argument block)
-    std::vector<int32_t> fs_slot; std::vector<double> fs_val;
-    for (int i = 0; i < ht.n; ++i) if (ht.fixed_v[i]) { fs_slot.push_back(i); fs_val.push_back(ht.v_set[i]); }
-    h->F2.n_fixed = (int32_t)fs_slot.size();
-    h->F2.fixed_slot0 = fs_slot.empty() ? 0 : fs_slot[0]; h->F2.fixed_val0 = fs_val.empty() ? 1.0 : fs_val[0];
-    h->F2.fixed_slot = nullptr; h->F2.fixed_val = nullptr;
-    if ((rc = dev_upload(h, &h->F2.recs, f2recs)) || (rc = dev_upload(h, &h->F2.anc, f2anc)) || (rc = dev_upload(h, &h->F2.zbus, f2z)) ||
-        (fs_slot.size() > 1 && ((rc = dev_upload(h, &h->F2.fixed_slot, fs_slot)) || (rc = dev_upload(h, &h->F2.fixed_val, fs_val))))) return bail(rc);
-  }
-
-  // ---- configs ----
-  h->SC.tolerance = cfg->tolerance; h->SC.alpha = cfg->acceleration_factor;
-  h->SC.max_iterations = cfg->max_iterations; h->SC.jacobian_exact = (cfg->jacobian_mode == GS_JACOBIAN_EXACT);
-  GsEnvCfg& E = h->EC;
-  E.timestep = cfg->timestep; E.v_min = cfg->v_min; E.v_max = cfg->v_max; E.f_min = cfg->f_min; E.f_max = cfg->f_max;
-  E.safety_penalty = cfg->safety_penalty; E.H = cfg->inertia_H; E.D = cfg->damping_D; E.f0 = cfg->f_nominal;
-  E.power_base = cfg->power_base; E.inv_power_base = 1.0 / cfg->power_base; E.episode_length = cfg->episode_length; E.stochastic_loads = cfg->stochastic_loads; E.fbs_warm_start = cfg->fbs_warm_start;
-  E.weather_variation = cfg->weather_variation; E.first_instance = first_instance;
-  // sum(load.active_power) in list order, starting from 0 like python's sum() (grid_env.py:744)
-  h->total_load = 0.0;
-  for (int l = 0; l < h->n_loads; ++l) h->total_load += topo->load_base[l];
-
-  // ---- layout maps ----
-  std::vector<int32_t> mo, mvm(n), mva(n), mfl(m), mld(m), mp(n), mq(n), mact(h->action_dim), mst;
-  std::vector<double> cst;
-  for (int i = 0; i < n; ++i) { mo.push_back(R.VM + i); mo.push_back(R.VA + i); }          // grid_env.py:758-759
-  for (int k = 0; k < m; ++k) { mo.push_back(R.FLOW + k); mo.push_back(R.ENVLOAD + k); }   // :762-763
-  mo.push_back(R.FREQ);                                                                     // :766
-  for (int l = 0; l < h->n_loads; ++l) {                                                    // :769-770 (static values)
-    cst.push_back(ht.load_base[l]); mo.push_back(-(int)cst.size());
-    cst.push_back(ht.load_q[l]); mo.push_back(-(int)cst.size());
-  }
-  for (int g = 0; g < h->n_gens; ++g) mo.push_back(R.GENP + g);                              // :773-777
-  for (int q = 0; q < h->n_bats; ++q) { mo.push_back(R.SOC + q); mo.push_back(R.BATP + q); } // :780-781
-  for (int i = 0; i < n; ++i) { mvm[i] = R.VM + i; mva[i] = R.VA + i; mp[i] = R.P + i; mq[i] = R.Q + i; }
-  for (int k = 0; k < m; ++k) { mfl[k] = R.FLOW + k; mld[k] = R.LOAD + k; }
-  for (int a = 0; a < h->action_dim; ++a) mact[a] = R.ACT + a;
-  for (int s : {R.TIME, R.STEP, R.VIOL, R.TOTLOSS, R.EPREW, R.FREQ, R.IRR, R.WIND, R.TEMP, R.CLOUD, R.SEEDLO, R.SEEDHI}) mst.push_back(s);
-  for (int q = 0; q < h->n_bats; ++q) mst.push_back(R.SOC + q);
-  for (int q = 0; q < h->n_bats; ++q) mst.push_back(R.BATP + q);
-  for (int g = 0; g < h->n_gens; ++g) mst.push_back(R.CURT + g);
-  for (int i = 0; i < n; ++i) mst.push_back(R.VM + i);
-  for (int i = 0; i < n; ++i) mst.push_back(R.VA + i);
-  for (int k = 0; k < m; ++k) mst.push_back(R.FLOW + k);
-  for (int k = 0; k < m; ++k) mst.push_back(R.ENVLOAD + k);
-  {   // the constants of an observation form one block (the static load powers); the step kernel skips it
-    int c0 = 0;
-    while (c0 < (int)mo.size() && mo[c0] >= 0) ++c0;
-    int c1 = c0;
-    while (c1 < (int)mo.size() && mo[c1] < 0) ++c1;
-    bool one_block = true;
-    for (int c = c1; c < (int)mo.size(); ++c) one_block = one_block && mo[c] >= 0;
-    if (one_block && !GS_EXPERIMENT_ENV("GS_PACK_ALL_COLUMNS")) { h->obs_skip0 = c0; h->obs_skip1 = c1; }
-  }
-  if ((int)mo.size() != h->obs_dim || (int)mst.size() != h->state_dim)
-    return bail(fail(nullptr, GS_E_INVALID, "internal: layout map size mismatch"));
-  { const double* q = nullptr; if ((rc = dev_upload(h, &q, cst))) return bail(rc); h->d_cst = const_cast<double*>(q); }
-  if ((rc = upload_map(h, &h->map_obs, mo)) || (rc = upload_map(h, &h->map_vm, mvm)) || (rc = upload_map(h, &h->map_va, mva)) ||
-      (rc = upload_map(h, &h->map_flow, mfl)) || (rc = upload_map(h, &h->map_load, mld)) || (rc = upload_map(h, &h->map_p, mp)) ||
-      (rc = upload_map(h, &h->map_q, mq)) || (rc = upload_map(h, &h->map_act, mact)) || (rc = upload_map(h, &h->map_state, mst)))
+  if (h->step == StepMember::nr_mesh2 &&
+      ((rc = dev_upload(h, &h->F2.mesh_items, h->mesh_items)) || (rc = dev_upload(h, &h->F2.mesh_rowinfo, h->mesh_rowinfo)))) return bail(rc);
+  if (h->second_gen() &&
+      ((rc = dev_upload(h, &h->F2.recs, h->f2recs)) || (rc = dev_upload(h, &h->F2.anc, h->f2anc)) || (rc = dev_upload(h, &h->F2.zbus, h->f2z)) ||
+       (h->fs_slot.size() > 1 && ((rc = dev_upload(h, &h->F2.fixed_slot, h->fs_slot)) || (rc = dev_upload(h, &h->F2.fixed_val, h->fs_val)))))) return bail(rc);
+  { const double* q = nullptr; if ((rc = dev_upload(h, &q, h->cst))) return bail(rc); h->d_cst = const_cast<double*>(q); }
+  if ((rc = upload_map(h, &h->map_obs, h->mo)) || (rc = upload_map(h, &h->map_vm, h->mvm)) || (rc = upload_map(h, &h->map_va, h->mva)) ||
+      (rc = upload_map(h, &h->map_flow, h->mfl)) || (rc = upload_map(h, &h->map_load, h->mld)) || (rc = upload_map(h, &h->map_p, h->mp)) ||
+      (rc = upload_map(h, &h->map_q, h->mq)) || (rc = upload_map(h, &h->map_act, h->mact)) || (rc = upload_map(h, &h->map_state, h->mst)) ||
+      (rc = upload_map(h, &h->rows_f, h->rf)) || (rc = upload_map(h, &h->rows_i, h->ri)) || (rc = upload_map(h, &h->rows_u, h->ru)))
     return bail(rc);
-  std::vector<int32_t> rf(SF_COUNT), ri(SI_COUNT), ru(SU_COUNT);
-  rf[SF_REWARD] = R.REWARD; rf[SF_VMAX] = R.VMAX; rf[SF_VMIN] = R.VMIN; rf[SF_LOSSES] = R.LOSSES; rf[SF_EPREW] = R.EPREW; rf[SF_MAXMIS] = R.MAXMIS;
-  ri[SI_VIOL] = R.VIOL; ri[SI_STEP] = R.STEP; ri[SI_ITERS] = R.ITERS; ri[SI_STATUS] = R.STATUS;
-  ru[SU_TERM] = R.TERM; ru[SU_TRUNC] = R.TRUNC; ru[SU_CONV] = R.CONV;
-  for (int v = 0; v < 4; ++v) ru[SU_VF0 + v] = R.VFLAGS + v;
-  if ((rc = upload_map(h, &h->rows_f, rf)) || (rc = upload_map(h, &h->rows_i, ri)) || (rc = upload_map(h, &h->rows_u, ru))) return bail(rc);
 
   // ---- big buffers ----
-  const size_t slab_doubles = (size_t)h->groups * R.total * GS_LANES;
+  const size_t slab_doubles = (size_t)h->groups * h->R.total * GS_LANES;
   if ((rc = dev_alloc(h, &h->slab, slab_doubles))) return bail(rc);
   if (hipMemset(h->slab, 0, slab_doubles * sizeof(double)) != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipMemset(slab) failed"));
-  const size_t widest = std::max<size_t>({(size_t)h->obs_dim, (size_t)h->state_dim, (size_t)n, (size_t)m, (size_t)h->action_dim, 1});
+  const size_t widest = std::max<size_t>({(size_t)h->obs_dim, (size_t)h->state_dim, (size_t)h->n, (size_t)h->m, (size_t)h->action_dim, 1});
   h->in_doubles = (size_t)h->B * widest; h->out_doubles = (size_t)h->B * widest;
   if ((rc = dev_alloc(h, &h->d_in, h->in_doubles)) || (rc = dev_alloc(h, &h->d_out, h->out_doubles)) ||
       (rc = dev_alloc(h, &h->d_obs2[0], (size_t)h->Bp * h->obs_dim)) || (rc = dev_alloc(h, &h->d_obs2[1], (size_t)h->Bp * h->obs_dim))) return bail(rc);
@@ -1434,126 +705,18 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     h->hd_f = (double*)dv; h->hd_i = (int32_t*)(dv + nf); h->hd_v4 = (uint32_t*)(dv + nf + ni); h->hd_u = (uint8_t*)(dv + nf + ni + nv);
   }
 #if defined(GS_BUILD_EXPERIMENTS)
-  // ---- sparse block LU in LDS (kernels_sparse.hip): the level schedule without the split over waves, the flat-start factors ----
-  if (h->solve_kernel == 8) {
+  if (h->solve == SolveMember::nr_sparse_lds) {
     GsSparseArgs& Sp = h->SA;
-    const int NL = ht.lu_n_levels;
-    std::vector<int32_t> a_ptr{0}, a, b_ptr{0}, b_rec, b_pair, r_ptr{0}, r_rec, r_pair, c_ptr{0}, cc;
-    for (int L = 0; L < NL; ++L) {
-      std::map<int32_t, std::vector<std::pair<int32_t, int32_t>>> tgt;        // target code -> updates, as for linsolve_lu
-      for (int t = 0; t < ht.lu_n_piv; ++t) {
-        if (ht.lu_piv_level[t] != L) continue;
-        const int k = ht.lu_piv_bus[t];
-        a.push_back(k); a.push_back(-1);
-        for (int q = ht.lu_nb_ptr[t]; q < ht.lu_nb_ptr[t + 1]; ++q) {
-          a.push_back(k); a.push_back(ht.lu_nb_jk[q]);
-          tgt[-(1 + ht.n + ht.lu_nb_bus[q])].push_back({ht.lu_nb_jk[q], k});
-        }
-        for (int q = ht.lu_pair_ptr[t]; q < ht.lu_pair_ptr[t + 1]; ++q) tgt[ht.lu_pair_ij[q]].push_back({ht.lu_pair_ik[q], ht.lu_pair_kj[q]});
-        cc.push_back(t);
-      }
-      // longest records first: the lanes of one pass then carry records of similar length
-      std::vector<std::pair<int32_t, std::vector<std::pair<int32_t, int32_t>>>> order(tgt.begin(), tgt.end());
-      std::stable_sort(order.begin(), order.end(), [](const auto& x, const auto& y) { return x.second.size() > y.second.size(); });
-      for (auto& e : order) {
-        b_rec.push_back(e.first); b_rec.push_back((int32_t)e.second.size()); b_rec.push_back((int32_t)b_pair.size() / 2);
-        for (auto& u : e.second) { b_pair.push_back(u.first); b_pair.push_back(u.second); }
-        if (e.first < -ht.n) {
-          r_rec.push_back(e.first); r_rec.push_back((int32_t)e.second.size()); r_rec.push_back((int32_t)r_pair.size() / 2);
-          for (auto& u : e.second) { r_pair.push_back(u.first); r_pair.push_back(u.second); }
-        }
-      }
-      a_ptr.push_back((int32_t)a.size() / 2); b_ptr.push_back((int32_t)b_rec.size() / 3); r_ptr.push_back((int32_t)r_rec.size() / 3);
-      c_ptr.push_back((int32_t)cc.size());
-    }
-    Sp.n = ht.n; Sp.n_slots = ht.lu_n_slots; Sp.n_orig = ht.lu_n_orig; Sp.n_piv = ht.lu_n_piv; Sp.n_levels = NL;
-    Sp.max_it = cfg->max_iterations; Sp.jacobian_exact = cfg->jacobian_mode == GS_JACOBIAN_EXACT ? 1 : 0; Sp.rows_total = h->R.total;
-    Sp.tol = cfg->tolerance; Sp.alpha = cfg->acceleration_factor;
-    // one packed copy of everything the elimination chases pointers through: staged into LDS once per workgroup
-    std::vector<int32_t> ipack; std::vector<double> dpack;
-    auto addi = [&](const std::vector<int32_t>& v) { const int32_t o = (int32_t)ipack.size(); ipack.insert(ipack.end(), v.begin(), v.end()); return o; };
-    auto addd = [&](const std::vector<double>& v) { const int32_t o = (int32_t)dpack.size(); dpack.insert(dpack.end(), v.begin(), v.end()); return o; };
-    Sp.o_row_ptr = addi(ht.row_ptr); Sp.o_col = addi(ht.col); Sp.o_th_free = addi(ht.th_free); Sp.o_vm_free = addi(ht.vm_free); Sp.o_fixed_v = addi(ht.fixed_v);
-    Sp.o_piv_bus = addi(ht.lu_piv_bus); Sp.o_nb_ptr = addi(ht.lu_nb_ptr); Sp.o_nb_bus = addi(ht.lu_nb_bus); Sp.o_nb_kj = addi(ht.lu_nb_kj);
-    Sp.o_a_ptr = addi(a_ptr); Sp.o_a = addi(a); Sp.o_b_ptr = addi(b_ptr); Sp.o_b_rec = addi(b_rec); Sp.o_b_pair = addi(b_pair);
-    Sp.o_r_ptr = addi(r_ptr); Sp.o_r_rec = addi(r_rec); Sp.o_r_pair = addi(r_pair); Sp.o_c_ptr = addi(c_ptr); Sp.o_c = addi(cc);
-    Sp.od_G = addd(ht.G); Sp.od_B = addd(ht.B); Sp.od_Gd = addd(ht.Gd); Sp.od_Bd = addd(ht.Bd); Sp.od_vset = addd(ht.v_set);
-    Sp.ipack_n = (int32_t)ipack.size(); Sp.dpack_n = (int32_t)dpack.size();
-    if ((rc = dev_upload(h, &Sp.ipack, ipack)) || (rc = dev_upload(h, &Sp.dpack, dpack))) return bail(rc);
+    if ((rc = dev_upload(h, &Sp.ipack, h->ipack)) || (rc = dev_upload(h, &Sp.dpack, h->dpack))) return bail(rc);
     Sp.orig_slot = T.lu_orig_slot; Sp.orig_i = T.lu_orig_i; Sp.orig_j = T.lu_orig_j; Sp.orig_pos = T.lu_orig_pos;
-    Sp.R = h->R;
-    const size_t shared_bytes = ((((size_t)Sp.dpack_n + 1) & ~(size_t)1) * 8 + (size_t)Sp.ipack_n * 4 + 15) & ~(size_t)15;
-    Sp.wave_bytes = (int32_t)((((size_t)4 * (ht.lu_n_slots + ht.n) + (size_t)7 * ht.n) * sizeof(double) + 15) & ~(size_t)15);
-    int waves = (int)((160 * 1024 - 512 - (long long)shared_bytes) / Sp.wave_bytes);
-    if (const char* e = GS_EXPERIMENT_ENV("GS_SPARSE_LDS_WAVES")) waves = std::min(waves, atoi(e));
-    waves = std::max(0, std::min(4, waves));
-    if (waves < 1 || ht.n > 256)
-      return bail(fail(nullptr, GS_E_TOPOLOGY, "sparse_lds: the schedule (%zu bytes) and one instance (%d bytes) do not fit the LDS, or more than 256 buses", shared_bytes, Sp.wave_bytes));
-    Sp.waves = waves;
-    h->sparse_lds = shared_bytes + (size_t)waves * Sp.wave_bytes;
-    if (hipFuncSetAttribute((const void*)gs_k_nr_sparse_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(gs_k_nr_sparse_lds) failed"));
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    h->sparse_grid = std::max(1, std::min((h->B + waves - 1) / waves, cus));      // persistent: one workgroup per CU, instances strided over the wavefronts
-    // the flat-start Jacobian is the same for every instance: factor it once, here, with the solver kernel itself (GS_LU_NO_FLAT=1: off)
-    if (!getenv("GS_LU_NO_FLAT")) {
-      double* flat = nullptr;
-      if ((rc = dev_alloc(h, &flat, (size_t)4 * (ht.lu_n_slots + ht.n) + 4))) return bail(rc);
-      GsSparseArgs once = Sp;
-      once.flat_out = flat; once.mode = 1; once.max_it = 1;
-      hipLaunchKernelGGL(gs_k_nr_sparse_lds, dim3(1), dim3(64 * Sp.waves), h->sparse_lds, h->stream, once, h->slab, 1);
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
-        return bail(fail(nullptr, GS_E_HIP, "sparse_lds: factorisation of the flat-start Jacobian failed"));
-      Sp.flat = flat;
-    }
   }
 #endif
-  // Sparse block LU: iteration 0 of every solve factors the flat-start Jacobian, which is the same for every instance.  One
-  // ordinary solve of group 0, capped at one iteration, leaves those factors in the rows of lane 0; they are kept as a table
-  // of wave-uniform scalars (GsTables::lu_flat) and iteration 0 then only carries its right-hand side through
-  // (kernels_solve.hip, linsolve_lu_flat: bit-identical -- the same blocks, the same operations).  GS_LU_NO_FLAT=1: off.
-  if (h->solve_kernel == 1 && ht.lu_n_piv > 0 && !getenv("GS_LU_NO_FLAT")) {
-    double* tab = nullptr;
-    const int nblk = ht.lu_n_slots + ht.n;
-    if ((rc = dev_alloc(h, &tab, (size_t)4 * nblk + 4))) return bail(rc);
-    hipLaunchKernelGGL(gs_k_fill_rows, dim3(1), dim3(64), 0, h->stream, R.P.base, 2, ht.n, R.total, h->slab, -0.01);
-    hipLaunchKernelGGL(gs_k_fill_rows, dim3(1), dim3(64), 0, h->stream, R.Q.base, 2, ht.n, R.total, h->slab, 0.0);
-    GsSolveCfg once = h->SC; once.max_iterations = 1; once.stamps = nullptr;
-    hipLaunchKernelGGL(gs_k_nr_lu, dim3(1), dim3(64 * h->W), h->dyn_lds, h->stream, h->T, h->R, once, h->slab, 1);
-    if (ht.lu_n_slots > 0)
-      hipLaunchKernelGGL(gs_k_gather_lane, dim3((4 * ht.lu_n_slots + 255) / 256), dim3(256), 0, h->stream, R.LU, 4 * ht.lu_n_slots, 0, h->slab, tab);
-    hipLaunchKernelGGL(gs_k_gather_lane, dim3((4 * ht.n + 255) / 256), dim3(256), 0, h->stream, R.LUD, 4 * ht.n, 0, h->slab, tab + (size_t)4 * ht.lu_n_slots);
-    double status = 0.0;
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(&status, h->slab + GS_ELEM(R.STATUS, 0), sizeof status, hipMemcpyDeviceToHost) != hipSuccess)
-      return bail(fail(nullptr, GS_E_HIP, "sparse LU: factorisation of the flat-start Jacobian failed"));
-    const double flag = status == (double)GS_STATUS_SINGULAR ? 1.0 : 0.0;
-    if (hipMemcpy(tab + (size_t)4 * nblk, &flag, sizeof flag, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(h->slab, 0, (size_t)R.total * GS_LANES * sizeof(double)) != hipSuccess)      // group 0 as gs_create leaves every group
-      return bail(fail(nullptr, GS_E_HIP, "sparse LU: flat-start table"));
-    h->T.lu_flat = tab;
-  }
-  // Newton-Raphson on the second-generation frame: the constants of the flat-start elimination (GsF2Tables::nrflat), written by
-  // ONE workgroup of the step kernel itself on the zeroed state of group 0, then group 0 is cleared again.  GS_NR_NO_FLAT=1: off.
-  if ((h->nr2 || h->nrm) && h->f2_npos > 0 && !getenv("GS_NR_NO_FLAT")) {
-    double* tab = nullptr;
-    if ((rc = dev_alloc(h, &tab, (size_t)h->f2_npos * 16))) return bail(rc);
-    if (hipMemset(tab, 0, (size_t)h->f2_npos * 16 * sizeof(double)) != hipSuccess ||
-        hipMemset(h->d_in, 0, h->in_doubles * sizeof(double)) != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipMemset failed"));      // (d_in: zero actions for the capture step)
-    GsF2Tables cap = h->F2; cap.nrflat = tab; cap.nrflat_mode = 1; cap.wg_offset = 0;
-    GsPackArgs pa{}; GsFusedChecks fc{}; GsRolloutStep rsv{};
-    GsSolveCfg sc = h->SC; sc.stamps = nullptr;
-    const dim3 b2(64 * h->f2_nw);
-    const int Bc = std::min(h->B, h->f2_iw);
-    if (h->nrm) hipLaunchKernelGGL(gs_k_step_nr_mesh2, dim3(1), b2, h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc, h->EC, h->slab, Bc, h->d_in, h->total_load, pa, fc, rsv);
-    else if (h->f2_small) hipLaunchKernelGGL(gs_k_step_nr_flow2s, dim3(1), b2, h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc, h->EC, h->slab, Bc, h->d_in, h->total_load, pa, fc, rsv);
-    else hipLaunchKernelGGL(gs_k_step_nr_flow2, dim3(1), b2, h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc, h->EC, h->slab, Bc, h->d_in, h->total_load, pa, fc, rsv);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemset(h->slab, 0, (size_t)R.total * GS_LANES * sizeof(double)) != hipSuccess)
-      return bail(fail(nullptr, GS_E_HIP, "Newton-Raphson: flat-start table"));
-    h->F2.nrflat = tab; h->F2.nrflat_mode = 2;
-  }
+  if ((rc = flat_start_captures(h))) return bail(rc);
+  if (h->split_ok &&
+      (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
+       hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+       hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess))
+    return bail(fail(nullptr, GS_E_HIP, "second step stream: hipStreamCreate / hipEventCreate failed"));
   if (hipDeviceSynchronize() != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipDeviceSynchronize failed"));
   *out = h;
   return GS_OK;
@@ -1599,21 +762,18 @@ int gs_dims(const gs_handle* h, int32_t* n, int32_t* m, int32_t* obs_dim, int32_
 
 int gs_describe(const gs_handle* h, char* buf, int32_t buflen) {
   if (!h || !buf || buflen <= 0) return fail(nullptr, GS_E_INVALID, "bad arguments");
-  static const char* kn[] = {"nr_tree", "nr_sparse_lu", "fbs", "nr_dense_pivot", "nr_tree_lds", "fbs_lds", "fbs_flow", "nr_dense_mfma", "nr_sparse_lds"};
-  snprintf(buf, buflen,
-           "{\"kernel\": \"%s\", \"n\": %d, \"m\": %d, \"nnz\": %d, \"forest\": %s, \"levels\": %d, \"max_level_width\": %d, "
-           "\"lu_slots\": %d, \"lu_orig\": %d, \"lu_pairs\": %lld, \"waves_per_group\": %d, \"groups\": %d, "
-           "\"rows_per_group\": %d, \"slab_bytes\": %zu, \"obs_dim\": %d, \"action_dim\": %d, "
-           "\"instances_per_workgroup\": %d, \"workgroups\": %d, \"step_lds_bytes\": %zu, \"step_launches\": %d, \"solve_kernel\": \"%s\", \"flow2\": \"%s\", "
-           "\"mesh2\": \"%s\", \"mesh_levels\": %d, \"mesh_rows\": %d, \"mesh_message_units\": %d, \"mesh_messages\": %d, \"mesh_accumulators\": %d, "
-           "\"dense_form\": \"%s\", \"dense_workgroups\": %d, \"dense_lds_bytes\": %zu}",
-           h->flow2 ? (h->f2_small ? "fbs_flow2s" : h->f2_wide ? "fbs_flow2x" : h->f2_half ? "fbs_flow2h" : "fbs_flow2") : h->nrm ? "nr_mesh2" : h->nr2 ? (h->f2_small ? "nr_flow2s" : "nr_flow2") : kn[h->solve_kernel], h->n, h->m, h->topo.nnz, h->topo.is_forest ? "true" : "false", h->topo.n_levels,
-           h->topo.max_level_width, h->topo.lu_n_slots, h->topo.lu_n_orig, (long long)h->topo.lu_n_pairs, (h->flow2 || h->nr2 || h->nrm) ? h->f2_nw : h->W, h->groups,
-           h->R.total, (size_t)h->groups * h->R.total * GS_LANES * sizeof(double), h->obs_dim, h->action_dim,
-           (h->flow2 || h->nr2 || h->nrm) ? h->f2_iw : 64, (h->flow2 || h->nr2 || h->nrm) ? (64 / h->f2_iw) * h->groups : h->groups, (h->flow2 || h->nr2 || h->nrm) ? (size_t)h->F2.lds_bytes : h->dyn_lds + 24576, h->split_ok ? 2 : 1,
-           kn[h->solve_kernel], (h->flow2 || h->nr2 || h->nrm) ? "on" : (h->flow2_why.empty() ? "n/a" : h->flow2_why.c_str()),
-           h->nrm ? "on" : (h->mesh_why.empty() ? "n/a" : h->mesh_why.c_str()), h->mesh_levels, h->mesh_rows, h->mesh_units, h->mesh_messages, h->mesh_accs,
-           h->solve_kernel == 7 ? (h->dense_blockrow ? "block_row" : "panel") : "n/a", h->solve_kernel == 7 ? h->dense_grid : 0, h->solve_kernel == 7 ? h->dense_lds : (size_t)0);
+  gs_plan_format(*h, h->topo, buf, buflen);
+  return GS_OK;
+}
+
+int gs_plan_describe(const gs_topology* topo, const gs_config* cfg, int32_t batch, int32_t cus, char* buf, int32_t buflen) {
+  if (!buf || buflen <= 0 || cus < 1) return fail(nullptr, GS_E_INVALID, "bad arguments");
+  int rc = check_args(topo, cfg, batch);
+  if (rc) return rc;
+  HostTopology ht;
+  GsPlan p;
+  if ((rc = plan_handle(*topo, *cfg, batch, cus, ht, p))) return rc;
+  gs_plan_format(p, ht, buf, buflen);
   return GS_OK;
 }
 
@@ -1951,7 +1111,7 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   // was built in round 2 and is bit-identical, but slower: inlined into a loop the step's ~1 KB argument block stays live
   // across iterations (230 spilled registers); as an out-of-line call reading its arguments from memory the block lands in
   // scratch (59 M env-steps/s against 150 M for a launch per step).)
-  const bool fused = h->flow2 || h->nr2 || h->nrm;
+  const bool fused = h->second_gen();
   for (int t = 0; t < T; ++t) {
     double* nxt = ro.obs_seq + (size_t)(t + 1) * B * D;
     GsRolloutStep rs{ro.rew, ro.done, ro.obs_seq + (size_t)t * B * D, h->map_obs, h->d_cst, ro.term_count, ro.term_idx, ro.term_obs, ro.term_cap, h->obs_dim, t, 1};

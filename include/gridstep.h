@@ -172,6 +172,9 @@ int gs_dims(const gs_handle* h, int32_t* n, int32_t* m, int32_t* obs_dim, int32_
             int32_t* state_dim, int32_t* batch);
 /* how the topology was compiled: linear solver chosen, tree depth, fill, waves per group */
 int gs_describe(const gs_handle* h, char* buf, int32_t buflen);
+/* the same JSON for a handle that gs_create would build from these arguments on a device of `cus` compute units, planned on the
+ * host alone (no device needed; the GS_* switches as for gs_create) */
+int gs_plan_describe(const gs_topology* topo, const gs_config* cfg, int32_t batch, int32_t cus, char* buf, int32_t buflen);
 int gs_synchronize(gs_handle* h);
 
 /* ---- solver plug point: NewtonRaphsonSolver.solve (power_flow.py:89-211) ---------------

@@ -431,3 +431,22 @@ def test_dataflow_sweeps_on_a_bus_with_many_children(monkeypatch):
     assert np.all(a.bus_voltages[3] == 1.0) and np.all(a.bus_angles[3] == 0.0) and np.all(a.line_flows[3] == 0.0)
     np.testing.assert_allclose(a.line_flows, b.line_flows, rtol=1e-10, atol=1e-14)
     flow.close(); sync.close()
+
+
+def test_describe_of_a_handle_equals_its_host_side_plan(monkeypatch):
+    """gs_describe of real handles against gs_plan_describe with the device's compute units, over tests/test_plan.py's matrix of
+    feeders, configurations and GS_* switches: what the CPU tests expect of the plan is what the handles get."""
+    import torch
+    from tests.test_plan import CASES, config
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    for name, maker, B, settings, switches, _ in CASES:
+        spec = maker()
+        for k, v in switches.items():
+            monkeypatch.setenv(k, v)
+        h = _lib.Handle(spec, config(spec, **settings), B)
+        try:
+            assert h.describe() == _lib.plan_describe(spec, config(spec, **settings), B, cus), name
+        finally:
+            h.close()
+            for k in switches:
+                monkeypatch.delenv(k)
