@@ -11,7 +11,7 @@ import ctypes as C
 import json
 import os
 import sys
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -21,7 +21,7 @@ from .feeders import FeederSpec
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgridstep.so")
 
-GS_ABI_VERSION = 1
+GS_ABI_VERSION = 2
 GS_OK, GS_E_INVALID, GS_E_NO_DEVICE, GS_E_HIP, GS_E_TOPOLOGY, GS_E_STATE, GS_E_COMM, GS_E_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 JACOBIAN = {"as_coded": 0, "exact": 1}
 ZERO_Z = {"open": 0, "epsilon": 1}
@@ -41,7 +41,8 @@ class gs_topology(C.Structure):
                 ("n_loads", C.c_int32), ("load_bus", _ip), ("load_base", _dp), ("load_pf", _dp),
                 ("n_gens", C.c_int32), ("gen_bus", _ip), ("gen_kind", _ip), ("gen_cap", _dp),
                 ("gen_p0", _dp), ("gen_p1", _dp), ("gen_p2", _dp),
-                ("n_bats", C.c_int32), ("bat_bus", _ip), ("bat_cap", _dp), ("bat_rating", _dp), ("bat_eff", _dp)]
+                ("n_bats", C.c_int32), ("bat_bus", _ip), ("bat_cap", _dp), ("bat_rating", _dp), ("bat_eff", _dp),
+                ("line_r_inst", _dp), ("line_x_inst", _dp)]
 
 
 class gs_config(C.Structure):
@@ -134,6 +135,8 @@ SYMBOLS = [
     ("gs_debug_write_rows", C.c_int, [_H, C.c_int32, _dp]),
     ("gs_debug_read_rows", C.c_int, [_H, C.c_int32, _dp]),
     ("gs_fallback_linear", C.c_int, [_H, _dp, _dp, _dp, _dp, _up, _up, C.POINTER(C.c_int32)]),
+    ("gs_set_line_impedances", C.c_int, [_H, _dp, _dp, _up]),
+    ("gs_get_line_impedances", C.c_int, [_H, _dp, _dp]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -255,8 +258,31 @@ def _device_address(x, shape) -> int:
     return int(cai["data"][0])
 
 
-def _topology_of(spec: FeederSpec):
-    """gs_topology of a FeederSpec and the arrays it points into (keep them alive while the struct is in use)."""
+def check_line_impedances(spec: FeederSpec, r, x, rows: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-instance line impedances ``r``, ``x`` of shape [rows, m] as C-contiguous float64, checked against the rules of
+    gs_topology::line_r_inst (include/gridstep.h): finite, r >= 0, a line of zero nominal impedance keeps its nominal r and x in
+    every instance, every other line keeps hypot(r, x) > 1e-12.  Raises ValueError."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    shape = (int(rows), int(spec.m))
+    if r.shape != shape or x.shape != shape:
+        raise ValueError(f"line impedances: r and x must have shape {shape}, got {r.shape} and {x.shape}")
+    if not (np.isfinite(r).all() and np.isfinite(x).all()):
+        raise ValueError("line impedances: every value must be finite")
+    if (r < 0).any():
+        raise ValueError("line impedances: r must be >= 0")
+    zero = ~(np.hypot(np.asarray(spec.r, dtype=np.float64), np.asarray(spec.x, dtype=np.float64)) > 1e-12)
+    if zero.any() and not (np.array_equal(r[:, zero], np.broadcast_to(np.asarray(spec.r)[zero], (shape[0], int(zero.sum())))) and
+                           np.array_equal(x[:, zero], np.broadcast_to(np.asarray(spec.x)[zero], (shape[0], int(zero.sum()))))):
+        raise ValueError("line impedances: a line of zero nominal impedance keeps its nominal r and x in every instance")
+    if not (np.hypot(r[:, ~zero], x[:, ~zero]) > 1e-12).all():
+        raise ValueError("line impedances: a line of non-zero nominal impedance cannot have zero impedance")
+    return r, x
+
+
+def _topology_of(spec: FeederSpec, line_impedances=None):
+    """gs_topology of a FeederSpec and the arrays it points into (keep them alive while the struct is in use).
+    ``line_impedances``: None or (r, x), C-contiguous float64 [batch, m] (gs_topology::line_r_inst / line_x_inst)."""
     keep = dict(frm=_i32(spec.frm), to=_i32(spec.to), r=_f64(spec.r), x=_f64(spec.x), rating=_f64(spec.rating),
                 bus_type=np.ascontiguousarray(spec.bus_type, dtype=np.uint8), v_set=_f64(spec.v_set),
                 load_bus=_i32(spec.load_bus), load_base=_f64(spec.load_base), load_pf=_f64(spec.load_pf),
@@ -278,6 +304,9 @@ def _topology_of(spec: FeederSpec):
     t.n_bats = spec.n_bats
     t.bat_bus, t.bat_cap = _ptr(keep["bat_bus"], _ip), _ptr(keep["bat_cap"], _dp)
     t.bat_rating, t.bat_eff = _ptr(keep["bat_rating"], _dp), _ptr(keep["bat_eff"], _dp)
+    if line_impedances is not None:
+        keep["r_inst"], keep["x_inst"] = _f64(line_impedances[0]), _f64(line_impedances[1])
+        t.line_r_inst, t.line_x_inst = _ptr(keep["r_inst"], _dp), _ptr(keep["x_inst"], _dp)
     return t, keep
 
 
@@ -299,11 +328,11 @@ def flat_newton_map(spec, zero_z="open") -> np.ndarray:
     return out
 
 
-def plan_describe(spec: FeederSpec, cfg: gs_config, batch: int, cus: int = 256) -> dict:
+def plan_describe(spec: FeederSpec, cfg: gs_config, batch: int, cus: int = 256, line_impedances=None) -> dict:
     """gs_plan_describe: what Handle(spec, cfg, batch).describe() returns on a device with ``cus`` compute units, planned on the host
-    (no device needed)."""
+    (no device needed).  ``line_impedances``: None or per-instance (r, x), [batch, m] each."""
     lib = load()
-    t, keep = _topology_of(spec)
+    t, keep = _topology_of(spec, line_impedances)
     buf = C.create_string_buffer(4096)
     rc = lib.gs_plan_describe(C.byref(t), C.byref(cfg), int(batch), int(cus), buf, 4096)
     if rc != GS_OK:
@@ -359,13 +388,14 @@ def mesh_schedule(spec: FeederSpec, nw: int = 4, ni: int = 10, acc_cap: int = 4,
 class Handle:
     """Owns one gs_handle (one GPU, one stream).  All array arguments are NumPy, batch-major."""
 
-    def __init__(self, spec: FeederSpec, cfg: gs_config, batch: int, device: int = 0, first_instance: int = 0):
+    def __init__(self, spec: FeederSpec, cfg: gs_config, batch: int, device: int = 0, first_instance: int = 0, line_impedances=None):
         self._lib = load()
         self._h = _H()
         self.spec = spec
         self.B = int(batch)
         self.obs_dtype = np.dtype(np.float64)      # np.float32: step() / download_step() hand out the block rounded on the device (gs_step_f32)
-        t, keep = _topology_of(spec)
+        t, keep = _topology_of(spec, line_impedances)
+        self._pz = line_impedances is not None
         rc = self._lib.gs_create(C.byref(t), C.byref(cfg), self.B, int(device), int(first_instance), C.byref(self._h))
         if rc != GS_OK:
             self._h = _H()
@@ -389,6 +419,23 @@ class Handle:
 
     def last_error(self) -> str:
         return self._lib.gs_last_error(self._h).decode()
+
+    # -- per-instance line impedances (gs_set_line_impedances / gs_get_line_impedances) --------------------------------------
+    def set_line_impedances(self, r: np.ndarray, x: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
+        r, x = _f64(r), _f64(x)
+        if r.shape != (self.B, self.m) or x.shape != (self.B, self.m):
+            raise PowerFlowError(f"line impedances must have shape {(self.B, self.m)}")
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mk.shape != (self.B,):
+                raise PowerFlowError(f"mask must have shape ({self.B},)")
+        self._check(self._lib.gs_set_line_impedances(self._h, _ptr(r, _dp), _ptr(x, _dp), None if mk is None else _ptr(mk, _up)))
+
+    def get_line_impedances(self) -> Tuple[np.ndarray, np.ndarray]:
+        r = np.empty((self.B, self.m)); x = np.empty((self.B, self.m))
+        self._check(self._lib.gs_get_line_impedances(self._h, _ptr(r, _dp), _ptr(x, _dp)))
+        return r, x
 
     def _adopt(self, child) -> None:
         if not hasattr(self, "_children"):

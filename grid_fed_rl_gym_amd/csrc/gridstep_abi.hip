@@ -129,6 +129,10 @@ struct gs_handle : GsPlan {
   // gs_fallback_linear: line reactances, dict-order bus lists and staging, created on first use
   std::vector<double> line_x;
   bool fb_ready = false; GsFallbackArgs FB{};
+  // per-instance line impedances (GsPlan::pz): what the handle holds ([B][m], host copy and device copy, the fallback reads the
+  // device one), the nominal values they are checked against, the arguments of gs_k_line_params (LP.pz: the step kernels' entries)
+  std::vector<double> inst_r, inst_x, nominal_r, nominal_x;
+  GsLineParamArgs LP{}; uint8_t* d_pzmask = nullptr;
   double *fb_load = nullptr, *fb_gen = nullptr, *fb_tl = nullptr, *fb_tg = nullptr; uint8_t* fb_mask = nullptr; int32_t* fb_applied = nullptr;
   // host copies of the per-instance scalars: ONE page-locked block the device addresses -- gs_k_scalars stores into it itself (three
   // copies through the runtime's staging buffer cost 80 us of a 0.9 ms env.step()); hd_*: the same block as the device sees it
@@ -380,6 +384,24 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
 #define GS_F2(k) do { hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv); \
                       if (n_first < n_wg) hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv); } while (0)
 #define GS_F2_PAIR(kc, k) do { if (fc.enabled) GS_F2(kc); else GS_F2(k); } while (0)
+      if (h->pz) {           // per-instance line impedances: the members' PZ kernels, the entries behind the argument block
+        const double* pz = h->LP.pz;
+#define GS_F2Z(k) do { hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz); \
+                       if (n_first < n_wg) hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz); } while (0)
+#define GS_F2Z_PAIR(kc, k) do { if (fc.enabled) GS_F2Z(kc); else GS_F2Z(k); } while (0)
+        switch (h->step) {
+          case StepMember::fbs_flow2s: GS_F2Z_PAIR(gs_k_stepc_fbs_flow2s_pz, gs_k_step_fbs_flow2s_pz); break;
+          case StepMember::fbs_flow2h: GS_F2Z_PAIR(gs_k_stepc_fbs_flow2h_pz, gs_k_step_fbs_flow2h_pz); break;
+          case StepMember::fbs_flow2x: GS_F2Z_PAIR(gs_k_stepc_fbs_flow2x_pz, gs_k_step_fbs_flow2x_pz); break;
+          case StepMember::nr_flow2s: GS_F2Z_PAIR(gs_k_stepc_nr_flow2s_pz, gs_k_step_nr_flow2s_pz); break;
+          case StepMember::nr_flow2: GS_F2Z_PAIR(gs_k_stepc_nr_flow2_pz, gs_k_step_nr_flow2_pz); break;
+          default: return fail(h, GS_E_STATE, "per-instance line impedances: no PZ kernel for this member");
+        }
+#undef GS_F2Z_PAIR
+#undef GS_F2Z
+        HIPCHK(h, hipGetLastError());
+        return GS_OK;
+      }
       switch (h->step) {
         case StepMember::fbs_flow2s: GS_F2_PAIR(gs_k_stepc_fbs_flow2s, gs_k_step_fbs_flow2s); break;
         case StepMember::fbs_flow2h: GS_F2_PAIR(gs_k_stepc_fbs_flow2h, gs_k_step_fbs_flow2h); break;
@@ -450,6 +472,22 @@ int check_args(const gs_topology* topo, const gs_config* cfg, int32_t batch) {
   if (cfg->max_iterations < 1) return fail(nullptr, GS_E_INVALID, "max_iterations must be >= 1");
   if (!(cfg->power_base > 0.0)) return fail(nullptr, GS_E_INVALID, "power_base must be > 0");
   if (!(cfg->timestep > 0.0)) return fail(nullptr, GS_E_INVALID, "timestep must be > 0");
+  if ((topo->line_r_inst == nullptr) != (topo->line_x_inst == nullptr))
+    return fail(nullptr, GS_E_INVALID, "line_r_inst and line_x_inst go together (both NULL or both [batch][m])");
+  if (topo->line_r_inst && topo->m > 0 && topo->r && topo->x) {
+    const std::string why = gs_check_line_impedances(*topo, batch, topo->line_r_inst, topo->line_x_inst, nullptr);
+    if (!why.empty()) return fail(nullptr, GS_E_INVALID, "%s", why.c_str());
+  }
+  return GS_OK;
+}
+
+// gs_k_line_params for the instances of mask (device, NULL = all)
+int launch_line_params(gs_handle* h, const uint8_t* d_mask) {
+  GsLineParamArgs A = h->LP;
+  A.mask = d_mask;
+  const size_t threads = (size_t)h->groups * GS_LANES * (A.n_slots + A.m);
+  hipLaunchKernelGGL(gs_k_line_params, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
   return GS_OK;
 }
 
@@ -519,8 +557,9 @@ int flat_start_captures(gs_handle* h) {
   }
   // Newton-Raphson on the second-generation frame: the constants of the flat-start elimination (GsF2Tables::nrflat), written by
   // ONE workgroup of the step kernel itself on the zeroed state of group 0, then group 0 is cleared again.  GS_NR_NO_FLAT=1: off.
-  const bool nr2 = h->step == StepMember::nr_flow2s || h->step == StepMember::nr_flow2 || h->step == StepMember::nr_mesh2;
-  if (nr2 && h->f2_npos > 0 && !getenv("GS_NR_NO_FLAT")) {
+  // (GsPlan::nr_flat: a Newton-Raphson member, GS_NR_NO_FLAT unset, no per-instance impedances -- the table is the flat start's of
+  // the shared Ybus)
+  if (h->nr_flat) {
     double* tab = nullptr;
     if ((rc = dev_alloc(h, &tab, (size_t)h->f2_npos * 16))) return rc;
     if (hipMemset(tab, 0, (size_t)h->f2_npos * 16 * sizeof(double)) != hipSuccess ||
@@ -586,6 +625,7 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
   const HostTopology& ht = h->topo;
   h->EC.first_instance = first_instance;
   h->line_x.assign(topo->x, topo->x + topo->m);
+  h->nominal_r.assign(topo->r, topo->r + topo->m); h->nominal_x.assign(topo->x, topo->x + topo->m);
   auto bail = [&](int rc) { gs_destroy(h); return rc; };
   if (hipSetDevice(device) != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipSetDevice failed"));
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
@@ -672,6 +712,24 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
   if (h->second_gen() &&
       ((rc = dev_upload(h, &h->F2.recs, h->f2recs)) || (rc = dev_upload(h, &h->F2.anc, h->f2anc)) || (rc = dev_upload(h, &h->F2.zbus, h->f2z)) ||
        (h->fs_slot.size() > 1 && ((rc = dev_upload(h, &h->F2.fixed_slot, h->fs_slot)) || (rc = dev_upload(h, &h->F2.fixed_val, h->fs_val)))))) return bail(rc);
+  if (h->pz) {
+    GsLineParamArgs& A = h->LP;
+    const size_t Bm = (size_t)h->B * h->m;
+    h->inst_r.assign(topo->line_r_inst, topo->line_r_inst + Bm); h->inst_x.assign(topo->line_x_inst, topo->line_x_inst + Bm);
+    A.B = h->B; A.groups = h->groups; A.n_slots = ht.n + 3; A.m = ht.m; A.newton = (h->step == StepMember::nr_flow2s || h->step == StepMember::nr_flow2) ? 1 : 0;
+    A.lyr_nom = T.lyr; A.lyi_nom = T.lyi;
+    double *dr = nullptr, *dx = nullptr, *dpz = nullptr;
+    const size_t n_pz = (size_t)h->groups * GS_PZ_NQ(A.n_slots, A.m) * GS_LANES * 2;
+    if ((rc = dev_upload(h, &A.zero_z, h->pz_zero)) || (rc = dev_upload(h, &A.ops_ptr, h->pz_ops_ptr)) || (rc = dev_upload(h, &A.ops, h->pz_ops)) ||
+        (rc = dev_upload(h, &A.has, h->pz_has)) || (rc = dev_alloc(h, &dr, Bm)) || (rc = dev_alloc(h, &dx, Bm)) ||
+        (rc = dev_alloc(h, &h->d_pzmask, (size_t)h->B)) || (rc = dev_alloc(h, &dpz, n_pz))) return bail(rc);
+    A.r = dr; A.x = dx; A.pz = dpz;
+    if (hipMemcpy(dr, h->inst_r.data(), Bm * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dx, h->inst_x.data(), Bm * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(dpz, 0, n_pz * sizeof(double)) != hipSuccess)
+      return bail(fail(nullptr, GS_E_HIP, "per-instance line impedances: upload failed"));
+    if ((rc = launch_line_params(h, nullptr))) return bail(fail(nullptr, rc, "%s", h->err.c_str()));
+  }
   { const double* q = nullptr; if ((rc = dev_upload(h, &q, h->cst))) return bail(rc); h->d_cst = const_cast<double*>(q); }
   if ((rc = upload_map(h, &h->map_obs, h->mo)) || (rc = upload_map(h, &h->map_vm, h->mvm)) || (rc = upload_map(h, &h->map_va, h->mva)) ||
       (rc = upload_map(h, &h->map_flow, h->mfl)) || (rc = upload_map(h, &h->map_load, h->mld)) || (rc = upload_map(h, &h->map_p, h->mp)) ||
@@ -785,9 +843,47 @@ int gs_synchronize(gs_handle* h) {
   return GS_OK;
 }
 
+// ---- per-instance line impedances ------------------------------------------------------------
+int gs_set_line_impedances(gs_handle* h, const double* r, const double* x, const uint8_t* mask) {
+  if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (!h->pz) return fail(h, GS_E_STATE, "gs_set_line_impedances: the handle was created without per-instance line impedances "
+                                         "(gs_topology::line_r_inst / line_x_inst)");
+  if (!r || !x) return fail(h, GS_E_INVALID, "gs_set_line_impedances: r and x are [B][m] and go together");
+  gs_topology nominal{};
+  nominal.m = h->m; nominal.r = h->nominal_r.data(); nominal.x = h->nominal_x.data();
+  const std::string why = gs_check_line_impedances(nominal, h->B, r, x, mask);
+  if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
+  GS_ENTER(h);
+  const size_t m = (size_t)h->m;
+  for (int b = 0; b < h->B; ++b) {
+    if (mask && !mask[b]) continue;
+    std::copy(r + b * m, r + (b + 1) * m, h->inst_r.begin() + b * m);
+    std::copy(x + b * m, x + (b + 1) * m, h->inst_x.begin() + b * m);
+  }
+  // (a step still in flight may read the entries: the stream orders the copies and the derivation behind it)
+  HIPCHK(h, hipMemcpyAsync(const_cast<double*>(h->LP.r), h->inst_r.data(), h->inst_r.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(const_cast<double*>(h->LP.x), h->inst_x.data(), h->inst_x.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (mask) HIPCHK(h, hipMemcpyAsync(h->d_pzmask, mask, (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+  int rc = launch_line_params(h, mask ? h->d_pzmask : nullptr);
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // (the caller's mask and the host copies are pageable)
+  return GS_OK;
+}
+
+int gs_get_line_impedances(const gs_handle* h, double* r, double* x) {
+  if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (!h->pz) return fail(const_cast<gs_handle*>(h), GS_E_STATE, "gs_get_line_impedances: the handle has no per-instance line impedances");
+  if (r) std::copy(h->inst_r.begin(), h->inst_r.end(), r);
+  if (x) std::copy(h->inst_x.begin(), h->inst_x.end(), x);
+  return GS_OK;
+}
+
 // ---- solver -------------------------------------------------------------------------------
+static const char* const kPzNoSolve = "gs_solve / gs_solve_device: this handle has per-instance line impedances, which the solver API does not "
+                                      "support (the step, rollout and fallback entry points do)";
 int gs_upload_injections(gs_handle* h, const double* P_spec, const double* Q_spec) {
   if (!h || !P_spec) return fail(h, GS_E_INVALID, "handle / P_spec is NULL");
+  if (h->pz) return fail(h, GS_E_STATE, "%s", kPzNoSolve);
   GS_ENTER(h);
   int rc = unpack_from_host(h, h->map_p, h->n, P_spec);
   if (rc) return rc;
@@ -805,6 +901,7 @@ int gs_upload_injections(gs_handle* h, const double* P_spec, const double* Q_spe
 
 int gs_solve_device(gs_handle* h) {
   if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (h->pz) return fail(h, GS_E_STATE, "%s", kPzNoSolve);
   GS_ENTER(h);
   h->rows_stale = false;            // the solve writes every result row
   return launch_solve(h);
@@ -1756,6 +1853,7 @@ int gs_fallback_linear(gs_handle* h, const double* load_w, const double* gen_w, 
   }
   GsFallbackArgs A = h->FB;
   A.env_mode = load_w ? 0 : 1;
+  if (h->pz) { A.line_x = h->LP.x; A.line_x_stride = h->m; }       // every instance's own reactances
   if (load_w) {
     HIPCHK(h, hipMemcpyAsync(h->fb_load, load_w, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->fb_gen, gen_w, (size_t)B * n * sizeof(double), hipMemcpyHostToDevice, h->stream));

@@ -121,10 +121,10 @@ struct GsFallbackArgs {
   const double* load_w; const double* gen_w;          // [B][n] batch-major, or NULL with env_mode
   const double* tot_load; const double* tot_gen;      // [B] or NULL
   const int32_t* load_order; const int32_t* gen_order;   // buses in the order the reference's dicts are filled (env_mode)
-  const double* line_x;                                // [m] line reactance
+  const double* line_x;                                // [m] line reactance, or [B][m] with line_x_stride = m (per-instance impedances)
   const uint8_t* mask;                                 // [B] or NULL = where CONV == 0
   int32_t* applied;                                    // [B] out
-  int32_t n_load_order, n_gen_order, env_mode, pad;
+  int32_t n_load_order, n_gen_order, env_mode, line_x_stride;
 };
 
 // One forest work item (a bus, in the order ONE wave meets it in the sweeps) with everything the
@@ -551,3 +551,25 @@ struct GsFusedChecks {
   int32_t enabled, Bp;
 };
 
+// ---- per-instance line impedances (gs_topology::line_r_inst / line_x_inst, gs_set_line_impedances) ----
+// The values the second-generation step kernels read per instance instead of the handle's shared tables, as 16-byte (re, im) pairs
+// laid out batch-innermost in the order the step kernels address instances: entry q of instance b = g * 64 + L at
+//   pz[((size_t)g * nq + q) * GS_LANES + L],  nq = 2 * n_slots + m,
+//   q = s              (slot s < n_slots)  sweeps: z of the branch to the parent | Newton-Raphson: (G_ip, B_ip)
+//   q = n_slots + s                        sweeps: its admittance y = -Y_ip     | Newton-Raphson: (G_ii, B_ii)
+//   q = 2 * n_slots + k (line k)           the line's series admittance (lyr, lyi) of the epilogue
+// Slots without an entry in the shared tables (slack, ZERO / ONE / DUMMY) hold (0, 0).  Written by gs_k_line_params with the
+// host's arithmetic (topology.cpp reciprocal(), Ybus accumulated in line order from 0, plan.cpp's z = 1 / y): an instance at the
+// nominal values gets the shared tables' bits.
+#define GS_PZ_NQ(n_slots, m) (2 * (n_slots) + (m))
+struct GsLineParamArgs {
+  const double* r; const double* x;      // [B][m] per-instance series impedance, per unit
+  const uint8_t* mask;                   // [B] or NULL (all)
+  const double* lyr_nom; const double* lyi_nom;   // [m] the shared tables' line admittances (lines whose nominal |z| <= 1e-12 keep them)
+  const uint8_t* zero_z;                 // [m] 1: the line's nominal |z| <= 1e-12
+  // per slot, two lists of Ybus contributions in line order, each entry k * 2 + (1: subtract the line's y): list s is the branch
+  // entry Y(s, parent), list n_slots + s the diagonal Y(s, s); ptr [2 * n_slots + 1].  has[s]: the slot has entries (else (0, 0))
+  const int32_t* ops_ptr; const int32_t* ops; const uint8_t* has;
+  double* pz;                            // [groups][nq][64] double pairs
+  int32_t B, groups, n_slots, m, newton, pad;
+};

@@ -46,6 +46,20 @@ __global__ void gs_k_step_nr_flow2(GsTables T, GsF2Tables F, GsRows R, GsSolveCf
                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
 __global__ void gs_k_stepc_nr_flow2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                                     const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
+// per-instance line impedances (kernels_flow2.hip): the second-generation members with PZ = 1, and the kernel that derives their entries
+#define GS_DECLARE_F2_PZ(name)                                                                                                 \
+  __global__ void gs_k_step_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B, \
+                                        const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC,         \
+                                        GsRolloutStep RS, const double* __restrict__ pz);                                              \
+  __global__ void gs_k_stepc_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B, \
+                                         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC,        \
+                                         GsRolloutStep RS, const double* __restrict__ pz);
+GS_DECLARE_F2_PZ(fbs_flow2s)
+GS_DECLARE_F2_PZ(fbs_flow2h)
+GS_DECLARE_F2_PZ(fbs_flow2x)
+GS_DECLARE_F2_PZ(nr_flow2s)
+GS_DECLARE_F2_PZ(nr_flow2)
+__global__ void gs_k_line_params(GsLineParamArgs A);
 __global__ void gs_k_step_nr_mesh2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
 __global__ void gs_k_stepc_nr_mesh2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,

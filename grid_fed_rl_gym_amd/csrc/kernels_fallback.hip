@@ -69,7 +69,7 @@ gs_k_fallback_linear(GsTables T, GsRows R, GsFallbackArgs A, double* __restrict_
   if (T.n > 1) {                                                          // :373-382
     pfl = (tg - tl) / (double)(T.m > 1 ? T.m : 1);
     for (int k = 0; k < T.m; ++k) {
-      const double x = cld(A.line_x, k);
+      const double x = cld(A.line_x + (size_t)(valid ? b : 0) * A.line_x_stride, k);
       if (x > 0.0) {
         const double th = ROW(R.VA + cld(T.lfrom, k));
         if (apply) ROW(R.VA + cld(T.lto, k)) = th - pfl * x / 100.0;

@@ -246,10 +246,13 @@ struct F2Stamp {
 // positions): the sweep kernel runs 16 x 4, Newton-Raphson -- whose bus state (voltage, the T and s of the elimination)
 // lives in registers across its two sweeps -- 8 x 8, i.e. twice the registers per wave.
 enum { F2_FBS = 0, F2_NR = 1, F2_NRM = 2 };      // NRM: Newton-Raphson on a meshed feeder (block LU with fill-in, mesh_schedule.h)
-template <int SOLVER, int CHK, int NW, int NI, int IW>
+// PZ = 1: per-instance line impedances (gs_internal.h GsLineParamArgs): the branch z / y, the Newton-Raphson (G, B) pairs and the
+// epilogue's line admittances come from `pz`, the instance's own values, instead of the handle's shared tables; PZ = 0 never reads it.
+template <int SOLVER, int CHK, int NW, int NI, int IW, int PZ = 0>
 __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, const GsRows& R, const GsSolveCfg& C, const GsEnvCfg& E,
                                         double* __restrict__ slab, int B, const double* __restrict__ actions, double total_load,
-                                        const GsPackArgs& PA, const GsFusedChecks& FC, const GsRolloutStep& RS) {
+                                        const GsPackArgs& PA, const GsFusedChecks& FC, const GsRolloutStep& RS,
+                                        const double* __restrict__ pz = nullptr) {
   f2_touch_arguments();
   // IW instances per workgroup (32; 16 or 8 for small feeders, where more of a wavefront's lanes go to different buses):
   // lane = hv * IW + l, sub-group hv of the wave works on its own bus for instance l
@@ -266,6 +269,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
   const int b = g * GS_LANES + L;
   const bool valid = b < B;
   const GsLaneRows S = gs_lane_rows(slab, g, R.total, L);
+  // PZ: this lane's per-instance entries (pz_at(q): entry q, one 16-byte load; every lane of the grid lies inside the groups)
+  const double* const pz_lane = PZ ? pz + ((size_t)g * GS_PZ_NQ(F.n_slots, T.m) * GS_LANES + L) * 2 : nullptr;
+  auto pz_at = [&](int q) -> double2 { return *(const double2*)(pz_lane + (size_t)q * (2 * GS_LANES)); };
   // Scalars of the start-up, read from the kernel arguments ONCE: the compiler treats an argument as free to read again
   // wherever it is short of scalar registers, and the start-up was 47 scalar loads, most of them waited for one by one
   // (~150 cycles each, 4 k cycles before the first barrier); a value that went through F2_KEEP is kept (or parked in a
@@ -595,7 +601,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     for (int j = 0; j < NI; ++j) {
       int bus = ibus[j]; F2_OPAQUE(bus);
       const int par = pos_tab[(pos0 + j) * 4 + 1];
-      const double2 v = f2_ld2(bufA + f2_slot(bus, l)), vp = f2_ld2(bufA + f2_slot(par, l)), y = f2_ld2(o_z + 32u * bus);
+      const double2 v = f2_ld2(bufA + f2_slot(bus, l)), vp = f2_ld2(bufA + f2_slot(par, l)), y = PZ ? pz_at(bus) : f2_ld2(o_z + 32u * bus);
       const double dr = v.x - vp.x, di = v.y - vp.y;
       // branch admittance = -Y_ip
       kr[j] = __builtin_fma(-y.x, dr, y.y * di); ki[j] = -__builtin_fma(y.x, di, y.y * dr);
@@ -693,7 +699,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
         int bus = ibus[j]; F2_OPAQUE(bus);
         int pj = pos0 + j; F2_OPAQUE(pj);
         const f2_i4 px = *F2_P(const f2_i4, o_anc + 4u * F.pos_off + 16u * pj);      // bus, parent, ring, parent's ring
-        const double2 yo = f2_ld2(o_z + 32u * bus), yd = f2_ld2(o_z + 32u * bus + 16u);       // (G_ip, B_ip), (G_ii, B_ii)
+        const double2 yo = PZ ? pz_at(bus) : f2_ld2(o_z + 32u * bus), yd = PZ ? pz_at(nsl + bus) : f2_ld2(o_z + 32u * bus + 16u);       // (G_ip, B_ip), (G_ii, B_ii)
         const double2 v = f2_ld2(bufA + f2_slot(bus, l)), vp = f2_ld2(bufA + f2_slot(px[1], l));
         const double v2 = __builtin_fma(v.x, v.x, v.y * v.y), rvm = f2_rsq(v2), vmi = v2 * rvm;
         const double rvmp = f2_rsq(__builtin_fma(vp.x, vp.x, vp.y * vp.y));
@@ -1391,7 +1397,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
       const bool root = (roots >> j) & 1u;
       const double ep = root ? f2_ld(f2_slot(F.slack, l)) : 1.0;
       const double dr = 1.0 - ep;
-      const double kr = q->yr * dr, ki = q->yi * dr;
+      double qyr, qyi;
+      if constexpr (PZ != 0) { const double2 y = pz_at(nsl + ibus[j]); qyr = y.x; qyi = y.y; } else { qyr = q->yr; qyi = q->yi; }
+      const double kr = qyr * dr, ki = qyi * dr;
       const double pc = kr, qc = -ki;
       const double dP = p - pc, dQ = 0.0 - qc;
       lmax = fmax(lmax, fmax(fabs(dP), fabs(dQ)));
@@ -1421,7 +1429,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     double sr[NI], si[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      const double2 z = f2_ld2(o_z + 16u * ibus[j]);
+      // (PZ: the instance's z, read where it is used from the L2-resident entries; held in registers across the step the
+      // 16-instance member spilled 19 vector registers at its 128)
+      const double2 z = PZ ? pz_at(ibus[j]) : f2_ld2(o_z + 16u * ibus[j]);
       sr[j] = __builtin_fma(JR[j], z.x, -(JI[j] * z.y)); si[j] = __builtin_fma(JR[j], z.y, JI[j] * z.x);      // D = z J
       f2_st2(bufA + f2_slot(ibus[j], l), make_double2(sr[j], si[j]));
     }
@@ -1537,7 +1547,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
   for (int k0 = wave * HV + hv; k0 < ((m + HV * NW - 1) / (HV * NW)) * (HV * NW); k0 += HV * NW) {
     const bool on = k0 < m; const int k = on ? k0 : m - 1;
     const int li = T.lfrom[k], lj = T.lto[k];
-    const double yr = T.lyr[k], yi = T.lyi[k], rating = T.lrating[k], rinv = T.lrating_inv[k];
+    double yr, yi;
+    if constexpr (PZ != 0) { const double2 y = pz_at(2 * nsl + k); yr = y.x; yi = y.y; } else { yr = T.lyr[k]; yi = T.lyi[k]; }
+    const double rating = T.lrating[k], rinv = T.lrating_inv[k];
     const double2 vi = final_ef(li), vj = final_ef(lj);
     const double dr = vi.x - vj.x, di = vi.y - vj.y;
     const double ir = __builtin_fma(yr, dr, -(yi * di)), ii = __builtin_fma(yr, di, yi * dr);        // I = y (Vi - Vj)
@@ -1814,3 +1826,89 @@ F2_KERNELS(fbs_flow2x, F2_FBS, GS_F2X_WAVES, GS_F2X_ITEMS, GS_F2H_IW)
 // Newton-Raphson on a meshed feeder (a few loops on a tree): 8 instances per workgroup, 4 wavefronts, up to GS_F2M_ITEMS rows each,
 // two workgroups per CU (two waves per SIMD: 256 registers)
 F2_KERNELS_OCC(nr_mesh2, F2_NRM, GS_F2M_WAVES, GS_F2M_ITEMS, GS_F2S_IW, __attribute__((amdgpu_waves_per_eu(2, 2))))
+
+// ---- per-instance line impedances: the same members with PZ = 1.  The pointer to the per-instance entries is an argument of
+// their own behind the block the members above read (F2ArgBlock: offsets unchanged); it is read from the formal parameter.
+#define F2_KERNELS_PZ_OCC(name, SOLVER, NW, NI, IW, OCC)                                                                   \
+  extern "C" __global__ void __launch_bounds__(64 * NW) OCC                                                                \
+  gs_k_step_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,    \
+                        const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, \
+                        const double* __restrict__ pz) {                                                                   \
+    F2_ARGS_IN_PLACE;                                                                                                      \
+    f2_step<SOLVER, 0, NW, NI, IW, 1>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, A->RS, pz); \
+  }                                                                                                                        \
+  extern "C" __global__ void __launch_bounds__(64 * NW) OCC                                                                \
+  gs_k_stepc_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,   \
+                         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, \
+                         const double* __restrict__ pz) {                                                                  \
+    F2_ARGS_IN_PLACE;                                                                                                      \
+    f2_step<SOLVER, 1, NW, NI, IW, 1>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, A->RS, pz); \
+  }
+F2_KERNELS_PZ_OCC(nr_flow2, F2_NR, 8, 8, 32, )
+F2_KERNELS_PZ_OCC(fbs_flow2s, F2_FBS, GS_F2S_WAVES, GS_F2S_ITEMS, GS_F2S_IW, )
+F2_KERNELS_PZ_OCC(nr_flow2s, F2_NR, GS_F2NS_WAVES, GS_F2NS_ITEMS, GS_F2S_IW, )
+F2_KERNELS_PZ_OCC(fbs_flow2h, F2_FBS, GS_F2H_WAVES, GS_F2H_ITEMS, GS_F2H_IW, __attribute__((amdgpu_waves_per_eu(4, 4))))
+F2_KERNELS_PZ_OCC(fbs_flow2x, F2_FBS, GS_F2X_WAVES, GS_F2X_ITEMS, GS_F2H_IW, )
+
+// The per-instance entries of instances b (every lane of the slab groups; a padding lane past B takes instance B - 1's values)
+// from their [B][m] impedances: one thread per (instance, slot or line), the host's arithmetic operation for operation
+// (topology.cpp reciprocal(), the Ybus sums in line order from 0, plan.cpp's z = 1 / y), no contraction.
+namespace {
+#pragma clang fp contract(off)
+__device__ __forceinline__ double2 lp_reciprocal(double r, double x) {      // topology.cpp reciprocal(): CPython's complex 1 / z
+  double2 y;
+  if (fabs(r) >= fabs(x)) {
+    const double ratio = x / r;
+    const double denom = r + x * ratio;
+    y.x = (1.0 + 0.0 * ratio) / denom;
+    y.y = (0.0 - 1.0 * ratio) / denom;
+  } else {
+    const double ratio = r / x;
+    const double denom = r * ratio + x;
+    y.x = (1.0 * ratio + 0.0) / denom;
+    y.y = (0.0 * ratio - 1.0) / denom;
+  }
+  return y;
+}
+__device__ __forceinline__ double2 lp_line_y(const GsLineParamArgs& A, int b, int k) {
+  if (A.zero_z[k]) return make_double2(A.lyr_nom[k], A.lyi_nom[k]);      // open circuit / epsilon: the nominal treatment
+  return lp_reciprocal(A.r[(size_t)b * A.m + k], A.x[(size_t)b * A.m + k]);
+}
+__device__ __forceinline__ double2 lp_ybus(const GsLineParamArgs& A, int b, int list) {      // one Ybus entry, accumulated in line order
+  double2 acc = make_double2(0.0, 0.0);
+  for (int p = A.ops_ptr[list]; p < A.ops_ptr[list + 1]; ++p) {
+    const int op = A.ops[p];
+    const double2 y = lp_line_y(A, b, op >> 1);
+    if (op & 1) { acc.x += -y.x; acc.y += -y.y; } else { acc.x += y.x; acc.y += y.y; }
+  }
+  return acc;
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(256) gs_k_line_params(GsLineParamArgs A) {
+  const int per = A.n_slots + A.m;
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)A.groups * GS_LANES * per) return;
+  const int lane = (int)(t / per), q = (int)(t % per);
+  const int b = lane < A.B ? lane : A.B - 1;
+  if (A.mask && !A.mask[b]) return;
+  const int g = lane / GS_LANES, L = lane % GS_LANES, nq = GS_PZ_NQ(A.n_slots, A.m);
+  double2* const out = (double2*)A.pz + (size_t)g * nq * GS_LANES + L;
+  if (q >= A.n_slots) {                                    // a line: its series admittance
+    const int k = q - A.n_slots;
+    out[(size_t)(2 * A.n_slots + k) * GS_LANES] = lp_line_y(A, b, k);
+    return;
+  }
+  double2 e0 = make_double2(0.0, 0.0), e1 = make_double2(0.0, 0.0);
+  if (A.has[q]) {
+    const double2 yp = lp_ybus(A, b, q);                   // Y(s, parent)
+    if (A.newton) { e0 = yp; e1 = lp_ybus(A, b, A.n_slots + q); }
+    else {                                                 // branch admittance = -Y_ip; z = 1 / y (plan.cpp)
+      const double yr = -yp.x, yi = -yp.y, yd = yr * yr + yi * yi;
+      e0 = make_double2(yr / yd, -yi / yd); e1 = make_double2(yr, yi);
+    }
+  }
+  out[(size_t)q * GS_LANES] = e0;
+  out[(size_t)(A.n_slots + q) * GS_LANES] = e1;
+}
+

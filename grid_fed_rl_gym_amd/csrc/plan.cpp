@@ -825,6 +825,69 @@ bool flat_newton_map(const HostTopology& ht, int tiles, int steps, std::vector<d
   return true;
 }
 
+// ---- per-instance line impedances: only the second-generation radial members take them (their topology tables stay valid; the
+// instance's numbers come from gs_k_line_params).  The branch entry Y(s, parent) and the diagonal Y(s, s) of every slot that has
+// one in the shared tables, as the line-order lists of topology.cpp's add() calls that reach it.
+std::string plan_line_params(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, GsPlan& p) {
+  const bool ok = p.step == StepMember::fbs_flow2s || p.step == StepMember::fbs_flow2h || p.step == StepMember::fbs_flow2x ||
+                  p.step == StepMember::nr_flow2s || p.step == StepMember::nr_flow2;
+  if (!ok) {
+    std::string why = !p.flow2_why.empty() ? p.flow2_why : !p.mesh_why.empty() ? p.mesh_why
+                    : p.step == StepMember::nr_mesh2 ? "a meshed network (nr_mesh2)"
+                    : cfg.solver_kind == GS_SOLVER_FBS && cfg.fbs_warm_start ? "warm start"
+                    : cfg.solver_kind == GS_SOLVER_NR && cfg.jacobian_mode != GS_JACOBIAN_EXACT ? "as-coded Jacobian"
+                    : !ht.is_forest ? "a meshed network" : std::string("the step runs on ") + kSolveName[(int)p.solve];
+    return "per-instance line impedances need a second-generation radial step member: " + why;
+  }
+  const bool newton = p.step == StepMember::nr_flow2s || p.step == StepMember::nr_flow2;
+  const int nsl = ht.n + 3, m = ht.m;
+  p.pz_zero.assign((size_t)m, 0);
+  for (int k = 0; k < m; ++k) p.pz_zero[k] = std::hypot(topo.r[k], topo.x[k]) > 1e-12 ? 0 : 1;
+  p.pz_has.assign((size_t)nsl, 0);
+  for (int i = 0; i < ht.n; ++i)
+    if (i != ht.slack && ht.lvl_pos[i] >= 0 && ht.fbs_parent[i] >= 0) p.pz_has[i] = 1;
+  // the ops of one Ybus entry (a, c): add(i, j, -y), add(j, i, -y), add(i, i, y), add(j, j, y) of every line in order (topology.cpp)
+  auto ops_of = [&](int a, int c) {
+    for (int k = 0; k < m; ++k) {
+      if (ht.lyr[k] == 0.0 && ht.lyi[k] == 0.0) continue;
+      const int i = ht.lfrom[k], j = ht.lto[k];
+      if (i == a && j == c) p.pz_ops.push_back(2 * k + 1);
+      if (j == a && i == c) p.pz_ops.push_back(2 * k + 1);
+      if (a == c && i == a) p.pz_ops.push_back(2 * k);
+      if (a == c && j == a) p.pz_ops.push_back(2 * k);
+    }
+  };
+  p.pz_ops_ptr.assign((size_t)2 * nsl + 1, 0);
+  p.pz_ops.clear();
+  for (int list = 0; list < 2 * nsl; ++list) {
+    p.pz_ops_ptr[list] = (int32_t)p.pz_ops.size();
+    const int s = list % nsl;
+    if (s < ht.n && p.pz_has[s]) { if (list < nsl) ops_of(s, ht.fbs_parent[s]); else if (newton) ops_of(s, s); }
+  }
+  p.pz_ops_ptr[2 * nsl] = (int32_t)p.pz_ops.size();
+  return "";
+}
+
+std::string gs_check_line_impedances(const gs_topology& topo, int batch, const double* r_inst, const double* x_inst, const uint8_t* mask) {
+  if (!r_inst || !x_inst) return "line impedances: r and x go together";
+  char msg[256];
+  for (int b = 0; b < batch; ++b) {
+    if (mask && !mask[b]) continue;
+    for (int k = 0; k < topo.m; ++k) {
+      const double r = r_inst[(size_t)b * topo.m + k], x = x_inst[(size_t)b * topo.m + k];
+      if (!std::isfinite(r) || !std::isfinite(x)) snprintf(msg, sizeof msg, "line impedances: instance %d line %d is not finite", b, k);
+      else if (!(r >= 0.0)) snprintf(msg, sizeof msg, "line impedances: instance %d line %d has r < 0", b, k);
+      else if (!(std::hypot(topo.r[k], topo.x[k]) > 1e-12)) {
+        if (r == topo.r[k] && x == topo.x[k]) continue;
+        snprintf(msg, sizeof msg, "line impedances: instance %d line %d: a line of zero nominal impedance keeps its nominal r, x", b, k);
+      } else if (!(std::hypot(r, x) > 1e-12)) snprintf(msg, sizeof msg, "line impedances: instance %d line %d has zero impedance", b, k);
+      else continue;
+      return msg;
+    }
+  }
+  return "";
+}
+
 std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, int batch, int cus, GsPlan& p) {
   p.B = batch; p.Bp = (batch + 63) / 64 * 64; p.groups = p.Bp / 64;
   int W = cfg.waves_per_group;
@@ -843,6 +906,12 @@ std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTop
   plan_rows(ht, p);
   plan_work_lists(ht, p);
   plan_second_gen(topo, cfg, ht, auto_w, p);
+  {
+    const bool nr2 = p.step == StepMember::nr_flow2s || p.step == StepMember::nr_flow2 || p.step == StepMember::nr_mesh2;
+    p.pz = topo.line_r_inst != nullptr;
+    p.nr_flat = nr2 && p.f2_npos > 0 && !getenv("GS_NR_NO_FLAT") && !p.pz;
+    if (p.pz && (why = plan_line_params(topo, cfg, ht, p)).empty() == false) { p.err_code = GS_E_TOPOLOGY; return why; }
+  }
   if (ht.has_lu) plan_lu_schedule(ht, p);
   if (p.solve == SolveMember::nr_dense_mfma && !(why = plan_dense(cfg, ht, cus, p)).empty()) return why;
 #if defined(GS_BUILD_EXPERIMENTS)
@@ -873,12 +942,13 @@ void gs_plan_format(const GsPlan& p, const HostTopology& ht, char* buf, int bufl
            "\"rows_per_group\": %d, \"slab_bytes\": %zu, \"obs_dim\": %d, \"action_dim\": %d, "
            "\"instances_per_workgroup\": %d, \"workgroups\": %d, \"step_lds_bytes\": %zu, \"step_launches\": %d, \"solve_kernel\": \"%s\", \"flow2\": \"%s\", "
            "\"mesh2\": \"%s\", \"mesh_levels\": %d, \"mesh_rows\": %d, \"mesh_message_units\": %d, \"mesh_messages\": %d, \"mesh_accumulators\": %d, "
-           "\"dense_form\": \"%s\", \"dense_workgroups\": %d, \"dense_lds_bytes\": %zu}",
+           "\"dense_form\": \"%s\", \"dense_workgroups\": %d, \"dense_lds_bytes\": %zu, \"per_instance_z\": %d, \"nr_flat_start_table\": %d}",
            f2 ? kStepName[(int)p.step] : kSolveName[(int)p.solve], p.n, p.m, ht.nnz, ht.is_forest ? "true" : "false", ht.n_levels,
            ht.max_level_width, ht.lu_n_slots, ht.lu_n_orig, (long long)ht.lu_n_pairs, f2 ? p.f2_nw : p.W, p.groups,
            p.R.total, (size_t)p.groups * p.R.total * GS_LANES * sizeof(double), p.obs_dim, p.action_dim,
            f2 ? p.f2_iw : 64, f2 ? (64 / p.f2_iw) * p.groups : p.groups, f2 ? (size_t)p.F2.lds_bytes : p.dyn_lds + 24576, p.split_ok ? 2 : 1,
            kSolveName[(int)p.solve], f2 ? "on" : (p.flow2_why.empty() ? "n/a" : p.flow2_why.c_str()),
            p.step == StepMember::nr_mesh2 ? "on" : (p.mesh_why.empty() ? "n/a" : p.mesh_why.c_str()), p.mesh_levels, p.mesh_rows, p.mesh_units,
-           p.mesh_messages, p.mesh_accs, dense ? (p.dense_blockrow ? "block_row" : "panel") : "n/a", dense ? p.dense_grid : 0, dense ? p.dense_lds : (size_t)0);
+           p.mesh_messages, p.mesh_accs, dense ? (p.dense_blockrow ? "block_row" : "panel") : "n/a", dense ? p.dense_grid : 0, dense ? p.dense_lds : (size_t)0,
+           p.pz ? 1 : 0, p.nr_flat ? 1 : 0);
 }

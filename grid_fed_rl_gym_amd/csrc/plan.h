@@ -70,12 +70,19 @@ struct GsPlan {
   std::vector<int32_t> ipack; std::vector<double> dpack;                      // GsSparseArgs::ipack / dpack
 #endif
 
+  // per-instance line impedances (gs_topology::line_r_inst / line_x_inst): the step member's PZ kernels, the tables of
+  // gs_k_line_params (GsLineParamArgs); nr_flat: Newton-Raphson's flat-start table is captured (gs_create) and read
+  bool pz = false, nr_flat = false;
+  std::vector<int32_t> pz_ops_ptr, pz_ops; std::vector<uint8_t> pz_has, pz_zero;
+
   bool second_gen() const { return step != StepMember::none; }
 };
 
 // Plans a handle of `batch` instances for a device of `cus` compute units.  Returns "" or the rejection message (out.err_code:
 // its GS_E_* code).  Reads the GS_* switches of gs_internal.h.
 std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, int batch, int cus, GsPlan& out);
+// "" or why per-instance impedances r_inst / x_inst [B][m] break the rules of gs_topology (rows where mask[b] != 0, or all)
+std::string gs_check_line_impedances(const gs_topology& topo, int batch, const double* r_inst, const double* x_inst, const uint8_t* mask);
 // gs_describe's JSON for a handle with this plan
 void gs_plan_format(const GsPlan& p, const HostTopology& ht, char* buf, int buflen);
 // GsF2Tables::mesh_w of an all-PQ network (see plan.cpp); false: J0 singular or the sizes do not fit

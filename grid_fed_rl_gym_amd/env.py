@@ -66,7 +66,8 @@ class BatchedGridEnvironment:
                  tolerance: float = 1e-6, max_iterations: int = 50, acceleration_factor: float = 1.0,
                  linear_solver: str = "auto", power_base: Optional[float] = None, device: int = 0,
                  first_instance: int = 0, waves_per_group: int = 0, warm_start: bool = False,
-                 pinned_host_buffers: bool = False, recycle_host_buffers: bool = True, obs_dtype: Any = np.float64, **kwargs: Any) -> None:
+                 pinned_host_buffers: bool = False, recycle_host_buffers: bool = True, obs_dtype: Any = np.float64,
+                 line_impedances: Optional[Tuple[Any, Any]] = None, **kwargs: Any) -> None:
         spec = feeder if isinstance(feeder, FeederSpec) else flatten_feeder(feeder)
         if renewable_sources is not None:
             keep = [g for g in range(spec.n_gens)
@@ -104,7 +105,10 @@ class BatchedGridEnvironment:
                                f_min=float(frequency_limits[0]), f_max=float(frequency_limits[1]),
                                safety_penalty=self.safety_penalty, power_base=self.power_base,
                                waves_per_group=int(waves_per_group), fbs_warm_start=int(bool(warm_start) and solver == "fbs"))
-        self._h = _lib.Handle(spec, cfg, self.num_envs, device, first_instance)
+        # line_impedances=(r, x), [num_envs, m] per unit: every instance solves on its own line data (domain randomisation of the
+        # network; gs_topology::line_r_inst / line_x_inst) -- served by the second-generation radial step members
+        pz = None if line_impedances is None else _lib.check_line_impedances(spec, line_impedances[0], line_impedances[1], self.num_envs)
+        self._h = _lib.Handle(spec, cfg, self.num_envs, device, first_instance, line_impedances=pz)
         # obs_dtype=np.float32 (opt-in): step() returns the observation block in the dtype the reference DECLARES for its observation
         # space (grid_env.py:346) -- rounded on the device, half the bytes over PCIe; reset(), step_device() and the rollout collector
         # stay float64, and so does every parity test
@@ -231,6 +235,26 @@ class BatchedGridEnvironment:
     def last_solution(self) -> Dict[str, np.ndarray]:
         """The load-flow solution of the last step as it stands on the device (PowerFlowSolution fields, batched)."""
         return self._h.download_solution()
+
+    def set_line_impedances(self, r: Any, x: Any, mask: Optional[Any] = None) -> None:
+        """New per-instance line impedances ([num_envs, m] each) for the instances of ``mask`` ([num_envs] bool, None = all),
+        in effect from the next step.  Not environment state: reset() and set_state() leave them alone.  Only on an environment
+        created with ``line_impedances`` (otherwise the library's GS_E_STATE, as PowerFlowError)."""
+        if not getattr(self._h, "_pz", False):
+            self._h.set_line_impedances(np.zeros((self.num_envs, self.spec.m)), np.zeros((self.num_envs, self.spec.m)), mask)
+        rows = np.ones(self.num_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
+        if rows.shape != (self.num_envs,):
+            raise ValueError(f"mask must have shape ({self.num_envs},)")
+        r = np.ascontiguousarray(r, dtype=np.float64); x = np.ascontiguousarray(x, dtype=np.float64)
+        if r.shape != (self.num_envs, self.spec.m) or x.shape != (self.num_envs, self.spec.m):
+            raise ValueError(f"line impedances: r and x must have shape {(self.num_envs, self.spec.m)}")
+        _lib.check_line_impedances(self.spec, r[rows], x[rows], int(rows.sum()))
+        self._h.set_line_impedances(r, x, None if mask is None else rows)
+
+    @property
+    def line_impedances(self) -> Tuple[np.ndarray, np.ndarray]:
+        """Host copies (r, x), [num_envs, m] each, of the per-instance line impedances the device solves on."""
+        return self._h.get_line_impedances()
 
     @property
     def handle(self) -> "_lib.Handle":

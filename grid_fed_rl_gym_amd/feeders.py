@@ -505,3 +505,19 @@ def feeder_to_dict(spec: FeederSpec) -> Dict[str, Any]:
                    "power_factor": float(spec.load_pf[l])} for l in range(spec.n_loads)],
         "generators": gens,
     }
+
+
+def randomized_line_impedances(spec: FeederSpec, num_envs: int, rel: float = 0.1, seed: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-instance line impedances for domain randomisation of the network: (r, x), [num_envs, m] each, the nominal values times
+    seeded multipliers U(1 - rel, 1 + rel), drawn independently per instance, line and component.  Lines of zero nominal
+    impedance stay exactly nominal (BatchedGridEnvironment(line_impedances=...) requires it)."""
+    if not (0.0 <= rel < 1.0):
+        raise ValueError("rel must be in [0, 1)")
+    rng = np.random.default_rng(seed)
+    shape = (int(num_envs), int(spec.m))
+    r0, x0 = np.asarray(spec.r, dtype=np.float64), np.asarray(spec.x, dtype=np.float64)
+    r = r0[None, :] * rng.uniform(1.0 - rel, 1.0 + rel, shape)
+    x = x0[None, :] * rng.uniform(1.0 - rel, 1.0 + rel, shape)
+    zero = ~(np.hypot(r0, x0) > 1e-12)
+    r[:, zero] = r0[zero]; x[:, zero] = x0[zero]
+    return np.ascontiguousarray(r), np.ascontiguousarray(x)

@@ -100,9 +100,12 @@ class ShardedGridEnvironment:
         self.transport, self.group = transport, group
         if transport in ("rccl", "loopback") and self.global_num_envs % self.world != 0:
             raise ValueError("the RCCL all-gather needs equal shards (global_num_envs % world == 0)")
+        li = env_kwargs.pop("line_impedances", None)
+        if li is not None:      # global [global_num_envs, m] arrays: this shard's rows
+            li = (np.asarray(li[0])[self.start:self.stop], np.asarray(li[1])[self.start:self.stop])
         self.env = BatchedGridEnvironment(feeder, num_envs=self.stop - self.start,
                                           device=self.rank if device is None else device,
-                                          first_instance=self.start, **env_kwargs)
+                                          first_instance=self.start, line_impedances=li, **env_kwargs)
         self._comm = False
 
     def init_rccl(self, unique_id: Any = None) -> None:

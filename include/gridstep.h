@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 1
+#define GS_ABI_VERSION 2
 
 enum {
   GS_OK = 0,
@@ -89,6 +89,16 @@ typedef struct gs_topology {
   const double* bat_cap;          /* [n_bats] dynamics.py:178 */
   const double* bat_rating;       /* [n_bats] dynamics.py:179 */
   const double* bat_eff;          /* [n_bats] dynamics.py:180 */
+  /* Per-instance line impedances (domain randomisation of the network): [batch][m] per unit, or both NULL.  Both non-NULL makes a
+   * per-instance-impedance handle: instance b solves on its own Ybus (power_flow.py:48-73) and reports its own line flows
+   * (:329-358), built from line_r_inst[b] / line_x_inst[b]; exactly one non-NULL is GS_E_INVALID.  r / x above stay mandatory:
+   * they define the topology and which lines are zero-impedance.  Every value must be finite with r >= 0; a line whose nominal
+   * hypot(r, x) <= 1e-12 must keep its nominal values in every instance (it keeps its open-circuit / epsilon treatment,
+   * power_flow.py:63), every other line needs hypot(r, x) > 1e-12 -- so islanding never depends on the instance.  Only a
+   * second-generation radial step member serves such a handle (gs_describe "kernel": fbs_flow2s / fbs_flow2h / fbs_flow2x /
+   * nr_flow2s / nr_flow2, "per_instance_z": 1); anything else is GS_E_TOPOLOGY.  gs_solve / gs_solve_device are GS_E_STATE on it. */
+  const double* line_r_inst;
+  const double* line_x_inst;
 } gs_topology;
 
 /* Solver + environment configuration.  Replaces the constructor kwargs of
@@ -176,6 +186,13 @@ int gs_describe(const gs_handle* h, char* buf, int32_t buflen);
  * host alone (no device needed; the GS_* switches as for gs_create) */
 int gs_plan_describe(const gs_topology* topo, const gs_config* cfg, int32_t batch, int32_t cus, char* buf, int32_t buflen);
 int gs_synchronize(gs_handle* h);
+/* Per-instance line impedances of a handle created with gs_topology::line_r_inst / line_x_inst (else GS_E_STATE): r / x [B][m] per
+ * unit, mask [B] (!= 0: take this instance's row) or NULL (all).  The selected instances solve on the new values from the next
+ * gs_step / rollout step on; the rules of gs_topology apply (GS_E_INVALID, handle unchanged).  The values are not environment
+ * state: gs_reset, the in-place resets of gs_rollout and gs_set_state leave them alone. */
+int gs_set_line_impedances(gs_handle* h, const double* r, const double* x, const uint8_t* mask);
+/* the values the handle holds, [B][m] each (either pointer may be NULL); GS_E_STATE on a handle without per-instance impedances */
+int gs_get_line_impedances(const gs_handle* h, double* r, double* x);
 
 /* ---- solver plug point: NewtonRaphsonSolver.solve (power_flow.py:89-211) ---------------
  * P_spec[B][n] is the net specified injection (generation - load, what :112-121 builds from
@@ -196,7 +213,8 @@ int gs_download_solution(gs_handle* h, const gs_solution_view* out);
  * renewables, battery powers: grid_env.py:683-720).  total_load / total_gen: [B] sums of the dict values in the
  * caller's dict order, or NULL = summed over the buses in index order (host arrays) / in the order the
  * reference's dicts are filled (device state).  applied_out: NULL or [B], 1 where the answer was replaced;
- * n_applied: NULL or their count.  Follow with gs_download_solution / gs_checks_run / gs_download_step as usual. */
+ * n_applied: NULL or their count.  Follow with gs_download_solution / gs_checks_run / gs_download_step as usual.
+ * On a per-instance-impedance handle every instance's angles use its own line reactances (gs_set_line_impedances). */
 int gs_fallback_linear(gs_handle* h, const double* load_w, const double* gen_w, const double* total_load,
                        const double* total_gen, const uint8_t* mask, uint8_t* applied_out, int32_t* n_applied);
 
