@@ -320,23 +320,12 @@ void launch_linear(gs_handle* h) {
 
 int launch_solve(gs_handle* h) {
   LaunchTimer lt(h, GS_K_SOLVE);
-  dim3 grid(h->groups), block(64 * h->W);
-#define GS_SOLVE(k) hipLaunchKernelGGL(k, grid, block, h->dyn_lds, h->stream, h->T, h->R, h->SC, h->slab, h->B)
-  switch (h->solve) {
-    case SolveMember::nr_tree: GS_SOLVE(gs_k_nr_tree); break;
-    case SolveMember::nr_tree_lds: GS_SOLVE(gs_k_nr_tree_lds); break;
-    case SolveMember::nr_sparse_lu: GS_SOLVE(gs_k_nr_lu); break;
-    case SolveMember::nr_dense_pivot: GS_SOLVE(gs_k_nr_dense); break;
-    case SolveMember::fbs: GS_SOLVE(gs_k_fbs); break;
-    case SolveMember::fbs_lds: GS_SOLVE(gs_k_fbs_lds); break;
-    case SolveMember::fbs_flow: GS_SOLVE(gs_k_fbs_flow); break;
-    case SolveMember::nr_dense_mfma:
-    case SolveMember::nr_sparse_lds:
-      launch_linear(h);
-      GS_SOLVE(gs_k_posts_nr_dmfma);
-      break;
+  GsSolveFn k = gs_solve_kernels[(int)h->solve].solve;
+  if (!k) {         // nr_dense_mfma / nr_sparse_lds: the linear solve, then line flows, losses and angles
+    launch_linear(h);
+    k = gs_k_posts_nr_dmfma;
   }
-#undef GS_SOLVE
+  hipLaunchKernelGGL(k, dim3(h->groups), dim3(64 * h->W), h->dyn_lds, h->stream, h->T, h->R, h->SC, h->slab, h->B);
   HIPCHK(h, hipGetLastError());
   return GS_OK;
 }
@@ -368,8 +357,8 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
     const GsFusedChecks fc = fused_checks_args(h);
     const GsRolloutStep rsv = rs ? *rs : GsRolloutStep{};
     if (h->second_gen()) {        // 64 / IW workgroups per 64-instance slab group, each with its own IW instances
-      const int per_group = 64 / h->f2_iw, n_wg = h->groups * per_group;
-      const dim3 b2(64 * h->f2_nw);
+      const int per_group = 64 / h->f2().iw, n_wg = h->groups * per_group;
+      const dim3 b2(64 * h->f2().nw);
       // (two half-grid launches on two streams, see gs_handle::forked; the halves are whole 64-instance slab groups)
       // (per-launch event pairs, gs_timing_enable(1), bracket ONE launch on the main stream: the step stays whole then)
       const bool split = h->split_ok && !h->timing;
@@ -381,62 +370,28 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
       }
       GsF2Tables f2a = h->F2, f2b = h->F2;
       f2a.wg_offset = 0; f2b.wg_offset = n_first;
-#define GS_F2(k) do { hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv); \
-                      if (n_first < n_wg) hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv); } while (0)
-#define GS_F2_PAIR(kc, k) do { if (fc.enabled) GS_F2(kc); else GS_F2(k); } while (0)
-      if (h->pz) {           // per-instance line impedances: the members' PZ kernels, the entries behind the argument block
-        const double* pz = h->LP.pz;
-#define GS_F2Z(k) do { hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz); \
-                       if (n_first < n_wg) hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz); } while (0)
-#define GS_F2Z_PAIR(kc, k) do { if (fc.enabled) GS_F2Z(kc); else GS_F2Z(k); } while (0)
-        switch (h->step) {
-          case StepMember::fbs_flow2s: GS_F2Z_PAIR(gs_k_stepc_fbs_flow2s_pz, gs_k_step_fbs_flow2s_pz); break;
-          case StepMember::fbs_flow2h: GS_F2Z_PAIR(gs_k_stepc_fbs_flow2h_pz, gs_k_step_fbs_flow2h_pz); break;
-          case StepMember::fbs_flow2x: GS_F2Z_PAIR(gs_k_stepc_fbs_flow2x_pz, gs_k_step_fbs_flow2x_pz); break;
-          case StepMember::nr_flow2s: GS_F2Z_PAIR(gs_k_stepc_nr_flow2s_pz, gs_k_step_nr_flow2s_pz); break;
-          case StepMember::nr_flow2: GS_F2Z_PAIR(gs_k_stepc_nr_flow2_pz, gs_k_step_nr_flow2_pz); break;
-          default: return fail(h, GS_E_STATE, "per-instance line impedances: no PZ kernel for this member");
-        }
-#undef GS_F2Z_PAIR
-#undef GS_F2Z
-        HIPCHK(h, hipGetLastError());
+      // pz...: the PZ kernels' pointer to the per-instance line impedances, behind the argument block
+      auto launch = [&](auto k, auto... pz) -> int {
+        if (!k) return fail(h, GS_E_STATE, "%s: no such step kernel", h->f2().name);
+        hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz...);
+        if (n_first < n_wg)
+          hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz...);
         return GS_OK;
-      }
-      switch (h->step) {
-        case StepMember::fbs_flow2s: GS_F2_PAIR(gs_k_stepc_fbs_flow2s, gs_k_step_fbs_flow2s); break;
-        case StepMember::fbs_flow2h: GS_F2_PAIR(gs_k_stepc_fbs_flow2h, gs_k_step_fbs_flow2h); break;
-        case StepMember::fbs_flow2x: GS_F2_PAIR(gs_k_stepc_fbs_flow2x, gs_k_step_fbs_flow2x); break;
-#if defined(GS_BUILD_EXPERIMENTS)
-        case StepMember::fbs_flow2: GS_F2_PAIR(gs_k_stepc_fbs_flow2, gs_k_step_fbs_flow2); break;
-#endif
-        case StepMember::nr_flow2s: GS_F2_PAIR(gs_k_stepc_nr_flow2s, gs_k_step_nr_flow2s); break;
-        case StepMember::nr_flow2: GS_F2_PAIR(gs_k_stepc_nr_flow2, gs_k_step_nr_flow2); break;
-        case StepMember::nr_mesh2: GS_F2_PAIR(gs_k_stepc_nr_mesh2, gs_k_step_nr_mesh2); break;
-        case StepMember::none: break;
-      }
-#undef GS_F2_PAIR
-#undef GS_F2
+      };
+      const GsStepKernels& k = gs_step_kernels[(int)h->step];
+      const int rc = h->pz ? launch(fc.enabled ? k.pz.stepc : k.pz.step, (const double*)h->LP.pz) : launch(fc.enabled ? k.plain.stepc : k.plain.step);
+      if (rc) return rc;
       HIPCHK(h, hipGetLastError());
       return GS_OK;
     }
+    const GsStepFns<GsStepFn> k = gs_solve_kernels[(int)h->solve].step;
 #define GS_STEP(k) hipLaunchKernelGGL(k, grid, block, h->dyn_lds, h->stream, h->T, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc)
-#define GS_STEP_PAIR(kc, k) do { if (fc.enabled) GS_STEP(kc); else GS_STEP(k); } while (0)
-    switch (h->solve) {
-      case SolveMember::nr_tree: GS_STEP_PAIR(gs_k_stepc_nr_tree, gs_k_step_nr_tree); break;
-      case SolveMember::nr_tree_lds: GS_STEP_PAIR(gs_k_stepc_nr_tree_lds, gs_k_step_nr_tree_lds); break;
-      case SolveMember::nr_sparse_lu: GS_STEP_PAIR(gs_k_stepc_nr_lu, gs_k_step_nr_lu); break;
-      case SolveMember::nr_dense_pivot: GS_STEP_PAIR(gs_k_stepc_nr_dense, gs_k_step_nr_dense); break;
-      case SolveMember::fbs: GS_STEP_PAIR(gs_k_stepc_fbs, gs_k_step_fbs); break;
-      case SolveMember::fbs_lds: GS_STEP_PAIR(gs_k_stepc_fbs_lds, gs_k_step_fbs_lds); break;
-      case SolveMember::fbs_flow: GS_STEP_PAIR(gs_k_stepc_fbs_flow, gs_k_step_fbs_flow); break;
-      case SolveMember::nr_dense_mfma:      // prologue | the linear solve, one workgroup / wavefront per instance | epilogue + observation pack
-      case SolveMember::nr_sparse_lds:
-        GS_STEP(gs_k_pre_nr_dmfma);
-        launch_linear(h);
-        GS_STEP_PAIR(gs_k_postc_nr_dmfma, gs_k_post_nr_dmfma);
-        break;
+    if (k.step) GS_STEP(fc.enabled ? k.stepc : k.step);
+    else {        // nr_dense_mfma / nr_sparse_lds: prologue | the linear solve, one workgroup / wavefront per instance | epilogue + observation pack
+      GS_STEP(gs_k_pre_nr_dmfma);
+      launch_linear(h);
+      GS_STEP(fc.enabled ? gs_k_postc_nr_dmfma : gs_k_post_nr_dmfma);
     }
-#undef GS_STEP_PAIR
 #undef GS_STEP
     HIPCHK(h, hipGetLastError()); }
   return GS_OK;     // the observation block was written by the step kernel itself
@@ -541,7 +496,7 @@ int flat_start_captures(gs_handle* h) {
     hipLaunchKernelGGL(gs_k_fill_rows, dim3(1), dim3(64), 0, h->stream, R.P.base, 2, ht.n, R.total, h->slab, -0.01);
     hipLaunchKernelGGL(gs_k_fill_rows, dim3(1), dim3(64), 0, h->stream, R.Q.base, 2, ht.n, R.total, h->slab, 0.0);
     GsSolveCfg once = h->SC; once.max_iterations = 1; once.stamps = nullptr;
-    hipLaunchKernelGGL(gs_k_nr_lu, dim3(1), dim3(64 * h->W), h->dyn_lds, h->stream, h->T, h->R, once, h->slab, 1);
+    hipLaunchKernelGGL(gs_solve_kernels[(int)h->solve].solve, dim3(1), dim3(64 * h->W), h->dyn_lds, h->stream, h->T, h->R, once, h->slab, 1);
     if (ht.lu_n_slots > 0)
       hipLaunchKernelGGL(gs_k_gather_lane, dim3((4 * ht.lu_n_slots + 255) / 256), dim3(256), 0, h->stream, R.LU, 4 * ht.lu_n_slots, 0, h->slab, tab);
     hipLaunchKernelGGL(gs_k_gather_lane, dim3((4 * ht.n + 255) / 256), dim3(256), 0, h->stream, R.LUD, 4 * ht.n, 0, h->slab, tab + (size_t)4 * ht.lu_n_slots);
@@ -561,19 +516,15 @@ int flat_start_captures(gs_handle* h) {
   // the shared Ybus)
   if (h->nr_flat) {
     double* tab = nullptr;
-    if ((rc = dev_alloc(h, &tab, (size_t)h->f2_npos * 16))) return rc;
-    if (hipMemset(tab, 0, (size_t)h->f2_npos * 16 * sizeof(double)) != hipSuccess ||
+    const size_t npos = h->f2().positions();
+    if ((rc = dev_alloc(h, &tab, npos * 16))) return rc;
+    if (hipMemset(tab, 0, npos * 16 * sizeof(double)) != hipSuccess ||
         hipMemset(h->d_in, 0, h->in_doubles * sizeof(double)) != hipSuccess) return fail(nullptr, GS_E_HIP, "hipMemset failed");      // (d_in: zero actions for the capture step)
     GsF2Tables cap = h->F2; cap.nrflat = tab; cap.nrflat_mode = 1; cap.wg_offset = 0;
     GsPackArgs pa{}; GsFusedChecks fc{}; GsRolloutStep rsv{};
     GsSolveCfg sc = h->SC; sc.stamps = nullptr;
-    const dim3 b2(64 * h->f2_nw);
-    const int Bc = std::min(h->B, h->f2_iw);
-#define GS_CAPTURE(k) hipLaunchKernelGGL(k, dim3(1), b2, h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc, h->EC, h->slab, Bc, h->d_in, h->total_load, pa, fc, rsv)
-    if (h->step == StepMember::nr_mesh2) GS_CAPTURE(gs_k_step_nr_mesh2);
-    else if (h->step == StepMember::nr_flow2s) GS_CAPTURE(gs_k_step_nr_flow2s);
-    else GS_CAPTURE(gs_k_step_nr_flow2);
-#undef GS_CAPTURE
+    hipLaunchKernelGGL(gs_step_kernels[(int)h->step].plain.step, dim3(1), dim3(64 * h->f2().nw), h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc,
+                       h->EC, h->slab, std::min(h->B, h->f2().iw), h->d_in, h->total_load, pa, fc, rsv);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
         hipMemset(h->slab, 0, (size_t)R.total * GS_LANES * sizeof(double)) != hipSuccess)
       return fail(nullptr, GS_E_HIP, "Newton-Raphson: flat-start table");
@@ -632,32 +583,19 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     return bail(fail(nullptr, GS_E_HIP, "hipStreamCreate failed"));
 
   {
-    const void* fns[] = {(const void*)gs_k_nr_tree, (const void*)gs_k_step_nr_tree, (const void*)gs_k_nr_tree_lds,
-                         (const void*)gs_k_step_nr_tree_lds, (const void*)gs_k_nr_lu, (const void*)gs_k_step_nr_lu,
-                         (const void*)gs_k_nr_dense, (const void*)gs_k_step_nr_dense, (const void*)gs_k_fbs,
-                         (const void*)gs_k_step_fbs, (const void*)gs_k_fbs_lds, (const void*)gs_k_step_fbs_lds,
-                         (const void*)gs_k_stepc_nr_tree, (const void*)gs_k_stepc_nr_tree_lds, (const void*)gs_k_stepc_nr_lu,
-                         (const void*)gs_k_stepc_nr_dense, (const void*)gs_k_stepc_fbs, (const void*)gs_k_stepc_fbs_lds,
-                         (const void*)gs_k_fbs_flow, (const void*)gs_k_step_fbs_flow, (const void*)gs_k_stepc_fbs_flow,
-                         (const void*)gs_k_pre_nr_dmfma, (const void*)gs_k_post_nr_dmfma, (const void*)gs_k_postc_nr_dmfma,
-                         (const void*)gs_k_posts_nr_dmfma};
-    // the attribute is per function, i.e. shared by every handle of the process: always raise it to
-    // the most any handle may ask for (160 KB per workgroup minus the 24 KB static block)
+    // the attribute is per function, i.e. shared by every handle of the process: always raise it to the most any handle may ask
+    // for -- the first generation: 160 KB per workgroup minus the 24 KB static block; the second has no static LDS
+    auto raise = [](auto f, int bytes) { return !f || hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess; };
     const int max_dyn = 160 * 1024 - 24576;
-    for (const void* f : fns)
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, max_dyn) != hipSuccess)
-        return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", max_dyn));
-    for (const void* f : {
+    bool ok = raise(gs_k_pre_nr_dmfma, max_dyn) && raise(gs_k_post_nr_dmfma, max_dyn) && raise(gs_k_postc_nr_dmfma, max_dyn) && raise(gs_k_posts_nr_dmfma, max_dyn);
+    for (const GsSolveKernels& k : gs_solve_kernels) ok = ok && raise(k.solve, max_dyn) && raise(k.step.step, max_dyn) && raise(k.step.stepc, max_dyn);
+    if (!ok) return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", max_dyn));
+    for (const GsStepKernels& k : gs_step_kernels)
+      ok = ok && raise(k.plain.step, 160 * 1024) && raise(k.plain.stepc, 160 * 1024) && raise(k.pz.step, 160 * 1024) && raise(k.pz.stepc, 160 * 1024);
 #if defined(GS_BUILD_EXPERIMENTS)
-                          (const void*)gs_k_step_fbs_flow2, (const void*)gs_k_stepc_fbs_flow2, (const void*)gs_k_nr_sparse_lds,
+    ok = ok && raise(gs_k_nr_sparse_lds, 160 * 1024);
 #endif
-                          (const void*)gs_k_step_nr_flow2,
-                          (const void*)gs_k_stepc_nr_flow2, (const void*)gs_k_step_fbs_flow2s, (const void*)gs_k_stepc_fbs_flow2s,
-                          (const void*)gs_k_step_nr_flow2s, (const void*)gs_k_stepc_nr_flow2s, (const void*)gs_k_step_fbs_flow2h,
-                          (const void*)gs_k_stepc_fbs_flow2h, (const void*)gs_k_step_fbs_flow2x, (const void*)gs_k_stepc_fbs_flow2x,
-                          (const void*)gs_k_step_nr_mesh2, (const void*)gs_k_stepc_nr_mesh2})      // no static LDS in these
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", 160 * 1024));
+    if (!ok) return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", 160 * 1024));
     hipError_t e = hipFuncSetAttribute((const void*)gs_k_nr_dense_mfma2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
 #if defined(GS_BUILD_EXPERIMENTS)
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gs_k_nr_dense_mfma, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
@@ -716,7 +654,7 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     GsLineParamArgs& A = h->LP;
     const size_t Bm = (size_t)h->B * h->m;
     h->inst_r.assign(topo->line_r_inst, topo->line_r_inst + Bm); h->inst_x.assign(topo->line_x_inst, topo->line_x_inst + Bm);
-    A.B = h->B; A.groups = h->groups; A.n_slots = ht.n + 3; A.m = ht.m; A.newton = (h->step == StepMember::nr_flow2s || h->step == StepMember::nr_flow2) ? 1 : 0;
+    A.B = h->B; A.groups = h->groups; A.n_slots = ht.n + 3; A.m = ht.m; A.newton = h->f2().newton() ? 1 : 0;
     A.lyr_nom = T.lyr; A.lyi_nom = T.lyi;
     double *dr = nullptr, *dx = nullptr, *dpz = nullptr;
     const size_t n_pz = (size_t)h->groups * GS_PZ_NQ(A.n_slots, A.m) * GS_LANES * 2;

@@ -42,6 +42,16 @@
 #define GS_CONST
 #endif
 
+// The big kernels read their arguments where they use them, through a pointer to the argument block (`Block`: a struct that mirrors
+// the kernel's parameter list) that the compiler cannot see through.  Taken from the formal parameters, all scalar words are loaded
+// at the top of the kernel and, for lack of scalar registers, parked in vector lanes: a quarter of the vector instructions of a
+// second-generation step were v_writelane / v_readlane, in kernels bound by vector instruction issue (rocprofv3
+// SQ_ACTIVE_INST_VALU: 75 % of the launch); 250 to 340 spilled scalar registers in the first-generation step kernels.
+#define GS_ARGS_IN_PLACE(Block, name)                                                                                           \
+  const __attribute__((address_space(4))) char* ka_ = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr(); \
+  asm volatile("" : "+s"(ka_));                                                                                                \
+  const Block* name = (const Block*)ka_
+
 #if defined(__HIPCC__)
 // A lane's view of its group's slab rows, through a buffer descriptor.  Row r of the lane is at
 // group base + r * 512 B + lane * 8 B; with the descriptor holding the group base, a wave-uniform row index goes into
@@ -396,25 +406,10 @@ struct GsPackArgs {
 // phase issues half the instructions per workgroup, and there are twice as many workgroups.  What used to be
 // wave-uniform (bus index, impedance, child list, row index) is now uniform per HALF: it lives in vector registers,
 // loaded from the per-(wave, item, half) records below.
+// Each member's shape -- waves NW, items per sub-group NI, instances per workgroup IW -- is its row of kStepMembers (members.h).
 #define GS_F2_PITCH 33            /* 16-byte entries per LDS slot: 32 lanes + 1 (transposed reads conflict-free) */
-#define GS_F2_ITEMS 4             /* buses per half wave: 16 waves x 2 halves x 4 = 128 positions of the forest's preorder */
-#define GS_F2_WAVES 16
-#define GS_F2N_WAVES 8            /* the Newton-Raphson member of the family: 8 waves x 2 halves x 8 buses (its bus state needs the registers) */
-#define GS_F2N_ITEMS 8
-#define GS_F2S_IW 8               /* small feeders: 8 instances per workgroup, the eight sub-groups of a wavefront on eight buses */
-#define GS_F2H_IW 16       // half-size member: 16 instances per workgroup, two workgroups per CU
-#define GS_F2H_WAVES 8
-#define GS_F2H_ITEMS 4
-#define GS_F2X_WAVES 8        // wide member: 16 instances per workgroup, eight buses per sub-group (up to 256 buses)
-#define GS_F2X_ITEMS 8
-#define GS_F2S_WAVES 2            /* sweeps: 2 waves x 8 sub-groups x 1 bus = 16 positions */
-#define GS_F2S_ITEMS 1
-#define GS_F2NS_WAVES 4           /* Newton-Raphson: 4 waves x 1 item, each a group of 8 buses of one level (2 x 2: 124 M env-steps/s on config 2; 4 x 1: 147 M -- the load draws get waves of their own) */
-#define GS_F2NS_ITEMS 1
-#define GS_F2M_WAVES 4            /* the meshed Newton-Raphson member: 4 waves x up to 9 rows of 8 sub-groups */
-#define GS_F2M_ITEMS 10
 #define GS_F2_CHILDREN 8          /* children per bus in the Newton-Raphson kernel's LDS child tables */
-struct GsF2Rec {                  // one preorder position p = ((wave * 2 + half) * GS_F2_ITEMS + item); 96 bytes
+struct GsF2Rec {                  // one preorder position p = ((wave * (64 / IW) + sub-group) * NI + item); 96 bytes
   int32_t bus, parent, flags, last;         // slot indices; flags: bit0 active, bit1 root (parent is the slack bus); last: the bus at the LAST position of this bus's subtree
   int32_t nl, l0, l1, ng;                   // devices at the bus, reference accumulation order (grid_env.py:689-718)
   int32_t g0, g1, nb, b0;
@@ -462,7 +457,7 @@ enum {
 #define GS_MESH_F_NADJ_SHIFT 24
 
 struct GsF2Tables {
-  const GsF2Rec* recs;            // [GS_F2_WAVES * 2 * GS_F2_ITEMS]
+  const GsF2Rec* recs;            // [NW * (64 / IW) * NI] of the member (StepMemberRow::positions)
   const int32_t* anc;             // sweeps: [n_jump][n_slots] 2^r-th ancestor of every slot on its way to the slack, ZERO beyond;
                                   // Newton-Raphson: child buses [n][8], child ring slots [n][8], child counts [n_slots], then at
                                   // pos_off (a multiple of 4) per position (bus, parent, own ring slot, parent's ring slot); n_anc_ints in all

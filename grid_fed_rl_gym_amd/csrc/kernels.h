@@ -2,68 +2,30 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gs_internal.h"
+#include <array>
 
-#define GS_DECLARE_KERNELS(name)                                                                               \
-  __global__ void gs_k_##name(GsTables T, GsRows R, GsSolveCfg C, double* __restrict__ slab, int B);           \
-  __global__ void gs_k_step_##name(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab,  \
-                                   int B, const double* __restrict__ actions, double total_load, GsPackArgs PA,        \
-                                   GsFusedChecks FC);                                                          \
-  __global__ void gs_k_stepc_##name(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, \
-                                    int B, const double* __restrict__ actions, double total_load, GsPackArgs PA,       \
-                                    GsFusedChecks FC);
+#include "gs_internal.h"
+#include "members.h"
+
+// The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
+// such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
+// they launch the gs_k_*_nr_dmfma kernels below around their solver); the second (kernels_flow2.hip): step, stepc and their PZ
+// forms per StepMember.
+typedef void (*GsSolveFn)(GsTables T, GsRows R, GsSolveCfg C, double* slab, int B);
+typedef void (*GsStepFn)(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions, double total_load,
+                         GsPackArgs PA, GsFusedChecks FC);
+typedef void (*GsF2StepFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions,
+                           double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
+typedef void (*GsF2StepPzFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions,
+                             double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, const double* pz);
+template <class Fn> struct GsStepFns { Fn step = nullptr, stepc = nullptr; };      // the plain step and the step with the checks
+struct GsSolveKernels { GsSolveFn solve; GsStepFns<GsStepFn> step; };
+struct GsStepKernels { GsStepFns<GsF2StepFn> plain; GsStepFns<GsF2StepPzFn> pz; };
+extern const std::array<GsSolveKernels, (size_t)SolveMember::nr_sparse_lds + 1> gs_solve_kernels;
+extern const std::array<GsStepKernels, kStepMemberCount> gs_step_kernels;
 
 extern "C" {
-GS_DECLARE_KERNELS(nr_tree)
-GS_DECLARE_KERNELS(nr_tree_lds)
-GS_DECLARE_KERNELS(nr_lu)
-GS_DECLARE_KERNELS(nr_dense)
-GS_DECLARE_KERNELS(fbs)
-GS_DECLARE_KERNELS(fbs_lds)
-GS_DECLARE_KERNELS(fbs_flow)
-__global__ void gs_k_step_fbs_flow2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_step_fbs_flow2h(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_step_fbs_flow2x(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_stepc_fbs_flow2x(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_stepc_fbs_flow2h(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_stepc_fbs_flow2s(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_step_fbs_flow2s(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_stepc_nr_flow2s(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_step_nr_flow2s(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-
-__global__ void gs_k_stepc_fbs_flow2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                     const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_step_nr_flow2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                   const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_stepc_nr_flow2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-// per-instance line impedances (kernels_flow2.hip): the second-generation members with PZ = 1, and the kernel that derives their entries
-#define GS_DECLARE_F2_PZ(name)                                                                                                 \
-  __global__ void gs_k_step_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B, \
-                                        const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC,         \
-                                        GsRolloutStep RS, const double* __restrict__ pz);                                              \
-  __global__ void gs_k_stepc_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B, \
-                                         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC,        \
-                                         GsRolloutStep RS, const double* __restrict__ pz);
-GS_DECLARE_F2_PZ(fbs_flow2s)
-GS_DECLARE_F2_PZ(fbs_flow2h)
-GS_DECLARE_F2_PZ(fbs_flow2x)
-GS_DECLARE_F2_PZ(nr_flow2s)
-GS_DECLARE_F2_PZ(nr_flow2)
 __global__ void gs_k_line_params(GsLineParamArgs A);
-__global__ void gs_k_step_nr_mesh2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                   const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-__global__ void gs_k_stepc_nr_mesh2(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
-                                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
 __global__ void gs_k_pre_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                                   const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC);
 __global__ void gs_k_post_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,

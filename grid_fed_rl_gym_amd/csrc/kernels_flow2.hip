@@ -29,9 +29,12 @@
 #include <math.h>
 #include <limits.h>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/gridstep.h"
 #include "gs_internal.h"
+#include "kernels.h"
+#include "members.h"
 
 #define ROW(r) S[(size_t)(r) * GS_LANES]
 #include "env_device.h"
@@ -242,10 +245,9 @@ struct F2Stamp {
   }
 };
 
-// SOLVER: 0 forward/backward sweep, 1 Newton-Raphson.  NW wavefronts per workgroup, NI buses per half wave (NW * 2 * NI = 128
-// positions): the sweep kernel runs 16 x 4, Newton-Raphson -- whose bus state (voltage, the T and s of the elimination)
-// lives in registers across its two sweeps -- 8 x 8, i.e. twice the registers per wave.
-enum { F2_FBS = 0, F2_NR = 1, F2_NRM = 2 };      // NRM: Newton-Raphson on a meshed feeder (block LU with fill-in, mesh_schedule.h)
+// SOLVER: F2_FBS forward/backward sweep, F2_NR Newton-Raphson, F2_NRM Newton-Raphson on a meshed feeder.  NW wavefronts per
+// workgroup, NI buses per sub-group, IW instances per workgroup: the member's row of kStepMembers (members.h).  Newton-Raphson
+// keeps its bus state (voltage, the T and s of the elimination) in registers across its two sweeps: twice the registers per wave.
 // PZ = 1: per-instance line impedances (gs_internal.h GsLineParamArgs): the branch z / y, the Newton-Raphson (G, B) pairs and the
 // epilogue's line admittances come from `pz`, the instance's own values, instead of the handle's shared tables; PZ = 0 never reads it.
 template <int SOLVER, int CHK, int NW, int NI, int IW, int PZ = 0>
@@ -1788,67 +1790,61 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     atomicMax(&C.stamps[17 + 2 * bid], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 
-// The step kernels read their arguments where they use them, through a pointer to the argument block the compiler cannot see
-// through.  Taken from the formal parameters, all ~400 scalar words are loaded at the top of the kernel and, for lack of
-// scalar registers, parked in vector lanes: a quarter of the vector instructions of a step were v_writelane / v_readlane,
-// in kernels bound by vector instruction issue (rocprofv3 SQ_ACTIVE_INST_VALU: 75 % of the launch).
-#define F2_ARGS_IN_PLACE                                                                                                   \
-  const __attribute__((address_space(4))) char* ka_ = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr(); \
-  asm volatile("" : "+s"(ka_));                                                                                            \
-  const F2ArgBlock* A = (const F2ArgBlock*)ka_
-#define F2_KERNELS_OCC(name, SOLVER, NW, NI, IW, OCC)                                                                      \
-  extern "C" __global__ void __launch_bounds__(64 * NW) OCC                                                                \
-  gs_k_step_##name(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,         \
-                   const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS) { \
-    F2_ARGS_IN_PLACE;                                                                                                      \
-    f2_step<SOLVER, 0, NW, NI, IW>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, A->RS); \
-  }                                                                                                                        \
-  extern "C" __global__ void __launch_bounds__(64 * NW) OCC /* the step with the post-step checks in its epilogue */       \
-  gs_k_stepc_##name(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,        \
-                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS) { \
-    F2_ARGS_IN_PLACE;                                                                                                      \
-    f2_step<SOLVER, 1, NW, NI, IW>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, A->RS); \
+// The step kernels of member `name`, shaped by its row of kStepMembers: F2_KERNELS defines gs_k_step_<name> and gs_k_stepc_<name>
+// (the post-step checks in its epilogue), F2_KERNELS_PZ their per-instance line impedance forms gs_k_step_<name>_pz /
+// gs_k_stepc_<name>_pz (PZ = 1: the pointer to the per-instance entries is an argument of its own behind the block the others read,
+// F2ArgBlock's offsets unchanged, and is read from the formal parameter).  OCC: the member's occupancy attribute.  Each line also
+// files its two kernels under the member's enum value (f2_kernels / f2_kernels_pz), where the launch table below finds them.
+template <StepMember M> constexpr GsStepFns<GsF2StepFn> f2_kernels() { return {}; }
+template <StepMember M> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pz() { return {}; }
+#define F2_PZ_PARAM_0
+#define F2_PZ_PARAM_1 , const double* __restrict__ pz
+#define F2_PZ_ARG_0 nullptr
+#define F2_PZ_ARG_1 pz
+#define F2_KERNEL(kernel, name, CHK, PZ, OCC)                                                                               \
+  extern "C" __global__ void __launch_bounds__(64 * step_row(StepMember::name).nw) OCC                                      \
+  kernel(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,                     \
+         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS F2_PZ_PARAM_##PZ) { \
+    constexpr StepMemberRow r = step_row(StepMember::name);                                                                 \
+    GS_ARGS_IN_PLACE(F2ArgBlock, A);                                                                                        \
+    f2_step<r.solver, CHK, r.nw, r.ni, r.iw, PZ>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, \
+                                               A->RS, F2_PZ_ARG_##PZ);                                                      \
   }
-#define F2_KERNELS(name, SOLVER, NW, NI, IW) F2_KERNELS_OCC(name, SOLVER, NW, NI, IW, )
-#if defined(GS_BUILD_EXPERIMENTS)
-F2_KERNELS(fbs_flow2, F2_FBS, 16, 4, 32)       // up to 128 buses below the slack, 32 instances per workgroup (GS_FLOW2_IW=32; the 16-instance member is the default)
-#endif
-F2_KERNELS(nr_flow2, F2_NR, 8, 8, 32)
-F2_KERNELS(fbs_flow2s, F2_FBS, GS_F2S_WAVES, GS_F2S_ITEMS, GS_F2S_IW)        // up to 16 buses: 8 instances per workgroup, eight buses per wavefront
-F2_KERNELS(nr_flow2s, F2_NR, GS_F2NS_WAVES, GS_F2NS_ITEMS, GS_F2S_IW)          // up to 4 groups of 8 same-level buses
-// 16 instances per workgroup, four buses per wavefront, 8 waves: two workgroups share a CU (four waves per SIMD as above),
-// so that one's LDS-bound solver phase runs beside the other's VALU-bound prologue / epilogue: +6 % at B = 8192, +11 % at
-// 16384, +30 % at 4096 over the 32-instance member (the host's default for the sweep solver; 8 instances per workgroup
-// with four workgroups per CU was tried too: -20 %, the per-instance scalar chains then fill an eighth of a wavefront)
-F2_KERNELS_OCC(fbs_flow2h, F2_FBS, GS_F2H_WAVES, GS_F2H_ITEMS, GS_F2H_IW, __attribute__((amdgpu_waves_per_eu(4, 4))))
-// up to 256 buses below the slack: eight buses per sub-group (twice the registers: two waves per SIMD), one workgroup per CU
-F2_KERNELS(fbs_flow2x, F2_FBS, GS_F2X_WAVES, GS_F2X_ITEMS, GS_F2H_IW)
-// Newton-Raphson on a meshed feeder (a few loops on a tree): 8 instances per workgroup, 4 wavefronts, up to GS_F2M_ITEMS rows each,
-// two workgroups per CU (two waves per SIMD: 256 registers)
-F2_KERNELS_OCC(nr_mesh2, F2_NRM, GS_F2M_WAVES, GS_F2M_ITEMS, GS_F2S_IW, __attribute__((amdgpu_waves_per_eu(2, 2))))
+#define F2_KERNELS(name, OCC)                                                                                               \
+  F2_KERNEL(gs_k_step_##name, name, 0, 0, OCC)                                                                              \
+  F2_KERNEL(gs_k_stepc_##name, name, 1, 0, OCC)                                                                             \
+  template <> constexpr GsStepFns<GsF2StepFn> f2_kernels<StepMember::name>() { return {gs_k_step_##name, gs_k_stepc_##name}; }
+#define F2_KERNELS_PZ(name, OCC)                                                                                            \
+  F2_KERNEL(gs_k_step_##name##_pz, name, 0, 1, OCC)                                                                         \
+  F2_KERNEL(gs_k_stepc_##name##_pz, name, 1, 1, OCC)                                                                        \
+  template <> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pz<StepMember::name>() { return {gs_k_step_##name##_pz, gs_k_stepc_##name##_pz}; }
 
-// ---- per-instance line impedances: the same members with PZ = 1.  The pointer to the per-instance entries is an argument of
-// their own behind the block the members above read (F2ArgBlock: offsets unchanged); it is read from the formal parameter.
-#define F2_KERNELS_PZ_OCC(name, SOLVER, NW, NI, IW, OCC)                                                                   \
-  extern "C" __global__ void __launch_bounds__(64 * NW) OCC                                                                \
-  gs_k_step_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,    \
-                        const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, \
-                        const double* __restrict__ pz) {                                                                   \
-    F2_ARGS_IN_PLACE;                                                                                                      \
-    f2_step<SOLVER, 0, NW, NI, IW, 1>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, A->RS, pz); \
-  }                                                                                                                        \
-  extern "C" __global__ void __launch_bounds__(64 * NW) OCC                                                                \
-  gs_k_stepc_##name##_pz(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,   \
-                         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, \
-                         const double* __restrict__ pz) {                                                                  \
-    F2_ARGS_IN_PLACE;                                                                                                      \
-    f2_step<SOLVER, 1, NW, NI, IW, 1>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, A->RS, pz); \
-  }
-F2_KERNELS_PZ_OCC(nr_flow2, F2_NR, 8, 8, 32, )
-F2_KERNELS_PZ_OCC(fbs_flow2s, F2_FBS, GS_F2S_WAVES, GS_F2S_ITEMS, GS_F2S_IW, )
-F2_KERNELS_PZ_OCC(nr_flow2s, F2_NR, GS_F2NS_WAVES, GS_F2NS_ITEMS, GS_F2S_IW, )
-F2_KERNELS_PZ_OCC(fbs_flow2h, F2_FBS, GS_F2H_WAVES, GS_F2H_ITEMS, GS_F2H_IW, __attribute__((amdgpu_waves_per_eu(4, 4))))
-F2_KERNELS_PZ_OCC(fbs_flow2x, F2_FBS, GS_F2X_WAVES, GS_F2X_ITEMS, GS_F2H_IW, )
+#if defined(GS_BUILD_EXPERIMENTS)
+F2_KERNELS(fbs_flow2, )
+#endif
+F2_KERNELS(nr_flow2, )
+F2_KERNELS(fbs_flow2s, )
+F2_KERNELS(nr_flow2s, )
+// fbs_flow2h: two workgroups share a CU (four waves per SIMD), so that one's LDS-bound solver phase runs beside the other's
+// VALU-bound prologue / epilogue: +6 % at B = 8192, +11 % at 16384, +30 % at 4096 over the 32-instance member (the host's default
+// for the sweep solver; 8 instances per workgroup with four workgroups per CU was tried too: -20 %, the per-instance scalar chains
+// then fill an eighth of a wavefront)
+F2_KERNELS(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
+F2_KERNELS(fbs_flow2x, )         // (twice the registers of fbs_flow2h: two waves per SIMD, one workgroup per CU)
+F2_KERNELS(nr_mesh2, __attribute__((amdgpu_waves_per_eu(2, 2))))      // two workgroups per CU (two waves per SIMD: 256 registers)
+F2_KERNELS_PZ(nr_flow2, )
+F2_KERNELS_PZ(fbs_flow2s, )
+F2_KERNELS_PZ(nr_flow2s, )
+F2_KERNELS_PZ(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
+F2_KERNELS_PZ(fbs_flow2x, )
+
+#if !defined(__HIP_DEVICE_COMPILE__)      // (host only: the device pass would put a copy of the table into the code object)
+template <size_t... M> constexpr std::array<GsStepKernels, sizeof...(M)> f2_launch_table(std::index_sequence<M...>) {
+  static_assert(((kStepMembers[M].pz == (f2_kernels_pz<StepMember(M)>().step != nullptr)) && ...), "kStepMembers: pz disagrees with F2_KERNELS_PZ");
+  return {{{f2_kernels<StepMember(M)>(), f2_kernels_pz<StepMember(M)>()}...}};
+}
+extern const std::array<GsStepKernels, kStepMemberCount> gs_step_kernels = f2_launch_table(std::make_index_sequence<kStepMemberCount>());
+#endif
 
 // The per-instance entries of instances b (every lane of the slab groups; a padding lane past B takes instance B - 1's values)
 // from their [B][m] impedances: one thread per (instance, slot or line), the host's arithmetic operation for operation

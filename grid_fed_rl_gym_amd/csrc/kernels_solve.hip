@@ -29,6 +29,7 @@
 
 #include "../../include/gridstep.h"
 #include "gs_internal.h"
+#include "kernels.h"
 
 #define ROW(r) S[(size_t)(r) * GS_LANES]
 #define ROW2(r) S.pair((size_t)(r) * GS_LANES)        /* (row r, row r + 1) of the lane as one double2; r even */
@@ -1869,35 +1870,29 @@ __device__ __forceinline__ void main_body(const GsTables& T, const GsRows& R, co
   stamp(c, ST_EPILOGUE);
 }
 
-// The kernels read their arguments where they use them, through a pointer to the argument block the compiler cannot see
-// through (kernels_flow2.hip F2_ARGS_IN_PLACE says why: taken from the formal parameters every scalar word is loaded at the
-// top and parked in vector lanes -- 250 to 340 spilled scalar registers in the step kernels of this file).
+// (arguments read in place: gs_internal.h GS_ARGS_IN_PLACE)
 struct GsStepArgBlock { GsTables T; GsRows R; GsSolveCfg C; GsEnvCfg E; double* slab; int B; const double* actions; double total_load;
                         GsPackArgs PA; GsFusedChecks FC; };
 struct GsSolveArgBlock { GsTables T; GsRows R; GsSolveCfg C; double* slab; int B; };
-#define GS_ARGS_IN_PLACE(Block)                                                                               \
-  const __attribute__((address_space(4))) char* ka_ = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr(); \
-  asm volatile("" : "+s"(ka_));                                                                               \
-  const Block* A = (const Block*)ka_
 #define GS_DEFINE_KERNELS(name, KIND)                                                                         \
   extern "C" __global__ void __launch_bounds__(1024)                                                          \
   gs_k_##name(GsTables T, GsRows R, GsSolveCfg C, double* __restrict__ slab, int B) {                         \
     GsEnvCfg E{};                                                                                             \
     GsPackArgs PA{};                                                                                          \
     GsFusedChecks FC{};                                                                                       \
-    GS_ARGS_IN_PLACE(GsSolveArgBlock);                                                                        \
+    GS_ARGS_IN_PLACE(GsSolveArgBlock, A);                                                                     \
     main_body<KIND, 0, 0>(A->T, A->R, A->C, E, A->slab, A->B, nullptr, 0.0, PA, FC);                          \
   }                                                                                                           \
   extern "C" __global__ void __launch_bounds__(1024)                                                          \
   gs_k_step_##name(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,          \
                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC) {  \
-    GS_ARGS_IN_PLACE(GsStepArgBlock);                                                                         \
+    GS_ARGS_IN_PLACE(GsStepArgBlock, A);                                                                      \
     main_body<KIND, 1, 0>(A->T, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC);    \
   }                                                                                                           \
   extern "C" __global__ void __launch_bounds__(1024)   /* the step with the post-step checks in its epilogue */ \
   gs_k_stepc_##name(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,         \
                     const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC) { \
-    GS_ARGS_IN_PLACE(GsStepArgBlock);                                                                         \
+    GS_ARGS_IN_PLACE(GsStepArgBlock, A);                                                                      \
     main_body<KIND, 1, 1>(A->T, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC);    \
   }
 
@@ -1905,25 +1900,25 @@ struct GsSolveArgBlock { GsTables T; GsRows R; GsSolveCfg C; double* slab; int B
 extern "C" __global__ void __launch_bounds__(1024)
 gs_k_pre_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                   const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC) {
-  GS_ARGS_IN_PLACE(GsStepArgBlock);
+  GS_ARGS_IN_PLACE(GsStepArgBlock, A);
   main_body<KIND_LU, 1, 0, 1>(A->T, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC);
 }
 extern "C" __global__ void __launch_bounds__(1024)
 gs_k_post_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                    const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC) {
-  GS_ARGS_IN_PLACE(GsStepArgBlock);
+  GS_ARGS_IN_PLACE(GsStepArgBlock, A);
   main_body<KIND_LU, 1, 0, 2>(A->T, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC);
 }
 extern "C" __global__ void __launch_bounds__(1024)
 gs_k_postc_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                     const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC) {
-  GS_ARGS_IN_PLACE(GsStepArgBlock);
+  GS_ARGS_IN_PLACE(GsStepArgBlock, A);
   main_body<KIND_LU, 1, 1, 2>(A->T, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC);
 }
 extern "C" __global__ void __launch_bounds__(1024)       // solver-only API (gs_solve): line flows, losses, wrapped angles
 gs_k_posts_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, double* __restrict__ slab, int B) {
   GsEnvCfg E{}; GsPackArgs PA{}; GsFusedChecks FC{};
-  GS_ARGS_IN_PLACE(GsSolveArgBlock);
+  GS_ARGS_IN_PLACE(GsSolveArgBlock, A);
   main_body<KIND_LU, 0, 0, 2>(A->T, A->R, A->C, E, A->slab, A->B, nullptr, 0.0, PA, FC);
 }
 
@@ -1934,3 +1929,13 @@ GS_DEFINE_KERNELS(nr_dense, KIND_DENSE)
 GS_DEFINE_KERNELS(fbs, KIND_FBS)
 GS_DEFINE_KERNELS(fbs_lds, KIND_FBS_LDS)
 GS_DEFINE_KERNELS(fbs_flow, KIND_FBS_FLOW)
+
+// The launch table of the first generation (kernels.h), in SolveMember order: which kernels a member runs.  nr_dense_mfma and
+// nr_sparse_lds have none of their own: the gs_k_*_nr_dmfma kernels above run around their solver.
+// (host only: the device pass would put a copy of the table into the code object)
+#if !defined(__HIP_DEVICE_COMPILE__)
+#define GS_SOLVE_KERNELS(name) {gs_k_##name, {gs_k_step_##name, gs_k_stepc_##name}}
+extern const std::array<GsSolveKernels, (size_t)SolveMember::nr_sparse_lds + 1> gs_solve_kernels = {{
+    GS_SOLVE_KERNELS(nr_tree), GS_SOLVE_KERNELS(nr_lu) /* nr_sparse_lu */, GS_SOLVE_KERNELS(fbs), GS_SOLVE_KERNELS(nr_dense) /* nr_dense_pivot */,
+    GS_SOLVE_KERNELS(nr_tree_lds), GS_SOLVE_KERNELS(fbs_lds), GS_SOLVE_KERNELS(fbs_flow), {} /* nr_dense_mfma */, {} /* nr_sparse_lds */}};
+#endif

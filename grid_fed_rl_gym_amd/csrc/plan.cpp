@@ -20,15 +20,9 @@ std::string reject(GsPlan& p, int code, const char* fmt, ...) {
   return buf;
 }
 
-// gs_describe's names of the members, in enum order
+// gs_describe's names of the first-generation members, in enum order (the second generation's: kStepMembers)
 const char* const kSolveName[] = {"nr_tree", "nr_sparse_lu", "fbs", "nr_dense_pivot", "nr_tree_lds", "fbs_lds", "fbs_flow", "nr_dense_mfma", "nr_sparse_lds"};
-const char* const kStepName[] = {"none", "fbs_flow2s", "fbs_flow2h", "fbs_flow2x",
-#if defined(GS_BUILD_EXPERIMENTS)
-                                 "fbs_flow2",
-#endif
-                                 "nr_flow2s", "nr_flow2", "nr_mesh2"};
 static_assert(sizeof kSolveName / sizeof *kSolveName == (size_t)SolveMember::nr_sparse_lds + 1, "kSolveName");
-static_assert(sizeof kStepName / sizeof *kStepName == (size_t)StepMember::nr_mesh2 + 1, "kStepName");
 
 // devices at bus i, in the reference's accumulation order (grid_env.py:689-718): GsInjRec and GsF2Rec
 template <typename Rec>
@@ -325,16 +319,13 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
     // small feeders: 8 instances per workgroup, the eight sub-groups of a wavefront on eight buses; 129 ... 256 buses: eight
     // buses per sub-group; default: 16 instances per workgroup, two workgroups per CU (GS_FLOW2_IW=32 asks for the
     // 32-instance member, one per CU)
-    const bool small = N <= GS_F2S_WAVES * (64 / GS_F2S_IW) * GS_F2S_ITEMS && !getenv("GS_NO_FLOW2_SMALL");
-    const bool wide = !small && N > GS_F2_WAVES * 2 * GS_F2_ITEMS;
+    const bool small = N <= step_row(StepMember::fbs_flow2s).positions() && !getenv("GS_NO_FLOW2_SMALL");
+    const bool wide = !small && N > step_row(StepMember::fbs_flow2h).positions();
     StepMember sm = small ? StepMember::fbs_flow2s : wide ? StepMember::fbs_flow2x : StepMember::fbs_flow2h;
-    int NW = small ? GS_F2S_WAVES : wide ? GS_F2X_WAVES : GS_F2H_WAVES, NI = small ? GS_F2S_ITEMS : wide ? GS_F2X_ITEMS : GS_F2H_ITEMS,
-        IW = small ? GS_F2S_IW : GS_F2H_IW;
 #if defined(GS_BUILD_EXPERIMENTS)
-    if (sm == StepMember::fbs_flow2h && GS_EXPERIMENT_ENV("GS_FLOW2_IW") && atoi(GS_EXPERIMENT_ENV("GS_FLOW2_IW")) == 32) {
-      sm = StepMember::fbs_flow2; NW = GS_F2_WAVES; NI = GS_F2_ITEMS; IW = 32; }
+    if (sm == StepMember::fbs_flow2h && GS_EXPERIMENT_ENV("GS_FLOW2_IW") && atoi(GS_EXPERIMENT_ENV("GS_FLOW2_IW")) == 32) sm = StepMember::fbs_flow2;
 #endif
-    const int NPOS = NW * (64 / IW) * NI;
+    const int NW = step_row(sm).nw, IW = step_row(sm).iw, NPOS = step_row(sm).positions();
     const size_t off = f2_layout(topo, ht, F, NW, IW, 0, (size_t)n_jump * nsl * 4, 2);
     F.n_jump = n_jump;
     if (getenv("GS_NO_FLOW2")) why = "disabled by GS_NO_FLOW2";
@@ -347,7 +338,7 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
     else if (off > 160 * 1024) why = "LDS tables do not fit";
     else if (ht.n < 2 || ht.m < 1 || N < 1) why = "trivial network";
     if (why.empty()) {
-      p.step = sm; p.f2_iw = IW; p.f2_nw = NW;
+      p.step = sm;
       GsF2Rec idle{}; idle.bus = SL_DUMMY; idle.parent = SL_ONE; idle.last = SL_DUMMY;
       p.f2recs.assign((size_t)NPOS, idle);
       p.f2z.assign((size_t)nsl * 2, 0.0);
@@ -401,11 +392,11 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
       return mx;
     };
     std::vector<std::vector<std::vector<int>>> mine; std::vector<std::vector<int>> mine_lv;
-    bool small = !getenv("GS_NO_FLOW2_SMALL") && deal(GS_F2NS_WAVES, 64 / GS_F2S_IW, mine, mine_lv) <= GS_F2NS_ITEMS;
-    const int NW = small ? GS_F2NS_WAVES : GS_F2N_WAVES, NI = small ? GS_F2NS_ITEMS : GS_F2N_ITEMS, IW = small ? GS_F2S_IW : 32, HV = 64 / IW;
+    const StepMemberRow& rs = step_row(StepMember::nr_flow2s);
+    const StepMember sm = !getenv("GS_NO_FLOW2_SMALL") && deal(rs.nw, 64 / rs.iw, mine, mine_lv) <= rs.ni ? StepMember::nr_flow2s : StepMember::nr_flow2;
+    const int NW = step_row(sm).nw, NI = step_row(sm).ni, IW = step_row(sm).iw, HV = 64 / IW;
     const int max_items = deal(NW, HV, mine, mine_lv);
-    const int NPOS = NW * HV * NI, maxw = ht.max_level_width;
-    p.f2_npos = NPOS;
+    const int NPOS = step_row(sm).positions(), maxw = ht.max_level_width;
     // the ring's zero entry: behind the ring's two parities and behind the K slots that share the region
     const size_t ring_entry = (size_t)3 * IW * 16;
     const int ring_zero = (int)std::max<size_t>((size_t)2 * maxw, ((size_t)nsl * (IW + 1) * 16 + ring_entry - 1) / ring_entry);
@@ -424,7 +415,7 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
     else if (off > 160 * 1024) why = "LDS tables do not fit";
     else if (ht.n < 2 || ht.m < 1) why = "trivial network";
     if (why.empty()) {
-      p.step = small ? StepMember::nr_flow2s : StepMember::nr_flow2; p.f2_iw = IW; p.f2_nw = NW;
+      p.step = sm;
       GsF2Rec idle{}; idle.bus = SL_DUMMY; idle.parent = SL_ONE; idle.last = SL_DUMMY; idle.level = -1;
       p.f2recs.assign((size_t)NPOS, idle);
       p.f2z.assign((size_t)nsl * 4, 0.0);
@@ -471,7 +462,8 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
   // -- Newton-Raphson on a meshed feeder: the block LU as rows of lane items (mesh_schedule.h), 8 instances per workgroup
   if (p.solve == SolveMember::nr_sparse_lu && !ht.is_forest) {
     std::string& why = p.mesh_why;
-    const int NW = GS_F2M_WAVES, NI = GS_F2M_ITEMS, IW = GS_F2S_IW, HV = 64 / IW;
+    const StepMemberRow& row = step_row(StepMember::nr_mesh2);
+    const int NW = row.nw, NI = row.ni, IW = row.iw, HV = 64 / IW;
     bool all_pq = true;
     for (int i = 0; i < ht.n; ++i) if (i != ht.slack && !(ht.th_free[i] && ht.vm_free[i])) all_pq = false;
     MeshSchedule S;
@@ -500,7 +492,7 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
       if (off > 160 * 1024) why = "LDS tables do not fit";
     }
     if (why.empty()) {
-      p.step = StepMember::nr_mesh2; p.f2_iw = IW; p.f2_nw = NW; p.f2_npos = NW * HV * NI;
+      p.step = StepMember::nr_mesh2;
       // ---- iteration 0 as a matrix product (GsF2Tables::mesh_w): the flat-start Jacobian, inverted once on the host
       if (!getenv("GS_NR_NO_FLAT") && ht.n <= 128 && flat_newton_map(ht, 16, 32, p.mesh_w)) { F.mesh_w_steps = 32; F.mesh_slack = ht.slack; }
       p.mesh_levels = S.n_levels; p.mesh_rows = S.n_rows; p.mesh_units = S.msg_units; p.mesh_messages = S.n_messages; p.mesh_accs = S.n_accumulators;
@@ -829,9 +821,7 @@ bool flat_newton_map(const HostTopology& ht, int tiles, int steps, std::vector<d
 // instance's numbers come from gs_k_line_params).  The branch entry Y(s, parent) and the diagonal Y(s, s) of every slot that has
 // one in the shared tables, as the line-order lists of topology.cpp's add() calls that reach it.
 std::string plan_line_params(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, GsPlan& p) {
-  const bool ok = p.step == StepMember::fbs_flow2s || p.step == StepMember::fbs_flow2h || p.step == StepMember::fbs_flow2x ||
-                  p.step == StepMember::nr_flow2s || p.step == StepMember::nr_flow2;
-  if (!ok) {
+  if (!p.f2().pz) {
     std::string why = !p.flow2_why.empty() ? p.flow2_why : !p.mesh_why.empty() ? p.mesh_why
                     : p.step == StepMember::nr_mesh2 ? "a meshed network (nr_mesh2)"
                     : cfg.solver_kind == GS_SOLVER_FBS && cfg.fbs_warm_start ? "warm start"
@@ -839,7 +829,7 @@ std::string plan_line_params(const gs_topology& topo, const gs_config& cfg, cons
                     : !ht.is_forest ? "a meshed network" : std::string("the step runs on ") + kSolveName[(int)p.solve];
     return "per-instance line impedances need a second-generation radial step member: " + why;
   }
-  const bool newton = p.step == StepMember::nr_flow2s || p.step == StepMember::nr_flow2;
+  const bool newton = p.f2().newton();
   const int nsl = ht.n + 3, m = ht.m;
   p.pz_zero.assign((size_t)m, 0);
   for (int k = 0; k < m; ++k) p.pz_zero[k] = std::hypot(topo.r[k], topo.x[k]) > 1e-12 ? 0 : 1;
@@ -906,12 +896,9 @@ std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTop
   plan_rows(ht, p);
   plan_work_lists(ht, p);
   plan_second_gen(topo, cfg, ht, auto_w, p);
-  {
-    const bool nr2 = p.step == StepMember::nr_flow2s || p.step == StepMember::nr_flow2 || p.step == StepMember::nr_mesh2;
-    p.pz = topo.line_r_inst != nullptr;
-    p.nr_flat = nr2 && p.f2_npos > 0 && !getenv("GS_NR_NO_FLAT") && !p.pz;
-    if (p.pz && (why = plan_line_params(topo, cfg, ht, p)).empty() == false) { p.err_code = GS_E_TOPOLOGY; return why; }
-  }
+  p.pz = topo.line_r_inst != nullptr;
+  p.nr_flat = p.f2().newton() && !getenv("GS_NR_NO_FLAT") && !p.pz;
+  if (p.pz && (why = plan_line_params(topo, cfg, ht, p)).empty() == false) { p.err_code = GS_E_TOPOLOGY; return why; }
   if (ht.has_lu) plan_lu_schedule(ht, p);
   if (p.solve == SolveMember::nr_dense_mfma && !(why = plan_dense(cfg, ht, cus, p)).empty()) return why;
 #if defined(GS_BUILD_EXPERIMENTS)
@@ -919,7 +906,7 @@ std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTop
 #endif
   // a step as two half-grid launches on two streams: only where each half still gives every CU a workgroup
   p.lean = p.second_gen() && !getenv("GS_EAGER_ROWS");
-  p.split_ok = p.second_gen() && 2 * (size_t)p.F2.lds_bytes <= 160 * 1024 && !getenv("GS_NO_SPLIT") && p.groups * (64 / p.f2_iw) >= 512 &&
+  p.split_ok = p.second_gen() && 2 * (size_t)p.F2.lds_bytes <= 160 * 1024 && !getenv("GS_NO_SPLIT") && p.groups * (64 / p.f2().iw) >= 512 &&
                p.groups >= 2;
   p.SC.tolerance = cfg.tolerance; p.SC.alpha = cfg.acceleration_factor;
   p.SC.max_iterations = cfg.max_iterations; p.SC.jacobian_exact = (cfg.jacobian_mode == GS_JACOBIAN_EXACT);
@@ -943,10 +930,10 @@ void gs_plan_format(const GsPlan& p, const HostTopology& ht, char* buf, int bufl
            "\"instances_per_workgroup\": %d, \"workgroups\": %d, \"step_lds_bytes\": %zu, \"step_launches\": %d, \"solve_kernel\": \"%s\", \"flow2\": \"%s\", "
            "\"mesh2\": \"%s\", \"mesh_levels\": %d, \"mesh_rows\": %d, \"mesh_message_units\": %d, \"mesh_messages\": %d, \"mesh_accumulators\": %d, "
            "\"dense_form\": \"%s\", \"dense_workgroups\": %d, \"dense_lds_bytes\": %zu, \"per_instance_z\": %d, \"nr_flat_start_table\": %d}",
-           f2 ? kStepName[(int)p.step] : kSolveName[(int)p.solve], p.n, p.m, ht.nnz, ht.is_forest ? "true" : "false", ht.n_levels,
-           ht.max_level_width, ht.lu_n_slots, ht.lu_n_orig, (long long)ht.lu_n_pairs, f2 ? p.f2_nw : p.W, p.groups,
+           f2 ? p.f2().name : kSolveName[(int)p.solve], p.n, p.m, ht.nnz, ht.is_forest ? "true" : "false", ht.n_levels,
+           ht.max_level_width, ht.lu_n_slots, ht.lu_n_orig, (long long)ht.lu_n_pairs, f2 ? p.f2().nw : p.W, p.groups,
            p.R.total, (size_t)p.groups * p.R.total * GS_LANES * sizeof(double), p.obs_dim, p.action_dim,
-           f2 ? p.f2_iw : 64, f2 ? (64 / p.f2_iw) * p.groups : p.groups, f2 ? (size_t)p.F2.lds_bytes : p.dyn_lds + 24576, p.split_ok ? 2 : 1,
+           f2 ? p.f2().iw : 64, f2 ? (64 / p.f2().iw) * p.groups : p.groups, f2 ? (size_t)p.F2.lds_bytes : p.dyn_lds + 24576, p.split_ok ? 2 : 1,
            kSolveName[(int)p.solve], f2 ? "on" : (p.flow2_why.empty() ? "n/a" : p.flow2_why.c_str()),
            p.step == StepMember::nr_mesh2 ? "on" : (p.mesh_why.empty() ? "n/a" : p.mesh_why.c_str()), p.mesh_levels, p.mesh_rows, p.mesh_units,
            p.mesh_messages, p.mesh_accs, dense ? (p.dense_blockrow ? "block_row" : "panel") : "n/a", dense ? p.dense_grid : 0, dense ? p.dense_lds : (size_t)0,

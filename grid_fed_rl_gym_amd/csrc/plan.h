@@ -9,19 +9,8 @@
 
 #include "../../include/gridstep.h"
 #include "gs_internal.h"
+#include "members.h"
 #include "topology.h"
-
-// The member that solves the load flow (gs_solve, and the step unless a second-generation member takes it); the names are
-// gs_describe's "solve_kernel" strings.
-enum class SolveMember { nr_tree, nr_sparse_lu, fbs, nr_dense_pivot, nr_tree_lds, fbs_lds, fbs_flow, nr_dense_mfma, nr_sparse_lds };
-// The second-generation step kernel (kernels_flow2.hip) that runs the environment step instead of the first-generation one.
-enum class StepMember {
-  none, fbs_flow2s, fbs_flow2h, fbs_flow2x,
-#if defined(GS_BUILD_EXPERIMENTS)
-  fbs_flow2,
-#endif
-  nr_flow2s, nr_flow2, nr_mesh2
-};
 
 // the per-instance scalars gs_k_scalars copies to the host (rows rf / ri / ru of the plan)
 enum { SF_REWARD = 0, SF_VMAX, SF_VMIN, SF_LOSSES, SF_EPREW, SF_MAXMIS, SF_COUNT };
@@ -40,8 +29,7 @@ struct GsPlan {
   GsSolveCfg SC{};
   GsEnvCfg EC{};                           // (first_instance: gs_create's)
   double total_load = 0.0;
-  // second-generation step kernels: 64 / f2_iw workgroups per slab group, f2_nw waves each
-  GsF2Tables F2{}; int f2_iw = 32, f2_nw = 16, f2_npos = 0;
+  GsF2Tables F2{};                         // second-generation step kernels: 64 / f2().iw workgroups per slab group
   std::string flow2_why, mesh_why;         // why no second-generation member took the step ("" = not considered)
   int mesh_levels = 0, mesh_rows = 0, mesh_units = 0, mesh_messages = 0, mesh_accs = 0;
   // nr_dense_mfma: a launch of its own between the two halves of the step / solve
@@ -76,6 +64,7 @@ struct GsPlan {
   std::vector<int32_t> pz_ops_ptr, pz_ops; std::vector<uint8_t> pz_has, pz_zero;
 
   bool second_gen() const { return step != StepMember::none; }
+  const StepMemberRow& f2() const { return step_row(step); }
 };
 
 // Plans a handle of `batch` instances for a device of `cus` compute units.  Returns "" or the rejection message (out.err_code:
