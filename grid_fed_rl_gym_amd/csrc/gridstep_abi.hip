@@ -519,7 +519,8 @@ int flat_start_captures(gs_handle* h) {
     const size_t npos = h->f2().positions();
     if ((rc = dev_alloc(h, &tab, npos * 16))) return rc;
     if (hipMemset(tab, 0, npos * 16 * sizeof(double)) != hipSuccess ||
-        hipMemset(h->d_in, 0, h->in_doubles * sizeof(double)) != hipSuccess) return fail(nullptr, GS_E_HIP, "hipMemset failed");      // (d_in: zero actions for the capture step)
+        hipMemset(h->d_in, 0, h->in_doubles * sizeof(double)) != hipSuccess ||     // (d_in: zero actions for the capture step)
+        hipDeviceSynchronize() != hipSuccess) return fail(nullptr, GS_E_HIP, "hipMemset failed");      // (and the memsets done before the capture reads)
     GsF2Tables cap = h->F2; cap.nrflat = tab; cap.nrflat_mode = 1; cap.wg_offset = 0;
     GsPackArgs pa{}; GsFusedChecks fc{}; GsRolloutStep rsv{};
     GsSolveCfg sc = h->SC; sc.stamps = nullptr;
@@ -662,9 +663,11 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
         (rc = dev_upload(h, &A.has, h->pz_has)) || (rc = dev_alloc(h, &dr, Bm)) || (rc = dev_alloc(h, &dx, Bm)) ||
         (rc = dev_alloc(h, &h->d_pzmask, (size_t)h->B)) || (rc = dev_alloc(h, &dpz, n_pz))) return bail(rc);
     A.r = dr; A.x = dx; A.pz = dpz;
+    // (the handle's stream is non-blocking: it is not ordered behind the null stream's copies and memsets, which may still be
+    // running when they return -- gs_k_line_params then read r / x half copied, or the memset zeroed entries it had written)
     if (hipMemcpy(dr, h->inst_r.data(), Bm * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dx, h->inst_x.data(), Bm * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(dpz, 0, n_pz * sizeof(double)) != hipSuccess)
+        hipMemset(dpz, 0, n_pz * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       return bail(fail(nullptr, GS_E_HIP, "per-instance line impedances: upload failed"));
     if ((rc = launch_line_params(h, nullptr))) return bail(fail(nullptr, rc, "%s", h->err.c_str()));
   }
@@ -707,6 +710,8 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     Sp.orig_slot = T.lu_orig_slot; Sp.orig_i = T.lu_orig_i; Sp.orig_j = T.lu_orig_j; Sp.orig_pos = T.lu_orig_pos;
   }
 #endif
+  // (the captures run on the handle's stream: the tables, the zeroed slab and the rest of the null stream's work go first)
+  if (hipDeviceSynchronize() != hipSuccess) return bail(fail(nullptr, GS_E_HIP, "hipDeviceSynchronize failed"));
   if ((rc = flat_start_captures(h))) return bail(rc);
   if (h->split_ok &&
       (hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess ||
@@ -1882,7 +1887,8 @@ int gs_checks_create(gs_handle* h, const gs_checks_config* cfg, gs_checks** out)
             hipMalloc((void**)&c->freq, Bp * sizeof(double)) == hipSuccess;
   ok = ok && hipMemset(c->prev, 0, (size_t)h->groups * (h->n + 1) * GS_LANES * sizeof(double)) == hipSuccess &&
        hipMemset(c->state, 0, 3 * Bp * sizeof(int32_t)) == hipSuccess && hipMemset(c->out_i, 0, (size_t)GS_CI_COUNT * Bp * sizeof(int32_t)) == hipSuccess &&
-       hipMemset(c->out_f, 0, (size_t)GS_CF_COUNT * Bp * sizeof(double)) == hipSuccess;
+       hipMemset(c->out_f, 0, (size_t)GS_CF_COUNT * Bp * sizeof(double)) == hipSuccess &&
+       hipDeviceSynchronize() == hipSuccess;        // (done before the check kernels, which run on the handle's non-blocking stream)
   if (!ok) { gs_checks_destroy(c); return fail(h, GS_E_NOMEM, "device allocation for the checks failed"); }
   *out = c;
   return GS_OK;

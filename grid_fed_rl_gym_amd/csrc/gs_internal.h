@@ -458,14 +458,15 @@ enum {
 
 struct GsF2Tables {
   const GsF2Rec* recs;            // [NW * (64 / IW) * NI] of the member (StepMemberRow::positions)
-  const int32_t* anc;             // sweeps: [n_jump][n_slots] 2^r-th ancestor of every slot on its way to the slack, ZERO beyond;
+  const int32_t* anc;             // sweeps: [n_jump][n_slots][4] the ancestors 4^r, 2 * 4^r and 3 * 4^r steps up of every slot, ZERO
+                                  // beyond the slack's children (4th entry unused);
                                   // Newton-Raphson: child buses [n][8], child ring slots [n][8], child counts [n_slots], then at
                                   // pos_off (a multiple of 4) per position (bus, parent, own ring slot, parent's ring slot); n_anc_ints in all
   const double* zbus;             // sweeps: [n_slots][2] impedance of the branch from each bus to its parent (0 where there is none);
                                   // Newton-Raphson: [n_slots][4] (G_ip, B_ip, G_ii, B_ii)
   int32_t n_slots;                // n + 3: buses, then ZERO (0, 0), ONE (1, 0), DUMMY
   int32_t slack;                  // slot of the slack bus
-  int32_t n_jump;                 // rounds of the forward sweep's pointer jumping: ceil(log2(depth)), rounded up to even
+  int32_t n_jump;                 // rounds of the forward sweep's radix-4 pointer jumping: ceil(log4(depth)), rounded up to even, at least 2
   int32_t n_levels, pos_off, n_anc_ints, wg_offset;   // Newton-Raphson: levels of the tree below the slack; layout of `anc`
   int32_t off_tile, off_anc, off_z, off_env, off_red, off_atom, lds_bytes;     // LDS byte offsets (slots at 0)
   int32_t off_prof, ring_zero;    // ring_zero (Newton-Raphson): index of the ring entry that stays zero;     // the 24 hourly factors of the load profile (dynamics.py:37-44), copied from kDailyProfile at kernel start

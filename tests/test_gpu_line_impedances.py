@@ -282,3 +282,25 @@ def test_full_size_123_bus_8192_instances():
     assert got[0][4]["power_flow_converged"].all()
     picks = np.linspace(0, B - 1, 16).astype(int)
     _check_against_oracle(got, _oracle_steps(fs, solver, r, x, seeds, actions, picks), picks)
+
+
+@pytest.mark.parametrize("solver", ["fbs", "nr"])
+def test_full_size_nominal_instances_are_bit_identical_to_the_shared_handle(solver, monkeypatch):
+    """Every one of 8192 instances, not a sample: gs_create zeroes and uploads the per-instance entries and derives them
+    (gs_k_line_params) on the handle's stream, and an entry lost to an unordered copy or memset shows in some instances only."""
+    fs = P.ieee123_like()
+    B = 8192
+    r = np.tile(fs.r, (B, 1)); x = np.tile(fs.x, (B, 1))
+    rng = np.random.default_rng(6)
+    seeds = np.arange(B, dtype=np.uint64) + 4
+    actions = [rng.uniform(-1, 1, (B, fs.n_bats + fs.n_gens)) for _ in range(2)]
+    pz = P.BatchedGridEnvironment(fs, num_envs=B, line_impedances=(r, x), **_kw(fs, solver))
+    got = _run(pz, seeds, actions)
+    pz.close()
+    if solver == "nr":
+        monkeypatch.setenv("GS_NR_NO_FLAT", "1")
+    shared = P.BatchedGridEnvironment(fs, num_envs=B, **_kw(fs, solver))
+    ref = _run(shared, seeds, actions)
+    shared.close()
+    assert got[0][4]["power_flow_converged"].all()
+    _equal_runs(got, ref)
