@@ -42,7 +42,7 @@ class gs_topology(C.Structure):
                 ("n_gens", C.c_int32), ("gen_bus", _ip), ("gen_kind", _ip), ("gen_cap", _dp),
                 ("gen_p0", _dp), ("gen_p1", _dp), ("gen_p2", _dp),
                 ("n_bats", C.c_int32), ("bat_bus", _ip), ("bat_cap", _dp), ("bat_rating", _dp), ("bat_eff", _dp),
-                ("line_r_inst", _dp), ("line_x_inst", _dp)]
+                ("line_r_inst", _dp), ("line_x_inst", _dp), ("load_base_inst", _dp)]
 
 
 class gs_config(C.Structure):
@@ -137,6 +137,8 @@ SYMBOLS = [
     ("gs_fallback_linear", C.c_int, [_H, _dp, _dp, _dp, _dp, _up, _up, C.POINTER(C.c_int32)]),
     ("gs_set_line_impedances", C.c_int, [_H, _dp, _dp, _up]),
     ("gs_get_line_impedances", C.c_int, [_H, _dp, _dp]),
+    ("gs_set_load_powers", C.c_int, [_H, _dp, _up]),
+    ("gs_get_load_powers", C.c_int, [_H, _dp]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -280,9 +282,26 @@ def check_line_impedances(spec: FeederSpec, r, x, rows: int) -> Tuple[np.ndarray
     return r, x
 
 
-def _topology_of(spec: FeederSpec, line_impedances=None):
+def check_load_powers(spec: FeederSpec, load_powers, rows: int) -> np.ndarray:
+    """Per-instance load powers of shape [rows, n_loads] (watts) as C-contiguous float64, checked against the rules of
+    gs_topology::load_base_inst (include/gridstep.h): the feeder has loads, every value finite and >= 0.  Raises ValueError."""
+    if int(spec.n_loads) == 0:
+        raise ValueError("load powers: the feeder has no loads")
+    pl = np.ascontiguousarray(load_powers, dtype=np.float64)
+    shape = (int(rows), int(spec.n_loads))
+    if pl.shape != shape:
+        raise ValueError(f"load powers must have shape {shape}, got {pl.shape}")
+    if not np.isfinite(pl).all():
+        raise ValueError("load powers: every value must be finite")
+    if (pl < 0).any():
+        raise ValueError("load powers must be >= 0")
+    return pl
+
+
+def _topology_of(spec: FeederSpec, line_impedances=None, load_powers=None):
     """gs_topology of a FeederSpec and the arrays it points into (keep them alive while the struct is in use).
-    ``line_impedances``: None or (r, x), C-contiguous float64 [batch, m] (gs_topology::line_r_inst / line_x_inst)."""
+    ``line_impedances``: None or (r, x), C-contiguous float64 [batch, m] (gs_topology::line_r_inst / line_x_inst);
+    ``load_powers``: None or C-contiguous float64 [batch, n_loads] (gs_topology::load_base_inst)."""
     keep = dict(frm=_i32(spec.frm), to=_i32(spec.to), r=_f64(spec.r), x=_f64(spec.x), rating=_f64(spec.rating),
                 bus_type=np.ascontiguousarray(spec.bus_type, dtype=np.uint8), v_set=_f64(spec.v_set),
                 load_bus=_i32(spec.load_bus), load_base=_f64(spec.load_base), load_pf=_f64(spec.load_pf),
@@ -307,6 +326,9 @@ def _topology_of(spec: FeederSpec, line_impedances=None):
     if line_impedances is not None:
         keep["r_inst"], keep["x_inst"] = _f64(line_impedances[0]), _f64(line_impedances[1])
         t.line_r_inst, t.line_x_inst = _ptr(keep["r_inst"], _dp), _ptr(keep["x_inst"], _dp)
+    if load_powers is not None:
+        keep["load_inst"] = _f64(load_powers)
+        t.load_base_inst = _ptr(keep["load_inst"], _dp)
     return t, keep
 
 
@@ -328,11 +350,12 @@ def flat_newton_map(spec, zero_z="open") -> np.ndarray:
     return out
 
 
-def plan_describe(spec: FeederSpec, cfg: gs_config, batch: int, cus: int = 256, line_impedances=None) -> dict:
+def plan_describe(spec: FeederSpec, cfg: gs_config, batch: int, cus: int = 256, line_impedances=None, load_powers=None) -> dict:
     """gs_plan_describe: what Handle(spec, cfg, batch).describe() returns on a device with ``cus`` compute units, planned on the host
-    (no device needed).  ``line_impedances``: None or per-instance (r, x), [batch, m] each."""
+    (no device needed).  ``line_impedances``: None or per-instance (r, x), [batch, m] each; ``load_powers``: None or per-instance
+    load powers, [batch, n_loads]."""
     lib = load()
-    t, keep = _topology_of(spec, line_impedances)
+    t, keep = _topology_of(spec, line_impedances, load_powers)
     buf = C.create_string_buffer(4096)
     rc = lib.gs_plan_describe(C.byref(t), C.byref(cfg), int(batch), int(cus), buf, 4096)
     if rc != GS_OK:
@@ -388,14 +411,16 @@ def mesh_schedule(spec: FeederSpec, nw: int = 4, ni: int = 10, acc_cap: int = 4,
 class Handle:
     """Owns one gs_handle (one GPU, one stream).  All array arguments are NumPy, batch-major."""
 
-    def __init__(self, spec: FeederSpec, cfg: gs_config, batch: int, device: int = 0, first_instance: int = 0, line_impedances=None):
+    def __init__(self, spec: FeederSpec, cfg: gs_config, batch: int, device: int = 0, first_instance: int = 0, line_impedances=None,
+                 load_powers=None):
         self._lib = load()
         self._h = _H()
         self.spec = spec
         self.B = int(batch)
         self.obs_dtype = np.dtype(np.float64)      # np.float32: step() / download_step() hand out the block rounded on the device (gs_step_f32)
-        t, keep = _topology_of(spec, line_impedances)
+        t, keep = _topology_of(spec, line_impedances, load_powers)
         self._pz = line_impedances is not None
+        self._pl = load_powers is not None
         rc = self._lib.gs_create(C.byref(t), C.byref(cfg), self.B, int(device), int(first_instance), C.byref(self._h))
         if rc != GS_OK:
             self._h = _H()
@@ -436,6 +461,23 @@ class Handle:
         r = np.empty((self.B, self.m)); x = np.empty((self.B, self.m))
         self._check(self._lib.gs_get_line_impedances(self._h, _ptr(r, _dp), _ptr(x, _dp)))
         return r, x
+
+    # -- per-instance load powers (gs_set_load_powers / gs_get_load_powers) ---------------------------------------------------
+    def set_load_powers(self, load_powers: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
+        pl = _f64(load_powers)
+        if pl.shape != (self.B, int(self.spec.n_loads)):
+            raise PowerFlowError(f"load powers must have shape {(self.B, int(self.spec.n_loads))}")
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mk.shape != (self.B,):
+                raise PowerFlowError(f"mask must have shape ({self.B},)")
+        self._check(self._lib.gs_set_load_powers(self._h, _ptr(pl, _dp), None if mk is None else _ptr(mk, _up)))
+
+    def get_load_powers(self) -> np.ndarray:
+        pl = np.empty((self.B, int(self.spec.n_loads)))
+        self._check(self._lib.gs_get_load_powers(self._h, _ptr(pl, _dp)))
+        return pl
 
     def _adopt(self, child) -> None:
         if not hasattr(self, "_children"):

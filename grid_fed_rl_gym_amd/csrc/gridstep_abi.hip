@@ -133,6 +133,10 @@ struct gs_handle : GsPlan {
   // device one), the nominal values they are checked against, the arguments of gs_k_line_params (LP.pz: the step kernels' entries)
   std::vector<double> inst_r, inst_x, nominal_r, nominal_x;
   GsLineParamArgs LP{}; uint8_t* d_pzmask = nullptr;
+  // per-instance load powers (GsPlan::pl): what the handle holds ([B][n_loads], host copy and device copy) and the arguments of
+  // gs_k_load_params (LL.pl: the step kernels' entries)
+  std::vector<double> inst_load;
+  GsLoadParamArgs LL{}; uint8_t* d_plmask = nullptr;
   double *fb_load = nullptr, *fb_gen = nullptr, *fb_tl = nullptr, *fb_tg = nullptr; uint8_t* fb_mask = nullptr; int32_t* fb_applied = nullptr;
   // host copies of the per-instance scalars: ONE page-locked block the device addresses -- gs_k_scalars stores into it itself (three
   // copies through the runtime's staging buffer cost 80 us of a 0.9 ms env.step()); hd_*: the same block as the device sees it
@@ -260,6 +264,18 @@ int launch_pack(gs_handle* h, const int32_t* map, int C, double* dst) {
   return GS_OK;
 }
 
+// A whole observation block [B][obs_dim] from the rows: every column, the constants included -- on a per-instance-loads handle
+// (GsPlan::pl) the static load columns of each instance are its own, written over the shared constants
+int launch_pack_obs(gs_handle* h, double* dst) {
+  const int rc = launch_pack(h, h->map_obs, h->obs_dim, dst);
+  if (rc || !h->pl) return rc;
+  const size_t threads = (size_t)h->B * 2 * h->n_loads;
+  hipLaunchKernelGGL(gs_k_load_columns, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->LL.pl, dst, h->B, h->obs_dim,
+                     2 * h->n + 2 * h->m + 1, h->n_loads);
+  HIPCHK(h, hipGetLastError());
+  return GS_OK;
+}
+
 int launch_unpack(gs_handle* h, const int32_t* map, int C, const double* src, int stride = 0) {
   if (C <= 0) return GS_OK;
   LaunchTimer lt(h, GS_K_UNPACK);
@@ -370,7 +386,7 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
       }
       GsF2Tables f2a = h->F2, f2b = h->F2;
       f2a.wg_offset = 0; f2b.wg_offset = n_first;
-      // pz...: the PZ kernels' pointer to the per-instance line impedances, behind the argument block
+      // pz...: the PZ / PL kernels' pointers to the per-instance line impedances / load powers, behind the argument block
       auto launch = [&](auto k, auto... pz) -> int {
         if (!k) return fail(h, GS_E_STATE, "%s: no such step kernel", h->f2().name);
         hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz...);
@@ -379,7 +395,11 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
         return GS_OK;
       };
       const GsStepKernels& k = gs_step_kernels[(int)h->step];
-      const int rc = h->pz ? launch(fc.enabled ? k.pz.stepc : k.pz.step, (const double*)h->LP.pz) : launch(fc.enabled ? k.plain.stepc : k.plain.step);
+      const double *pz = h->LP.pz, *pl = h->LL.pl;
+      const int rc = h->pz && h->pl ? launch(fc.enabled ? k.pz_pl.stepc : k.pz_pl.step, pz, pl)
+                     : h->pz        ? launch(fc.enabled ? k.pz.stepc : k.pz.step, pz)
+                     : h->pl        ? launch(fc.enabled ? k.pl.stepc : k.pl.step, pl)
+                                    : launch(fc.enabled ? k.plain.stepc : k.plain.step);
       if (rc) return rc;
       HIPCHK(h, hipGetLastError());
       return GS_OK;
@@ -433,6 +453,20 @@ int check_args(const gs_topology* topo, const gs_config* cfg, int32_t batch) {
     const std::string why = gs_check_line_impedances(*topo, batch, topo->line_r_inst, topo->line_x_inst, nullptr);
     if (!why.empty()) return fail(nullptr, GS_E_INVALID, "%s", why.c_str());
   }
+  if (topo->load_base_inst) {
+    const std::string why = gs_check_load_powers(topo->n_loads, batch, topo->load_base_inst, nullptr);
+    if (!why.empty()) return fail(nullptr, GS_E_INVALID, "%s", why.c_str());
+  }
+  return GS_OK;
+}
+
+// gs_k_load_params for the instances of mask (device, NULL = all)
+int launch_load_params(gs_handle* h, const uint8_t* d_mask) {
+  GsLoadParamArgs A = h->LL;
+  A.mask = d_mask;
+  const size_t threads = (size_t)h->groups * GS_LANES * (GS_PL_NP(A.n_loads) + 1);
+  hipLaunchKernelGGL(gs_k_load_params, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
   return GS_OK;
 }
 
@@ -592,7 +626,8 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     for (const GsSolveKernels& k : gs_solve_kernels) ok = ok && raise(k.solve, max_dyn) && raise(k.step.step, max_dyn) && raise(k.step.stepc, max_dyn);
     if (!ok) return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", max_dyn));
     for (const GsStepKernels& k : gs_step_kernels)
-      ok = ok && raise(k.plain.step, 160 * 1024) && raise(k.plain.stepc, 160 * 1024) && raise(k.pz.step, 160 * 1024) && raise(k.pz.stepc, 160 * 1024);
+      ok = ok && raise(k.plain.step, 160 * 1024) && raise(k.plain.stepc, 160 * 1024) && raise(k.pz.step, 160 * 1024) && raise(k.pz.stepc, 160 * 1024) &&
+           raise(k.pl.step, 160 * 1024) && raise(k.pl.stepc, 160 * 1024) && raise(k.pz_pl.step, 160 * 1024) && raise(k.pz_pl.stepc, 160 * 1024);
 #if defined(GS_BUILD_EXPERIMENTS)
     ok = ok && raise(gs_k_nr_sparse_lds, 160 * 1024);
 #endif
@@ -670,6 +705,22 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
         hipMemset(dpz, 0, n_pz * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       return bail(fail(nullptr, GS_E_HIP, "per-instance line impedances: upload failed"));
     if ((rc = launch_line_params(h, nullptr))) return bail(fail(nullptr, rc, "%s", h->err.c_str()));
+  }
+  if (h->pl) {
+    GsLoadParamArgs& A = h->LL;
+    const size_t Bl = (size_t)h->B * h->n_loads;
+    h->inst_load.assign(topo->load_base_inst, topo->load_base_inst + Bl);
+    A.B = h->B; A.groups = h->groups; A.n_loads = h->n_loads;
+    double *db = nullptr, *dpl = nullptr;
+    const size_t n_pl = (size_t)h->groups * GS_PL_NQ(A.n_loads) * GS_LANES * 2;
+    if ((rc = dev_upload(h, &A.tan_phi, h->pl_tan)) || (rc = dev_alloc(h, &db, Bl)) || (rc = dev_alloc(h, &h->d_plmask, (size_t)h->B)) ||
+        (rc = dev_alloc(h, &dpl, n_pl))) return bail(rc);
+    A.base = db; A.pl = dpl;
+    // (as for the line impedances above: the null stream's copy and memset are complete before the handle's stream derives from them)
+    if (hipMemcpy(db, h->inst_load.data(), Bl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(dpl, 0, n_pl * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      return bail(fail(nullptr, GS_E_HIP, "per-instance load powers: upload failed"));
+    if ((rc = launch_load_params(h, nullptr))) return bail(fail(nullptr, rc, "%s", h->err.c_str()));
   }
   { const double* q = nullptr; if ((rc = dev_upload(h, &q, h->cst))) return bail(rc); h->d_cst = const_cast<double*>(q); }
   if ((rc = upload_map(h, &h->map_obs, h->mo)) || (rc = upload_map(h, &h->map_vm, h->mvm)) || (rc = upload_map(h, &h->map_va, h->mva)) ||
@@ -821,6 +872,36 @@ int gs_get_line_impedances(const gs_handle* h, double* r, double* x) {
   return GS_OK;
 }
 
+// ---- per-instance load powers -----------------------------------------------------------------
+int gs_set_load_powers(gs_handle* h, const double* base, const uint8_t* mask) {
+  if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (!h->pl) return fail(h, GS_E_STATE, "gs_set_load_powers: the handle was created without per-instance load powers "
+                                         "(gs_topology::load_base_inst)");
+  if (!base) return fail(h, GS_E_INVALID, "gs_set_load_powers: base is [B][n_loads]");
+  const std::string why = gs_check_load_powers(h->n_loads, h->B, base, mask);
+  if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
+  GS_ENTER(h);
+  const size_t nl = (size_t)h->n_loads;
+  for (int b = 0; b < h->B; ++b) {
+    if (mask && !mask[b]) continue;
+    std::copy(base + b * nl, base + (b + 1) * nl, h->inst_load.begin() + b * nl);
+  }
+  // (a step still in flight may read the entries: the stream orders the copy and the derivation behind it)
+  HIPCHK(h, hipMemcpyAsync(const_cast<double*>(h->LL.base), h->inst_load.data(), h->inst_load.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (mask) HIPCHK(h, hipMemcpyAsync(h->d_plmask, mask, (size_t)h->B, hipMemcpyHostToDevice, h->stream));
+  int rc = launch_load_params(h, mask ? h->d_plmask : nullptr);
+  if (rc) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // (the caller's mask and the host copy are pageable)
+  return GS_OK;
+}
+
+int gs_get_load_powers(const gs_handle* h, double* base) {
+  if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (!h->pl) return fail(const_cast<gs_handle*>(h), GS_E_STATE, "gs_get_load_powers: the handle has no per-instance load powers");
+  if (base) std::copy(h->inst_load.begin(), h->inst_load.end(), base);
+  return GS_OK;
+}
+
 // ---- solver -------------------------------------------------------------------------------
 static const char* const kPzNoSolve = "gs_solve / gs_solve_device: this handle has per-instance line impedances, which the solver API does not "
                                       "support (the step, rollout and fallback entry points do)";
@@ -889,7 +970,7 @@ int gs_reset(gs_handle* h, const uint64_t* seeds, const uint8_t* mask, double* o
   h->was_reset = true;
   if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));       // no gather may still be reading an observation buffer
   h->gather_pending[0] = h->gather_pending[1] = false; h->obs_cur = 0;
-  int rc = launch_pack(h, h->map_obs, h->obs_dim, h->d_obs2[0]);   // every column, the constants included
+  int rc = launch_pack_obs(h, h->d_obs2[0]);   // every column, the constants included
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(h->d_obs2[1], h->d_obs2[0], (size_t)h->B * h->obs_dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   if (obs_out) HIPCHK(h, hipMemcpyAsync(obs_out, h->d_obs2[0], (size_t)h->B * h->obs_dim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1161,6 +1242,12 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
       GsRolloutPostArgs pa{fused ? nullptr : ro.rew, fused ? nullptr : ro.done, nxt, h->map_obs, h->d_cst, ro.term_count, ro.term_idx, ro.term_obs, ro.term_cap, h->obs_dim, t, h->B};
       hipLaunchKernelGGL(gs_k_rollout_post, dim3(h->groups), dim3(256), 0, h->stream, h->T, h->R, h->EC, h->slab, pa);
       HIPCHK(h, hipGetLastError());
+      if (h->pl) {      // (the fresh rows it wrote carry the shared constants: every instance's own static load columns over them)
+        const size_t threads = (size_t)h->B * 2 * h->n_loads;
+        hipLaunchKernelGGL(gs_k_load_columns, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->LL.pl, nxt, h->B,
+                           h->obs_dim, 2 * h->n + 2 * h->m + 1, h->n_loads);
+        HIPCHK(h, hipGetLastError());
+      }
     }
   }
   if ((rc = join_streams(h))) return rc;
@@ -1247,7 +1334,7 @@ int gs_set_state(gs_handle* h, const double* state) {
   // handle that is restored without ever having been reset (resume in a new process) must get them here
   if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
   h->gather_pending[0] = h->gather_pending[1] = false;
-  if ((rc = launch_pack(h, h->map_obs, h->obs_dim, h->d_obs2[h->obs_cur]))) return rc;
+  if ((rc = launch_pack_obs(h, h->d_obs2[h->obs_cur]))) return rc;
   HIPCHK(h, hipMemcpyAsync(h->d_obs2[h->obs_cur ^ 1], h->d_obs2[h->obs_cur], (size_t)h->B * h->obs_dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->was_reset = true;

@@ -569,3 +569,31 @@ struct GsLineParamArgs {
   double* pz;                            // [groups][nq][64] double pairs
   int32_t B, groups, n_slots, m, newton, pad;
 };
+
+// ---- per-instance load powers (gs_topology::load_base_inst, gs_set_load_powers) ----
+// What the second-generation step kernels read per instance instead of GsTables::load_base / load_q and the total_load argument:
+// Load.base_power of every load (grid_env.py:683-720, dynamics.py:54-75), its static reactive power base * tan(acos(pf))
+// (grid_env.py:769-770, base.py:283) and the sum of the base powers (grid_env.py:744).  Outside the slab, in the same order as the
+// line impedance entries above -- 16-byte pairs, batch-innermost, entry q of instance b = g * 64 + L at
+//   pl[((size_t)g * nq + q) * GS_LANES + L],  np = ceil(n_loads / 2), nq = 2 * np + 1,
+//   q = p       (p < np)   (P of load 2 p, P of load 2 p + 1): the two pairs of a Philox call's four loads are entries 2 p', 2 p' + 1
+//   q = np + p             (Q of load 2 p, Q of load 2 p + 1), Q = P * tan(acos(pf)), the host's product (topology.cpp)
+//   q = 2 np               (sum of P in list order from 0.0 as plan.cpp forms total_load, 0)
+// The odd half of the last pair of an odd n_loads holds 0.  Written by gs_k_load_params: an instance at the nominal load_base
+// gets the shared tables' bits.
+#define GS_PL_NP(n_loads) (((n_loads) + 1) / 2)
+#define GS_PL_NQ(n_loads) (2 * GS_PL_NP(n_loads) + 1)
+struct GsLoadParamArgs {
+  const double* base;                    // [B][n_loads] per-instance Load.base_power, watts
+  const uint8_t* mask;                   // [B] or NULL (all)
+  const double* tan_phi;                 // [n_loads] tan(acos(pf)), shared
+  double* pl;                            // [groups][nq][64] double pairs
+  int32_t B, groups, n_loads, pad;
+};
+#if defined(__HIPCC__)
+// constant ci of an observation (plan.cpp plan_maps: 2 l = P of load l, 2 l + 1 = its Q) as instance b holds it
+__device__ __forceinline__ double gs_pl_const(const double* __restrict__ pl, int n_loads, int b, int ci) {
+  const int l = ci >> 1, q = ((ci & 1) ? GS_PL_NP(n_loads) : 0) + (l >> 1);
+  return pl[(((size_t)(b / GS_LANES) * GS_PL_NQ(n_loads) + q) * GS_LANES + (b % GS_LANES)) * 2 + (l & 1)];
+}
+#endif

@@ -9,8 +9,8 @@
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
-// they launch the gs_k_*_nr_dmfma kernels below around their solver); the second (kernels_flow2.hip): step, stepc and their PZ
-// forms per StepMember.
+// they launch the gs_k_*_nr_dmfma kernels below around their solver); the second (kernels_flow2.hip): step, stepc and their PZ /
+// PL forms per StepMember.
 typedef void (*GsSolveFn)(GsTables T, GsRows R, GsSolveCfg C, double* slab, int B);
 typedef void (*GsStepFn)(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions, double total_load,
                          GsPackArgs PA, GsFusedChecks FC);
@@ -20,12 +20,17 @@ typedef void (*GsF2StepPzFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, G
                              double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, const double* pz);
 template <class Fn> struct GsStepFns { Fn step = nullptr, stepc = nullptr; };      // the plain step and the step with the checks
 struct GsSolveKernels { GsSolveFn solve; GsStepFns<GsStepFn> step; };
-struct GsStepKernels { GsStepFns<GsF2StepFn> plain; GsStepFns<GsF2StepPzFn> pz; };
+typedef void (*GsF2StepPzPlFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions,
+                               double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, const double* pz, const double* pl);
+// plain; pz: per-instance line impedances; pl: per-instance load powers (one pointer behind the block, GsF2StepPzFn's shape); pz_pl: both
+struct GsStepKernels { GsStepFns<GsF2StepFn> plain; GsStepFns<GsF2StepPzFn> pz, pl; GsStepFns<GsF2StepPzPlFn> pz_pl; };
 extern const std::array<GsSolveKernels, (size_t)SolveMember::nr_sparse_lds + 1> gs_solve_kernels;
 extern const std::array<GsStepKernels, kStepMemberCount> gs_step_kernels;
 
 extern "C" {
 __global__ void gs_k_line_params(GsLineParamArgs A);
+__global__ void gs_k_load_params(GsLoadParamArgs A);
+__global__ void gs_k_load_columns(const double* __restrict__ pl, double* __restrict__ out, int B, int obs_dim, int c0, int n_loads);
 __global__ void gs_k_pre_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,
                                   const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC);
 __global__ void gs_k_post_nr_dmfma(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,

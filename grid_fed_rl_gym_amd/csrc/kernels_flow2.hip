@@ -250,11 +250,14 @@ struct F2Stamp {
 // keeps its bus state (voltage, the T and s of the elimination) in registers across its two sweeps: twice the registers per wave.
 // PZ = 1: per-instance line impedances (gs_internal.h GsLineParamArgs): the branch z / y, the Newton-Raphson (G, B) pairs and the
 // epilogue's line admittances come from `pz`, the instance's own values, instead of the handle's shared tables; PZ = 0 never reads it.
-template <int SOLVER, int CHK, int NW, int NI, int IW, int PZ = 0>
+// PL = 1: per-instance load powers (gs_internal.h GsLoadParamArgs): the base powers of the load draw, the sum of the frequency update
+// and the static (P_l, Q_l) observation columns -- which such a handle's step writes itself, every step -- come from `pl` instead of
+// T.load_base, the total_load argument and the columns left in place at reset; PL = 0 never reads it.
+template <int SOLVER, int CHK, int NW, int NI, int IW, int PZ = 0, int PL = 0>
 __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, const GsRows& R, const GsSolveCfg& C, const GsEnvCfg& E,
                                         double* __restrict__ slab, int B, const double* __restrict__ actions, double total_load,
                                         const GsPackArgs& PA, const GsFusedChecks& FC, const GsRolloutStep& RS,
-                                        const double* __restrict__ pz = nullptr) {
+                                        const double* __restrict__ pz = nullptr, const double* __restrict__ pl = nullptr) {
   f2_touch_arguments();
   // IW instances per workgroup (32; 16 or 8 for small feeders, where more of a wavefront's lanes go to different buses):
   // lane = hv * IW + l, sub-group hv of the wave works on its own bus for instance l
@@ -274,6 +277,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
   // PZ: this lane's per-instance entries (pz_at(q): entry q, one 16-byte load; every lane of the grid lies inside the groups)
   const double* const pz_lane = PZ ? pz + ((size_t)g * GS_PZ_NQ(F.n_slots, T.m) * GS_LANES + L) * 2 : nullptr;
   auto pz_at = [&](int q) -> double2 { return *(const double2*)(pz_lane + (size_t)q * (2 * GS_LANES)); };
+  // PL: this lane's load entries, addressed the same way (pl_at(q): one 16-byte load)
+  const double* const pl_lane = PL ? pl + ((size_t)g * GS_PL_NQ(T.n_loads) * GS_LANES + L) * 2 : nullptr;
+  auto pl_at = [&](int q) -> double2 { return *(const double2*)(pl_lane + (size_t)q * (2 * GS_LANES)); };
   // Scalars of the start-up, read from the kernel arguments ONCE: the compiler treats an argument as free to read again
   // wherever it is short of scalar registers, and the start-up was 47 scalar loads, most of them waited for one by one
   // (~150 cycles each, 4 k cycles before the first barrier); a value that went through F2_KEEP is kept (or parked in a
@@ -377,6 +383,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
         double* row = RS.obs_prev + (size_t)(b - l + k) * RS.obs_dim;
         for (int c = threadIdx.x; c < RS.obs_dim; c += NT) {
           const int sidx = RS.map[c];
+          if constexpr (PL != 0)       // (the instance's own static load columns)
+            row[c] = (sidx >= 0) ? Sk.lane_row((size_t)sidx * GS_LANES).get() : gs_pl_const(pl, T.n_loads, b - l + k, -sidx - 1);
+          else
           row[c] = (sidx >= 0) ? Sk.lane_row((size_t)sidx * GS_LANES).get() : RS.cst[-sidx - 1];
         }
       }
@@ -463,7 +472,11 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
       const int l0 = 4 * p;
       double base4[4];                 // asked for before the draw, whose ~350 instructions cover the round trip
 #pragma unroll
-      for (int k = 0; k < 4; ++k) base4[k] = T.load_base[min(l0 + k, nl_ - 1)];
+      for (int k = 0; k < 4; ++k) base4[k] = PL ? 0.0 : T.load_base[min(l0 + k, nl_ - 1)];
+      if constexpr (PL != 0) {         // (loads l0, l0 + 1 | l0 + 2, l0 + 3: entries 2 p and 2 p + 1, two 16-byte loads per lane)
+        const double2 b01 = pl_at(2 * p), b23 = pl_at(min(2 * p + 1, GS_PL_NP(nl_) - 1));
+        base4[0] = b01.x; base4[1] = b01.y; base4[2] = b23.x; base4[3] = b23.y;
+      }
       double z[4] = {0.0, 0.0, 0.0, 0.0};
       if (E.stochastic_loads) rng_normal_quad(seed, inst, snew, DRAW_LOAD0 + p, z);
       double lp[4];
@@ -1675,6 +1688,16 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
           for (int cp = lane; cp < m; cp += 64) {
             const double2 v = f2_ld2(o_tile + (unsigned)cp * SB + ((unsigned)r << 4)); o[2 * n + 2 * cp] = v.x; o[2 * n + 2 * cp + 1] = v.y; }
         }
+        if constexpr (PL != 0) {
+          // the static (P_l, Q_l) columns of instance br (grid_env.py:769-770): lane = load, consecutive lanes on consecutive
+          // column pairs; the entries are the ones the draw waves of this workgroup read at the step's start
+          const double* const pr = pl + ((size_t)g * GS_PL_NQ(nl_) * GS_LANES + hs * IW + r) * 2;
+          double* const ol = o + 2 * n + 2 * m + 1;
+          for (int cp = lane; cp < nl_; cp += 64) {
+            const size_t e = (size_t)(cp >> 1) * (2 * GS_LANES) + (cp & 1);
+            ol[2 * cp] = pr[e]; ol[2 * cp + 1] = pr[e + (size_t)GS_PL_NP(nl_) * (2 * GS_LANES)];
+          }
+        }
       }
     }
     stp.hit(F2_ST_EPILOGUE);
@@ -1700,7 +1723,9 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     total_curt += p * (1.0 - env_lds[(F.env_curt + gi) * IW + l]);
   }
   const double totloss = totloss0 + gs_div_by(losses * dt, 3600.0, 1.0 / 3600.0);      // grid_env.py:739
-  const double imbalance = gs_div_by(total_gen - total_load - losses * E.power_base, 1e6, 1.0 / 1e6);
+  double load_sum = total_load;                                        // sum(load.active_power), grid_env.py:744
+  if constexpr (PL != 0) load_sum = pl_at(2 * GS_PL_NP(nl_)).x;        // (the instance's own, formed once per upload by gs_k_load_params)
+  const double imbalance = gs_div_by(total_gen - load_sum - losses * E.power_base, 1e6, 1.0 / 1e6);
   double f = f_old;                                                    // dynamics.py:260-273
   f += ((imbalance - E.D * (f - E.f0)) / (2.0 * E.H * E.f0)) * dt;
   f = fmax(55.0, fmin(65.0, f));
@@ -1793,31 +1818,50 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
 // The step kernels of member `name`, shaped by its row of kStepMembers: F2_KERNELS defines gs_k_step_<name> and gs_k_stepc_<name>
 // (the post-step checks in its epilogue), F2_KERNELS_PZ their per-instance line impedance forms gs_k_step_<name>_pz /
 // gs_k_stepc_<name>_pz (PZ = 1: the pointer to the per-instance entries is an argument of its own behind the block the others read,
-// F2ArgBlock's offsets unchanged, and is read from the formal parameter).  OCC: the member's occupancy attribute.  Each line also
-// files its two kernels under the member's enum value (f2_kernels / f2_kernels_pz), where the launch table below finds them.
+// F2ArgBlock's offsets unchanged, and is read from the formal parameter), F2_KERNELS_PL the per-instance load power forms
+// gs_k_step*_<name>_pl (PL = 1, its pointer in the same place) and F2_KERNELS_PZ_PL the forms with both, gs_k_step*_<name>_pz_pl
+// (pz, then pl).  OCC: the member's occupancy attribute.  Each line also files its two kernels under the member's enum value
+// (f2_kernels / f2_kernels_pz / f2_kernels_pl / f2_kernels_pz_pl), where the launch table below finds them.
 template <StepMember M> constexpr GsStepFns<GsF2StepFn> f2_kernels() { return {}; }
 template <StepMember M> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pz() { return {}; }
+template <StepMember M> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pl() { return {}; }
+template <StepMember M> constexpr GsStepFns<GsF2StepPzPlFn> f2_kernels_pz_pl() { return {}; }
 #define F2_PZ_PARAM_0
 #define F2_PZ_PARAM_1 , const double* __restrict__ pz
 #define F2_PZ_ARG_0 nullptr
 #define F2_PZ_ARG_1 pz
-#define F2_KERNEL(kernel, name, CHK, PZ, OCC)                                                                               \
+#define F2_PL_PARAM_0
+#define F2_PL_PARAM_1 , const double* __restrict__ pl
+#define F2_PL_ARG_0 nullptr
+#define F2_PL_ARG_1 pl
+#define F2_KERNEL(kernel, name, CHK, PZ, PL, OCC)                                                                           \
   extern "C" __global__ void __launch_bounds__(64 * step_row(StepMember::name).nw) OCC                                      \
   kernel(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,                     \
-         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS F2_PZ_PARAM_##PZ) { \
+         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS F2_PZ_PARAM_##PZ \
+         F2_PL_PARAM_##PL) {                                                                                                \
     constexpr StepMemberRow r = step_row(StepMember::name);                                                                 \
     GS_ARGS_IN_PLACE(F2ArgBlock, A);                                                                                        \
-    f2_step<r.solver, CHK, r.nw, r.ni, r.iw, PZ>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, A->FC, \
-                                               A->RS, F2_PZ_ARG_##PZ);                                                      \
+    f2_step<r.solver, CHK, r.nw, r.ni, r.iw, PZ, PL>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, \
+                                                   A->FC, A->RS, F2_PZ_ARG_##PZ, F2_PL_ARG_##PL);                           \
   }
 #define F2_KERNELS(name, OCC)                                                                                               \
-  F2_KERNEL(gs_k_step_##name, name, 0, 0, OCC)                                                                              \
-  F2_KERNEL(gs_k_stepc_##name, name, 1, 0, OCC)                                                                             \
+  F2_KERNEL(gs_k_step_##name, name, 0, 0, 0, OCC)                                                                           \
+  F2_KERNEL(gs_k_stepc_##name, name, 1, 0, 0, OCC)                                                                          \
   template <> constexpr GsStepFns<GsF2StepFn> f2_kernels<StepMember::name>() { return {gs_k_step_##name, gs_k_stepc_##name}; }
 #define F2_KERNELS_PZ(name, OCC)                                                                                            \
-  F2_KERNEL(gs_k_step_##name##_pz, name, 0, 1, OCC)                                                                         \
-  F2_KERNEL(gs_k_stepc_##name##_pz, name, 1, 1, OCC)                                                                        \
+  F2_KERNEL(gs_k_step_##name##_pz, name, 0, 1, 0, OCC)                                                                      \
+  F2_KERNEL(gs_k_stepc_##name##_pz, name, 1, 1, 0, OCC)                                                                     \
   template <> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pz<StepMember::name>() { return {gs_k_step_##name##_pz, gs_k_stepc_##name##_pz}; }
+#define F2_KERNELS_PL(name, OCC)                                                                                            \
+  F2_KERNEL(gs_k_step_##name##_pl, name, 0, 0, 1, OCC)                                                                      \
+  F2_KERNEL(gs_k_stepc_##name##_pl, name, 1, 0, 1, OCC)                                                                     \
+  template <> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pl<StepMember::name>() { return {gs_k_step_##name##_pl, gs_k_stepc_##name##_pl}; }
+#define F2_KERNELS_PZ_PL(name, OCC)                                                                                         \
+  F2_KERNEL(gs_k_step_##name##_pz_pl, name, 0, 1, 1, OCC)                                                                   \
+  F2_KERNEL(gs_k_stepc_##name##_pz_pl, name, 1, 1, 1, OCC)                                                                  \
+  template <> constexpr GsStepFns<GsF2StepPzPlFn> f2_kernels_pz_pl<StepMember::name>() {                                    \
+    return {gs_k_step_##name##_pz_pl, gs_k_stepc_##name##_pz_pl};                                                           \
+  }
 
 #if defined(GS_BUILD_EXPERIMENTS)
 F2_KERNELS(fbs_flow2, )
@@ -1837,11 +1881,28 @@ F2_KERNELS_PZ(fbs_flow2s, )
 F2_KERNELS_PZ(nr_flow2s, )
 F2_KERNELS_PZ(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
 F2_KERNELS_PZ(fbs_flow2x, )
+// per-instance load powers: every member, and together with the line impedances wherever a member has the _pz form
+#if defined(GS_BUILD_EXPERIMENTS)
+F2_KERNELS_PL(fbs_flow2, )
+#endif
+F2_KERNELS_PL(nr_flow2, )
+F2_KERNELS_PL(fbs_flow2s, )
+F2_KERNELS_PL(nr_flow2s, )
+F2_KERNELS_PL(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
+F2_KERNELS_PL(fbs_flow2x, )
+F2_KERNELS_PL(nr_mesh2, __attribute__((amdgpu_waves_per_eu(2, 2))))
+F2_KERNELS_PZ_PL(nr_flow2, )
+F2_KERNELS_PZ_PL(fbs_flow2s, )
+F2_KERNELS_PZ_PL(nr_flow2s, )
+F2_KERNELS_PZ_PL(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
+F2_KERNELS_PZ_PL(fbs_flow2x, )
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host only: the device pass would put a copy of the table into the code object)
 template <size_t... M> constexpr std::array<GsStepKernels, sizeof...(M)> f2_launch_table(std::index_sequence<M...>) {
   static_assert(((kStepMembers[M].pz == (f2_kernels_pz<StepMember(M)>().step != nullptr)) && ...), "kStepMembers: pz disagrees with F2_KERNELS_PZ");
-  return {{{f2_kernels<StepMember(M)>(), f2_kernels_pz<StepMember(M)>()}...}};
+  static_assert((((M != 0) == (f2_kernels_pl<StepMember(M)>().step != nullptr)) && ...), "every step member has its F2_KERNELS_PL forms");
+  static_assert(((kStepMembers[M].pz == (f2_kernels_pz_pl<StepMember(M)>().step != nullptr)) && ...), "kStepMembers: pz disagrees with F2_KERNELS_PZ_PL");
+  return {{{f2_kernels<StepMember(M)>(), f2_kernels_pz<StepMember(M)>(), f2_kernels_pl<StepMember(M)>(), f2_kernels_pz_pl<StepMember(M)>()}...}};
 }
 extern const std::array<GsStepKernels, kStepMemberCount> gs_step_kernels = f2_launch_table(std::make_index_sequence<kStepMemberCount>());
 #endif
@@ -1908,3 +1969,39 @@ extern "C" __global__ void __launch_bounds__(256) gs_k_line_params(GsLineParamAr
   out[(size_t)(A.n_slots + q) * GS_LANES] = e1;
 }
 
+
+// The per-instance load entries (gs_internal.h GsLoadParamArgs) of every lane of the slab groups (a padding lane past B takes
+// instance B - 1's values) from their [B][n_loads] base powers: one thread per (lane, pair of loads), plus one per lane for the
+// sum -- in list order from 0.0, as plan.cpp forms total_load.  Q = P * tan(acos(pf)) is the host's product (topology.cpp).
+extern "C" __global__ void __launch_bounds__(256) gs_k_load_params(GsLoadParamArgs A) {
+#pragma clang fp contract(off)
+  const int np = GS_PL_NP(A.n_loads), per = np + 1;
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)A.groups * GS_LANES * per) return;
+  const int lane = (int)(t / per), q = (int)(t % per);
+  const int b = lane < A.B ? lane : A.B - 1;
+  if (A.mask && !A.mask[b]) return;
+  const int g = lane / GS_LANES, L = lane % GS_LANES;
+  double2* const out = (double2*)A.pl + (size_t)g * GS_PL_NQ(A.n_loads) * GS_LANES + L;
+  const double* const base = A.base + (size_t)b * A.n_loads;
+  if (q == np) {
+    double sum = 0.0;
+    for (int l = 0; l < A.n_loads; ++l) sum += base[l];
+    out[(size_t)(2 * np) * GS_LANES] = make_double2(sum, 0.0);
+    return;
+  }
+  const int l0 = 2 * q, l1 = l0 + 1;
+  const double p0 = base[l0], p1 = l1 < A.n_loads ? base[l1] : 0.0;
+  out[(size_t)q * GS_LANES] = make_double2(p0, p1);
+  out[(size_t)(np + q) * GS_LANES] = make_double2(p0 * A.tan_phi[l0], l1 < A.n_loads ? p1 * A.tan_phi[l1] : 0.0);
+}
+
+// out[b][c0 + 2 l], out[b][c0 + 2 l + 1] = (P_l, Q_l) of instance b: the static load columns of an observation block [B][obs_dim]
+// that gs_k_pack has filled from the shared constants (reset, restored checkpoint, the fresh rows behind a rollout's last step)
+extern "C" __global__ void __launch_bounds__(256)
+gs_k_load_columns(const double* __restrict__ pl, double* __restrict__ out, int B, int obs_dim, int c0, int n_loads) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)B * 2 * n_loads) return;
+  const int b = (int)(t / (2 * n_loads)), ci = (int)(t % (2 * n_loads));
+  out[(size_t)b * obs_dim + c0 + ci] = gs_pl_const(pl, n_loads, b, ci);
+}

@@ -752,7 +752,8 @@ std::string plan_maps(const HostTopology& ht, GsPlan& p) {
     while (c1 < (int)mo.size() && mo[c1] < 0) ++c1;
     bool one_block = true;
     for (int c = c1; c < (int)mo.size(); ++c) one_block = one_block && mo[c] >= 0;
-    if (one_block && !GS_EXPERIMENT_ENV("GS_PACK_ALL_COLUMNS")) { p.obs_skip0 = c0; p.obs_skip1 = c1; }
+    // (per-instance load powers: no column is the same for every instance -- the step writes them all, the copies move them all)
+    if (one_block && !GS_EXPERIMENT_ENV("GS_PACK_ALL_COLUMNS") && !p.pl) { p.obs_skip0 = c0; p.obs_skip1 = c1; }
   }
   if ((int)mo.size() != p.obs_dim || (int)mst.size() != p.state_dim) return reject(p, GS_E_INVALID, "internal: layout map size mismatch");
   p.rf.resize(SF_COUNT); p.ri.resize(SI_COUNT); p.ru.resize(SU_COUNT);
@@ -878,6 +879,38 @@ std::string gs_check_line_impedances(const gs_topology& topo, int batch, const d
   return "";
 }
 
+// ---- per-instance load powers: every second-generation step member takes them (nothing of its tables depends on the loads; the
+// flat start of the Newton-Raphson members does not either, so their flat-start table / W product stays)
+std::string plan_load_params(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, GsPlan& p) {
+  if (!p.second_gen()) {
+    std::string why = !p.flow2_why.empty() ? p.flow2_why : !p.mesh_why.empty() ? p.mesh_why
+                    : cfg.solver_kind == GS_SOLVER_FBS && cfg.fbs_warm_start ? "warm start"
+                    : cfg.solver_kind == GS_SOLVER_NR && cfg.jacobian_mode != GS_JACOBIAN_EXACT ? "as-coded Jacobian"
+                    : std::string("the step runs on ") + kSolveName[(int)p.solve];
+    return "per-instance load powers need a second-generation step member: " + why;
+  }
+  p.pl_tan.resize((size_t)topo.n_loads);
+  for (int l = 0; l < topo.n_loads; ++l) p.pl_tan[l] = std::tan(std::acos(topo.load_pf[l]));      // topology.cpp: load_q = base * this
+  return "";
+}
+
+std::string gs_check_load_powers(int n_loads, int batch, const double* base_inst, const uint8_t* mask) {
+  if (n_loads <= 0) return "load powers: the feeder has no loads";
+  if (!base_inst) return "load powers: base is NULL";
+  char msg[256];
+  for (int b = 0; b < batch; ++b) {
+    if (mask && !mask[b]) continue;
+    for (int l = 0; l < n_loads; ++l) {
+      const double v = base_inst[(size_t)b * n_loads + l];
+      if (!std::isfinite(v)) snprintf(msg, sizeof msg, "load powers: instance %d load %d is not finite", b, l);
+      else if (!(v >= 0.0)) snprintf(msg, sizeof msg, "load powers: instance %d load %d is negative", b, l);
+      else continue;
+      return msg;
+    }
+  }
+  return "";
+}
+
 std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, int batch, int cus, GsPlan& p) {
   p.B = batch; p.Bp = (batch + 63) / 64 * 64; p.groups = p.Bp / 64;
   int W = cfg.waves_per_group;
@@ -899,6 +932,8 @@ std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTop
   p.pz = topo.line_r_inst != nullptr;
   p.nr_flat = p.f2().newton() && !getenv("GS_NR_NO_FLAT") && !p.pz;
   if (p.pz && (why = plan_line_params(topo, cfg, ht, p)).empty() == false) { p.err_code = GS_E_TOPOLOGY; return why; }
+  p.pl = topo.load_base_inst != nullptr;
+  if (p.pl && (why = plan_load_params(topo, cfg, ht, p)).empty() == false) { p.err_code = GS_E_TOPOLOGY; return why; }
   if (ht.has_lu) plan_lu_schedule(ht, p);
   if (p.solve == SolveMember::nr_dense_mfma && !(why = plan_dense(cfg, ht, cus, p)).empty()) return why;
 #if defined(GS_BUILD_EXPERIMENTS)
@@ -929,7 +964,8 @@ void gs_plan_format(const GsPlan& p, const HostTopology& ht, char* buf, int bufl
            "\"rows_per_group\": %d, \"slab_bytes\": %zu, \"obs_dim\": %d, \"action_dim\": %d, "
            "\"instances_per_workgroup\": %d, \"workgroups\": %d, \"step_lds_bytes\": %zu, \"step_launches\": %d, \"solve_kernel\": \"%s\", \"flow2\": \"%s\", "
            "\"mesh2\": \"%s\", \"mesh_levels\": %d, \"mesh_rows\": %d, \"mesh_message_units\": %d, \"mesh_messages\": %d, \"mesh_accumulators\": %d, "
-           "\"dense_form\": \"%s\", \"dense_workgroups\": %d, \"dense_lds_bytes\": %zu, \"per_instance_z\": %d, \"nr_flat_start_table\": %d}",
+           "\"dense_form\": \"%s\", \"dense_workgroups\": %d, \"dense_lds_bytes\": %zu, \"per_instance_z\": %d, \"nr_flat_start_table\": %d, "
+           "\"per_instance_loads\": %d}",
            f2 ? p.f2().name : kSolveName[(int)p.solve], p.n, p.m, ht.nnz, ht.is_forest ? "true" : "false", ht.n_levels,
            ht.max_level_width, ht.lu_n_slots, ht.lu_n_orig, (long long)ht.lu_n_pairs, f2 ? p.f2().nw : p.W, p.groups,
            p.R.total, (size_t)p.groups * p.R.total * GS_LANES * sizeof(double), p.obs_dim, p.action_dim,
@@ -937,5 +973,5 @@ void gs_plan_format(const GsPlan& p, const HostTopology& ht, char* buf, int bufl
            kSolveName[(int)p.solve], f2 ? "on" : (p.flow2_why.empty() ? "n/a" : p.flow2_why.c_str()),
            p.step == StepMember::nr_mesh2 ? "on" : (p.mesh_why.empty() ? "n/a" : p.mesh_why.c_str()), p.mesh_levels, p.mesh_rows, p.mesh_units,
            p.mesh_messages, p.mesh_accs, dense ? (p.dense_blockrow ? "block_row" : "panel") : "n/a", dense ? p.dense_grid : 0, dense ? p.dense_lds : (size_t)0,
-           p.pz ? 1 : 0, p.nr_flat ? 1 : 0);
+           p.pz ? 1 : 0, p.nr_flat ? 1 : 0, p.pl ? 1 : 0);
 }

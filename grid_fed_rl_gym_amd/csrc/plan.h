@@ -63,6 +63,12 @@ struct GsPlan {
   bool pz = false, nr_flat = false;
   std::vector<int32_t> pz_ops_ptr, pz_ops; std::vector<uint8_t> pz_has, pz_zero;
 
+  // per-instance load powers (gs_topology::load_base_inst): the step member's PL kernels read gs_k_load_params' entries
+  // (GsLoadParamArgs); such a handle has no block of constant observation columns (obs_skip0 == obs_skip1): its step writes the
+  // static load columns itself.  pl_tan: tan(acos(pf)) per load, topology.cpp's expression
+  bool pl = false;
+  std::vector<double> pl_tan;
+
   bool second_gen() const { return step != StepMember::none; }
   const StepMemberRow& f2() const { return step_row(step); }
 };
@@ -72,6 +78,8 @@ struct GsPlan {
 std::string gs_plan(const gs_topology& topo, const gs_config& cfg, const HostTopology& ht, int batch, int cus, GsPlan& out);
 // "" or why per-instance impedances r_inst / x_inst [B][m] break the rules of gs_topology (rows where mask[b] != 0, or all)
 std::string gs_check_line_impedances(const gs_topology& topo, int batch, const double* r_inst, const double* x_inst, const uint8_t* mask);
+// "" or why per-instance load powers base_inst [B][n_loads] break the rules of gs_topology (rows where mask[b] != 0, or all)
+std::string gs_check_load_powers(int n_loads, int batch, const double* base_inst, const uint8_t* mask);
 // gs_describe's JSON for a handle with this plan
 void gs_plan_format(const GsPlan& p, const HostTopology& ht, char* buf, int buflen);
 // GsF2Tables::mesh_w of an all-PQ network (see plan.cpp); false: J0 singular or the sizes do not fit

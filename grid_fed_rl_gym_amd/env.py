@@ -67,7 +67,7 @@ class BatchedGridEnvironment:
                  linear_solver: str = "auto", power_base: Optional[float] = None, device: int = 0,
                  first_instance: int = 0, waves_per_group: int = 0, warm_start: bool = False,
                  pinned_host_buffers: bool = False, recycle_host_buffers: bool = True, obs_dtype: Any = np.float64,
-                 line_impedances: Optional[Tuple[Any, Any]] = None, **kwargs: Any) -> None:
+                 line_impedances: Optional[Tuple[Any, Any]] = None, load_powers: Optional[Any] = None, **kwargs: Any) -> None:
         spec = feeder if isinstance(feeder, FeederSpec) else flatten_feeder(feeder)
         if renewable_sources is not None:
             keep = [g for g in range(spec.n_gens)
@@ -108,7 +108,10 @@ class BatchedGridEnvironment:
         # line_impedances=(r, x), [num_envs, m] per unit: every instance solves on its own line data (domain randomisation of the
         # network; gs_topology::line_r_inst / line_x_inst) -- served by the second-generation radial step members
         pz = None if line_impedances is None else _lib.check_line_impedances(spec, line_impedances[0], line_impedances[1], self.num_envs)
-        self._h = _lib.Handle(spec, cfg, self.num_envs, device, first_instance, line_impedances=pz)
+        # load_powers, [num_envs, n_loads] watts: instance b is the environment whose loads have base_power = load_powers[b] (domain
+        # randomisation of the loading; gs_topology::load_base_inst) -- served by every second-generation step member
+        pl = None if load_powers is None else _lib.check_load_powers(spec, load_powers, self.num_envs)
+        self._h = _lib.Handle(spec, cfg, self.num_envs, device, first_instance, line_impedances=pz, load_powers=pl)
         # obs_dtype=np.float32 (opt-in): step() returns the observation block in the dtype the reference DECLARES for its observation
         # space (grid_env.py:346) -- rounded on the device, half the bytes over PCIe; reset(), step_device() and the rollout collector
         # stay float64, and so does every parity test
@@ -255,6 +258,26 @@ class BatchedGridEnvironment:
     def line_impedances(self) -> Tuple[np.ndarray, np.ndarray]:
         """Host copies (r, x), [num_envs, m] each, of the per-instance line impedances the device solves on."""
         return self._h.get_line_impedances()
+
+    def set_load_powers(self, load_powers: Any, mask: Optional[Any] = None) -> None:
+        """New per-instance load powers ([num_envs, n_loads], watts) for the instances of ``mask`` ([num_envs] bool, None = all),
+        in effect from the next step.  Not environment state: reset() and set_state() leave them alone.  Only on an environment
+        created with ``load_powers`` (otherwise the library's GS_E_STATE, as PowerFlowError)."""
+        if not getattr(self._h, "_pl", False):
+            self._h.set_load_powers(np.zeros((self.num_envs, self.spec.n_loads)), mask)
+        rows = np.ones(self.num_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
+        if rows.shape != (self.num_envs,):
+            raise ValueError(f"mask must have shape ({self.num_envs},)")
+        pl = np.ascontiguousarray(load_powers, dtype=np.float64)
+        if pl.shape != (self.num_envs, self.spec.n_loads):
+            raise ValueError(f"load powers must have shape {(self.num_envs, self.spec.n_loads)}")
+        _lib.check_load_powers(self.spec, pl[rows], int(rows.sum()))
+        self._h.set_load_powers(pl, None if mask is None else rows)
+
+    @property
+    def load_powers(self) -> np.ndarray:
+        """Host copy, [num_envs, n_loads], of the per-instance load powers the device draws around."""
+        return self._h.get_load_powers()
 
     @property
     def handle(self) -> "_lib.Handle":

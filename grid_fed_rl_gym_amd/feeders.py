@@ -521,3 +521,16 @@ def randomized_line_impedances(spec: FeederSpec, num_envs: int, rel: float = 0.1
     zero = ~(np.hypot(r0, x0) > 1e-12)
     r[:, zero] = r0[zero]; x[:, zero] = x0[zero]
     return np.ascontiguousarray(r), np.ascontiguousarray(x)
+
+
+def randomized_load_powers(spec: FeederSpec, num_envs: int, low: float = 0.5, high: float = 1.5, seed: int = 0,
+                           per_load: bool = False) -> np.ndarray:
+    """Per-instance load powers for domain randomisation of the loading: [num_envs, n_loads] watts, the nominal ``load_base`` times
+    seeded factors U(low, high) -- one loading multiplier per instance, or with ``per_load`` an independent factor per instance and
+    load (BatchedGridEnvironment(load_powers=...))."""
+    if not (0.0 <= low <= high) or not np.isfinite(high):
+        raise ValueError("need 0 <= low <= high, finite")
+    rng = np.random.default_rng(seed)
+    shape = (int(num_envs), int(spec.n_loads) if per_load else 1)
+    base = np.asarray(spec.load_base, dtype=np.float64)
+    return np.ascontiguousarray(np.broadcast_to(rng.uniform(low, high, shape), (int(num_envs), int(spec.n_loads))) * base[None, :])

@@ -103,9 +103,12 @@ class ShardedGridEnvironment:
         li = env_kwargs.pop("line_impedances", None)
         if li is not None:      # global [global_num_envs, m] arrays: this shard's rows
             li = (np.asarray(li[0])[self.start:self.stop], np.asarray(li[1])[self.start:self.stop])
+        lp = env_kwargs.pop("load_powers", None)
+        if lp is not None:      # global [global_num_envs, n_loads] array: this shard's rows
+            lp = np.asarray(lp)[self.start:self.stop]
         self.env = BatchedGridEnvironment(feeder, num_envs=self.stop - self.start,
                                           device=self.rank if device is None else device,
-                                          first_instance=self.start, line_impedances=li, **env_kwargs)
+                                          first_instance=self.start, line_impedances=li, load_powers=lp, **env_kwargs)
         self._comm = False
 
     def init_rccl(self, unique_id: Any = None) -> None:

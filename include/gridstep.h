@@ -99,6 +99,15 @@ typedef struct gs_topology {
    * nr_flow2s / nr_flow2, "per_instance_z": 1); anything else is GS_E_TOPOLOGY.  gs_solve / gs_solve_device are GS_E_STATE on it. */
   const double* line_r_inst;
   const double* line_x_inst;
+  /* Per-instance load powers (domain randomisation of the loading): [batch][n_loads] watts, or NULL.  Non-NULL makes a
+   * per-instance-loads handle: instance b behaves as the reference environment whose loads have base_power = load_base_inst[b][l] --
+   * its realised load powers (dynamics.py:54-75, into the injections of grid_env.py:683-720), the sum of load.active_power in its
+   * frequency update (grid_env.py:744) and the static [P_l, Q_l] columns of its observation (grid_env.py:769-770, Q_l = P_l *
+   * tan(acos(load_pf[l])) with the shared power factor) all follow the instance.  load_base above stays mandatory (the nominal
+   * values).  Every value must be finite and >= 0, and n_loads > 0 (GS_E_INVALID).  Only a second-generation step member serves
+   * such a handle (gs_describe "kernel": fbs_flow2s / fbs_flow2h / fbs_flow2x / nr_flow2s / nr_flow2 / nr_mesh2,
+   * "per_instance_loads": 1); anything else is GS_E_TOPOLOGY.  Combines with line_r_inst / line_x_inst on the radial members. */
+  const double* load_base_inst;
 } gs_topology;
 
 /* Solver + environment configuration.  Replaces the constructor kwargs of
@@ -193,6 +202,13 @@ int gs_synchronize(gs_handle* h);
 int gs_set_line_impedances(gs_handle* h, const double* r, const double* x, const uint8_t* mask);
 /* the values the handle holds, [B][m] each (either pointer may be NULL); GS_E_STATE on a handle without per-instance impedances */
 int gs_get_line_impedances(const gs_handle* h, double* r, double* x);
+/* Per-instance load powers of a handle created with gs_topology::load_base_inst (else GS_E_STATE): base [B][n_loads] watts, mask [B]
+ * (!= 0: take this instance's row) or NULL (all).  The selected instances draw, sum and report the new values from the next gs_step /
+ * rollout step on (grid_env.py:683-720, 744, 769-770); the rules of gs_topology apply (GS_E_INVALID, handle unchanged).  The values
+ * are not environment state: gs_reset, the in-place resets of gs_rollout and gs_set_state leave them alone. */
+int gs_set_load_powers(gs_handle* h, const double* base, const uint8_t* mask);
+/* the values the handle holds, [B][n_loads]; GS_E_STATE on a handle without per-instance load powers */
+int gs_get_load_powers(const gs_handle* h, double* base);
 
 /* ---- solver plug point: NewtonRaphsonSolver.solve (power_flow.py:89-211) ---------------
  * P_spec[B][n] is the net specified injection (generation - load, what :112-121 builds from

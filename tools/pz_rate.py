@@ -4,7 +4,9 @@ between), median of five, each configuration in a fresh process of its own.  123
     shared        the handle's one set of line impedances
     no_flat       (Newton-Raphson) the shared handle under GS_NR_NO_FLAT=1: iteration 0 eliminated like the per-instance handle does
     per_instance  +-10 % per-instance impedances (randomized_line_impedances)
-    python tools/pz_rate.py            (on the GPU box; prints one JSON line per configuration and the ratios)"""
+    python tools/pz_rate.py            (on the GPU box; prints one JSON line per configuration and the ratios)
+    python tools/pz_rate.py --loads    per-instance load powers (randomized_load_powers, one U(0.5, 1.5) multiplier per instance) on the same
+                                       protocol: shared | loads | per_instance (line impedances) | both, for both solvers"""
 import json
 import os
 import subprocess
@@ -17,8 +19,10 @@ sys.path.insert(0, %r)
 import grid_fed_rl_gym_amd as P
 solver, mode, B = sys.argv[1], sys.argv[2], int(sys.argv[3])
 fs = P.ieee123_like()
-li = P.randomized_line_impedances(fs, B, rel=0.1, seed=0) if mode == "per_instance" else None
-env = P.BatchedGridEnvironment(fs, num_envs=B, solver=solver, stochastic_loads=True, weather_variation=True, line_impedances=li)
+kw = {}
+if mode in ("per_instance", "both"): kw["line_impedances"] = P.randomized_line_impedances(fs, B, rel=0.1, seed=0)
+if mode in ("loads", "both"): kw["load_powers"] = P.randomized_load_powers(fs, B, low=0.5, high=1.5, seed=0)
+env = P.BatchedGridEnvironment(fs, num_envs=B, solver=solver, stochastic_loads=True, weather_variation=True, **kw)
 h = env.handle
 acts = np.random.default_rng(5678).uniform(-1, 1, (8, B, fs.action_dim)); h.upload_actions(acts)
 env.reset(seed=np.arange(B, dtype=np.uint64))
@@ -48,8 +52,22 @@ def run(solver, mode, B):
     return json.loads(line)
 
 
+def main_loads(B):
+    res = {}
+    for solver in ("fbs", "nr"):
+        for mode in ("shared", "loads", "per_instance", "both"):
+            res[(solver, mode)] = run(solver, mode, B)["env_steps_per_s"]
+    print(json.dumps(dict(fbs_loads_over_shared=res[("fbs", "loads")] / res[("fbs", "shared")],
+                          nr_loads_over_shared=res[("nr", "loads")] / res[("nr", "shared")],
+                          fbs_both_over_per_instance=res[("fbs", "both")] / res[("fbs", "per_instance")],
+                          nr_both_over_per_instance=res[("nr", "both")] / res[("nr", "per_instance")])), flush=True)
+
+
 def main():
-    B = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
+    args = [a for a in sys.argv[1:] if a != "--loads"]
+    B = int(args[0]) if args else 8192
+    if "--loads" in sys.argv[1:]:
+        return main_loads(B)
     res = {}
     for solver, modes in (("fbs", ("shared", "per_instance")), ("nr", ("shared", "no_flat", "per_instance"))):
         for mode in modes:
