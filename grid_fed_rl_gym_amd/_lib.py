@@ -78,7 +78,17 @@ class gs_rollout_device(C.Structure):
                 ("n_terminal", C.c_int32), ("reserved", C.c_int32), ("terminal_index", C.c_void_p), ("terminal_obs", C.c_void_p)]
 
 
-POLICY = {"uploaded": 0, "random": 1}
+POLICY = {"uploaded": 0, "random": 1, "mlp": 2}
+ACTIVATION = {"relu": 0, "tanh": 1, "elu": 2}
+HEAD = {"tanh": 0, "gaussian_tanh": 1}
+GS_POLICY_MAX_LAYERS = 4
+
+
+class gs_policy_mlp(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_layers", C.c_int32), ("dims", C.c_int32 * (GS_POLICY_MAX_LAYERS + 1)),
+                ("activation", C.c_int32), ("head", C.c_int32), ("stochastic", C.c_int32),
+                ("weights", _dp * GS_POLICY_MAX_LAYERS), ("biases", _dp * GS_POLICY_MAX_LAYERS)]
+
 
 # every symbol include/gridstep.h declares: (name, restype, argtypes)
 _H = C.c_void_p
@@ -139,6 +149,9 @@ SYMBOLS = [
     ("gs_get_line_impedances", C.c_int, [_H, _dp, _dp]),
     ("gs_set_load_powers", C.c_int, [_H, _dp, _up]),
     ("gs_get_load_powers", C.c_int, [_H, _dp]),
+    ("gs_policy_mlp_check", C.c_int, [C.POINTER(gs_policy_mlp), C.c_int32, C.c_int32]),
+    ("gs_policy_mlp_set", C.c_int, [_H, C.POINTER(gs_policy_mlp)]),
+    ("gs_policy_mlp_eval", C.c_int, [_H, C.c_uint64, C.c_int32, _dp]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -330,6 +343,31 @@ def _topology_of(spec: FeederSpec, line_impedances=None, load_powers=None):
         keep["load_inst"] = _f64(load_powers)
         t.load_base_inst = _ptr(keep["load_inst"], _dp)
     return t, keep
+
+
+def policy_struct(weights, biases, activation="relu", head="gaussian_tanh", stochastic=False, n_layers=None):
+    """gs_policy_mlp of per-layer ``weights`` ([out, in], torch's Linear.weight layout) and ``biases`` and the arrays it points
+    into (keep them alive while the struct is in use).  ``n_layers`` overrides the count (the refusal tests pass 0 and 5)."""
+    keep = {"w": [_f64(w) for w in weights], "b": [_f64(b) for b in biases]}
+    p = gs_policy_mlp()
+    p.struct_size = C.sizeof(gs_policy_mlp)
+    p.n_layers = len(keep["w"]) if n_layers is None else int(n_layers)
+    p.activation, p.head, p.stochastic = ACTIVATION[activation], HEAD[head], int(bool(stochastic))
+    for l, (w, b) in enumerate(zip(keep["w"][:GS_POLICY_MAX_LAYERS], keep["b"])):
+        if w.ndim != 2 or b.shape != (w.shape[0],):
+            raise ValueError(f"layer {l}: weights must be [out, in] and biases [out], got {w.shape} and {b.shape}")
+        if l and w.shape[1] != keep["w"][l - 1].shape[0]:
+            raise ValueError(f"layer {l} takes {w.shape[1]} inputs, layer {l - 1} gives {keep['w'][l - 1].shape[0]}")
+        p.dims[l], p.dims[l + 1] = w.shape[1], w.shape[0]
+        p.weights[l], p.biases[l] = _ptr(w, _dp), _ptr(b, _dp)
+    return p, keep
+
+
+def policy_check(p: gs_policy_mlp, obs_dim: int, action_dim: int) -> Tuple[int, str]:
+    """gs_policy_mlp_check: (return code, message) -- the rules of gs_policy_mlp on the host alone (no GPU)."""
+    lib = load()
+    rc = lib.gs_policy_mlp_check(C.byref(p), int(obs_dim), int(action_dim))
+    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
 
 
 MESH_ITEM_DTYPE = np.dtype([("vk_off", "<i4"), ("vj_off", "<i4"), ("xk_off", "<i4"), ("xj_off", "<i4"), ("flags", "<i4"), ("cq_off", "<i4"),
@@ -787,9 +825,20 @@ class Handle:
         return out
 
     # -- rollout collection ------------------------------------------------------------------
+    def set_policy(self, p: Optional[gs_policy_mlp]) -> None:
+        """gs_policy_mlp_set: install (a copy of) the policy on the device; None removes it."""
+        self._check(self._lib.gs_policy_mlp_set(self._h, None if p is None else C.byref(p)))
+
+    def policy_eval(self, seed: int = 0, t: int = 0) -> np.ndarray:
+        """gs_policy_mlp_eval: the installed policy's actions [B, action_dim] on the observation the environment stands at."""
+        a = np.empty((self.B, self.action_dim))
+        self._check(self._lib.gs_policy_mlp_eval(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(t), _ptr(a, _dp)))
+        return a
+
     def rollout(self, T: int, policy: str = "random", seed: int = 0, actions=None) -> None:
         """gs_rollout: T env steps back to back on the device (asynchronous).  policy "random": uniform actions in
-        (-1, 1) drawn on the device from ``seed``; "uploaded": ``actions`` [T, B, A]."""
+        (-1, 1) drawn on the device from ``seed``; "uploaded": ``actions`` [T, B, A]; "mlp": the policy of ``set_policy``
+        acts on every observation (``seed``: its noise)."""
         a = None
         if policy == "uploaded":
             a = _f64(actions)

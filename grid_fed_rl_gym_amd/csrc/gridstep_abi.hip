@@ -24,6 +24,7 @@
 #include "topology.h"
 #include "mesh_schedule.h"
 #include "plan.h"
+#include "policy.h"
 
 namespace {
 
@@ -120,6 +121,9 @@ struct gs_handle : GsPlan {
     int32_t* term_count = nullptr; int32_t* term_idx = nullptr; double* term_obs = nullptr;
     int32_t n_term = 0;
   } ro;
+  // gs_policy_mlp_set: the policy's packed weights and biases (one allocation), the actions of gs_policy_mlp_eval [B][A], and the
+  // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
+  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; } pol;
   double* d_cst = nullptr;
   int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
           *map_p = nullptr, *map_q = nullptr, *map_act = nullptr, *map_state = nullptr;
@@ -793,6 +797,8 @@ void gs_destroy(gs_handle* h) {
   if (h->span_a) { (void)hipEventDestroy(h->span_a); (void)hipEventDestroy(h->span_b); }
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->d_actions) (void)hipFree(h->d_actions);
+  if (h->pol.blob) (void)hipFree(h->pol.blob);
+  if (h->pol.act) (void)hipFree(h->pol.act);
   for (void* p : {(void*)h->ro.obs_seq, (void*)h->ro.act, (void*)h->ro.rew, (void*)h->ro.done, (void*)h->ro.term_count,
                   (void*)h->ro.term_idx, (void*)h->ro.term_obs})
     if (p) (void)hipFree(p);
@@ -1163,6 +1169,60 @@ int gs_step_device(gs_handle* h, int32_t k) {
 }
 
 
+// ---- the MLP policy (policy.h, kernels_policy.hip) ------------------------------------------------------
+int gs_policy_mlp_check(const gs_policy_mlp* p, int32_t obs_dim, int32_t action_dim) {
+  const std::string why = gs_policy_check(p, obs_dim, action_dim);
+  return why.empty() ? GS_OK : fail(nullptr, GS_E_INVALID, "%s", why.c_str());
+}
+
+int gs_policy_mlp_set(gs_handle* h, const gs_policy_mlp* p) {
+  if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (p) {         // (a refused policy leaves the installed one in place)
+    const std::string why = gs_policy_check(p, h->obs_dim, h->action_dim);
+    if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
+  }
+  GS_ENTER(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  gs_handle::Policy& pol = h->pol;
+  if (pol.blob) { (void)hipFree(pol.blob); pol.blob = nullptr; }
+  pol.set = false;
+  if (!p) return GS_OK;
+  const GsPolicyImage im = gs_policy_pack(*p);
+  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL_LDS_BYTES));
+  if (!pol.act) HIPCHK(h, hipMalloc((void**)&pol.act, (size_t)h->B * h->action_dim * sizeof(double)));
+  HIPCHK(h, hipMalloc((void**)&pol.blob, im.blob.size() * sizeof(double)));
+  HIPCHK(h, hipMemcpy(pol.blob, im.blob.data(), im.blob.size() * sizeof(double), hipMemcpyHostToDevice));
+  GsPolicyArgs& a = pol.args;
+  a = GsPolicyArgs{};
+  a.B = h->B; a.D = h->obs_dim; a.A = h->action_dim; a.n_layers = p->n_layers; a.activation = p->activation; a.head = p->head;
+  a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance;
+  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayer{pol.blob + im.w_off[l], pol.blob + im.b_off[l], im.kb[l], im.nt[l]};
+  pol.set = true;
+  return GS_OK;
+}
+
+// one launch: actions[B][A] of the installed policy on obs[B][obs_dim] (device pointers), on the handle's main stream
+static int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t) {
+  GsPolicyArgs a = h->pol.args;
+  a.obs = obs; a.act = act; a.seed = seed; a.t = t;
+  hipLaunchKernelGGL(gs_k_policy_mlp, dim3((unsigned)((h->B + GS_POL_ROWS - 1) / GS_POL_ROWS)), dim3(64 * GS_POL_WAVES), GS_POL_LDS_BYTES, h->stream, a);
+  HIPCHK(h, hipGetLastError());
+  return GS_OK;
+}
+
+int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* actions_host) {
+  if (!h || !actions_host) return fail(h, GS_E_INVALID, "handle / actions_host is NULL");
+  if (!h->pol.set) return fail(h, GS_E_STATE, "gs_policy_mlp_eval before gs_policy_mlp_set");
+  if (!h->was_reset) return fail(h, GS_E_STATE, "gs_policy_mlp_eval before gs_reset");
+  GS_ENTER(h);
+  int rc = launch_policy(h, h->d_obs2[h->obs_cur], h->pol.act, policy_seed, t);
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpyAsync(actions_host, h->pol.act, (size_t)h->B * h->action_dim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return GS_OK;
+}
+
+
 // ---- device-resident rollout collection ---------------------------------------------------------------
 // T fused env steps back to back, nothing on the host in between (algorithms/base.py:268-298, batched).
 // Device layout (gs_rollout_device_view): obs_seq[T + 1][B][obs_dim] -- slot t is what step t started from, slot
@@ -1203,7 +1263,8 @@ static int rollout_ensure(gs_handle* h, int T) {
 
 int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, const double* actions) {
   if (!h || T <= 0) return fail(h, GS_E_INVALID, "handle is NULL or T <= 0");
-  if (policy != GS_POLICY_UPLOADED && policy != GS_POLICY_RANDOM) return fail(h, GS_E_INVALID, "unknown policy %d", policy);
+  if (policy != GS_POLICY_UPLOADED && policy != GS_POLICY_RANDOM && policy != GS_POLICY_MLP) return fail(h, GS_E_INVALID, "unknown policy %d", policy);
+  if (policy == GS_POLICY_MLP && !h->pol.set) return fail(h, GS_E_STATE, "GS_POLICY_MLP before gs_policy_mlp_set");
   if (policy == GS_POLICY_UPLOADED && !actions && h->action_dim > 0) return fail(h, GS_E_INVALID, "GS_POLICY_UPLOADED needs actions[T][B][action_dim]");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_rollout before gs_reset");
   GS_ENTER(h);
@@ -1216,7 +1277,7 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   if (A > 0) {
     if (policy == GS_POLICY_UPLOADED) {
       HIPCHK(h, hipMemcpyAsync(ro.act, actions, (size_t)T * B * A * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    } else {
+    } else if (policy == GS_POLICY_RANDOM) {
       const long long total = (long long)T * B * ((A + 3) / 4);
       hipLaunchKernelGGL(gs_k_rollout_actions, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ro.act, (int)T, (int)B, (int)A,
                          policy_seed, h->EC.first_instance, 0u);
@@ -1232,9 +1293,13 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   // was built in round 2 and is bit-identical, but slower: inlined into a loop the step's ~1 KB argument block stays live
   // across iterations (230 spilled registers); as an out-of-line call reading its arguments from memory the block lands in
   // scratch (59 M env-steps/s against 150 M for a launch per step).)
-  const bool fused = h->second_gen();
+  // GS_POLICY_MLP: the policy of step t + 1 must see the FRESH observation of an instance that step t finished (the reference calls
+  // env.reset() and then the policy, algorithms/base.py:289-290), so the bookkeeping cannot wait for the next step kernel: the small
+  // kernel follows every step, as for the first-generation members, and the policy kernel reads the slot behind it
+  const bool fused = h->second_gen() && policy != GS_POLICY_MLP;
   for (int t = 0; t < T; ++t) {
     double* nxt = ro.obs_seq + (size_t)(t + 1) * B * D;
+    if (policy == GS_POLICY_MLP && (rc = launch_policy(h, ro.obs_seq + (size_t)t * B * D, ro.act + (size_t)t * B * A, policy_seed, t))) return rc;
     GsRolloutStep rs{ro.rew, ro.done, ro.obs_seq + (size_t)t * B * D, h->map_obs, h->d_cst, ro.term_count, ro.term_idx, ro.term_obs, ro.term_cap, h->obs_dim, t, 1};
     if ((rc = step_kernels(h, ro.act + (size_t)t * B * A, nxt, fused ? &rs : nullptr))) return rc;
     if (!fused || t == T - 1) {

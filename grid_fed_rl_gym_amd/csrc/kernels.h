@@ -6,6 +6,7 @@
 
 #include "gs_internal.h"
 #include "members.h"
+#include "policy.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -47,6 +48,7 @@ __global__ void gs_k_polar_to_rect(GsTables T, GsRows R, double* __restrict__ sl
 __global__ void gs_k_rollout_actions(double* __restrict__ act, int T, int B, int A, uint64_t seed, int64_t first_instance, uint32_t t0);
 __global__ void gs_k_fill_const_columns(double* __restrict__ out, long long rows, int obs_dim, int skip0, int skip1,
                                         const int32_t* __restrict__ map, const double* __restrict__ cst);
+__global__ void gs_k_policy_mlp(GsPolicyArgs P);
 __global__ void gs_k_rollout_post(GsTables T, GsRows R, GsEnvCfg E, double* __restrict__ slab, GsRolloutPostArgs A);
 __global__ void gs_k_pack(const int32_t* __restrict__ src, const double* __restrict__ cst, int C, int rows_total,
                           const double* __restrict__ slab, double* __restrict__ out, int B);

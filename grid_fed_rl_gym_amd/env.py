@@ -279,6 +279,23 @@ class BatchedGridEnvironment:
         """Host copy, [num_envs, n_loads], of the per-instance load powers the device draws around."""
         return self._h.get_load_powers()
 
+    def set_policy(self, policy: Optional[Any], stochastic: bool = False) -> None:
+        """Install an ``MLPPolicy`` on the device (gs_policy_mlp_set) for ``policy_actions`` and ``rollout_device(policy=...)``;
+        ``stochastic``: sample tanh(mean + std * eps) instead of tanh(mean) (Gaussian head only).  None removes it.  Not
+        environment state: reset() and set_state() leave it alone."""
+        if policy is None:
+            self._h.set_policy(None)
+            return
+        p, keep = policy.to_struct(stochastic=stochastic)
+        self._h.set_policy(p)
+
+    def policy_actions(self, seed: int = 0, t: int = 0) -> np.ndarray:
+        """The installed policy's actions [num_envs, action_dim] on the observation the environment stands at
+        (gs_policy_mlp_eval); does not step.  ``seed`` / ``t``: the noise of a stochastic policy, as rollout step t draws it."""
+        if self._needs_reset:
+            raise RuntimeError("reset() before policy_actions()")
+        return self._h.policy_eval(seed, t)
+
     @property
     def handle(self) -> "_lib.Handle":
         return self._h

@@ -31,14 +31,35 @@ def collect_random_data(env: BatchedGridEnvironment, num_steps: int, seed: int =
     return out
 
 
+def collect_policy_data(env: BatchedGridEnvironment, policy, num_steps: int, stochastic: bool = False, seed: int = 0,
+                        reset: bool = True) -> Dict[str, np.ndarray]:
+    """``collect_random_data`` under ``policy`` (an ``MLPPolicy``) instead of random actions: before every step one kernel
+    evaluates the policy on the observation block where it lies (``gs_rollout`` with ``GS_POLICY_MLP``), an instance that
+    finished being shown its fresh observation after the reset, as the reference calls ``env.reset()`` and then the policy.
+    Same dictionary, same transition order.  ``stochastic``: sample the Gaussian head (noise from ``seed``)."""
+    rollout_device(env, num_steps, seed=seed, reset=reset, policy=policy, stochastic=stochastic)
+    d = env.handle.rollout_download()
+    T, B = int(num_steps), env.num_envs
+    out = {k: d[k].reshape((T * B,) + d[k].shape[2:]) for k in ("observations", "actions", "rewards", "next_observations")}
+    out["terminals"] = d["terminals"].reshape(T * B) != 0
+    return out
+
+
 def rollout_device(env: BatchedGridEnvironment, num_steps: int, seed: int = 0, actions: Optional[np.ndarray] = None,
-                   reset: bool = True):
+                   reset: bool = True, policy=None, stochastic: bool = False):
     """The same collection left on the GPU: returns the ``gs_rollout_device`` view (device pointers to
     ``obs_seq[T + 1, B, obs_dim]``, actions, rewards, done flags and the list of terminal observations) for a learner
-    that consumes it there.  Valid until the next rollout on the environment."""
+    that consumes it there.  Valid until the next rollout on the environment.  ``policy``: an ``MLPPolicy`` to install
+    and act with (``stochastic``: sample its Gaussian head), or True to act with the policy ``env.set_policy`` installed."""
+    if policy is not None and actions is not None:
+        raise ValueError("rollout_device: either actions or a policy")
     if reset or env._needs_reset:
         env.reset(seed=seed)
-    if actions is None:
+    if policy is not None:
+        if policy is not True:
+            env.set_policy(policy, stochastic=stochastic)
+        env.handle.rollout(int(num_steps), "mlp", seed=seed)
+    elif actions is None:
         env.handle.rollout(int(num_steps), "random", seed=seed)
     else:
         env.handle.rollout(int(num_steps), "uploaded", actions=np.asarray(actions, dtype=np.float64))

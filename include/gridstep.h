@@ -332,6 +332,46 @@ typedef struct gs_rollout_device {
 } gs_rollout_device;
 int gs_rollout_device_view(gs_handle* h, gs_rollout_device* out);
 
+/* ---- closed-loop rollouts: an MLP policy evaluated on the device between two steps of gs_rollout ---------------
+ * The reference's actors are plain MLPs (algorithms/base.py:157-177 `_build_mlp`: Linear + relu / tanh / elu) whose head is
+ * tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) * eps) (algorithms/offline.py:69-76, 114-136).
+ *   weights[l]  [dims[l + 1]][dims[l]] row-major float64 -- torch's Linear.weight --, biases[l] [dims[l + 1]]
+ *   activation  between the layers (not behind the last one)
+ *   head        GS_HEAD_TANH: dims[n_layers] = action_dim, a = tanh(out); GS_HEAD_GAUSSIAN_TANH: dims[n_layers] = 2 * action_dim,
+ *               out = [mean | log_std] as torch.chunk(out, 2, dim=-1) splits it, log_std clamped to [-20, 2]
+ *   stochastic  0: a = tanh(mean); 1 (Gaussian head only): a = tanh(mean + exp(log_std) * eps), eps for action a of instance b at
+ *               rollout step t = component a & 3 of the four normals of ONE Philox call keyed by policy_seed with counter
+ *               (global instance, t, a / 4, 'PNOI' = 0x504E4F49): Box-Muller cosine and sine on words (0, 1) and (2, 3),
+ *               u = (r + 1/2) 2^-32 -- so sharded handles (first_instance) draw what one handle would.
+ * Rules (GS_E_INVALID with a message): 1 <= n_layers <= 4; dims[0] = obs_dim; action_dim > 0; the last width matches the head;
+ * every width behind the first is in 1 .. 256; stochastic only with the Gaussian head; every weight and bias finite. */
+enum { GS_ACT_RELU = 0, GS_ACT_TANH = 1, GS_ACT_ELU = 2 };
+enum { GS_HEAD_TANH = 0, GS_HEAD_GAUSSIAN_TANH = 1 };
+enum { GS_POLICY_MLP = 2 };       /* gs_rollout's third policy: the one gs_policy_mlp_set installed */
+#define GS_POLICY_MAX_LAYERS 4
+typedef struct gs_policy_mlp {
+  int32_t struct_size;            /* = sizeof(gs_policy_mlp) */
+  int32_t n_layers;               /* linear layers, 1 .. GS_POLICY_MAX_LAYERS */
+  int32_t dims[GS_POLICY_MAX_LAYERS + 1];
+  int32_t activation;             /* GS_ACT_* */
+  int32_t head;                   /* GS_HEAD_* */
+  int32_t stochastic;
+  const double* weights[GS_POLICY_MAX_LAYERS];
+  const double* biases[GS_POLICY_MAX_LAYERS];
+} gs_policy_mlp;
+/* the rules above, on the host alone (no device needed) */
+int gs_policy_mlp_check(const gs_policy_mlp* p, int32_t obs_dim, int32_t action_dim);
+/* Checks `p` against the handle's obs_dim / action_dim and uploads it (the handle keeps its own copy, in the operand order of the
+ * matrix cores); NULL removes the policy.  The policy is not environment state: gs_reset, gs_set_state and the in-place resets of
+ * gs_rollout leave it alone. */
+int gs_policy_mlp_set(gs_handle* h, const gs_policy_mlp* p);
+/* The policy's actions [B][action_dim] on the observation the environment stands at (after gs_reset / a step / a rollout); does not
+ * step.  policy_seed / t: the noise of a stochastic policy, as rollout step t would draw it.  GS_E_STATE without a policy. */
+int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* actions_host);
+/* gs_rollout(h, T, GS_POLICY_MLP, policy_seed, NULL): before step t one kernel reads obs_seq[t] and writes actions[t] -- the
+ * observation of an instance that finished at step t - 1 being the fresh one after its in-place reset, as the reference calls
+ * env.reset() and then the policy (algorithms/base.py:289-290).  GS_E_STATE without a policy; everything else as above. */
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
