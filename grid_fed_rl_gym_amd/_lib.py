@@ -90,6 +90,13 @@ class gs_policy_mlp(C.Structure):
                 ("weights", _dp * GS_POLICY_MAX_LAYERS), ("biases", _dp * GS_POLICY_MAX_LAYERS)]
 
 
+COMPUTE = {"float64": 0, "float32": 1}      # GS_COMPUTE_F64 / GS_COMPUTE_F32
+
+
+class gs_policy_mlp_opts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("compute", C.c_int32), ("obs_shift", _dp), ("obs_scale", _dp)]
+
+
 # every symbol include/gridstep.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = [
@@ -152,6 +159,8 @@ SYMBOLS = [
     ("gs_policy_mlp_check", C.c_int, [C.POINTER(gs_policy_mlp), C.c_int32, C.c_int32]),
     ("gs_policy_mlp_set", C.c_int, [_H, C.POINTER(gs_policy_mlp)]),
     ("gs_policy_mlp_eval", C.c_int, [_H, C.c_uint64, C.c_int32, _dp]),
+    ("gs_policy_mlp_check_opts", C.c_int, [C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts), C.c_int32, C.c_int32]),
+    ("gs_policy_mlp_set_opts", C.c_int, [_H, C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts)]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -367,6 +376,28 @@ def policy_check(p: gs_policy_mlp, obs_dim: int, action_dim: int) -> Tuple[int, 
     """gs_policy_mlp_check: (return code, message) -- the rules of gs_policy_mlp on the host alone (no GPU)."""
     lib = load()
     rc = lib.gs_policy_mlp_check(C.byref(p), int(obs_dim), int(action_dim))
+    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+
+
+def policy_opts(compute="float64", obs_shift=None, obs_scale=None, struct_size=None):
+    """gs_policy_mlp_opts and the arrays it points into.  ``compute``: "float64" | "float32" or a raw GS_COMPUTE_* value;
+    ``struct_size`` overrides the size (the refusal tests pass a wrong one)."""
+    keep = {"shift": None if obs_shift is None else _f64(obs_shift).reshape(-1),
+            "scale": None if obs_scale is None else _f64(obs_scale).reshape(-1)}
+    o = gs_policy_mlp_opts()
+    o.struct_size = C.sizeof(gs_policy_mlp_opts) if struct_size is None else int(struct_size)
+    o.compute = COMPUTE[compute] if isinstance(compute, str) else int(compute)
+    if keep["shift"] is not None:
+        o.obs_shift = _ptr(keep["shift"], _dp)
+    if keep["scale"] is not None:
+        o.obs_scale = _ptr(keep["scale"], _dp)
+    return o, keep
+
+
+def policy_check_opts(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int, action_dim: int) -> Tuple[int, str]:
+    """gs_policy_mlp_check_opts: (return code, message) -- the rules of gs_policy_mlp and its options on the host alone."""
+    lib = load()
+    rc = lib.gs_policy_mlp_check_opts(C.byref(p), None if o is None else C.byref(o), int(obs_dim), int(action_dim))
     return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
 
 
@@ -825,9 +856,13 @@ class Handle:
         return out
 
     # -- rollout collection ------------------------------------------------------------------
-    def set_policy(self, p: Optional[gs_policy_mlp]) -> None:
-        """gs_policy_mlp_set: install (a copy of) the policy on the device; None removes it."""
-        self._check(self._lib.gs_policy_mlp_set(self._h, None if p is None else C.byref(p)))
+    def set_policy(self, p: Optional[gs_policy_mlp], opts: Optional[gs_policy_mlp_opts] = None) -> None:
+        """gs_policy_mlp_set / gs_policy_mlp_set_opts (with ``opts``): install (a copy of) the policy on the device; None
+        removes it."""
+        if opts is None:
+            self._check(self._lib.gs_policy_mlp_set(self._h, None if p is None else C.byref(p)))
+        else:
+            self._check(self._lib.gs_policy_mlp_set_opts(self._h, None if p is None else C.byref(p), C.byref(opts)))
 
     def policy_eval(self, seed: int = 0, t: int = 0) -> np.ndarray:
         """gs_policy_mlp_eval: the installed policy's actions [B, action_dim] on the observation the environment stands at."""

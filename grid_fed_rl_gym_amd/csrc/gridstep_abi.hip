@@ -123,7 +123,9 @@ struct gs_handle : GsPlan {
   } ro;
   // gs_policy_mlp_set: the policy's packed weights and biases (one allocation), the actions of gs_policy_mlp_eval [B][A], and the
   // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
-  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; } pol;
+  // compute: GS_COMPUTE_*; with GS_COMPUTE_F32 `blob` holds the float32 image and the normalisation vectors, and args32 is the
+  // argument block of gs_k_policy_mlp_f32 (kernels_policy_f32.hip)
+  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0; } pol;
   double* d_cst = nullptr;
   int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
           *map_p = nullptr, *map_q = nullptr, *map_act = nullptr, *map_state = nullptr;
@@ -1169,16 +1171,23 @@ int gs_step_device(gs_handle* h, int32_t k) {
 }
 
 
-// ---- the MLP policy (policy.h, kernels_policy.hip) ------------------------------------------------------
+// ---- the MLP policy (policy.h, kernels_policy.hip, kernels_policy_f32.hip) ------------------------------------------------------
 int gs_policy_mlp_check(const gs_policy_mlp* p, int32_t obs_dim, int32_t action_dim) {
   const std::string why = gs_policy_check(p, obs_dim, action_dim);
   return why.empty() ? GS_OK : fail(nullptr, GS_E_INVALID, "%s", why.c_str());
 }
 
-int gs_policy_mlp_set(gs_handle* h, const gs_policy_mlp* p) {
+int gs_policy_mlp_check_opts(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim, int32_t action_dim) {
+  const std::string why = gs_policy_check_opts(p, o, obs_dim, action_dim);
+  return why.empty() ? GS_OK : fail(nullptr, GS_E_INVALID, "%s", why.c_str());
+}
+
+int gs_policy_mlp_set(gs_handle* h, const gs_policy_mlp* p) { return gs_policy_mlp_set_opts(h, p, nullptr); }
+
+int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_opts* o) {
   if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
   if (p) {         // (a refused policy leaves the installed one in place)
-    const std::string why = gs_policy_check(p, h->obs_dim, h->action_dim);
+    const std::string why = gs_policy_check_opts(p, o, h->obs_dim, h->action_dim);
     if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
   }
   GS_ENTER(h);
@@ -1187,9 +1196,30 @@ int gs_policy_mlp_set(gs_handle* h, const gs_policy_mlp* p) {
   if (pol.blob) { (void)hipFree(pol.blob); pol.blob = nullptr; }
   pol.set = false;
   if (!p) return GS_OK;
+  if (!pol.act) HIPCHK(h, hipMalloc((void**)&pol.act, (size_t)h->B * h->action_dim * sizeof(double)));
+  if (gs_policy_is_f32(o)) {
+    const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
+    pol.lds32 = gs_pol32_lds_bytes(im.kb[0]);
+    HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, pol.lds32));
+    // one allocation: the float image (a multiple of 16 floats), then shift and scale
+    const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
+    HIPCHK(h, hipMalloc((void**)&pol.blob, image_bytes + norm_bytes));
+    const float* image = (const float*)pol.blob;
+    const double* norm = (const double*)((const char*)pol.blob + image_bytes);
+    HIPCHK(h, hipMemcpy((void*)image, im.blob.data(), image_bytes, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((void*)norm, im.norm.data(), norm_bytes, hipMemcpyHostToDevice));
+    GsPolicyArgsF32& a = pol.args32;
+    a = GsPolicyArgsF32{};
+    a.shift = norm; a.scale = norm + 16 * im.kb[0];
+    a.B = h->B; a.D = h->obs_dim; a.A = h->action_dim; a.n_layers = p->n_layers; a.activation = p->activation; a.head = p->head;
+    a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance; a.obs_stride = gs_pol32_obs_stride(im.kb[0]);
+    for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
+    pol.compute = GS_COMPUTE_F32;
+    pol.set = true;
+    return GS_OK;
+  }
   const GsPolicyImage im = gs_policy_pack(*p);
   HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL_LDS_BYTES));
-  if (!pol.act) HIPCHK(h, hipMalloc((void**)&pol.act, (size_t)h->B * h->action_dim * sizeof(double)));
   HIPCHK(h, hipMalloc((void**)&pol.blob, im.blob.size() * sizeof(double)));
   HIPCHK(h, hipMemcpy(pol.blob, im.blob.data(), im.blob.size() * sizeof(double), hipMemcpyHostToDevice));
   GsPolicyArgs& a = pol.args;
@@ -1197,15 +1227,23 @@ int gs_policy_mlp_set(gs_handle* h, const gs_policy_mlp* p) {
   a.B = h->B; a.D = h->obs_dim; a.A = h->action_dim; a.n_layers = p->n_layers; a.activation = p->activation; a.head = p->head;
   a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance;
   for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayer{pol.blob + im.w_off[l], pol.blob + im.b_off[l], im.kb[l], im.nt[l]};
+  pol.compute = GS_COMPUTE_F64;
   pol.set = true;
   return GS_OK;
 }
 
 // one launch: actions[B][A] of the installed policy on obs[B][obs_dim] (device pointers), on the handle's main stream
 static int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t) {
-  GsPolicyArgs a = h->pol.args;
-  a.obs = obs; a.act = act; a.seed = seed; a.t = t;
-  hipLaunchKernelGGL(gs_k_policy_mlp, dim3((unsigned)((h->B + GS_POL_ROWS - 1) / GS_POL_ROWS)), dim3(64 * GS_POL_WAVES), GS_POL_LDS_BYTES, h->stream, a);
+  const dim3 grid((unsigned)((h->B + GS_POL_ROWS - 1) / GS_POL_ROWS)), block(64 * GS_POL_WAVES);
+  if (h->pol.compute == GS_COMPUTE_F32) {
+    GsPolicyArgsF32 a = h->pol.args32;
+    a.obs = obs; a.act = act; a.seed = seed; a.t = t;
+    hipLaunchKernelGGL(gs_k_policy_mlp_f32, grid, block, h->pol.lds32, h->stream, a);
+  } else {
+    GsPolicyArgs a = h->pol.args;
+    a.obs = obs; a.act = act; a.seed = seed; a.t = t;
+    hipLaunchKernelGGL(gs_k_policy_mlp, grid, block, GS_POL_LDS_BYTES, h->stream, a);
+  }
   HIPCHK(h, hipGetLastError());
   return GS_OK;
 }

@@ -49,6 +49,7 @@ __global__ void gs_k_rollout_actions(double* __restrict__ act, int T, int B, int
 __global__ void gs_k_fill_const_columns(double* __restrict__ out, long long rows, int obs_dim, int skip0, int skip1,
                                         const int32_t* __restrict__ map, const double* __restrict__ cst);
 __global__ void gs_k_policy_mlp(GsPolicyArgs P);
+__global__ void gs_k_policy_mlp_f32(GsPolicyArgsF32 P);
 __global__ void gs_k_rollout_post(GsTables T, GsRows R, GsEnvCfg E, double* __restrict__ slab, GsRolloutPostArgs A);
 __global__ void gs_k_pack(const int32_t* __restrict__ src, const double* __restrict__ cst, int C, int rows_total,
                           const double* __restrict__ slab, double* __restrict__ out, int B);

@@ -37,6 +37,63 @@ std::string gs_policy_check(const gs_policy_mlp* p, int32_t obs_dim, int32_t act
   return "";
 }
 
+std::string gs_policy_check_opts(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim, int32_t action_dim) {
+  const std::string why = gs_policy_check(p, obs_dim, action_dim);
+  if (!why.empty() || !o) return why;
+  if (o->struct_size != (int32_t)sizeof(gs_policy_mlp_opts)) return fmt("gs_policy_mlp_opts struct_size %d != %d", o->struct_size, (int)sizeof(gs_policy_mlp_opts));
+  if (o->compute != GS_COMPUTE_F64 && o->compute != GS_COMPUTE_F32) return fmt("unknown compute %d", o->compute);
+  if (o->compute == GS_COMPUTE_F64) {
+    if (o->obs_shift || o->obs_scale)
+      return "obs_shift / obs_scale need GS_COMPUTE_F32: the float64 path takes raw observations, fold the normalisation into the first layer (as MLPPolicy does)";
+    return "";
+  }
+  for (int i = 0; i < p->dims[0]; ++i) {
+    if (o->obs_shift && !std::isfinite(o->obs_shift[i])) return fmt("obs_shift[%d] is not finite", i);
+    if (o->obs_scale && !std::isfinite(o->obs_scale[i])) return fmt("obs_scale[%d] is not finite", i);
+  }
+  // the largest double that still rounds to a finite float32: anything at or beyond FLT_MAX + half an ulp rounds to infinity
+  const double limit = 0x1.ffffffp127;
+  for (int l = 0; l < p->n_layers; ++l) {
+    const size_t nw = (size_t)p->dims[l + 1] * p->dims[l];
+    for (size_t i = 0; i < nw; ++i)
+      if (std::fabs(p->weights[l][i]) >= limit) return fmt("weights[%d] holds a value that is not finite in float32 (row %d, column %d)", l, (int)(i / p->dims[l]), (int)(i % p->dims[l]));
+    for (int i = 0; i < p->dims[l + 1]; ++i)
+      if (std::fabs(p->biases[l][i]) >= limit) return fmt("biases[%d][%d] is not finite in float32", l, i);
+  }
+  return "";
+}
+
+GsPolicyImageF32 gs_policy_pack_f32(const gs_policy_mlp& p, const gs_policy_mlp_opts& o) {
+  GsPolicyImageF32 im;
+  size_t total = 0;
+  for (int l = 0; l < p.n_layers; ++l) {
+    im.kb[l] = (p.dims[l] + 15) / 16;
+    im.nt[l] = (p.dims[l + 1] + 15) / 16;
+    im.w_off[l] = total; total += (size_t)im.nt[l] * im.kb[l] * 256;
+    im.b_off[l] = total; total += (size_t)im.nt[l] * 16;
+  }
+  im.blob.assign(total, 0.0f);
+  for (int l = 0; l < p.n_layers; ++l) {
+    const int K = p.dims[l], N = p.dims[l + 1];
+    float* w = im.blob.data() + im.w_off[l];
+    for (int nt = 0; nt < im.nt[l]; ++nt)
+      for (int kb = 0; kb < im.kb[l]; ++kb)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int j = 0; j < 4; ++j) {
+            const int n = 16 * nt + (lane & 15), k = 16 * kb + 4 * (lane >> 4) + j;
+            if (n < N && k < K) w[(((size_t)nt * im.kb[l] + kb) * 64 + lane) * 4 + j] = (float)p.weights[l][(size_t)n * K + k];
+          }
+    for (int n = 0; n < N; ++n) im.blob[im.b_off[l] + n] = (float)p.biases[l][n];
+  }
+  const int D = p.dims[0], D16 = 16 * im.kb[0];
+  im.norm.assign(2 * (size_t)D16, 0.0);
+  for (int i = 0; i < D; ++i) {
+    im.norm[i] = o.obs_shift ? o.obs_shift[i] : 0.0;
+    im.norm[D16 + i] = o.obs_scale ? o.obs_scale[i] : 1.0;
+  }
+  return im;
+}
+
 GsPolicyImage gs_policy_pack(const gs_policy_mlp& p) {
   GsPolicyImage im;
   size_t total = 0;

@@ -282,12 +282,22 @@ class BatchedGridEnvironment:
     def set_policy(self, policy: Optional[Any], stochastic: bool = False) -> None:
         """Install an ``MLPPolicy`` on the device (gs_policy_mlp_set) for ``policy_actions`` and ``rollout_device(policy=...)``;
         ``stochastic``: sample tanh(mean + std * eps) instead of tanh(mean) (Gaussian head only).  None removes it.  Not
-        environment state: reset() and set_state() leave it alone."""
+        environment state: reset() and set_state() leave it alone.  ``policy.compute`` picks the kernel: "float64" (the
+        default; normalisation folded into the first layer) or "float32" (gs_policy_mlp_set_opts with GS_COMPUTE_F32: the
+        normalisation as a float64 stage of its own, float32 layers, float64 head)."""
         if policy is None:
             self._h.set_policy(None)
+            self._policy_compute = None
             return
         p, keep = policy.to_struct(stochastic=stochastic)
-        self._h.set_policy(p)
+        opts, keep_opts = policy.to_opts()
+        self._h.set_policy(p, opts)         # (raises, and leaves the installed policy in place, if the library refuses it)
+        self._policy_compute = policy.compute
+
+    @property
+    def policy_compute(self) -> Optional[str]:
+        """What ``set_policy`` installed: None, "float64" or "float32"."""
+        return getattr(self, "_policy_compute", None)
 
     def policy_actions(self, seed: int = 0, t: int = 0) -> np.ndarray:
         """The installed policy's actions [num_envs, action_dim] on the observation the environment stands at

@@ -6,6 +6,12 @@ The reference's actors are plain MLPs (algorithms/base.py:157-177 ``_build_mlp``
 as NumPy arrays, hands it to the device (``env.set_policy`` / ``rollout_device(policy=...)`` / ``collect_policy_data``) and
 restates its forward pass in NumPy (``forward_np``) -- what the device kernel is tested against.  NumPy only: a torch module is
 read through duck typing (``from_sequential``), torch itself is never imported here.
+
+Two compute paths.  "float64" (the default) folds ``GridDataset``'s normalisation into the first layer and runs every layer in
+float64.  "float32" is the precision of the reference's torch actors: the normalisation stays a stage of its own,
+``z = (obs - mean) * (1 / std)`` in float64 on the raw observation and ONE rounding to float32 (a raw 1e5-watt column rounded to
+float32 first loses 2.4e-3 W, which a folded weight multiplies and the layer sums over every such column); weights, biases,
+products, sums and hidden activations are float32; the head is evaluated in float64 on the float32 pre-head values.
 """
 from __future__ import annotations
 
@@ -23,10 +29,15 @@ class MLPPolicy:
     ``activation`` ("relu" | "tanh" | "elu") between them, ``head`` "tanh" (last width = action_dim) or "gaussian_tanh" (last
     width = 2 * action_dim: mean | log_std, as ``torch.chunk`` splits).  ``obs_mean`` / ``obs_std``: ``GridDataset``'s observation
     normalisation, folded into the first layer here (``W1' = W1 / std``, ``b1' = b1 - W1 (mean / std)``), so that the policy --
-    and the device kernel -- take raw observations."""
+    and the device kernel -- take raw observations.  ``compute``: "float64" or "float32" (the module docstring); either way
+    ``weights`` / ``biases`` are the folded float64 arrays, and ``weight0`` / ``bias0`` / ``obs_mean`` / ``obs_std`` keep the
+    unfolded first layer and the normalisation (mean 0 and std 1 if none was given) for the float32 path."""
 
     def __init__(self, weights: Sequence[Any], biases: Sequence[Any], activation: str = "relu", head: str = "gaussian_tanh",
-                 obs_mean: Optional[Any] = None, obs_std: Optional[Any] = None) -> None:
+                 obs_mean: Optional[Any] = None, obs_std: Optional[Any] = None, compute: str = "float64") -> None:
+        if compute not in _lib.COMPUTE:
+            raise ValueError(f"compute must be one of {sorted(_lib.COMPUTE)}, got {compute!r}")
+        self.compute = compute
         if activation not in _lib.ACTIVATION:
             raise ValueError(f"activation must be one of {sorted(_lib.ACTIVATION)}, got {activation!r}")
         if head not in _lib.HEAD:
@@ -43,6 +54,9 @@ class MLPPolicy:
         self.activation, self.head = activation, head
         if (obs_mean is None) != (obs_std is None):
             raise ValueError("obs_mean and obs_std go together")
+        self.weight0, self.bias0 = self.weights[0].copy(), self.biases[0].copy()
+        self.obs_mean: Optional[np.ndarray] = None
+        self.obs_std: Optional[np.ndarray] = None
         if obs_mean is not None:
             mean = np.asarray(obs_mean, dtype=np.float64).reshape(-1)
             std = np.asarray(obs_std, dtype=np.float64).reshape(-1)
@@ -51,6 +65,7 @@ class MLPPolicy:
             w1 = self.weights[0]
             self.biases[0] = self.biases[0] - w1 @ (mean / std)
             self.weights[0] = w1 / std[None, :]
+            self.obs_mean, self.obs_std = mean.copy(), std.copy()
 
     @property
     def obs_dim(self) -> int:
@@ -63,7 +78,7 @@ class MLPPolicy:
 
     @classmethod
     def from_sequential(cls, module: Any, head: str = "gaussian_tanh", obs_mean: Optional[Any] = None,
-                        obs_std: Optional[Any] = None) -> "MLPPolicy":
+                        obs_std: Optional[Any] = None, compute: str = "float64") -> "MLPPolicy":
         """From a torch ``nn.Sequential`` of ``Linear`` and activation modules (what ``_build_mlp`` returns), by duck typing:
         a child with ``weight`` and ``bias`` is a linear layer (read through ``.detach().cpu().numpy()``), any other child
         names the activation by its class (ReLU / Tanh / ELU)."""
@@ -84,32 +99,71 @@ class MLPPolicy:
                 acts.append(kind)
         if len(acts) != len(weights) - 1 or len(set(acts)) > 1:
             raise ValueError("from_sequential: one and the same activation behind every linear layer but the last")
-        return cls(weights, biases, activation=acts[0] if acts else "relu", head=head, obs_mean=obs_mean, obs_std=obs_std)
+        return cls(weights, biases, activation=acts[0] if acts else "relu", head=head, obs_mean=obs_mean, obs_std=obs_std,
+                   compute=compute)
 
     def to_struct(self, stochastic: bool = False):
-        """(gs_policy_mlp, the arrays it points into)."""
+        """(gs_policy_mlp, the arrays it points into): the folded layers for compute "float64", the unfolded ones for
+        "float32" (``to_opts`` carries their normalisation)."""
         if stochastic and self.head != "gaussian_tanh":
             raise ValueError("a stochastic policy needs the Gaussian head")
+        if self.compute == "float32":
+            return _lib.policy_struct([self.weight0] + self.weights[1:], [self.bias0] + self.biases[1:], self.activation, self.head, stochastic)
         return _lib.policy_struct(self.weights, self.biases, self.activation, self.head, stochastic)
 
-    def pre_head_np(self, obs: Any) -> np.ndarray:
-        """The last linear layer's output on raw observations ``obs`` [..., obs_dim]."""
+    def to_opts(self):
+        """(gs_policy_mlp_opts or None, the arrays it points into): None for compute "float64" (plain gs_policy_mlp_set),
+        GS_COMPUTE_F32 with obs_shift = mean and obs_scale = 1 / std for "float32"."""
+        if self.compute != "float32":
+            return None, None
+        if self.obs_mean is None:
+            return _lib.policy_opts("float32")
+        return _lib.policy_opts("float32", self.obs_mean, 1.0 / self.obs_std)
+
+    def _activate(self, x: np.ndarray) -> np.ndarray:
+        zero = x.dtype.type(0)
+        if self.activation == "relu":
+            return np.maximum(x, zero)
+        if self.activation == "tanh":
+            return np.tanh(x)
+        return np.where(x > zero, x, np.expm1(np.minimum(x, zero)))
+
+    def normalise_f32(self, obs: Any) -> np.ndarray:
+        """The float32 path's first stage: ``(obs - mean) * (1 / std)`` in float64, rounded to float32 once."""
         x = np.asarray(obs, dtype=np.float64)
-        for l, (w, b) in enumerate(zip(self.weights, self.biases)):
+        if self.obs_mean is not None:
+            x = (x - self.obs_mean) * (1.0 / self.obs_std)
+        return x.astype(np.float32)
+
+    def pre_head_np(self, obs: Any, compute: Optional[str] = None, exact: bool = False) -> np.ndarray:
+        """The last linear layer's output on raw observations ``obs`` [..., obs_dim].  ``compute`` (default: the policy's own)
+        "float32": the device contract of GS_COMPUTE_F32 -- float32-rounded weights, biases and normalised observations,
+        float32 products, sums and activations; with ``exact`` the same rounded operands evaluated in float64 throughout
+        (what the float32 result is measured against)."""
+        compute = self.compute if compute is None else compute
+        if compute not in _lib.COMPUTE:
+            raise ValueError(f"compute must be one of {sorted(_lib.COMPUTE)}, got {compute!r}")
+        if compute == "float64":
+            if exact:
+                raise ValueError("exact goes with compute='float32'")
+            x = np.asarray(obs, dtype=np.float64)
+            layers = list(zip(self.weights, self.biases))
+        else:
+            work = np.float64 if exact else np.float32
+            x = self.normalise_f32(obs).astype(work)
+            layers = [(w.astype(np.float32).astype(work), b.astype(np.float32).astype(work))
+                      for w, b in zip([self.weight0] + self.weights[1:], [self.bias0] + self.biases[1:])]
+        for l, (w, b) in enumerate(layers):
             x = x @ w.T + b
-            if l < len(self.weights) - 1:
-                if self.activation == "relu":
-                    x = np.maximum(x, 0.0)
-                elif self.activation == "tanh":
-                    x = np.tanh(x)
-                else:
-                    x = np.where(x > 0.0, x, np.expm1(np.minimum(x, 0.0)))
+            if l < len(layers) - 1:
+                x = self._activate(x)
         return x
 
-    def forward_np(self, obs: Any, eps: Optional[Any] = None) -> np.ndarray:
+    def forward_np(self, obs: Any, eps: Optional[Any] = None, compute: Optional[str] = None, exact: bool = False) -> np.ndarray:
         """Actions [..., action_dim] on raw observations: ``tanh(out)`` (plain head), ``tanh(mean)`` (Gaussian head) or, with
-        ``eps`` [..., action_dim], ``tanh(mean + exp(clamp(log_std, -20, 2)) * eps)``."""
-        out = self.pre_head_np(obs)
+        ``eps`` [..., action_dim], ``tanh(mean + exp(clamp(log_std, -20, 2)) * eps)``.  The head is float64 on every path;
+        ``compute`` / ``exact``: as for ``pre_head_np``."""
+        out = self.pre_head_np(obs, compute, exact).astype(np.float64)
         if self.head == "tanh":
             if eps is not None:
                 raise ValueError("eps needs the Gaussian head")

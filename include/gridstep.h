@@ -372,6 +372,32 @@ int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* ac
  * observation of an instance that finished at step t - 1 being the fresh one after its in-place reset, as the reference calls
  * env.reset() and then the policy (algorithms/base.py:289-290).  GS_E_STATE without a policy; everything else as above. */
 
+/* ---- the float32 compute path of the MLP policy ------------------------------------------------------------------
+ * gs_policy_mlp_set_opts installs `p` like gs_policy_mlp_set, with options.  o == NULL, or compute == GS_COMPUTE_F64 without
+ * obs_shift / obs_scale, IS gs_policy_mlp_set(h, p): same kernel, same bits.  GS_COMPUTE_F32 (the precision of the reference's
+ * torch actors):
+ *   - weights and biases are rounded to the nearest float32 once, at install;
+ *   - the observation is normalised in float64, z = (obs - obs_shift) * obs_scale, and z is rounded to float32 once (a raw
+ *     1e5-watt column rounded to float32 first would lose 2.4e-3 W, which a folded first layer multiplies and sums);
+ *   - the layer products run on the f32 matrix instructions with f32 accumulation; bias, activation and the hidden activations
+ *     are float32;
+ *   - the head is evaluated in float64 on the float32 pre-head values: the log_std clamp, exp, the 'PNOI' noise and tanh are
+ *     those of the float64 path, draw for draw, so the stochastic contract above holds unchanged; actions are float64.
+ * gs_policy_mlp_eval, gs_rollout(GS_POLICY_MLP) and the "not environment state" rule apply to whichever variant is installed.
+ * Rules beyond those of gs_policy_mlp (GS_E_INVALID with a message; the installed policy stays): struct_size matches; compute is
+ * a GS_COMPUTE_* value; obs_shift / obs_scale only with GS_COMPUTE_F32 (for float64, fold the normalisation into the first
+ * layer); every obs_shift / obs_scale entry finite; every weight and bias still finite after rounding to float32. */
+enum { GS_COMPUTE_F64 = 0, GS_COMPUTE_F32 = 1 };
+typedef struct gs_policy_mlp_opts {
+  int32_t struct_size;            /* = sizeof(gs_policy_mlp_opts) */
+  int32_t compute;                /* GS_COMPUTE_* */
+  const double* obs_shift;        /* [dims[0]] or NULL (0) */
+  const double* obs_scale;        /* [dims[0]] or NULL (1): z = (obs - shift) * scale in float64, then rounded to float32 */
+} gs_policy_mlp_opts;
+/* the rules of gs_policy_mlp and of the options, on the host alone (no device needed); o == NULL: gs_policy_mlp_check */
+int gs_policy_mlp_check_opts(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim, int32_t action_dim);
+int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_opts* o);
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
