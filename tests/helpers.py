@@ -132,3 +132,35 @@ def stack_devices(spec, buses, loads=2, gens=2, bats=2):
         setattr(f, k, np.asarray(getattr(f, k), dtype=np.float64))
     f.name = spec.name + "_stacked"
     return f
+
+
+def oracle_collect(fs, cfg, actions, seeds, first_instance, policy_seed=None, instance_feeder=None):
+    """collect_random_data (algorithms/base.py:268-298) per instance with the oracle: reset, then T steps; where the
+    reference calls env.reset() after a finished transition the instance's seed moves one step along its chain.
+    instance_feeder(b): the feeder instance b solves (its own line impedances and load powers) where the instances differ.
+    "final" holds every instance's (spec, state) where the loop left it, "converged" and "min_voltage" [T, B] what the load flows
+    reported."""
+    T = actions.shape[0] if actions is not None else cfg.pop("T")
+    B = len(seeds)
+    out = dict(observations=np.empty((T, B, fs.obs_dim)), actions=np.empty((T, B, fs.action_dim)), rewards=np.empty((T, B)),
+               next_observations=np.empty((T, B, fs.obs_dim)), terminals=np.zeros((T, B), dtype=bool), final=[], converged=np.zeros((T, B), dtype=bool),
+               min_voltage=np.empty((T, B)))
+    spec = oracle_spec(fs, **cfg)
+    for b in range(B):
+        if instance_feeder is not None:
+            spec = oracle_spec(instance_feeder(b), **cfg)
+        seed = int(seeds[b])
+        obs, st = O.env_reset(spec, seed=seed, instance=first_instance + b)
+        for t in range(T):
+            a = actions[t, b] if actions is not None else O.rollout_random_actions(policy_seed, first_instance + b, t, fs.action_dim)
+            nxt, r, te, tr, inf = O.env_step(spec, st, a)
+            out["converged"][t, b] = inf["power_flow_converged"]; out["min_voltage"][t, b] = inf["min_voltage"]
+            out["observations"][t, b] = obs; out["actions"][t, b] = a; out["rewards"][t, b] = r
+            out["next_observations"][t, b] = nxt; out["terminals"][t, b] = te or tr
+            if te or tr:
+                seed = O.next_episode_seed(seed, first_instance + b)
+                obs, st = O.env_reset(spec, seed=seed, instance=first_instance + b)
+            else:
+                obs = nxt
+        out["final"].append((spec, st))
+    return out

@@ -13,7 +13,7 @@ import pytest
 
 import grid_fed_rl_gym_amd as P
 from oracle import oracle_np as O
-from tests.helpers import golden, oracle_spec
+from tests.helpers import golden, oracle_collect as _oracle_collect, oracle_spec
 
 pytestmark = pytest.mark.gpu
 
@@ -231,30 +231,6 @@ def test_rccl_allgather_two_ranks_on_one_device(tmp_path):
     one.close()
     for o in outs:
         assert np.array_equal(np.load(o), obs)
-
-
-def _oracle_collect(fs, cfg, actions, seeds, first_instance, policy_seed=None):
-    """collect_random_data (algorithms/base.py:268-298) per instance with the oracle: reset, then T steps; where the
-    reference calls env.reset() after a finished transition the instance's seed moves one step along its chain."""
-    T = actions.shape[0] if actions is not None else cfg.pop("T")
-    B = len(seeds)
-    spec = oracle_spec(fs, **cfg)
-    out = dict(observations=np.empty((T, B, fs.obs_dim)), actions=np.empty((T, B, fs.action_dim)), rewards=np.empty((T, B)),
-               next_observations=np.empty((T, B, fs.obs_dim)), terminals=np.zeros((T, B), dtype=bool))
-    for b in range(B):
-        seed = int(seeds[b])
-        obs, st = O.env_reset(spec, seed=seed, instance=first_instance + b)
-        for t in range(T):
-            a = actions[t, b] if actions is not None else O.rollout_random_actions(policy_seed, first_instance + b, t, fs.action_dim)
-            nxt, r, te, tr, _ = O.env_step(spec, st, a)
-            out["observations"][t, b] = obs; out["actions"][t, b] = a; out["rewards"][t, b] = r
-            out["next_observations"][t, b] = nxt; out["terminals"][t, b] = te or tr
-            if te or tr:
-                seed = O.next_episode_seed(seed, first_instance + b)
-                obs, st = O.env_reset(spec, seed=seed, instance=first_instance + b)
-            else:
-                obs = nxt
-    return out
 
 
 @pytest.mark.parametrize("solver,policy", [("nr", "uploaded"), ("fbs", "uploaded"), ("fbs", "random")])
