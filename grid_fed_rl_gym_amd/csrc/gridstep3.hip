@@ -510,7 +510,8 @@ int gs3_create(const gs3_topology* t, double tolerance, int32_t max_iterations, 
   *out = nullptr;
   if (!t || t->struct_size != (int32_t)sizeof(gs3_topology)) return fail3(nullptr, GS_E_INVALID, "gs3_topology missing or struct_size mismatch");
   const int n = t->n;
-  if (n < 2 || batch < 1 || max_iterations < 1 || !t->parent || !t->phases || !t->z_re || !t->z_im || !t->v_source)
+  if (n < 2) return fail3(nullptr, GS_E_INVALID, "a feeder needs the source and at least one more node (n = %d)", n);
+  if ( batch < 1 || max_iterations < 1 || !t->parent || !t->phases || !t->z_re || !t->z_im || !t->v_source)
     return fail3(nullptr, GS_E_INVALID, "bad arguments");
   if (t->source < 0 || t->source >= n || t->parent[t->source] != -1) return fail3(nullptr, GS_E_TOPOLOGY, "source must have parent -1");
   int ndev = 0;
