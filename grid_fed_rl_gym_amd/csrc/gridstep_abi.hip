@@ -270,16 +270,19 @@ int launch_pack(gs_handle* h, const int32_t* map, int C, double* dst) {
   return GS_OK;
 }
 
-// A whole observation block [B][obs_dim] from the rows: every column, the constants included -- on a per-instance-loads handle
-// (GsPlan::pl) the static load columns of each instance are its own, written over the shared constants
-int launch_pack_obs(gs_handle* h, double* dst) {
-  const int rc = launch_pack(h, h->map_obs, h->obs_dim, dst);
-  if (rc || !h->pl) return rc;
+// each instance's own static load columns of a per-instance-loads handle (GsPlan::pl) into the observation block dst [B][obs_dim]
+int launch_load_columns(gs_handle* h, double* dst) {
   const size_t threads = (size_t)h->B * 2 * h->n_loads;
   hipLaunchKernelGGL(gs_k_load_columns, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->LL.pl, dst, h->B, h->obs_dim,
                      2 * h->n + 2 * h->m + 1, h->n_loads);
   HIPCHK(h, hipGetLastError());
   return GS_OK;
+}
+// A whole observation block [B][obs_dim] from the rows: every column, the constants included -- on a per-instance-loads handle
+// the static load columns of each instance are its own, written over the shared constants
+int launch_pack_obs(gs_handle* h, double* dst) {
+  const int rc = launch_pack(h, h->map_obs, h->obs_dim, dst);
+  return rc || !h->pl ? rc : launch_load_columns(h, dst);
 }
 
 int launch_unpack(gs_handle* h, const int32_t* map, int C, const double* src, int stride = 0) {
@@ -392,21 +395,15 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
       }
       GsF2Tables f2a = h->F2, f2b = h->F2;
       f2a.wg_offset = 0; f2b.wg_offset = n_first;
-      // pz...: the PZ / PL kernels' pointers to the per-instance line impedances / load powers, behind the argument block
-      auto launch = [&](auto k, auto... pz) -> int {
-        if (!k) return fail(h, GS_E_STATE, "%s: no such step kernel", h->f2().name);
-        hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz...);
-        if (n_first < n_wg)
-          hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz...);
-        return GS_OK;
-      };
-      const GsStepKernels& k = gs_step_kernels[(int)h->step];
+      // the handle's form of its member; pz, pl: the per-instance line impedances / load powers, behind the argument block (null
+      // where the handle has none: its form does not read them)
+      const GsStepFns<GsF2StepFn>& form = gs_step_kernels[(int)h->step].form[h->pz][h->pl];
+      const GsF2StepFn k = fc.enabled ? form.stepc : form.step;
+      if (!k) return fail(h, GS_E_STATE, "%s: no such step kernel", h->f2().name);
       const double *pz = h->LP.pz, *pl = h->LL.pl;
-      const int rc = h->pz && h->pl ? launch(fc.enabled ? k.pz_pl.stepc : k.pz_pl.step, pz, pl)
-                     : h->pz        ? launch(fc.enabled ? k.pz.stepc : k.pz.step, pz)
-                     : h->pl        ? launch(fc.enabled ? k.pl.stepc : k.pl.step, pl)
-                                    : launch(fc.enabled ? k.plain.stepc : k.plain.step);
-      if (rc) return rc;
+      hipLaunchKernelGGL(k, dim3(n_first), b2, h->F2.lds_bytes, h->stream, h->T, f2a, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz, pl);
+      if (n_first < n_wg)
+        hipLaunchKernelGGL(k, dim3(n_wg - n_first), b2, h->F2.lds_bytes, h->stream2, h->T, f2b, h->R, h->SC, h->EC, h->slab, h->B, d_actions, h->total_load, pa, fc, rsv, pz, pl);
       HIPCHK(h, hipGetLastError());
       return GS_OK;
     }
@@ -564,8 +561,8 @@ int flat_start_captures(gs_handle* h) {
     GsF2Tables cap = h->F2; cap.nrflat = tab; cap.nrflat_mode = 1; cap.wg_offset = 0;
     GsPackArgs pa{}; GsFusedChecks fc{}; GsRolloutStep rsv{};
     GsSolveCfg sc = h->SC; sc.stamps = nullptr;
-    hipLaunchKernelGGL(gs_step_kernels[(int)h->step].plain.step, dim3(1), dim3(64 * h->f2().nw), h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc,
-                       h->EC, h->slab, std::min(h->B, h->f2().iw), h->d_in, h->total_load, pa, fc, rsv);
+    hipLaunchKernelGGL(gs_step_kernels[(int)h->step].form[0][0].step, dim3(1), dim3(64 * h->f2().nw), h->F2.lds_bytes, h->stream, h->T, cap, h->R, sc,
+                       h->EC, h->slab, std::min(h->B, h->f2().iw), h->d_in, h->total_load, pa, fc, rsv, nullptr, nullptr);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
         hipMemset(h->slab, 0, (size_t)R.total * GS_LANES * sizeof(double)) != hipSuccess)
       return fail(nullptr, GS_E_HIP, "Newton-Raphson: flat-start table");
@@ -632,8 +629,8 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
     for (const GsSolveKernels& k : gs_solve_kernels) ok = ok && raise(k.solve, max_dyn) && raise(k.step.step, max_dyn) && raise(k.step.stepc, max_dyn);
     if (!ok) return bail(fail(nullptr, GS_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%d) failed", max_dyn));
     for (const GsStepKernels& k : gs_step_kernels)
-      ok = ok && raise(k.plain.step, 160 * 1024) && raise(k.plain.stepc, 160 * 1024) && raise(k.pz.step, 160 * 1024) && raise(k.pz.stepc, 160 * 1024) &&
-           raise(k.pl.step, 160 * 1024) && raise(k.pl.stepc, 160 * 1024) && raise(k.pz_pl.step, 160 * 1024) && raise(k.pz_pl.stepc, 160 * 1024);
+      for (const auto& forms : k.form)
+        for (const GsStepFns<GsF2StepFn>& f : forms) ok = ok && raise(f.step, 160 * 1024) && raise(f.stepc, 160 * 1024);
 #if defined(GS_BUILD_EXPERIMENTS)
     ok = ok && raise(gs_k_nr_sparse_lds, 160 * 1024);
 #endif
@@ -1345,12 +1342,8 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
       GsRolloutPostArgs pa{fused ? nullptr : ro.rew, fused ? nullptr : ro.done, nxt, h->map_obs, h->d_cst, ro.term_count, ro.term_idx, ro.term_obs, ro.term_cap, h->obs_dim, t, h->B};
       hipLaunchKernelGGL(gs_k_rollout_post, dim3(h->groups), dim3(256), 0, h->stream, h->T, h->R, h->EC, h->slab, pa);
       HIPCHK(h, hipGetLastError());
-      if (h->pl) {      // (the fresh rows it wrote carry the shared constants: every instance's own static load columns over them)
-        const size_t threads = (size_t)h->B * 2 * h->n_loads;
-        hipLaunchKernelGGL(gs_k_load_columns, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->LL.pl, nxt, h->B,
-                           h->obs_dim, 2 * h->n + 2 * h->m + 1, h->n_loads);
-        HIPCHK(h, hipGetLastError());
-      }
+      // (the fresh rows it wrote carry the shared constants: every instance's own static load columns over them)
+      if (h->pl && (rc = launch_load_columns(h, nxt))) return rc;
     }
   }
   if ((rc = join_streams(h))) return rc;

@@ -10,21 +10,20 @@
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
-// they launch the gs_k_*_nr_dmfma kernels below around their solver); the second (kernels_flow2.hip): step, stepc and their PZ /
-// PL forms per StepMember.
+// they launch the gs_k_*_nr_dmfma kernels below around their solver); the second (kernels_flow2.hip): per StepMember, step and
+// stepc of each of its forms.  A form is an index, not a type: every second-generation step kernel has the one signature
+// GsF2StepFn, whose two trailing pointers are the per-instance line impedances (pz) and load powers (pl); a form reads the ones
+// it is built for and is launched with null for the others.
 typedef void (*GsSolveFn)(GsTables T, GsRows R, GsSolveCfg C, double* slab, int B);
 typedef void (*GsStepFn)(GsTables T, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions, double total_load,
                          GsPackArgs PA, GsFusedChecks FC);
 typedef void (*GsF2StepFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions,
-                           double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS);
-typedef void (*GsF2StepPzFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions,
-                             double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, const double* pz);
+                           double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, const double* pz, const double* pl);
 template <class Fn> struct GsStepFns { Fn step = nullptr, stepc = nullptr; };      // the plain step and the step with the checks
 struct GsSolveKernels { GsSolveFn solve; GsStepFns<GsStepFn> step; };
-typedef void (*GsF2StepPzPlFn)(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* slab, int B, const double* actions,
-                               double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS, const double* pz, const double* pl);
-// plain; pz: per-instance line impedances; pl: per-instance load powers (one pointer behind the block, GsF2StepPzFn's shape); pz_pl: both
-struct GsStepKernels { GsStepFns<GsF2StepFn> plain; GsStepFns<GsF2StepPzFn> pz, pl; GsStepFns<GsF2StepPzPlFn> pz_pl; };
+// form[pz][pl]: the kernels that read per-instance line impedances (pz = 1) and / or per-instance load powers (pl = 1);
+// {nullptr, nullptr} where the member has no such form
+struct GsStepKernels { GsStepFns<GsF2StepFn> form[2][2]; };
 extern const std::array<GsSolveKernels, (size_t)SolveMember::nr_sparse_lds + 1> gs_solve_kernels;
 extern const std::array<GsStepKernels, kStepMemberCount> gs_step_kernels;
 

@@ -1815,94 +1815,64 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     atomicMax(&C.stamps[17 + 2 * bid], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 
-// The step kernels of member `name`, shaped by its row of kStepMembers: F2_KERNELS defines gs_k_step_<name> and gs_k_stepc_<name>
-// (the post-step checks in its epilogue), F2_KERNELS_PZ their per-instance line impedance forms gs_k_step_<name>_pz /
-// gs_k_stepc_<name>_pz (PZ = 1: the pointer to the per-instance entries is an argument of its own behind the block the others read,
-// F2ArgBlock's offsets unchanged, and is read from the formal parameter), F2_KERNELS_PL the per-instance load power forms
-// gs_k_step*_<name>_pl (PL = 1, its pointer in the same place) and F2_KERNELS_PZ_PL the forms with both, gs_k_step*_<name>_pz_pl
-// (pz, then pl).  OCC: the member's occupancy attribute.  Each line also files its two kernels under the member's enum value
-// (f2_kernels / f2_kernels_pz / f2_kernels_pl / f2_kernels_pz_pl), where the launch table below finds them.
-template <StepMember M> constexpr GsStepFns<GsF2StepFn> f2_kernels() { return {}; }
-template <StepMember M> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pz() { return {}; }
-template <StepMember M> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pl() { return {}; }
-template <StepMember M> constexpr GsStepFns<GsF2StepPzPlFn> f2_kernels_pz_pl() { return {}; }
-#define F2_PZ_PARAM_0
-#define F2_PZ_PARAM_1 , const double* __restrict__ pz
-#define F2_PZ_ARG_0 nullptr
-#define F2_PZ_ARG_1 pz
-#define F2_PL_PARAM_0
-#define F2_PL_PARAM_1 , const double* __restrict__ pl
-#define F2_PL_ARG_0 nullptr
-#define F2_PL_ARG_1 pl
+// The step kernels of member `name`, shaped by its row of kStepMembers.  One line per member, F2_MEMBER(name, OCC), defines every
+// form it has -- gs_k_step_<name> and gs_k_stepc_<name> (the post-step checks in its epilogue), their per-instance line impedance
+// forms gs_k_step*_<name>_pz (PZ = 1), the per-instance load power forms gs_k_step*_<name>_pl (PL = 1) and the forms with both,
+// gs_k_step*_<name>_pz_pl -- under the member's one occupancy attribute OCC, and files them under the member's enum value
+// (f2_kernels<M>().form[PZ][PL]), where the launch table below finds them.  F2_MEMBER_NO_PZ: a member without the _pz forms.
+// Every kernel has the one signature (kernels.h GsF2StepFn): the two pointers to the per-instance entries are arguments of their
+// own behind the block the others read, F2ArgBlock's offsets unchanged; a form reads the ones it is built for, from the formal
+// parameter, and never looks at the others (the host passes null there).
+template <StepMember M> constexpr GsStepKernels f2_kernels() { return {}; }
+#define F2_PTR_0(p) nullptr
+#define F2_PTR_1(p) p
 #define F2_KERNEL(kernel, name, CHK, PZ, PL, OCC)                                                                           \
   extern "C" __global__ void __launch_bounds__(64 * step_row(StepMember::name).nw) OCC                                      \
   kernel(GsTables T, GsF2Tables F, GsRows R, GsSolveCfg C, GsEnvCfg E, double* __restrict__ slab, int B,                     \
-         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS F2_PZ_PARAM_##PZ \
-         F2_PL_PARAM_##PL) {                                                                                                \
+         const double* __restrict__ actions, double total_load, GsPackArgs PA, GsFusedChecks FC, GsRolloutStep RS,          \
+         const double* __restrict__ pz, const double* __restrict__ pl) {                                                    \
     constexpr StepMemberRow r = step_row(StepMember::name);                                                                 \
     GS_ARGS_IN_PLACE(F2ArgBlock, A);                                                                                        \
     f2_step<r.solver, CHK, r.nw, r.ni, r.iw, PZ, PL>(A->T, A->F, A->R, A->C, A->E, A->slab, A->B, A->actions, A->total_load, A->PA, \
-                                                   A->FC, A->RS, F2_PZ_ARG_##PZ, F2_PL_ARG_##PL);                           \
+                                                   A->FC, A->RS, F2_PTR_##PZ(pz), F2_PTR_##PL(pl));                         \
   }
-#define F2_KERNELS(name, OCC)                                                                                               \
-  F2_KERNEL(gs_k_step_##name, name, 0, 0, 0, OCC)                                                                           \
-  F2_KERNEL(gs_k_stepc_##name, name, 1, 0, 0, OCC)                                                                          \
-  template <> constexpr GsStepFns<GsF2StepFn> f2_kernels<StepMember::name>() { return {gs_k_step_##name, gs_k_stepc_##name}; }
-#define F2_KERNELS_PZ(name, OCC)                                                                                            \
-  F2_KERNEL(gs_k_step_##name##_pz, name, 0, 1, 0, OCC)                                                                      \
-  F2_KERNEL(gs_k_stepc_##name##_pz, name, 1, 1, 0, OCC)                                                                     \
-  template <> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pz<StepMember::name>() { return {gs_k_step_##name##_pz, gs_k_stepc_##name##_pz}; }
-#define F2_KERNELS_PL(name, OCC)                                                                                            \
-  F2_KERNEL(gs_k_step_##name##_pl, name, 0, 0, 1, OCC)                                                                      \
-  F2_KERNEL(gs_k_stepc_##name##_pl, name, 1, 0, 1, OCC)                                                                     \
-  template <> constexpr GsStepFns<GsF2StepPzFn> f2_kernels_pl<StepMember::name>() { return {gs_k_step_##name##_pl, gs_k_stepc_##name##_pl}; }
-#define F2_KERNELS_PZ_PL(name, OCC)                                                                                         \
-  F2_KERNEL(gs_k_step_##name##_pz_pl, name, 0, 1, 1, OCC)                                                                   \
-  F2_KERNEL(gs_k_stepc_##name##_pz_pl, name, 1, 1, 1, OCC)                                                                  \
-  template <> constexpr GsStepFns<GsF2StepPzPlFn> f2_kernels_pz_pl<StepMember::name>() {                                    \
-    return {gs_k_step_##name##_pz_pl, gs_k_stepc_##name##_pz_pl};                                                           \
+#define F2_FORM(name, suffix, PZ, PL, OCC)                                                                                  \
+  F2_KERNEL(gs_k_step_##name##suffix, name, 0, PZ, PL, OCC)                                                                 \
+  F2_KERNEL(gs_k_stepc_##name##suffix, name, 1, PZ, PL, OCC)
+#define F2_FNS(name, suffix) {gs_k_step_##name##suffix, gs_k_stepc_##name##suffix}
+#define F2_MEMBER_NO_PZ(name, OCC)                                                                                          \
+  F2_FORM(name, , 0, 0, OCC)                                                                                                \
+  F2_FORM(name, _pl, 0, 1, OCC)                                                                                             \
+  template <> constexpr GsStepKernels f2_kernels<StepMember::name>() { return {{{F2_FNS(name, ), F2_FNS(name, _pl)}, {}}}; }
+#define F2_MEMBER(name, OCC)                                                                                                \
+  F2_FORM(name, , 0, 0, OCC)                                                                                                \
+  F2_FORM(name, _pl, 0, 1, OCC)                                                                                             \
+  F2_FORM(name, _pz, 1, 0, OCC)                                                                                             \
+  F2_FORM(name, _pz_pl, 1, 1, OCC)                                                                                          \
+  template <> constexpr GsStepKernels f2_kernels<StepMember::name>() {                                                      \
+    return {{{F2_FNS(name, ), F2_FNS(name, _pl)}, {F2_FNS(name, _pz), F2_FNS(name, _pz_pl)}}};                              \
   }
 
 #if defined(GS_BUILD_EXPERIMENTS)
-F2_KERNELS(fbs_flow2, )
+F2_MEMBER_NO_PZ(fbs_flow2, )
 #endif
-F2_KERNELS(nr_flow2, )
-F2_KERNELS(fbs_flow2s, )
-F2_KERNELS(nr_flow2s, )
+F2_MEMBER(nr_flow2, )
+F2_MEMBER(fbs_flow2s, )
+F2_MEMBER(nr_flow2s, )
 // fbs_flow2h: two workgroups share a CU (four waves per SIMD), so that one's LDS-bound solver phase runs beside the other's
 // VALU-bound prologue / epilogue: +6 % at B = 8192, +11 % at 16384, +30 % at 4096 over the 32-instance member (the host's default
 // for the sweep solver; 8 instances per workgroup with four workgroups per CU was tried too: -20 %, the per-instance scalar chains
 // then fill an eighth of a wavefront)
-F2_KERNELS(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
-F2_KERNELS(fbs_flow2x, )         // (twice the registers of fbs_flow2h: two waves per SIMD, one workgroup per CU)
-F2_KERNELS(nr_mesh2, __attribute__((amdgpu_waves_per_eu(2, 2))))      // two workgroups per CU (two waves per SIMD: 256 registers)
-F2_KERNELS_PZ(nr_flow2, )
-F2_KERNELS_PZ(fbs_flow2s, )
-F2_KERNELS_PZ(nr_flow2s, )
-F2_KERNELS_PZ(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
-F2_KERNELS_PZ(fbs_flow2x, )
-// per-instance load powers: every member, and together with the line impedances wherever a member has the _pz form
-#if defined(GS_BUILD_EXPERIMENTS)
-F2_KERNELS_PL(fbs_flow2, )
-#endif
-F2_KERNELS_PL(nr_flow2, )
-F2_KERNELS_PL(fbs_flow2s, )
-F2_KERNELS_PL(nr_flow2s, )
-F2_KERNELS_PL(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
-F2_KERNELS_PL(fbs_flow2x, )
-F2_KERNELS_PL(nr_mesh2, __attribute__((amdgpu_waves_per_eu(2, 2))))
-F2_KERNELS_PZ_PL(nr_flow2, )
-F2_KERNELS_PZ_PL(fbs_flow2s, )
-F2_KERNELS_PZ_PL(nr_flow2s, )
-F2_KERNELS_PZ_PL(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
-F2_KERNELS_PZ_PL(fbs_flow2x, )
+F2_MEMBER(fbs_flow2h, __attribute__((amdgpu_waves_per_eu(4, 4))))
+F2_MEMBER(fbs_flow2x, )         // (twice the registers of fbs_flow2h: two waves per SIMD, one workgroup per CU)
+F2_MEMBER_NO_PZ(nr_mesh2, __attribute__((amdgpu_waves_per_eu(2, 2))))      // two workgroups per CU (two waves per SIMD: 256 registers)
 
 #if !defined(__HIP_DEVICE_COMPILE__)      // (host only: the device pass would put a copy of the table into the code object)
+template <size_t M> constexpr bool f2_has(int pz, int pl) { return f2_kernels<StepMember(M)>().form[pz][pl].step != nullptr; }
 template <size_t... M> constexpr std::array<GsStepKernels, sizeof...(M)> f2_launch_table(std::index_sequence<M...>) {
-  static_assert(((kStepMembers[M].pz == (f2_kernels_pz<StepMember(M)>().step != nullptr)) && ...), "kStepMembers: pz disagrees with F2_KERNELS_PZ");
-  static_assert((((M != 0) == (f2_kernels_pl<StepMember(M)>().step != nullptr)) && ...), "every step member has its F2_KERNELS_PL forms");
-  static_assert(((kStepMembers[M].pz == (f2_kernels_pz_pl<StepMember(M)>().step != nullptr)) && ...), "kStepMembers: pz disagrees with F2_KERNELS_PZ_PL");
-  return {{{f2_kernels<StepMember(M)>(), f2_kernels_pz<StepMember(M)>(), f2_kernels_pl<StepMember(M)>(), f2_kernels_pz_pl<StepMember(M)>()}...}};
+  static_assert((((M != 0) == f2_has<M>(0, 0) && (M != 0) == f2_has<M>(0, 1)) && ...), "every step member has its plain and _pl forms");
+  static_assert(((kStepMembers[M].pz == f2_has<M>(1, 0) && kStepMembers[M].pz == f2_has<M>(1, 1)) && ...), "kStepMembers: pz disagrees with the member's forms");
+  return {{f2_kernels<StepMember(M)>()...}};
 }
 extern const std::array<GsStepKernels, kStepMemberCount> gs_step_kernels = f2_launch_table(std::make_index_sequence<kStepMemberCount>());
 #endif
