@@ -1,0 +1,238 @@
+// handle.h -- what the translation units of the C ABI's host side share (host only, internal): the handle and the checks object,
+// error reporting, the stream join every entry point starts with, the handle's allocator, launch timing, and the helpers of
+// gridstep_abi.hip that the other files call.
+// Which file owns what: DESIGN.md section 1, "File map of the ABI's host side".
+//
+// Whatever has external linkage here lives in namespace gsi, which is hidden: libgridstep.so exports the C ABI and nothing else.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/gridstep.h"
+#include "gs_internal.h"
+#include "kernels.h"
+#include "topology.h"
+#include "plan.h"
+#include "policy.h"
+
+struct GsLoopComm;      // abi_comm.hip
+
+namespace gsi __attribute__((visibility("hidden"))) {
+
+typedef void* gs_ncclComm_t;
+struct TimedLaunch { int kid; hipEvent_t a, b; };
+
+}  // namespace gsi
+
+// A handle is its plan (plan.h: members, rows, launch shapes, host tables) and the device state built from it.
+struct gs_handle : GsPlan {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  gs_config cfg{};
+  HostTopology topo;
+  GsTables T{};
+  struct gs_checks* fused = nullptr;      // checks evaluated inside the step kernel's epilogue (gs_checks_set_fused)
+  // A step of the second-generation kernels goes out as TWO launches, each half of the workgroups, on two streams
+  // (GsPlan::split_ok): consecutive steps of one half need nothing from the other half, so the second stream's kernels slide
+  // into the launch gaps and the uneven tails of the first's (two handles of 4096 instances on two streams: 205 M env-steps/s
+  // against 186 M for one of 8192).  `forked`: stream2 holds step launches the main stream has not waited for yet; every entry
+  // point other than the step itself joins first (GS_ENTER).
+  bool forked = false;
+  hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_peer = nullptr, ev_peer2 = nullptr;
+  // The second-generation step kernels do not write the (|V|, angle) / (flow, |P| / rating) row pairs: those are the first
+  // 2 n + 2 m columns of the observation block the step writes anyway.  `rows_stale`: the rows lag behind `last_obs`, the block
+  // of the last step; every entry point that reads or partly rewrites them restores them first (ensure_rows).
+  bool rows_stale = false; const double* last_obs = nullptr;
+  unsigned long long* d_stamps = nullptr;
+  bool was_reset = false;
+  std::vector<void*> allocs;
+  char* arena = nullptr; size_t arena_left = 0;      // dev_alloc: the current chunk of small tables
+  double* slab = nullptr;
+  double* d_in = nullptr; size_t in_doubles = 0;
+  double* d_out = nullptr; size_t out_doubles = 0;
+  // [B][obs_dim] x 2, owned by the environment path: both written whole at reset, the changing columns of the other one by
+  // every step -- so that the all-gather of step k (on its own stream) can run while step k + 1 computes
+  double* d_obs2[2] = {nullptr, nullptr}; int obs_cur = 0;
+  hipStream_t comm_stream = nullptr; hipEvent_t ev_step = nullptr, ev_gather[2] = {nullptr, nullptr}; bool gather_pending[2] = {false, false};
+  // host observation arrays whose constant columns are in place (gs_host_obs_bind): gs_step / gs_download_step copy only the
+  // changing columns into these -- two strided copies instead of one whole block, 36 % fewer bytes over PCIe on the 123-bus feeder
+  std::vector<const double*> bound_obs;
+  float* d_obs32 = nullptr;                // float32 copy of the observation block (gs_step_f32 / gs_download_step_f32), on first use
+  hipEvent_t ev_scalars = nullptr;
+  double* d_actions = nullptr; int n_action_batches = 0;
+  // gs_rollout: [T + 1][B][obs_dim] observation sequence, [T][B][A] actions, [T][B] rewards / done flags, and the side
+  // list of terminal observations (the rows the in-place resets replaced)
+  struct Rollout {
+    int T_cap = 0, T = 0, term_cap = 0; uint64_t calls = 0;
+    double* obs_seq = nullptr; double* act = nullptr; double* rew = nullptr; uint8_t* done = nullptr;
+    int32_t* term_count = nullptr; int32_t* term_idx = nullptr; double* term_obs = nullptr;
+    int32_t n_term = 0;
+  } ro;
+  // gs_policy_mlp_set: the policy's packed weights and biases (one allocation), the actions of gs_policy_mlp_eval [B][A], and the
+  // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
+  // compute: GS_COMPUTE_*; with GS_COMPUTE_F32 `blob` holds the float32 image and the normalisation vectors, and args32 is the
+  // argument block of gs_k_policy_mlp_f32 (kernels_policy_f32.hip)
+  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0; } pol;
+  double* d_cst = nullptr;
+  int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
+          *map_p = nullptr, *map_q = nullptr, *map_act = nullptr, *map_state = nullptr;
+  int32_t *rows_f = nullptr, *rows_i = nullptr, *rows_u = nullptr;
+  double* sc_f = nullptr; int32_t* sc_i = nullptr; uint8_t* sc_u = nullptr;
+  uint64_t* d_seeds = nullptr; uint8_t* d_mask = nullptr;
+  // gs_fallback_linear: line reactances, dict-order bus lists and staging, created on first use
+  std::vector<double> line_x;
+  bool fb_ready = false; GsFallbackArgs FB{};
+  // per-instance line impedances (GsPlan::pz): what the handle holds ([B][m], host copy and device copy, the fallback reads the
+  // device one), the nominal values they are checked against, the arguments of gs_k_line_params (LP.pz: the step kernels' entries)
+  std::vector<double> inst_r, inst_x, nominal_r, nominal_x;
+  GsLineParamArgs LP{}; uint8_t* d_pzmask = nullptr;
+  // per-instance load powers (GsPlan::pl): what the handle holds ([B][n_loads], host copy and device copy) and the arguments of
+  // gs_k_load_params (LL.pl: the step kernels' entries)
+  std::vector<double> inst_load;
+  GsLoadParamArgs LL{}; uint8_t* d_plmask = nullptr;
+  double *fb_load = nullptr, *fb_gen = nullptr, *fb_tl = nullptr, *fb_tg = nullptr; uint8_t* fb_mask = nullptr; int32_t* fb_applied = nullptr;
+  // host copies of the per-instance scalars: ONE page-locked block the device addresses -- gs_k_scalars stores into it itself (three
+  // copies through the runtime's staging buffer cost 80 us of a 0.9 ms env.step()); hd_*: the same block as the device sees it
+  void* h_pin = nullptr;
+  double* h_f = nullptr; int32_t* h_i = nullptr; uint8_t* h_u = nullptr; uint32_t* h_v4 = nullptr;
+  double* hd_f = nullptr; int32_t* hd_i = nullptr; uint8_t* hd_u = nullptr; uint32_t* hd_v4 = nullptr;
+  // timing
+  bool timing = false;
+  bool timing_span = false, span_open = false; hipEvent_t span_a = nullptr, span_b = nullptr; int span_kid = 0; int64_t span_launches[8] = {0};
+  std::vector<gsi::TimedLaunch> timed; size_t timed_used = 0;
+  // comm
+  gsi::gs_ncclComm_t comm = nullptr; int rank = 0, world = 1; double* d_obs_full = nullptr;
+  double *d_gather_send = nullptr, *d_gather_recv = nullptr;     // compact observation blocks (changing columns only): [B][nd], [world * B][nd]
+  struct GsLoopComm* loop = nullptr;                              // the in-process transport (gs_comm_init_loopback) instead of RCCL
+  hipEvent_t ev_full = nullptr;                                   // gs_allgather_obs_view: the gathered block is complete
+  mutable std::string err;
+};
+
+// ---- post-step checks -------------------------------------------------------------------------------
+struct gs_checks {
+  gs_handle* h = nullptr;
+  GsChecksCfg C{};
+  double* prev = nullptr; int32_t* state = nullptr; int32_t* out_i = nullptr; double* out_f = nullptr;
+  uint8_t *bus_mask = nullptr, *line_mask = nullptr; double* freq = nullptr; bool use_freq = false, want_masks = true;
+  bool timing = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t ev_used = 0;
+};
+
+namespace gsi __attribute__((visibility("hidden"))) {
+
+// the message as the library's last error (gs_last_error; gridstep_abi.hip holds it) and, with a handle, as the handle's
+int fail(gs_handle* h, int code, const char* fmt, ...);
+
+// A peer's stream as it crosses the C ABI: NULL = none; hipStreamLegacy (1) = the legacy default stream, i.e. handle 0
+static inline hipStream_t peer_stream(void* s) { return s == (void*)hipStreamLegacy ? (hipStream_t)nullptr : (hipStream_t)s; }
+
+#define HIPCHK(h, expr)                                                                           \
+  do { hipError_t e_ = (expr);                                                                    \
+       if (e_ != hipSuccess) return fail((h), GS_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+// Work of the second step stream joins the main stream (see gs_handle::forked)
+static inline int join_streams(gs_handle* h) {
+  if (!h->forked) return GS_OK;
+  HIPCHK(h, hipEventRecord(h->ev_join, h->stream2));
+  HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+  h->forked = false;
+  return GS_OK;
+}
+#define GS_ENTER(h)                                                                               \
+  do { HIPCHK((h), hipSetDevice((h)->device));                                                    \
+       if ((h)->forked) { int rc_ = join_streams(h); if (rc_) return rc_; } } while (0)
+
+constexpr size_t GS_ARENA_SMALL = 64 * 1024, GS_ARENA_CHUNK = 2 * 1024 * 1024;
+template <typename X>
+int dev_alloc(gs_handle* h, X** p, size_t count) {
+  void* q = nullptr;
+  const size_t bytes = std::max<size_t>(count, 1) * sizeof(X);
+  // Tables (a few hundred bytes to a few KB each, forty of them) share 2 MB chunks: as allocations of their own each sat on a
+  // page of its own, and a workgroup's first touch of every one of them was an address-translation miss at kernel start.
+  if (bytes <= GS_ARENA_SMALL && !GS_EXPERIMENT_ENV("GS_NO_TABLE_ARENA")) {
+    const size_t need = (bytes + 255) & ~(size_t)255;
+    if (h->arena_left < need) {
+      hipError_t e = hipMalloc(&q, GS_ARENA_CHUNK);
+      if (e != hipSuccess) return fail(h, GS_E_NOMEM, "hipMalloc(%zu) failed: %s", (size_t)GS_ARENA_CHUNK, hipGetErrorString(e));
+      h->allocs.push_back(q);
+      h->arena = (char*)q; h->arena_left = GS_ARENA_CHUNK;
+    }
+    *p = (X*)h->arena;
+    h->arena += need; h->arena_left -= need;
+    return GS_OK;
+  }
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess) return fail(h, GS_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+  h->allocs.push_back(q);
+  *p = (X*)q;
+  return GS_OK;
+}
+
+template <typename X>
+int dev_upload(gs_handle* h, const X** p, const std::vector<X>& v) {
+  X* q = nullptr;
+  int rc = dev_alloc(h, &q, v.size());
+  if (rc) return rc;
+  if (!v.empty()) HIPCHK(h, hipMemcpy(q, v.data(), v.size() * sizeof(X), hipMemcpyHostToDevice));
+  *p = q;
+  return GS_OK;
+}
+
+inline int upload_map(gs_handle* h, int32_t** p, const std::vector<int32_t>& v) {
+  const int32_t* q = nullptr;
+  int rc = dev_upload(h, &q, v);
+  *p = const_cast<int32_t*>(q);
+  return rc;
+}
+
+// What did NOT go through dev_alloc (whose allocations live as long as the handle and go with it) is a hipMalloc of its own, owned
+// by whoever made it: freed with this, which leaves the pointer NULL
+template <typename X>
+void dev_free(X*& p) {
+  if (p) { (void)hipFree(p); p = nullptr; }
+}
+
+// ---- timing wrapper -------------------------------------------------------------------------
+struct LaunchTimer {
+  gs_handle* h; TimedLaunch* t = nullptr;
+  LaunchTimer(gs_handle* hh, int kid) : h(hh) {
+    if (h->timing_span) {          // one event pair around the whole timed region: no marker packets between the launches
+      if (!h->span_open) {
+        if (!h->span_a && (hipEventCreate(&h->span_a) != hipSuccess || hipEventCreate(&h->span_b) != hipSuccess)) return;
+        (void)hipEventRecord(h->span_a, h->stream);
+        h->span_open = true; h->span_kid = kid;
+        for (int k = 0; k < GS_K_COUNT; ++k) h->span_launches[k] = 0;
+      }
+      if (kid >= 0 && kid < GS_K_COUNT) h->span_launches[kid] += 1;
+      return;
+    }
+    if (!h->timing) return;
+    if (h->timed_used == h->timed.size()) {
+      TimedLaunch n; n.kid = kid;
+      if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) return;
+      h->timed.push_back(n);
+    }
+    t = &h->timed[h->timed_used++];
+    t->kid = kid;
+    (void)hipEventRecord(t->a, h->stream);
+  }
+  ~LaunchTimer() { if (t) (void)hipEventRecord(t->b, h->stream); }
+};
+
+// ---- helpers of gridstep_abi.hip that the other files call (described where they are defined) ----
+int launch_load_columns(gs_handle* h, double* dst);
+int ensure_rows(gs_handle* h);
+int pack_to_host(gs_handle* h, const int32_t* map, int C, double* host);
+int unpack_from_host(gs_handle* h, const int32_t* map, int C, const double* host);
+int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullptr, const GsRolloutStep* rs = nullptr);
+
+// ---- owners of what gs_destroy does not free itself (abi_rollout.hip) ----
+void policy_release(gs_handle* h);
+void rollout_release(gs_handle* h, bool keep_term_count = false);
+
+}  // namespace gsi
