@@ -16,7 +16,7 @@ from .solver import (BatchedNewtonRaphsonSolver, NewtonRaphsonSolver, FastDecoup
                      BatchedForwardBackwardSweepSolver, BatchedRobustPowerFlowSolver, DistributionPowerFlow, parallel_power_flow_batch,
                      injections_from_dicts)
 from .env import BatchedGridEnvironment, VectorizedEnvironment, Box
-from .rollout import collect_random_data, collect_policy_data, rollout_device, GridDataset
+from .rollout import collect_random_data, collect_policy_data, rollout_device, GridDataset, DeviceGridDataset
 from .policy import MLPPolicy
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -28,7 +28,7 @@ __all__ = [
     "BatchedNewtonRaphsonSolver", "NewtonRaphsonSolver", "FastDecoupledSolver",
     "BatchedForwardBackwardSweepSolver", "BatchedRobustPowerFlowSolver", "DistributionPowerFlow", "parallel_power_flow_batch",
     "injections_from_dicts", "BatchedGridEnvironment", "VectorizedEnvironment", "Box",
-    "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "GridDataset", "ShardedGridEnvironment", "LoopbackShards", "shard_range",
+    "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "GridDataset", "DeviceGridDataset", "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",
     "BatchedSafetyChecker", "BatchedSafetyMonitor", "PostStepChecks", "device_quality_score",
     "UnbalancedPowerFlow", "UnbalancedFeederSpec", "UnbalancedSolution", "unbalanced_from_single_phase", "ieee8500_like",

@@ -97,6 +97,20 @@ class gs_policy_mlp_opts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("compute", C.c_int32), ("obs_shift", _dp), ("obs_scale", _dp)]
 
 
+class gs_dataset_stats_view(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("rows_per_chunk", C.c_int32), ("n", C.c_int64), ("obs_dim", C.c_int32), ("action_dim", C.c_int32),
+                ("obs_mean", _dp), ("obs_std", _dp), ("act_mean", _dp), ("act_std", _dp), ("reward_mean", _dp), ("reward_std", _dp)]
+
+
+class gs_dataset_batch(C.Structure):
+    _fields_ = [("observations", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("next_observations", C.c_void_p),
+                ("terminals", C.c_void_p)]
+
+
+GS_DATASET_KEEP_STATS = 1
+DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminals")      # gs_dataset_batch's fields, in order
+
+
 # every symbol include/gridstep.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = [
@@ -124,6 +138,11 @@ SYMBOLS = [
     ("gs_rollout", C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, _dp]),
     ("gs_rollout_download", C.c_int, [_H, C.POINTER(gs_rollout_view)]),
     ("gs_rollout_device_view", C.c_int, [_H, C.POINTER(gs_rollout_device)]),
+    ("gs_dataset_build", C.c_int, [_H, C.c_uint32]),
+    ("gs_dataset_stats", C.c_int, [_H, C.POINTER(gs_dataset_stats_view)]),
+    ("gs_dataset_set_stats", C.c_int, [_H, C.POINTER(gs_dataset_stats_view)]),
+    ("gs_dataset_sample", C.c_int, [_H, C.c_int32, C.POINTER(C.c_int64), C.c_uint64, C.c_uint64, C.c_int32, C.c_int32,
+                                    C.POINTER(gs_dataset_batch), C.c_void_p]),
     ("gs_get_state", C.c_int, [_H, _dp]),
     ("gs_set_state", C.c_int, [_H, _dp]),
     ("gs_comm_unique_id", C.c_int, [_up]),
@@ -253,6 +272,38 @@ class DeviceArray:
     def __repr__(self) -> str:
         return f"DeviceArray(0x{self.ptr:x}, shape={self.shape}, typestr={self.typestr!r})"
 
+    def to_host(self) -> np.ndarray:
+        """A host copy (a plain ``hipMemcpy``, which waits for it): for looking at a batch or a view without a GPU framework.  The
+        caller orders it behind the producer (a call made without a consumer stream has returned complete)."""
+        out = np.empty(self.shape, dtype=np.dtype(self.typestr))
+        if out.nbytes:
+            rc = _hip_runtime().hipMemcpy(C.c_void_p(out.ctypes.data), C.c_void_p(self.ptr), C.c_size_t(out.nbytes), 2)   # hipMemcpyDeviceToHost
+            if rc != 0:
+                raise PowerFlowError(f"hipMemcpy of {self!r} failed: hipError {rc}")
+        return out
+
+
+_hip: Optional[C.CDLL] = None
+
+
+def _hip_runtime() -> C.CDLL:
+    """The HIP runtime libgridstep.so is linked against (already in the process once the library is loaded)."""
+    global _hip
+    if _hip is None:
+        load()
+        last = None
+        for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", "/opt/rocm/lib/libamdhip64.so"):
+            try:
+                _hip = C.CDLL(name)
+                break
+            except OSError as e:
+                last = e
+        if _hip is None:
+            raise PowerFlowError(f"the HIP runtime could not be loaded: {last}")
+        _hip.hipMemcpy.restype = C.c_int
+        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return _hip
+
 
 def _stream_arg(stream):
     """A consumer's / producer's ``hipStream_t`` for the C ABI: ``None`` = no stream (the caller synchronises itself); an
@@ -279,6 +330,22 @@ def _device_address(x, shape) -> int:
         raise PowerFlowError("device actions: an address, a torch tensor or an object with __cuda_array_interface__")
     if tuple(cai["shape"]) != tuple(shape) or cai["typestr"] not in ("<f8", "=f8") or cai.get("strides") not in (None,):
         raise PowerFlowError(f"device actions must be C-contiguous float64 of shape {tuple(shape)}")
+    return int(cai["data"][0])
+
+
+def _device_address_of(x, shape, dtype) -> int:
+    """``_device_address`` for a C-contiguous array of ``dtype`` (float64 / float32): a torch tensor or anything with
+    ``__cuda_array_interface__``."""
+    dt = np.dtype(dtype)
+    if hasattr(x, "data_ptr"):                      # torch
+        if tuple(x.shape) != tuple(shape) or str(x.dtype) != f"torch.{dt.name}" or not x.is_contiguous() or not getattr(x, "is_cuda", True):
+            raise PowerFlowError(f"expected a contiguous {dt.name} device tensor of shape {tuple(shape)}, got {tuple(x.shape)} {x.dtype}")
+        return int(x.data_ptr())
+    cai = getattr(x, "__cuda_array_interface__", None)
+    if cai is None:
+        raise PowerFlowError("expected a torch tensor or an object with __cuda_array_interface__")
+    if tuple(cai["shape"]) != tuple(shape) or np.dtype(cai["typestr"]) != dt or cai.get("strides") not in (None,):
+        raise PowerFlowError(f"expected a C-contiguous {dt.name} device array of shape {tuple(shape)}")
     return int(cai["data"][0])
 
 
@@ -918,6 +985,57 @@ class Handle:
         return dict(obs_seq=DeviceArray(v.obs_seq, (T + 1, B, D), "<f8"), actions=DeviceArray(v.actions, (T, B, A), "<f8"),
                     rewards=DeviceArray(v.rewards, (T, B), "<f8"), terminals=DeviceArray(v.terminals, (T, B), "|u1"),
                     terminal_index=DeviceArray(v.terminal_index, (n, 2), "<i4"), terminal_obs=DeviceArray(v.terminal_obs, (n, D), "<f8"))
+
+    # -- the device-resident dataset over the last rollout (gs_dataset_*) ---------------------------------------------------
+    def dataset_build(self, keep_stats: bool = False) -> None:
+        """gs_dataset_build (asynchronous): statistics and terminal map of the last rollout; ``keep_stats``: the map only."""
+        self._check(self._lib.gs_dataset_build(self._h, GS_DATASET_KEEP_STATS if keep_stats else 0))
+
+    def dataset_stats(self) -> dict:
+        """gs_dataset_stats: ``n``, ``rows_per_chunk`` and the raw statistics (standard deviations WITHOUT the + 1e-6)."""
+        out = dict(obs_mean=np.empty(self.obs_dim), obs_std=np.empty(self.obs_dim), act_mean=np.empty(self.action_dim),
+                   act_std=np.empty(self.action_dim), reward_mean=np.empty(1), reward_std=np.empty(1))
+        v = gs_dataset_stats_view(C.sizeof(gs_dataset_stats_view), 0, 0, 0, 0, *[_ptr(out[k], _dp) for k in
+                                  ("obs_mean", "obs_std", "act_mean", "act_std", "reward_mean", "reward_std")])
+        self._check(self._lib.gs_dataset_stats(self._h, C.byref(v)))
+        out["reward_mean"], out["reward_std"] = float(out["reward_mean"][0]), float(out["reward_std"][0])
+        out["n"], out["rows_per_chunk"] = int(v.n), int(v.rows_per_chunk)
+        return out
+
+    def dataset_set_stats(self, obs_mean, obs_std, act_mean, act_std, reward_mean, reward_std) -> None:
+        """gs_dataset_set_stats: install raw statistics (standard deviations WITHOUT the + 1e-6) in place of the computed ones."""
+        a = [_f64(np.atleast_1d(x)) for x in (obs_mean, obs_std, act_mean, act_std, reward_mean, reward_std)]
+        if a[0].shape != a[1].shape or a[2].shape != a[3].shape or a[0].ndim != 1 or a[2].ndim != 1 or a[4].shape != (1,) or a[5].shape != (1,):
+            raise PowerFlowError("dataset statistics: mean and std of a kind must be vectors of one length, the reward pair scalars")
+        v = gs_dataset_stats_view(C.sizeof(gs_dataset_stats_view), 0, 0, a[0].shape[0], a[2].shape[0], *[_ptr(x, _dp) for x in a])
+        self._check(self._lib.gs_dataset_set_stats(self._h, C.byref(v)))
+
+    def dataset_sample(self, n: int, indices=None, seed: int = 0, draw: int = 0, dtype=np.float64, normalize: bool = True, out=None,
+                       stream=None) -> dict:
+        """gs_dataset_sample: one minibatch as ``DeviceArray`` views keyed like ``GridDataset.sample_batch``.  ``indices``: int64 [n]
+        (host) or None (drawn on the device from ``seed`` / ``draw``); ``out``: dict of the caller's device arrays (torch tensors or
+        anything ``_device_address`` takes) for some or all keys, the handle's own buffers (valid until the next call) for the rest;
+        ``stream``: the consumer's stream (``_stream_arg``), None = the call returns when the batch is complete."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise PowerFlowError(f"dataset_sample: dtype {dt} (float64 or float32)")
+        n = int(n)
+        idx = None
+        if indices is not None:
+            idx = np.ascontiguousarray(indices, dtype=np.int64)
+            if idx.shape != (n,):
+                raise PowerFlowError(f"dataset_sample: indices shape {idx.shape} != ({n},)")
+        shapes = dict(observations=(n, self.obs_dim), actions=(n, self.action_dim), rewards=(n,), next_observations=(n, self.obs_dim),
+                      terminals=(n,))
+        b = gs_dataset_batch()
+        for k, x in (out or {}).items():
+            if k not in shapes:
+                raise PowerFlowError(f"dataset_sample: unknown output {k!r}")
+            setattr(b, k, _device_address_of(x, shapes[k], dt))
+        self._check(self._lib.gs_dataset_sample(self._h, n, None if idx is None else idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(draw) & 0xFFFFFFFFFFFFFFFF),
+                                                1 if dt == np.dtype(np.float32) else 0, int(bool(normalize)), C.byref(b), _stream_arg(stream)))
+        return {k: DeviceArray(getattr(b, k), shapes[k], dt.str) for k in DATASET_KEYS}
 
     def get_state(self) -> np.ndarray:
         st = np.empty((self.B, self.state_dim))

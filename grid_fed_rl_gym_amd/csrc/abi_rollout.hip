@@ -130,6 +130,7 @@ static int rollout_ensure(gs_handle* h, int T) {
   if (T <= ro.T_cap) return GS_OK;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   rollout_release(h, true);
+  dataset_release(h, true);      // (its map and partial results are sized by T; installed statistics stay)
   const size_t B = h->B, D = h->obs_dim, A = std::max(h->action_dim, 1);
   // an instance finishes at most once per min(episode_length, 11) steps (truncation needs more than 10 violating steps
   // since its last reset, grid_env.py:604) plus once for an episode that was already under way

@@ -588,6 +588,7 @@ void gs_destroy(gs_handle* h) {
   dev_free(h->d_actions);
   policy_release(h);
   rollout_release(h);
+  dataset_release(h);
   if (h->h_pin) (void)hipHostFree(h->h_pin);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -590,6 +590,27 @@ struct GsLoadParamArgs {
   double* pl;                            // [groups][nq][64] double pairs
   int32_t B, groups, n_loads, pad;
 };
+// ---- the device-resident dataset (kernels_dataset.hip, abi_dataset.hip) ----
+#define GS_DS_ROWS_PER_CHUNK 256         // rows one partial reduction covers (gs_dataset_stats_view::rows_per_chunk)
+#define GS_DS_GATHER_ROWS 4              // samples per workgroup of the gather, one wave each
+// one of the three row-major matrices [N][C] the statistics run over; its columns are filed at col0 .. col0 + C - 1 of the Ct
+// columns; panels = 64-lane column panels (a lane: a column pair if C is even, one column if odd)
+struct GsDsMatrix { const double* x; int32_t C, col0, panels, pad; };
+struct GsDsStatArgs {
+  GsDsMatrix m[3];                       // obs_seq[0 .. T-1], actions, rewards
+  double* part;                          // [chunks][Ct][2] (offset of the mean from the matrix's row 0, M2)
+  long long N, chunks;
+  int32_t Ct, pad;
+};
+struct GsDsGatherArgs {
+  const int32_t* idx;                    // [n] transitions to gather
+  const int32_t* map;                    // [N] row of terminal_obs, or -1
+  const double* obs_seq; const double* act; const double* rew; const uint8_t* done; const double* term_obs;
+  const double* stats;                   // mean[Ct], then std[Ct] at Cs (raw, without the + 1e-6)
+  void* out_obs; void* out_act; void* out_rew; void* out_next; void* out_term;
+  long long N;
+  int32_t n, B, D, A, Ct, Cs, term_cap, normalize, vec2, pad;
+};
 #if defined(__HIPCC__)
 // constant ci of an observation (plan.cpp plan_maps: 2 l = P of load l, 2 l + 1 = its Q) as instance b holds it
 __device__ __forceinline__ double gs_pl_const(const double* __restrict__ pl, int n_loads, int b, int ci) {

@@ -73,6 +73,18 @@ struct gs_handle : GsPlan {
     int32_t* term_count = nullptr; int32_t* term_idx = nullptr; double* term_obs = nullptr;
     int32_t n_term = 0;
   } ro;
+  // gs_dataset_*: the dataset over the last rollout (abi_dataset.hip).  built_on = ro.calls of the rollout the map (and, unless
+  // the statistics were installed or kept, the statistics) was built on, 0 = none; stats = mean[Ct] then std[Ct] at stride Cs
+  // (Ct = obs_dim + action_dim + 1, Cs = Ct rounded up to even) on the device; part = the chunks' partial results; idx / h_idx =
+  // the sample indices on the device / their page-locked staging copy; batch[k] = the handle's own buffer for output k
+  struct Dataset {
+    uint64_t built_on = 0; long long N = 0; bool have_stats = false;
+    double* stats = nullptr; double* part = nullptr; size_t part_doubles = 0;
+    int32_t* map = nullptr; size_t map_cap = 0;
+    int32_t* idx = nullptr; int32_t* h_idx = nullptr; int idx_cap = 0; hipEvent_t ev_idx = nullptr; bool idx_pending = false;
+    void* batch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t batch_bytes[5] = {0, 0, 0, 0, 0};
+    hipEvent_t ev_batch = nullptr;
+  } ds;
   // gs_policy_mlp_set: the policy's packed weights and biases (one allocation), the actions of gs_policy_mlp_eval [B][A], and the
   // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
   // compute: GS_COMPUTE_*; with GS_COMPUTE_F32 `blob` holds the float32 image and the normalisation vectors, and args32 is the
@@ -234,5 +246,8 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
 // ---- owners of what gs_destroy does not free itself (abi_rollout.hip) ----
 void policy_release(gs_handle* h);
 void rollout_release(gs_handle* h, bool keep_term_count = false);
+
+// ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
+void dataset_release(gs_handle* h, bool keep_stats = false);
 
 }  // namespace gsi

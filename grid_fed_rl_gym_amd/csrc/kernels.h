@@ -49,6 +49,15 @@ __global__ void gs_k_fill_const_columns(double* __restrict__ out, long long rows
                                         const int32_t* __restrict__ map, const double* __restrict__ cst);
 __global__ void gs_k_policy_mlp(GsPolicyArgs P);
 __global__ void gs_k_policy_mlp_f32(GsPolicyArgsF32 P);
+__global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
+__global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
+                              const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);
+__global__ void gs_k_ds_map_fill(int32_t* __restrict__ map, long long n);
+__global__ void gs_k_ds_map_scatter(int32_t* __restrict__ map, const int32_t* __restrict__ term_count, const int32_t* __restrict__ term_idx,
+                                    int term_cap, int T, int B);
+__global__ void gs_k_ds_draw(int32_t* __restrict__ idx, int n, long long N, uint64_t seed, uint64_t draw);
+__global__ void gs_k_ds_gather_f64(GsDsGatherArgs G);
+__global__ void gs_k_ds_gather_f32(GsDsGatherArgs G);
 __global__ void gs_k_rollout_post(GsTables T, GsRows R, GsEnvCfg E, double* __restrict__ slab, GsRolloutPostArgs A);
 __global__ void gs_k_pack(const int32_t* __restrict__ src, const double* __restrict__ cst, int C, int rows_total,
                           const double* __restrict__ slab, double* __restrict__ out, int B);

@@ -7,6 +7,9 @@ fused step kernels back to back, each writing its observation block straight int
 ``[T + 1, B, obs_dim]`` device buffer, random actions drawn on the device, finished instances reset in
 place where the reference calls ``env.reset()`` (base.py:289-290) -- one host copy at the end, or none
 (``rollout_device``).  NumPy only -- the learner side (torch) is out of scope.
+
+``DeviceGridDataset`` is ``GridDataset`` where the collection lies: statistics reduced on the device, minibatches gathered and
+normalised there (``gs_dataset_*``, include/gridstep.h), nothing copied to the host but the statistics.
 """
 from __future__ import annotations
 
@@ -14,6 +17,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
+from .components import PowerFlowError
 from .env import BatchedGridEnvironment
 
 
@@ -108,3 +112,86 @@ class GridDataset:
 
     def denormalize_observation(self, obs: np.ndarray) -> np.ndarray:
         return obs * self.obs_std + self.obs_mean if hasattr(self, "obs_mean") else obs
+
+
+_M32 = 0xFFFFFFFF
+
+
+def _philox4x32(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 (Salmon et al. 2011) on uint64 arrays holding 32-bit words."""
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & _M32, p1 & _M32, ((p0 >> 32) ^ c3 ^ k1) & _M32, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+class DeviceGridDataset:
+    """``GridDataset`` over the environment's LAST rollout, on the device: the same attributes (``size``, ``obs_mean``, ``obs_std``,
+    ``action_mean``, ``action_std``, ``reward_mean``, ``reward_std``; the standard deviations include the reference's + 1e-6) and the
+    same ``sample_batch`` keys, the batches being ``DeviceArray`` views (``torch.as_tensor(b[k], device="cuda")``) of memory the handle
+    owns, valid until the next ``sample_batch``.  The statistics come from a fixed reduction tree: a column that never varies has
+    its value as mean and a raw standard deviation of exactly 0 (``constant_columns``), where ``np.std`` leaves ~1e-9 of noise.
+    After a further rollout on the environment: ``rebuild()`` (new statistics) or ``rebuild(keep_stats=True)`` (same normalisation,
+    new terminal map); until then sampling raises."""
+
+    def __init__(self, env: BatchedGridEnvironment, normalize: bool = True) -> None:
+        if not getattr(env.handle, "_rollout_T", 0):
+            raise PowerFlowError("DeviceGridDataset: the environment holds no rollout (rollout_device / collect_random_data first)")
+        self.env, self.normalize = env, bool(normalize)
+        self._draw = 0
+        self.rebuild()
+
+    def rebuild(self, keep_stats: bool = False) -> None:
+        """Build on the environment's last rollout.  ``keep_stats``: keep the normalisation (after a new rollout under a retrained
+        policy), build only the terminal map."""
+        h = self.env.handle
+        h.dataset_build(keep_stats=keep_stats)
+        st = h.dataset_stats()
+        self.size, self.rows_per_chunk = st["n"], st["rows_per_chunk"]
+        self.raw = st
+        self.constant_columns = st["obs_std"] == 0.0
+        self.obs_mean, self.obs_std = st["obs_mean"], st["obs_std"] + 1e-6
+        self.action_mean, self.action_std = st["act_mean"], st["act_std"] + 1e-6
+        self.reward_mean, self.reward_std = st["reward_mean"], st["reward_std"] + 1e-6
+
+    @property
+    def policy_obs_std(self) -> np.ndarray:
+        """``obs_std`` with 1.0 on ``constant_columns``: what ``MLPPolicy.from_sequential(obs_std=)`` should divide by (a column
+        that never varies carries no information; dividing it by 1e-6 only amplifies what a later rollout adds to it)."""
+        return np.where(self.constant_columns, 1.0, self.obs_std)
+
+    def set_stats(self, obs_mean, obs_std, action_mean, action_std, reward_mean, reward_std) -> None:
+        """Install RAW statistics (standard deviations without the + 1e-6) in place of the computed ones."""
+        self.env.handle.dataset_set_stats(obs_mean, obs_std, action_mean, action_std, reward_mean, reward_std)
+        self.rebuild(keep_stats=True)
+
+    @staticmethod
+    def indices_np(seed: int, draw: int, n: int, N: int) -> np.ndarray:
+        """The indices ``sample_batch(n, seed=seed)`` draws on the device in its call number ``draw`` (gs_dataset_sample): sample i =
+        word i & 3 of Philox-4x32 keyed by ``seed`` with counter (i >> 2, draw low word, draw high word, 'SMPL'), index =
+        (word * N) >> 32.  Pure NumPy, no device."""
+        seed, draw, n, N = int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, int(n), int(N)
+        if not 0 < N < 2 ** 31:
+            raise ValueError(f"indices_np: N = {N} outside (0, 2^31)")
+        q = np.arange((n + 3) // 4, dtype=np.uint64)
+        full = lambda v: np.full(q.shape, v, dtype=np.uint64)
+        w = _philox4x32(q, full(draw & _M32), full(draw >> 32), full(0x534D504C), seed & _M32, seed >> 32)
+        words = np.stack(w, axis=1).reshape(-1)[:n]
+        return ((words * np.uint64(N)) >> np.uint64(32)).astype(np.int64)
+
+    def sample_batch(self, batch_size: int, seed: int = 0, indices=None, dtype=np.float64, out=None, stream=None) -> Dict[str, object]:
+        """One minibatch, gathered and normalised by one kernel.  Without ``indices`` they are drawn on the device with replacement
+        (``indices_np(seed, k, batch_size, size)`` for the k-th such call on this dataset).  ``out``: the caller's device arrays
+        (torch tensors) per key; ``stream``: the consumer's stream handle (None: the call returns when the batch is complete)."""
+        draw = 0
+        if indices is None:
+            draw, self._draw = self._draw, self._draw + 1
+        return self.env.handle.dataset_sample(batch_size, indices=indices, seed=seed, draw=draw, dtype=dtype, normalize=self.normalize,
+                                              out=out, stream=stream)
+
+    def denormalize_action(self, action):
+        return action * self.action_std + self.action_mean if self.normalize else action
+
+    def denormalize_observation(self, obs):
+        return obs * self.obs_std + self.obs_mean if self.normalize else obs

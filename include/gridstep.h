@@ -398,6 +398,66 @@ typedef struct gs_policy_mlp_opts {
 int gs_policy_mlp_check_opts(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim, int32_t action_dim);
 int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_opts* o);
 
+/* ---- the device-resident dataset: statistics of the last rollout and normalised minibatches ----------------------------
+ * What the reference's GridDataset (algorithms/base.py:180-266) does on the host, done where gs_rollout left the collection:
+ * the per-column normalisation statistics over its N = T * B transitions (transition index = t * B + b), and minibatches
+ * gathered by index with the terminal observations put in their place.  Additive to ABI 2.
+ *
+ * gs_dataset_build (asynchronous, on the handle's stream, over the LAST rollout) computes per-column mean and population
+ * standard deviation (np.std, ddof 0) of obs_seq[0 .. T-1] and of actions, the scalar pair of rewards, and the [T][B] int32 map
+ * from a transition to its row of terminal_obs (-1: the transition ended no episode).  The reduction is a fixed tree (shifted
+ * sums per chunk of rows_per_chunk rows, Chan's pairwise merge above them): no atomics, the same rollout
+ * gives the same bits, and a column whose values are all equal comes out as that value and a standard deviation of exactly 0.
+ * flags: GS_DATASET_KEEP_STATS builds the map only and keeps the statistics the handle holds (GS_E_STATE if it holds none).
+ * GS_E_STATE without a rollout; GS_E_INVALID if N >= 2^31.  The handle remembers which rollout the dataset was built on: after a
+ * further gs_rollout, gs_dataset_stats and gs_dataset_sample return GS_E_STATE until gs_dataset_build has run again. */
+enum { GS_DATASET_KEEP_STATS = 1 };
+int gs_dataset_build(gs_handle* h, uint32_t flags);
+/* The statistics as host copies (waits for the build); any pointer may be NULL.  The standard deviations are the raw ones: the
+ * reference's + 1e-6 (base.py:207-224) is applied where values are normalised, x_n = (x - mean) / (std + 1e-6).
+ * gs_dataset_stats fills n, obs_dim, action_dim and rows_per_chunk (the rows one partial reduction covers).
+ * gs_dataset_set_stats installs the caller's statistics in place of the computed ones (a normalisation that stays fixed over
+ * several rollouts; the map still needs gs_dataset_build(GS_DATASET_KEEP_STATS) after every rollout).  It needs no build.  Rules
+ * (GS_E_INVALID, the handle unchanged): struct_size, obs_dim and action_dim match the handle; every pointer set (act_* may be
+ * NULL where action_dim = 0); every value finite, every standard deviation >= 0.  n and rows_per_chunk are ignored. */
+typedef struct gs_dataset_stats_view {
+  int32_t struct_size;            /* = sizeof(gs_dataset_stats_view) */
+  int32_t rows_per_chunk;
+  int64_t n;                      /* transitions the dataset was built on */
+  int32_t obs_dim, action_dim;
+  double* obs_mean;               /* [obs_dim] */
+  double* obs_std;                /* [obs_dim] */
+  double* act_mean;               /* [action_dim] */
+  double* act_std;                /* [action_dim] */
+  double* reward_mean;            /* [1] */
+  double* reward_std;             /* [1] */
+} gs_dataset_stats_view;
+int gs_dataset_stats(gs_handle* h, gs_dataset_stats_view* view);
+int gs_dataset_set_stats(gs_handle* h, const gs_dataset_stats_view* view);
+/* One minibatch of n transitions, gathered by ONE kernel into five row-major arrays of `dtype` (GS_COMPUTE_F64 / GS_COMPUTE_F32):
+ *   observations [n][obs_dim], actions [n][action_dim], rewards [n], next_observations [n][obs_dim], terminals [n]
+ * terminals = 1.0 where bit 0 or bit 1 of the done flag is set (the reference's terminals.astype(float)); next_observations =
+ * terminal_obs[map[t][b]] where the map is >= 0, obs_seq[t + 1][b] otherwise.  normalize != 0: exactly (x - mean) / (std + 1e-6),
+ * IEEE subtraction, addition and division in float64 (next_observations with the observation statistics, rewards with the scalar
+ * pair), rounded ONCE to float32 for GS_COMPUTE_F32; normalize == 0: the raw values.
+ * indices: host int64[n], any value outside [0, N) refusing the call (GS_E_INVALID) before anything is launched; or NULL: drawn
+ * on the device with replacement (the reference's rng.integers(0, size, batch_size)): sample i of call `draw` is word i & 3 of
+ * ONE Philox-4x32 call keyed by `seed` with counter (i >> 2, draw low word, draw high word, 'SMPL' = 0x534D504C), mapped by
+ * idx = (uint64(word) * N) >> 32.  (That mapping gives every index floor(2^32 / N) or ceil(2^32 / N) of the 2^32 words: its
+ * probability differs from 1 / N by less than 2^-32, a relative bias below N / 2^32 -- 1.2e-4 at N = 524 288.)
+ * out: each pointer is the caller's device memory or NULL; for NULL the handle supplies a buffer of its own and writes the address
+ * back, valid until the next gs_dataset_sample or gs_rollout on the handle.  consumer_stream: as gs_step_device_view (made to wait
+ * on the device for the batch; NULL: the call returns when the batch is complete).  GS_E_STATE without a current build. */
+typedef struct gs_dataset_batch {
+  void* observations;
+  void* actions;
+  void* rewards;
+  void* next_observations;
+  void* terminals;
+} gs_dataset_batch;
+int gs_dataset_sample(gs_handle* h, int32_t n, const int64_t* indices, uint64_t seed, uint64_t draw, int32_t dtype, int32_t normalize,
+                      gs_dataset_batch* out, void* consumer_stream);
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
