@@ -466,6 +466,19 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
     const int NW = row.nw, NI = row.ni, IW = row.iw, HV = 64 / IW;
     bool all_pq = true;
     for (int i = 0; i < ht.n; ++i) if (i != ht.slack && !(ht.th_free[i] && ht.vm_free[i])) all_pq = false;
+    // every bus needs a path to the slack over the lines the Ybus holds (an open zero-impedance line is none): the block of an
+    // islanded bus is exactly singular at the flat start, which the member's iteration 0 reads from a table without testing det
+    std::vector<char> seen(ht.n, 0);
+    {
+      std::vector<int> todo{ht.slack};
+      seen[ht.slack] = 1;
+      while (!todo.empty()) {
+        const int u = todo.back(); todo.pop_back();
+        for (int q = ht.row_ptr[u]; q < ht.row_ptr[u + 1]; ++q) if (!seen[ht.col[q]]) { seen[ht.col[q]] = 1; todo.push_back(ht.col[q]); }
+      }
+    }
+    const bool connected = std::find(seen.begin(), seen.end(), 0) == seen.end();
+    const bool want_w = !getenv("GS_NR_NO_FLAT") && ht.n <= 128;         // iteration 0 as a matrix product (below)
     MeshSchedule S;
     if (getenv("GS_NO_FLOW2") || getenv("GS_NO_MESH2")) why = "disabled by GS_NO_FLOW2 / GS_NO_MESH2";
     else if (cfg.jacobian_mode != GS_JACOBIAN_EXACT) why = "as-coded Jacobian";
@@ -473,6 +486,7 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
     else if (ht.fixed_v[ht.slack] == 0) why = "no typed slack bus";
     else if (max_dev > 2) why = "more than two devices of a kind at one bus";
     else if (ht.n < 2 || ht.m < 1) why = "trivial network";
+    else if (!connected) why = "island without a path to the slack";
     else {
       const int off_tile = (int)up16((size_t)nsl * (IW + 1) * 16);          // where f2_layout puts the region (below)
       // message units that leave room for a second workgroup on the CU: 80 KB less everything else the workgroup keeps in LDS
@@ -491,10 +505,14 @@ void plan_second_gen(const gs_topology& topo, const gs_config& cfg, const HostTo
       F.lds_bytes = (int32_t)off;
       if (off > 160 * 1024) why = "LDS tables do not fit";
     }
+    // A network the member would take, connected, whose flat-start Jacobian still does not invert on the host (up to 128 buses: the
+    // W product's map): refused rather than run on a flat-start table that no iteration checks.  Beyond 128 buses no map is built
+    // and the captured table is read at iteration 0 without a det test; there the connectivity rule above is the only guard.
+    if (why.empty() && want_w && !flat_newton_map(ht, 16, 32, p.mesh_w)) { why = "flat-start Jacobian is singular"; p.mesh_w.clear(); }
     if (why.empty()) {
       p.step = StepMember::nr_mesh2;
       // ---- iteration 0 as a matrix product (GsF2Tables::mesh_w): the flat-start Jacobian, inverted once on the host
-      if (!getenv("GS_NR_NO_FLAT") && ht.n <= 128 && flat_newton_map(ht, 16, 32, p.mesh_w)) { F.mesh_w_steps = 32; F.mesh_slack = ht.slack; }
+      if (want_w) { F.mesh_w_steps = 32; F.mesh_slack = ht.slack; }
       p.mesh_levels = S.n_levels; p.mesh_rows = S.n_rows; p.mesh_units = S.msg_units; p.mesh_messages = S.n_messages; p.mesh_accs = S.n_accumulators;
       F.n_jump = 0; F.n_levels = S.n_levels; F.pos_off = 0; F.n_anc_ints = (int32_t)S.adj_ent.size(); F.ring_zero = 0;
       F.mesh_nz = (int32_t)S.ytab.size(); F.mesh_pairs = S.n_pairs;

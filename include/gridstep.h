@@ -189,7 +189,9 @@ int gs_create(const gs_topology* topo, const gs_config* cfg, int32_t batch, int3
 void gs_destroy(gs_handle* h);
 int gs_dims(const gs_handle* h, int32_t* n, int32_t* m, int32_t* obs_dim, int32_t* action_dim,
             int32_t* state_dim, int32_t* batch);
-/* how the topology was compiled: linear solver chosen, tree depth, fill, waves per group */
+/* how the topology was compiled: linear solver chosen, tree depth, fill, waves per group; "flow2" / "mesh2": "on", or why the
+ * second-generation member does not take the handle (a network with a bus that has no path to the slack: "island without a path
+ * to the slack" -- it stays with a kernel that tests every pivot and reports GS_STATUS_SINGULAR) */
 int gs_describe(const gs_handle* h, char* buf, int32_t buflen);
 /* the same JSON for a handle that gs_create would build from these arguments on a device of `cus` compute units, planned on the
  * host alone (no device needed; the GS_* switches as for gs_create) */

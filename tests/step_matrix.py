@@ -124,11 +124,11 @@ def instance_feeder(fs, b, rx, pl):
     return f
 
 
-def oracle_steps(fs, solver, actions, rx, pl, seed0=100):
-    """Every instance on its own lines and loads, from seed seed0 + b at the load peak, through actions [T, B, A]:
-    ({b: [(obs, reward, terminated, truncated, info, tie) per step]}, dict(vm [T, B, n], loading [T, B, m], frequency [T, B]))
-    tie: the step's stopping measure came within TIE of the tolerance (test_gpu_step_limits.py's _oracle)."""
-    T, B = actions.shape[:2]
+def oracle_instance_steps(fs, f, solver, b, actions_b, seed0=100, require_converged=True, **cfg):
+    """Instance b on its own feeder f (instance_feeder) from seed seed0 + b at the load peak through actions_b [T, A]:
+    [(obs, reward, terminated, truncated, info, tie, |V| [n], loading [m], frequency) per step]
+    tie: the step's stopping measure came within TIE of the tolerance (test_gpu_step_limits.py's _oracle).  cfg: oracle_cfg's
+    overrides (max_iterations); require_converged=False leaves an unsolved step to the caller (tests/unsolved_cases.py)."""
     trace = []
     mismatch = O.mismatch
 
@@ -136,23 +136,35 @@ def oracle_steps(fs, solver, actions, rx, pl, seed0=100):
         out = mismatch(*a)
         trace.append(2.0 * (np.sum(np.abs(out[1])) + np.sum(np.abs(out[2]))) if solver == "fbs" else out[3])
         return out
-    ref = {}
-    state = dict(vm=np.empty((T, B, fs.n)), loading=np.empty((T, B, fs.m)), frequency=np.empty((T, B)))
+    steps = []
     O.mismatch = measure
     try:
-        for b in range(B):
-            spec = oracle_spec(instance_feeder(fs, b, rx, pl), **oracle_cfg(fs, solver))
-            _, st = O.env_reset(spec, seed=seed0 + b, instance=b)
-            st.time = T0
-            ref[b] = []
-            for t in range(T):
-                trace.clear()
-                o, rw, te, tr, inf = O.env_step(spec, st, actions[t, b])
+        spec = oracle_spec(f, **oracle_cfg(fs, solver, **cfg))
+        _, st = O.env_reset(spec, seed=seed0 + b, instance=b)
+        st.time = T0
+        for t in range(len(actions_b)):
+            trace.clear()
+            o, rw, te, tr, inf = O.env_step(spec, st, actions_b[t])
+            if require_converged:
                 assert inf["power_flow_converged"] and inf["min_voltage"] > 0.9, (b, t, inf["min_voltage"])
-                ref[b].append((o, rw, te, tr, inf, any(abs(q / TOL - 1.0) < TIE for q in trace)))
-                state["vm"][t, b] = st.Vm; state["loading"][t, b] = st.loading; state["frequency"][t, b] = st.freq
+            steps.append((o, rw, te, tr, inf, any(abs(q / TOL - 1.0) < TIE for q in trace), st.Vm.copy(), st.loading.copy(), float(st.freq)))
     finally:
         O.mismatch = mismatch
+    return steps
+
+
+def oracle_steps(fs, solver, actions, rx, pl, seed0=100):
+    """Every instance on its own lines and loads, from seed seed0 + b at the load peak, through actions [T, B, A]:
+    ({b: [(obs, reward, terminated, truncated, info, tie) per step]}, dict(vm [T, B, n], loading [T, B, m], frequency [T, B]))
+    tie: the step's stopping measure came within TIE of the tolerance (test_gpu_step_limits.py's _oracle)."""
+    T, B = actions.shape[:2]
+    ref = {}
+    state = dict(vm=np.empty((T, B, fs.n)), loading=np.empty((T, B, fs.m)), frequency=np.empty((T, B)))
+    for b in range(B):
+        steps = oracle_instance_steps(fs, instance_feeder(fs, b, rx, pl), solver, b, actions[:, b], seed0)
+        ref[b] = [s[:6] for s in steps]
+        for t, s in enumerate(steps):
+            state["vm"][t, b], state["loading"][t, b], state["frequency"][t, b] = s[6], s[7], s[8]
     return ref, state
 
 
