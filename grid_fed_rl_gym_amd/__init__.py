@@ -16,8 +16,9 @@ from .solver import (BatchedNewtonRaphsonSolver, NewtonRaphsonSolver, FastDecoup
                      BatchedForwardBackwardSweepSolver, BatchedRobustPowerFlowSolver, DistributionPowerFlow, parallel_power_flow_batch,
                      injections_from_dicts)
 from .env import BatchedGridEnvironment, VectorizedEnvironment, Box
-from .rollout import collect_random_data, collect_policy_data, rollout_device, GridDataset, DeviceGridDataset
-from .policy import MLPPolicy
+from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy_data, evaluate_rollout, gae_np, rollout_device, GridDataset,
+                      DeviceGridDataset)
+from .policy import MLPPolicy, MLPValue
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
 from .feeders import feeder_from_dict, feeder_to_dict, network_dict_normalized
@@ -28,7 +29,7 @@ __all__ = [
     "BatchedNewtonRaphsonSolver", "NewtonRaphsonSolver", "FastDecoupledSolver",
     "BatchedForwardBackwardSweepSolver", "BatchedRobustPowerFlowSolver", "DistributionPowerFlow", "parallel_power_flow_batch",
     "injections_from_dicts", "BatchedGridEnvironment", "VectorizedEnvironment", "Box",
-    "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "GridDataset", "DeviceGridDataset", "ShardedGridEnvironment", "LoopbackShards", "shard_range",
+    "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "MLPValue", "collect_onpolicy_data", "evaluate_rollout", "gae_np", "GridDataset", "DeviceGridDataset", "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",
     "BatchedSafetyChecker", "BatchedSafetyMonitor", "PostStepChecks", "device_quality_score",
     "UnbalancedPowerFlow", "UnbalancedFeederSpec", "UnbalancedSolution", "unbalanced_from_single_phase", "ieee8500_like",

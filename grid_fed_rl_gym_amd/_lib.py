@@ -97,6 +97,28 @@ class gs_policy_mlp_opts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("compute", C.c_int32), ("obs_shift", _dp), ("obs_scale", _dp)]
 
 
+GS_HEAD_LINEAR = 2          # gs_policy_mlp.head of a value network (gs_value_mlp_set)
+
+
+class gs_gae_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("bootstrap_mask", C.c_int32), ("gamma", C.c_double), ("lam", C.c_double),
+                ("reward_shift", C.c_double), ("reward_scale", C.c_double)]
+
+
+class gs_rollout_onpolicy(C.Structure):
+    _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("n_terminal", C.c_int32), ("rows_per_tile", C.c_int32),
+                ("log_probs", C.c_void_p), ("values", C.c_void_p), ("terminal_values", C.c_void_p), ("advantages", C.c_void_p),
+                ("returns", C.c_void_p)]
+
+
+class gs_rollout_onpolicy_host(C.Structure):
+    _fields_ = [("log_probs", _dp), ("values", _dp), ("terminal_values", _dp), ("advantages", _dp), ("returns", _dp)]
+
+
+ONPOLICY_KEYS = ("log_probs", "values", "terminal_values", "advantages", "returns")      # gs_rollout_onpolicy_host's fields, in order
+BOOTSTRAP = {"terminated": 1, "truncated": 2}      # bits of gs_gae_config.bootstrap_mask
+
+
 class gs_dataset_stats_view(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("rows_per_chunk", C.c_int32), ("n", C.c_int64), ("obs_dim", C.c_int32), ("action_dim", C.c_int32),
                 ("obs_mean", _dp), ("obs_std", _dp), ("act_mean", _dp), ("act_std", _dp), ("reward_mean", _dp), ("reward_std", _dp)]
@@ -180,6 +202,13 @@ SYMBOLS = [
     ("gs_policy_mlp_eval", C.c_int, [_H, C.c_uint64, C.c_int32, _dp]),
     ("gs_policy_mlp_check_opts", C.c_int, [C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts), C.c_int32, C.c_int32]),
     ("gs_policy_mlp_set_opts", C.c_int, [_H, C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts)]),
+    ("gs_rollout_set_log_probs", C.c_int, [_H, C.c_int32]),
+    ("gs_value_mlp_check", C.c_int, [C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts), C.c_int32]),
+    ("gs_value_mlp_set", C.c_int, [_H, C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts)]),
+    ("gs_value_mlp_eval", C.c_int, [_H, _dp]),
+    ("gs_rollout_evaluate", C.c_int, [_H, C.POINTER(gs_gae_config)]),
+    ("gs_rollout_onpolicy_view", C.c_int, [_H, C.POINTER(gs_rollout_onpolicy), C.c_void_p]),
+    ("gs_rollout_onpolicy_download", C.c_int, [_H, C.POINTER(gs_rollout_onpolicy_host)]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -423,12 +452,13 @@ def _topology_of(spec: FeederSpec, line_impedances=None, load_powers=None):
 
 def policy_struct(weights, biases, activation="relu", head="gaussian_tanh", stochastic=False, n_layers=None):
     """gs_policy_mlp of per-layer ``weights`` ([out, in], torch's Linear.weight layout) and ``biases`` and the arrays it points
-    into (keep them alive while the struct is in use).  ``n_layers`` overrides the count (the refusal tests pass 0 and 5)."""
+    into (keep them alive while the struct is in use).  ``n_layers`` overrides the count (the refusal tests pass 0 and 5); ``head`` may be a
+    raw GS_HEAD_* value (GS_HEAD_LINEAR: a value network)."""
     keep = {"w": [_f64(w) for w in weights], "b": [_f64(b) for b in biases]}
     p = gs_policy_mlp()
     p.struct_size = C.sizeof(gs_policy_mlp)
     p.n_layers = len(keep["w"]) if n_layers is None else int(n_layers)
-    p.activation, p.head, p.stochastic = ACTIVATION[activation], HEAD[head], int(bool(stochastic))
+    p.activation, p.head, p.stochastic = ACTIVATION[activation], HEAD[head] if isinstance(head, str) else int(head), int(bool(stochastic))
     for l, (w, b) in enumerate(zip(keep["w"][:GS_POLICY_MAX_LAYERS], keep["b"])):
         if w.ndim != 2 or b.shape != (w.shape[0],):
             raise ValueError(f"layer {l}: weights must be [out, in] and biases [out], got {w.shape} and {b.shape}")
@@ -465,6 +495,13 @@ def policy_check_opts(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim
     """gs_policy_mlp_check_opts: (return code, message) -- the rules of gs_policy_mlp and its options on the host alone."""
     lib = load()
     rc = lib.gs_policy_mlp_check_opts(C.byref(p), None if o is None else C.byref(o), int(obs_dim), int(action_dim))
+    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+
+
+def value_check(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int) -> Tuple[int, str]:
+    """gs_value_mlp_check: (return code, message) -- the rules of a value network on the host alone (no GPU)."""
+    lib = load()
+    rc = lib.gs_value_mlp_check(C.byref(p), None if o is None else C.byref(o), int(obs_dim))
     return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
 
 
@@ -966,6 +1003,58 @@ class Handle:
                             _ptr(out.get("final_observation"), _dp), C.pointer(n))
         self._check(self._lib.gs_rollout_download(self._h, C.byref(v)))
         out["n_terminal"] = int(n.value)
+        return out
+
+    # -- on-policy rollouts: log-probabilities, the value network, advantages and returns (include/gridstep.h) -------------------
+    def rollout_log_probs(self, on: bool = True) -> None:
+        """gs_rollout_set_log_probs: whether rollouts under a stochastic policy record the log-probabilities of their actions."""
+        self._check(self._lib.gs_rollout_set_log_probs(self._h, int(bool(on))))
+
+    def set_value(self, p: Optional[gs_policy_mlp], opts: Optional[gs_policy_mlp_opts] = None) -> None:
+        """gs_value_mlp_set: install (a copy of) the value network on the device; None removes it."""
+        self._check(self._lib.gs_value_mlp_set(self._h, None if p is None else C.byref(p), None if opts is None else C.byref(opts)))
+
+    def value_eval(self) -> np.ndarray:
+        """gs_value_mlp_eval: the value network's estimates [B] on the observation the environment stands at."""
+        v = np.empty(self.B)
+        self._check(self._lib.gs_value_mlp_eval(self._h, _ptr(v, _dp)))
+        return v
+
+    def rollout_evaluate(self, gamma: float = 0.99, lam: float = 0.95, bootstrap_mask: int = 0, reward_shift: float = 0.0,
+                         reward_scale: float = 1.0) -> None:
+        """gs_rollout_evaluate (asynchronous): values, terminal values, advantages and returns of the last rollout."""
+        cfg = gs_gae_config(C.sizeof(gs_gae_config), int(bootstrap_mask), float(gamma), float(lam), float(reward_shift), float(reward_scale))
+        self._check(self._lib.gs_rollout_evaluate(self._h, C.byref(cfg)))
+
+    def rollout_onpolicy_view(self, stream=None) -> gs_rollout_onpolicy:
+        """Device pointers of the last rollout's on-policy arrays (gs_rollout_onpolicy_view)."""
+        v = gs_rollout_onpolicy()
+        self._check(self._lib.gs_rollout_onpolicy_view(self._h, C.byref(v), _stream_arg(stream)))
+        return v
+
+    def rollout_onpolicy_arrays(self, stream=None) -> dict:
+        """The same as zero-copy ``DeviceArray`` views: ``log_probs`` [T, B] (None if the rollout recorded none), ``values`` [T + 1, B],
+        ``terminal_values`` [n_terminal], ``advantages`` and ``returns`` [T, B]; plus ``rows_per_tile``.  Valid until the next rollout."""
+        v = self.rollout_onpolicy_view(stream)
+        T, B, n = int(v.T), int(v.B), int(v.n_terminal)
+        return dict(log_probs=DeviceArray(v.log_probs, (T, B), "<f8") if v.log_probs else None, values=DeviceArray(v.values, (T + 1, B), "<f8"),
+                    terminal_values=DeviceArray(v.terminal_values, (n,), "<f8"), advantages=DeviceArray(v.advantages, (T, B), "<f8"),
+                    returns=DeviceArray(v.returns, (T, B), "<f8"), rows_per_tile=int(v.rows_per_tile))
+
+    def rollout_onpolicy_download(self, want=ONPOLICY_KEYS, n_terminal: Optional[int] = None) -> dict:
+        """Host copies (gs_rollout_onpolicy_download) of the arrays named in ``want``; ``terminal_values`` needs ``n_terminal`` (what
+        ``rollout_download`` reported) or asks for it."""
+        T, B = getattr(self, "_rollout_T", 0), self.B
+        out = {}
+        for k in want:
+            if k not in ONPOLICY_KEYS:
+                raise PowerFlowError(f"rollout_onpolicy_download: unknown array {k!r}")
+            if k == "terminal_values":
+                out[k] = np.empty(int(self.rollout_device_view().n_terminal if n_terminal is None else n_terminal))
+            else:
+                out[k] = np.empty((T + 1, B) if k == "values" else (T, B))
+        v = gs_rollout_onpolicy_host(*[_ptr(out.get(k), _dp) for k in ONPOLICY_KEYS])
+        self._check(self._lib.gs_rollout_onpolicy_download(self._h, C.byref(v)))
         return out
 
     def rollout_device_view(self) -> gs_rollout_device:

@@ -23,6 +23,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   gs_handle::Rollout& ro = h->ro;
   dev_free(ro.obs_seq); dev_free(ro.act); dev_free(ro.rew); dev_free(ro.done); dev_free(ro.term_idx); dev_free(ro.term_obs);
   if (!keep_term_count) dev_free(ro.term_count);
+  onpolicy_release(h);           // (sized by T as well)
   ro.T_cap = 0;
 }
 
@@ -58,8 +59,8 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
   if (!pol.act) HIPCHK(h, hipMalloc((void**)&pol.act, (size_t)h->B * h->action_dim * sizeof(double)));
   if (gs_policy_is_f32(o)) {
     const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
-    pol.lds32 = gs_pol32_lds_bytes(im.kb[0]);
-    HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, pol.lds32));
+    pol.lds32 = p->stochastic ? gs_pol32_lds_bytes(im.kb[0], h->action_dim) : gs_pol32_lds_bytes(im.kb[0]);
+    HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL32_LDS_MAX));
     // one allocation: the float image (a multiple of 16 floats), then shift and scale
     const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
     HIPCHK(h, hipMalloc((void**)&pol.blob, image_bytes + norm_bytes));
@@ -78,30 +79,32 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
     return GS_OK;
   }
   const GsPolicyImage im = gs_policy_pack(*p);
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL_LDS_BYTES));
+  pol.lds64 = p->stochastic ? gs_pol_lds_bytes(h->action_dim) : GS_POL_LDS_BYTES;
+  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL_LDS_MAX));
   HIPCHK(h, hipMalloc((void**)&pol.blob, im.blob.size() * sizeof(double)));
   HIPCHK(h, hipMemcpy(pol.blob, im.blob.data(), im.blob.size() * sizeof(double), hipMemcpyHostToDevice));
   GsPolicyArgs& a = pol.args;
   a = GsPolicyArgs{};
   a.B = h->B; a.D = h->obs_dim; a.A = h->action_dim; a.n_layers = p->n_layers; a.activation = p->activation; a.head = p->head;
-  a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance;
+  a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance; a.logp_behind = gs_pol_logp_behind(h->action_dim);
   for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayer{pol.blob + im.w_off[l], pol.blob + im.b_off[l], im.kb[l], im.nt[l]};
   pol.compute = GS_COMPUTE_F64;
   pol.set = true;
   return GS_OK;
 }
 
-// one launch: actions[B][A] of the installed policy on obs[B][obs_dim] (device pointers), on the handle's main stream
-static int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t) {
+// one launch: actions[B][A] of the installed policy on obs[B][obs_dim] (device pointers), on the handle's main stream; logp: NULL or
+// [B], the log-probabilities of the actions a stochastic policy samples
+static int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t, double* logp = nullptr) {
   const dim3 grid((unsigned)((h->B + GS_POL_ROWS - 1) / GS_POL_ROWS)), block(64 * GS_POL_WAVES);
   if (h->pol.compute == GS_COMPUTE_F32) {
     GsPolicyArgsF32 a = h->pol.args32;
-    a.obs = obs; a.act = act; a.seed = seed; a.t = t;
+    a.obs = obs; a.act = act; a.seed = seed; a.t = t; a.logp = logp;
     hipLaunchKernelGGL(gs_k_policy_mlp_f32, grid, block, h->pol.lds32, h->stream, a);
   } else {
     GsPolicyArgs a = h->pol.args;
-    a.obs = obs; a.act = act; a.seed = seed; a.t = t;
-    hipLaunchKernelGGL(gs_k_policy_mlp, grid, block, GS_POL_LDS_BYTES, h->stream, a);
+    a.obs = obs; a.act = act; a.seed = seed; a.t = t; a.logp = logp;
+    hipLaunchKernelGGL(gs_k_policy_mlp, grid, block, h->pol.lds64, h->stream, a);
   }
   HIPCHK(h, hipGetLastError());
   return GS_OK;
@@ -169,6 +172,10 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   gs_handle::Rollout& ro = h->ro;
   const size_t B = h->B, D = h->obs_dim, A = h->action_dim;
   ro.T = T; ro.n_term = -1;
+  // a stochastic policy's log-probabilities are recorded with its actions (on-policy rollouts, abi_onpolicy.hip)
+  const bool stochastic = policy == GS_POLICY_MLP && (h->pol.compute == GS_COMPUTE_F32 ? h->pol.args32.stochastic : h->pol.args.stochastic);
+  ro.logp_recorded = stochastic && ro.record_logp;
+  if (ro.logp_recorded && !ro.logp) HIPCHK(h, hipMalloc((void**)&ro.logp, (size_t)ro.T_cap * B * sizeof(double)));
   HIPCHK(h, hipMemsetAsync(ro.term_count, 0, sizeof(int32_t), h->stream));
   if (A > 0) {
     if (policy == GS_POLICY_UPLOADED) {
@@ -195,7 +202,8 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   const bool fused = h->second_gen() && policy != GS_POLICY_MLP;
   for (int t = 0; t < T; ++t) {
     double* nxt = ro.obs_seq + (size_t)(t + 1) * B * D;
-    if (policy == GS_POLICY_MLP && (rc = launch_policy(h, ro.obs_seq + (size_t)t * B * D, ro.act + (size_t)t * B * A, policy_seed, t))) return rc;
+    if (policy == GS_POLICY_MLP && (rc = launch_policy(h, ro.obs_seq + (size_t)t * B * D, ro.act + (size_t)t * B * A, policy_seed, t,
+                                                       ro.logp_recorded ? ro.logp + (size_t)t * B : nullptr))) return rc;
     GsRolloutStep rs{ro.rew, ro.done, ro.obs_seq + (size_t)t * B * D, h->map_obs, h->d_cst, ro.term_count, ro.term_idx, ro.term_obs, ro.term_cap, h->obs_dim, t, 1};
     if ((rc = step_kernels(h, ro.act + (size_t)t * B * A, nxt, fused ? &rs : nullptr))) return rc;
     if (!fused || t == T - 1) {
@@ -216,7 +224,9 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   return GS_OK;      // asynchronous: gs_synchronize / gs_rollout_download / gs_rollout_device_view wait for it
 }
 
-static int rollout_finish(gs_handle* h) {
+}  // extern "C"
+
+int gsi::rollout_finish(gs_handle* h) {
   gs_handle::Rollout& ro = h->ro;
   if (ro.T <= 0) return fail(h, GS_E_STATE, "no rollout has been collected on this handle");
   GS_ENTER(h);
@@ -229,6 +239,8 @@ static int rollout_finish(gs_handle* h) {
   }
   return GS_OK;
 }
+
+extern "C" {
 
 int gs_rollout_device_view(gs_handle* h, gs_rollout_device* out) {
   if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");

@@ -587,6 +587,7 @@ void gs_destroy(gs_handle* h) {
   for (void* p : h->allocs) (void)hipFree(p);
   dev_free(h->d_actions);
   policy_release(h);
+  value_release(h);
   rollout_release(h);
   dataset_release(h);
   if (h->h_pin) (void)hipHostFree(h->h_pin);

@@ -72,6 +72,11 @@ struct gs_handle : GsPlan {
     double* obs_seq = nullptr; double* act = nullptr; double* rew = nullptr; uint8_t* done = nullptr;
     int32_t* term_count = nullptr; int32_t* term_idx = nullptr; double* term_obs = nullptr;
     int32_t n_term = 0;
+    // on-policy data of the last rollout (abi_onpolicy.hip): logp [T][B] (recorded: by the last rollout); values [T + 1][B],
+    // term_values [term_cap], adv / ret [T][B], made by gs_rollout_evaluate; evaluated_on = `calls` of the rollout they belong to
+    bool record_logp = true, logp_recorded = false;
+    double* logp = nullptr; double* values = nullptr; double* term_values = nullptr; double* adv = nullptr; double* ret = nullptr;
+    uint64_t evaluated_on = 0; hipEvent_t ev_eval = nullptr;
   } ro;
   // gs_dataset_*: the dataset over the last rollout (abi_dataset.hip).  built_on = ro.calls of the rollout the map (and, unless
   // the statistics were installed or kept, the statistics) was built on, 0 = none; stats = mean[Ct] then std[Ct] at stride Cs
@@ -89,7 +94,10 @@ struct gs_handle : GsPlan {
   // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
   // compute: GS_COMPUTE_*; with GS_COMPUTE_F32 `blob` holds the float32 image and the normalisation vectors, and args32 is the
   // argument block of gs_k_policy_mlp_f32 (kernels_policy_f32.hip)
-  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0; } pol;
+  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0, lds64 = GS_POL_LDS_BYTES; } pol;
+  // gs_value_mlp_set: the value network's float32 image and normalisation vectors (one allocation), the values of
+  // gs_value_mlp_eval [B], and the argument block of gs_k_value_mlp_f32 with everything but obs / out / rows filled in
+  struct Value { bool set = false; float* blob = nullptr; double* out = nullptr; GsValueArgs args{}; int lds = 0; } val;
   double* d_cst = nullptr;
   int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
           *map_p = nullptr, *map_q = nullptr, *map_act = nullptr, *map_state = nullptr;
@@ -246,6 +254,11 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
 // ---- owners of what gs_destroy does not free itself (abi_rollout.hip) ----
 void policy_release(gs_handle* h);
 void rollout_release(gs_handle* h, bool keep_term_count = false);
+int rollout_finish(gs_handle* h);      // waits for the last rollout's number of finished episodes (ro.n_term); GS_E_STATE without one
+
+// ---- owner of the value network and of the rollout's on-policy arrays (abi_onpolicy.hip) ----
+void value_release(gs_handle* h);
+void onpolicy_release(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);

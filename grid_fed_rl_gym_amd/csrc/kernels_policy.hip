@@ -14,12 +14,14 @@
 //     current two are issued (one wavefront per SIMD: nothing else hides the load latency).
 // Between layers all four wavefronts meet at a barrier, add the bias, apply the activation and write their columns to LDS; padded
 // columns come out as act(0) = 0 (zero weights and bias), which is what the next layer's padded k range expects.  The head reads
-// the last layer's rows from LDS, one thread per (instance, action).
+// the last layer's rows from LDS, one thread per (instance, action); for a sampling policy with P.logp set it also files the
+// action's log-probability term in LDS, and one thread per instance adds them in action order (policy_head.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "env_device.h"
 #include "policy.h"
+#include "policy_head.h"
 
 typedef double gp_v4 __attribute__((ext_vector_type(4)));
 typedef double gp_v2 __attribute__((ext_vector_type(2)));
@@ -159,15 +161,25 @@ gs_k_policy_mlp(GsPolicyArgs P) {
     }
     __syncthreads();
   }
-  // head: a = tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) eps)
+  // head: a = tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) eps); with P.logp the sampled action's log-probability term
+  // as well, into LDS: columns 2 A .. 3 A - 1 of the row where the tile has them, behind the tile otherwise (P.logp_behind)
+  const bool sample = P.head == GS_HEAD_GAUSSIAN_TANH && P.stochastic;
+  double* const terms = P.logp_behind ? gp_lds + GS_POL_ROWS * GS_POL_LDS_STRIDE : gp_lds + 2 * P.A;
+  const int tstride = P.logp_behind ? P.A : GS_POL_LDS_STRIDE;
   for (int idx = threadIdx.x; idx < GS_POL_ROWS * P.A; idx += blockDim.x) {
     const int r = idx / P.A, a = idx - r * P.A, b = row0 + r;
     if (b >= P.B) break;
     double x = gp_lds[r * GS_POL_LDS_STRIDE + a];
-    if (P.head == GS_HEAD_GAUSSIAN_TANH && P.stochastic) {
+    if (sample) {
       const double ls = fmin(fmax(gp_lds[r * GS_POL_LDS_STRIDE + P.A + a], -20.0), 2.0);
-      x += exp(ls) * gp_noise(P.seed, (uint64_t)(P.first_instance + b), (uint32_t)P.t, (uint32_t)(a >> 2), a & 3);
+      const double eps = gp_noise(P.seed, (uint64_t)(P.first_instance + b), (uint32_t)P.t, (uint32_t)(a >> 2), a & 3);
+      x += exp(ls) * eps;
+      const double act = tanh(x);
+      P.act[(size_t)b * P.A + a] = act;
+      if (P.logp) terms[r * tstride + a] = gs_logp_term(eps, ls, act);
+    } else {
+      P.act[(size_t)b * P.A + a] = tanh(x);
     }
-    P.act[(size_t)b * P.A + a] = tanh(x);
   }
+  if (sample && P.logp) gs_logp_rows<GS_POL_ROWS>(terms, tstride, P.A, row0, P.B, P.logp);
 }

@@ -17,93 +17,20 @@
 // runs at a quarter of the float32 rate -- four times, in the one loop that has to keep the matrix pipe fed.  An observation wider
 // than GS_POL32_PANEL_KB blocks is staged in several panels behind one another, the accumulators carried across.
 // Padded columns: zero weights and bias give act(0) = 0, and shift = scale = 0 beyond obs_dim give z = 0.
+// The stage, the operand loads and the product loop live in mlp_f32.h, templated on the row tiles, where the value kernel
+// (kernels_value.hip) shares them.  A sampling head with P.logp set also files the actions' log-probability terms in the
+// observation tile's LDS, and one thread per instance adds them in action order (policy_head.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "env_device.h"
+#include "mlp_f32.h"
 #include "policy.h"
-
-typedef float gq_v4 __attribute__((ext_vector_type(4)));
-typedef float gq_v2 __attribute__((ext_vector_type(2)));
-typedef double gq_d2 __attribute__((ext_vector_type(2)));
+#include "policy_head.h"
 
 namespace {
 
 constexpr int GQ_RT = GS_POL_ROWS / 16;      // row tiles per workgroup
-constexpr int GQ_CT = 4;                     // column tiles per wavefront
-constexpr int GQ_STAGE_ROWS = GS_POL_ROWS / GS_POL_WAVES;      // rows a wavefront normalises
-static_assert(GQ_CT * GS_POL_WAVES * 16 >= GS_POL_MAX_WIDTH, "every column tile of the widest layer has a wavefront");
-
-// z = (obs - shift) * scale, float64, rounded once; columns [16 kb0, 16 kb1) of the workgroup's rows into `tile` (row stride
-// P.obs_stride).  Wavefront w takes rows 8 w .. 8 w + 7 (rows clamped to the batch), a lane two adjacent columns.
-template <bool EVEN>
-__device__ __forceinline__ void gq_stage(const GsPolicyArgsF32& P, float* tile, int row0, int kb0, int kb1, int wave, int lane) {
-  const double* src[GQ_STAGE_ROWS];
-#pragma unroll
-  for (int r = 0; r < GQ_STAGE_ROWS; ++r) src[r] = P.obs + (size_t)min(row0 + GQ_STAGE_ROWS * wave + r, P.B - 1) * P.D;
-  const int D = P.D, width = 16 * (kb1 - kb0);
-  for (int c = 2 * lane; c < width; c += 128) {
-    const int k = 16 * kb0 + c;            // even, and below the padded width of shift / scale
-    const gq_d2 sh = *(const gq_d2*)(P.shift + k), sc = *(const gq_d2*)(P.scale + k);
-    gq_d2 v[GQ_STAGE_ROWS];
-#pragma unroll
-    for (int r = 0; r < GQ_STAGE_ROWS; ++r) {
-      if (EVEN) {      // D even: k < D means k + 1 < D, and the address is 16-byte aligned
-        v[r] = *(const gq_d2*)(src[r] + min(k, D - 2));
-      } else {
-        v[r] = gq_d2{src[r][min(k, D - 1)], src[r][min(k + 1, D - 1)]};
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < GQ_STAGE_ROWS; ++r) {
-      const double a = k < D ? v[r][0] : 0.0, b = k + 1 < D ? v[r][1] : 0.0;
-      *(gq_v2*)(tile + (GQ_STAGE_ROWS * wave + r) * P.obs_stride + c) = gq_v2{(float)((a - sh[0]) * sc[0]), (float)((b - sh[1]) * sc[1])};
-    }
-  }
-}
-
-struct GqFrag { gq_v4 x[GQ_RT], w[GQ_CT]; };
-
-// in[rt]: this lane's operand of block `kbase` (row 16 rt + (lane & 15), columns 4 (lane >> 4) ..) in LDS
-template <bool FULL>
-__device__ __forceinline__ void gq_load(GqFrag& f, const float* const (&in)[GQ_RT], int kbase, const float* __restrict__ wl, int kb_total, int kb, int nt,
-                                        int wave, int lane) {
-#pragma unroll
-  for (int rt = 0; rt < GQ_RT; ++rt) f.x[rt] = *(const gq_v4*)(in[rt] + 16 * (kb - kbase));
-#pragma unroll
-  for (int c = 0; c < GQ_CT; ++c) {
-    const int tile = wave + GS_POL_WAVES * c;
-    if (FULL || tile < nt) f.w[c] = *(const gq_v4*)(wl + (((size_t)tile * kb_total + kb) * 64 + lane) * 4);
-  }
-}
-
-// acc[rt][c] += in[rows of tile rt][16 kb0 .. 16 kb1) W[columns of tile wave + 4 c][the same]^T
-// FULL: the layer has all sixteen column tiles, so every wavefront has its four (no predicates in the loop)
-template <bool FULL>
-__device__ __forceinline__ void gq_layer(gq_v4 (&acc)[GQ_RT][GQ_CT], const float* const (&in)[GQ_RT], const GsPolicyLayerF32& L, int kb0, int kb1,
-                                         int wave, int lane) {
-  if (!FULL && wave >= L.nt) return;         // (a narrow layer: this wavefront has no column tile)
-  GqFrag cur, nxt;
-  gq_load<FULL>(cur, in, kb0, L.w, L.kb, kb0, L.nt, wave, lane);
-  for (int kb = kb0; kb < kb1; ++kb) {
-    if (kb + 1 < kb1) gq_load<FULL>(nxt, in, kb0, L.w, L.kb, kb + 1, L.nt, wave, lane);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int c = 0; c < GQ_CT; ++c) {
-        if (!FULL && wave + GS_POL_WAVES * c >= L.nt) continue;
-#pragma unroll
-        for (int rt = 0; rt < GQ_RT; ++rt) acc[rt][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.x[rt][j], cur.w[c][j], acc[rt][c], 0, 0, 0);
-      }
-    cur = nxt;
-  }
-}
-
-__device__ __forceinline__ float gq_activation(float x, int kind) {
-  if (kind == GS_ACT_RELU) return x > 0.0f ? x : 0.0f;
-  if (kind == GS_ACT_TANH) return tanhf(x);
-  return x > 0.0f ? x : expm1f(x);           // elu, alpha = 1
-}
 
 // component `comp` of the four normals of env_device.h's rng_normal_quad recipe, tag 'PNOI' (the float64 kernel's gp_noise, word
 // for word: the stochastic contract of gs_policy_mlp is one contract)
@@ -141,17 +68,17 @@ gs_k_policy_mlp_f32(GsPolicyArgsF32 P) {
       for (int kb0 = 0; kb0 < L.kb; kb0 += GS_POL32_PANEL_KB) {
         const int kb1 = min(kb0 + GS_POL32_PANEL_KB, L.kb);
         if (kb0) __syncthreads();            // every wavefront has read the previous panel
-        if (P.D & 1) gq_stage<false>(P, obs_lds, row0, kb0, kb1, wave, lane);
-        else gq_stage<true>(P, obs_lds, row0, kb0, kb1, wave, lane);
+        if (P.D & 1) gq_stage<GS_POL_ROWS, false>(P.obs, P.shift, P.scale, P.D, P.B, P.obs_stride, obs_lds, row0, kb0, kb1, wave, lane);
+        else gq_stage<GS_POL_ROWS, true>(P.obs, P.shift, P.scale, P.D, P.B, P.obs_stride, obs_lds, row0, kb0, kb1, wave, lane);
         __syncthreads();
-        if (full) gq_layer<true>(acc, in, L, kb0, kb1, wave, lane);
-        else gq_layer<false>(acc, in, L, kb0, kb1, wave, lane);
+        if (full) gq_layer<GQ_RT, true>(acc, in, L, kb0, kb1, wave, lane);
+        else gq_layer<GQ_RT, false>(acc, in, L, kb0, kb1, wave, lane);
       }
     } else {
 #pragma unroll
       for (int rt = 0; rt < GQ_RT; ++rt) in[rt] = act_lds + (16 * rt + (lane & 15)) * GS_POL32_ACT_STRIDE + 4 * (lane >> 4);
-      if (full) gq_layer<true>(acc, in, L, 0, L.kb, wave, lane);
-      else gq_layer<false>(acc, in, L, 0, L.kb, wave, lane);
+      if (full) gq_layer<GQ_RT, true>(acc, in, L, 0, L.kb, wave, lane);
+      else gq_layer<GQ_RT, false>(acc, in, L, 0, L.kb, wave, lane);
     }
     __syncthreads();                         // every wavefront has read the previous activations
     const bool last = l == P.n_layers - 1;
@@ -171,15 +98,24 @@ gs_k_policy_mlp_f32(GsPolicyArgsF32 P) {
     }
     __syncthreads();
   }
-  // head, in float64 on the float32 pre-head values: a = tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) eps)
+  // head, in float64 on the float32 pre-head values: a = tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) eps); with P.logp
+  // the sampled action's log-probability term as well, into the observation tile's LDS (no wavefront reads that any more)
+  const bool sample = P.head == GS_HEAD_GAUSSIAN_TANH && P.stochastic;
+  double* const terms = (double*)obs_lds;                                  // [GS_POL_ROWS][P.A]
   for (int idx = threadIdx.x; idx < GS_POL_ROWS * P.A; idx += blockDim.x) {
     const int r = idx / P.A, a = idx - r * P.A, b = row0 + r;
     if (b >= P.B) break;
     double x = (double)act_lds[r * GS_POL32_ACT_STRIDE + a];
-    if (P.head == GS_HEAD_GAUSSIAN_TANH && P.stochastic) {
+    if (sample) {
       const double ls = fmin(fmax((double)act_lds[r * GS_POL32_ACT_STRIDE + P.A + a], -20.0), 2.0);
-      x += exp(ls) * gq_noise(P.seed, (uint64_t)(P.first_instance + b), (uint32_t)P.t, (uint32_t)(a >> 2), a & 3);
+      const double eps = gq_noise(P.seed, (uint64_t)(P.first_instance + b), (uint32_t)P.t, (uint32_t)(a >> 2), a & 3);
+      x += exp(ls) * eps;
+      const double act = tanh(x);
+      P.act[(size_t)b * P.A + a] = act;
+      if (P.logp) terms[idx] = gs_logp_term(eps, ls, act);
+    } else {
+      P.act[(size_t)b * P.A + a] = tanh(x);
     }
-    P.act[(size_t)b * P.A + a] = tanh(x);
   }
+  if (sample && P.logp) gs_logp_rows<GS_POL_ROWS>(terms, P.A, P.A, row0, P.B, P.logp);
 }

@@ -63,6 +63,20 @@ std::string gs_policy_check_opts(const gs_policy_mlp* p, const gs_policy_mlp_opt
   return "";
 }
 
+std::string gs_value_check(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim) {
+  if (!p) return "value network is NULL";
+  if (p->struct_size != (int32_t)sizeof(gs_policy_mlp)) return fmt("gs_policy_mlp struct_size %d != %d", p->struct_size, (int)sizeof(gs_policy_mlp));
+  if (p->head != GS_HEAD_LINEAR) return fmt("a value network needs head GS_HEAD_LINEAR (have %d)", p->head);
+  if (p->stochastic != 0) return fmt("a value network is not stochastic (have %d)", p->stochastic);
+  if (p->n_layers < 1 || p->n_layers > GS_POLICY_MAX_LAYERS) return fmt("n_layers %d outside 1 .. %d", p->n_layers, GS_POLICY_MAX_LAYERS);
+  if (p->dims[p->n_layers] != 1) return fmt("a value network's last width must be 1 (have %d)", p->dims[p->n_layers]);
+  if (!o || o->compute != GS_COMPUTE_F32) return "a value network needs gs_policy_mlp_opts with compute = GS_COMPUTE_F32 (the precision of torch critics)";
+  // every other rule is the policy's: a plain head of one output
+  gs_policy_mlp q = *p;
+  q.head = GS_HEAD_TANH;
+  return gs_policy_check_opts(&q, o, obs_dim, 1);
+}
+
 GsPolicyImageF32 gs_policy_pack_f32(const gs_policy_mlp& p, const gs_policy_mlp_opts& o) {
   GsPolicyImageF32 im;
   size_t total = 0;

@@ -306,6 +306,22 @@ class BatchedGridEnvironment:
             raise RuntimeError("reset() before policy_actions()")
         return self._h.policy_eval(seed, t)
 
+    def set_value(self, value: Optional[Any]) -> None:
+        """Install an ``MLPValue`` on the device (gs_value_mlp_set) for ``value_estimates`` and ``evaluate_rollout``; None removes
+        it.  Like the policy it is not environment state."""
+        if value is None:
+            self._h.set_value(None)
+            return
+        p, keep = value.to_struct()
+        opts, keep_opts = value.to_opts()
+        self._h.set_value(p, opts)          # (raises, and leaves the installed network in place, if the library refuses it)
+
+    def value_estimates(self) -> np.ndarray:
+        """The installed value network's estimates [num_envs] on the observation the environment stands at (gs_value_mlp_eval)."""
+        if self._needs_reset:
+            raise RuntimeError("reset() before value_estimates()")
+        return self._h.value_eval()
+
     @property
     def handle(self) -> "_lib.Handle":
         return self._h

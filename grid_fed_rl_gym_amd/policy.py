@@ -12,6 +12,8 @@ float64.  "float32" is the precision of the reference's torch actors: the normal
 ``z = (obs - mean) * (1 / std)`` in float64 on the raw observation and ONE rounding to float32 (a raw 1e5-watt column rounded to
 float32 first loses 2.4e-3 W, which a folded weight multiplies and the layer sums over every such column); weights, biases,
 products, sums and hidden activations are float32; the head is evaluated in float64 on the float32 pre-head values.
+
+``MLPValue`` is a critic for ``env.set_value`` / ``evaluate_rollout``: the same layers with a scalar output, on the float32 path.
 """
 from __future__ import annotations
 
@@ -173,3 +175,80 @@ class MLPPolicy:
         if eps is None:
             return np.tanh(mean)
         return np.tanh(mean + np.exp(np.clip(log_std, LOG_STD_MIN, LOG_STD_MAX)) * np.asarray(eps, dtype=np.float64))
+
+    def log_prob_np(self, obs: Any, eps: Any, compute: Optional[str] = None, exact: bool = False) -> np.ndarray:
+        """The log-probability [...] of the action ``forward_np(obs, eps)`` samples, as the device records it with the action
+        (``log_probs`` of a stochastic rollout; include/gridstep.h): per action
+        ``-0.5 eps^2 - log_std - 0.5 log(2 pi) - log((1 - a^2) + 1e-6)``, ``log_std`` clamped, summed in action order from
+        action 0.  That is the reference's ``Normal(mean, std).log_prob(x)`` minus its tanh correction
+        (algorithms/offline.py:114-136), with ``(x - mean)^2 / (2 std^2)`` written as ``eps^2 / 2``.  Gaussian head only."""
+        if self.head != "gaussian_tanh":
+            raise ValueError("log_prob_np needs the Gaussian head")
+        out = self.pre_head_np(obs, compute, exact).astype(np.float64)
+        a = self.action_dim
+        eps = np.asarray(eps, dtype=np.float64)
+        ls = np.clip(out[..., a:], LOG_STD_MIN, LOG_STD_MAX)
+        act = np.tanh(out[..., :a] + np.exp(ls) * eps)
+        terms = (((-0.5 * eps) * eps - ls) - HALF_LOG_2PI) - np.log((1.0 - act * act) + 1e-6)
+        total = terms[..., 0].copy()
+        for k in range(1, a):
+            total += terms[..., k]
+        return total
+
+
+HALF_LOG_2PI = 0.9189385332046727      # 0.5 * log(2 pi)
+
+
+class MLPValue:
+    """A value network (critic) for ``env.set_value`` / ``evaluate_rollout``: the reference's ``_build_mlp`` with a scalar output
+    (IQL's and AWR's value functions).  ``weights`` / ``biases`` as for ``MLPPolicy``, the last layer of width 1; ``obs_mean`` /
+    ``obs_std``: the observation normalisation.  The device evaluates it at the precision of torch critics -- the float32 path of
+    ``MLPPolicy``: normalisation in float64 rounded once, float32 layers -- and returns the scalar widened to float64."""
+
+    def __init__(self, weights: Sequence[Any], biases: Sequence[Any], activation: str = "relu", obs_mean: Optional[Any] = None,
+                 obs_std: Optional[Any] = None) -> None:
+        self._net = MLPPolicy(weights, biases, activation=activation, head="tanh", obs_mean=obs_mean, obs_std=obs_std, compute="float32")
+        if self._net.weights[-1].shape[0] != 1:
+            raise ValueError(f"a value network's last layer has one output, got {self._net.weights[-1].shape[0]}")
+        self.activation = activation
+
+    @property
+    def obs_dim(self) -> int:
+        return self._net.obs_dim
+
+    @property
+    def obs_mean(self) -> Optional[np.ndarray]:
+        return self._net.obs_mean
+
+    @property
+    def obs_std(self) -> Optional[np.ndarray]:
+        return self._net.obs_std
+
+    @property
+    def weights(self) -> List[np.ndarray]:
+        """The layers as given (the first one unfolded: the normalisation is a stage of its own)."""
+        return [self._net.weight0] + self._net.weights[1:]
+
+    @property
+    def biases(self) -> List[np.ndarray]:
+        return [self._net.bias0] + self._net.biases[1:]
+
+    @classmethod
+    def from_sequential(cls, module: Any, obs_mean: Optional[Any] = None, obs_std: Optional[Any] = None) -> "MLPValue":
+        """From a torch ``nn.Sequential`` of ``Linear`` and activation modules, read as ``MLPPolicy.from_sequential`` reads it."""
+        net = MLPPolicy.from_sequential(module, head="tanh", compute="float32")
+        return cls([net.weight0] + net.weights[1:], [net.bias0] + net.biases[1:], activation=net.activation, obs_mean=obs_mean, obs_std=obs_std)
+
+    def to_struct(self):
+        """(gs_policy_mlp with head GS_HEAD_LINEAR, the arrays it points into)"""
+        return _lib.policy_struct(self.weights, self.biases, self.activation, _lib.GS_HEAD_LINEAR, False)
+
+    def to_opts(self):
+        """(gs_policy_mlp_opts with GS_COMPUTE_F32 and the normalisation, the arrays it points into)"""
+        return self._net.to_opts()
+
+    def forward_np(self, obs: Any, exact: bool = False) -> np.ndarray:
+        """Values [...] on raw observations [..., obs_dim], float64: the device contract (float32-rounded weights, biases and
+        normalised observations, float32 products, sums and activations); with ``exact`` the same rounded operands evaluated
+        in float64 throughout (what the float32 result is measured against)."""
+        return self._net.pre_head_np(obs, "float32", exact).astype(np.float64)[..., 0]

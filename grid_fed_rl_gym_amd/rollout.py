@@ -10,13 +10,19 @@ place where the reference calls ``env.reset()`` (base.py:289-290) -- one host co
 
 ``DeviceGridDataset`` is ``GridDataset`` where the collection lies: statistics reduced on the device, minibatches gathered and
 normalised there (``gs_dataset_*``, include/gridstep.h), nothing copied to the host but the statistics.
+
+``evaluate_rollout`` / ``collect_onpolicy_data`` add what a policy-gradient learner needs from a stochastic rollout -- the
+log-probabilities the policy kernels recorded, a value network's estimates over every row, advantages and returns
+(``gs_rollout_evaluate``); ``gae_np`` restates the device's recurrence.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from types import SimpleNamespace
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from . import _lib
 from .components import PowerFlowError
 from .env import BatchedGridEnvironment
 
@@ -68,6 +74,77 @@ def rollout_device(env: BatchedGridEnvironment, num_steps: int, seed: int = 0, a
     else:
         env.handle.rollout(int(num_steps), "uploaded", actions=np.asarray(actions, dtype=np.float64))
     return env.handle.rollout_device_view()
+
+
+def gae_np(rewards, values, terminals, terminal_values, terminal_index, gamma: float = 0.99, lam: float = 0.95, bootstrap_mask: int = 0,
+           reward_shift: float = 0.0, reward_scale: float = 1.0):
+    """(advantages, returns), [T, B] each: the recurrence of ``gs_rollout_evaluate`` (include/gridstep.h) restated in NumPy, every
+    operation IEEE float64 in the device's order.  ``rewards`` [T, B], ``values`` [T + 1, B], ``terminals`` [T, B] uint8 done flags
+    (bit 0 terminated, bit 1 truncated), ``terminal_values`` [n] the values of the terminal observations of the transitions
+    ``terminal_index`` [n, 2] (t, b).  ``bootstrap_mask``: the flag bits whose episode end bootstraps from its terminal value
+    (0: none, the reference's ``1 - terminals``).  The tail of an unfinished episode bootstraps from ``values[T]``."""
+    rewards, values = np.asarray(rewards, dtype=np.float64), np.asarray(values, dtype=np.float64)
+    terminals = np.asarray(terminals).astype(np.uint8)
+    T, B = rewards.shape
+    term_v = np.zeros((T, B))
+    idx = np.asarray(terminal_index, dtype=np.int64).reshape(-1, 2)
+    term_v[idx[:, 0], idx[:, 1]] = np.asarray(terminal_values, dtype=np.float64)[:len(idx)]
+    gamma, lam, mask = float(gamma), float(lam), int(bootstrap_mask)
+    gl = gamma * lam
+    adv, ret = np.empty((T, B)), np.empty((T, B))
+    adv_next = np.zeros(B)
+    for t in range(T - 1, -1, -1):
+        done = terminals[t] != 0
+        vnext = np.where(done, np.where((terminals[t] & mask) != 0, term_v[t], 0.0), values[t + 1])
+        r = (rewards[t] - float(reward_shift)) * float(reward_scale)
+        delta = (r + gamma * vnext) - values[t]
+        adv[t] = np.where(done, delta, delta + gl * adv_next)
+        ret[t] = adv[t] + values[t]
+        adv_next = adv[t]
+    return adv, ret
+
+
+def _bootstrap_mask(bootstrap) -> int:
+    if isinstance(bootstrap, (int, np.integer)):
+        return int(bootstrap)
+    names = {bootstrap} if isinstance(bootstrap, str) else set(bootstrap)
+    unknown = names - set(_lib.BOOTSTRAP)
+    if unknown:
+        raise ValueError(f"bootstrap: unknown episode end(s) {sorted(unknown)}; any of {sorted(_lib.BOOTSTRAP)}, or the raw mask")
+    return sum(_lib.BOOTSTRAP[k] for k in names)
+
+
+def evaluate_rollout(env: BatchedGridEnvironment, gamma: float = 0.99, lam: float = 0.95, bootstrap: Sequence[str] = (),
+                     reward_shift: float = 0.0, reward_scale: float = 1.0, stream=None):
+    """Values, advantages and returns of the environment's LAST rollout, computed on the device by the value network
+    ``env.set_value`` installed (``gs_rollout_evaluate``: one pass of the critic over ``obs_seq`` and the terminal observations, one
+    GAE kernel).  ``bootstrap``: which episode ends bootstrap from the value of their terminal observation -- any of "terminated"
+    (here: the time limit) and "truncated", or the raw mask; () is the reference's ``1 - terminals``.  Returns an object with
+    ``log_probs`` [T, B] (None unless the rollout was stochastic), ``values`` [T + 1, B], ``terminal_values`` [n_terminal],
+    ``advantages`` and ``returns`` [T, B] as zero-copy ``DeviceArray`` views (``torch.as_tensor(x, device="cuda")``), valid until
+    the next rollout, and ``rows_per_tile``.  ``stream``: the consumer's stream handle (None: the call returns when all is there)."""
+    h = env.handle
+    h.rollout_evaluate(gamma, lam, _bootstrap_mask(bootstrap), reward_shift, reward_scale)
+    return SimpleNamespace(**h.rollout_onpolicy_arrays(stream))
+
+
+def collect_onpolicy_data(env: BatchedGridEnvironment, policy, value, num_steps: int, seed: int = 0, reset: bool = True,
+                          gamma: float = 0.99, lam: float = 0.95, bootstrap: Sequence[str] = (), reward_shift: float = 0.0,
+                          reward_scale: float = 1.0) -> Dict[str, np.ndarray]:
+    """``collect_policy_data`` under the STOCHASTIC ``policy`` plus what a policy-gradient update needs, as host arrays in the
+    same transition order (index = t * B + b): ``log_probs``, ``values`` (of ``observations``), ``advantages`` and ``returns``
+    under the value network ``value`` (an ``MLPValue``), all computed on the device."""
+    rollout_device(env, num_steps, seed=seed, reset=reset, policy=policy, stochastic=True)
+    env.set_value(value)
+    env.handle.rollout_evaluate(gamma, lam, _bootstrap_mask(bootstrap), reward_shift, reward_scale)
+    d = env.handle.rollout_download()
+    T, B = int(num_steps), env.num_envs
+    out = {k: d[k].reshape((T * B,) + d[k].shape[2:]) for k in ("observations", "actions", "rewards", "next_observations")}
+    out["terminals"] = d["terminals"].reshape(T * B) != 0
+    o = env.handle.rollout_onpolicy_download(("log_probs", "values", "advantages", "returns"))
+    out["log_probs"], out["values"] = o["log_probs"].reshape(T * B), o["values"][:T].reshape(T * B)
+    out["advantages"], out["returns"] = o["advantages"].reshape(T * B), o["returns"].reshape(T * B)
+    return out
 
 
 class GridDataset:

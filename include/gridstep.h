@@ -400,6 +400,72 @@ typedef struct gs_policy_mlp_opts {
 int gs_policy_mlp_check_opts(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim, int32_t action_dim);
 int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_opts* o);
 
+/* ---- on-policy rollouts: log-probabilities, a value network, advantages and returns ---------------------
+ * What a policy-gradient learner needs from gs_rollout(GS_POLICY_MLP) beyond the five arrays, computed where the collection lies.
+ * Additive to ABI 2.
+ *
+ * Log-probabilities.  A rollout under a STOCHASTIC policy (Gaussian head) records log_probs[T][B], float64, written by the policy
+ * kernel's head with the action:
+ *   logp[b] = sum over a = 0 .. A-1 of  -0.5 eps^2 - ls - 0.5 log(2 pi) - log((1 - act^2) + 1e-6)
+ * ls the clamped log_std, eps the 'PNOI' draw, act the action written: the reference's Normal(mean, std).log_prob(x) minus its tanh
+ * correction (algorithms/offline.py:114-136) with (x - mean)^2 / (2 std^2) written as eps^2 / 2.  The sum runs in action order.
+ * Deterministic and GS_HEAD_TANH policies record none (the view's pointer is NULL).  gs_rollout_set_log_probs(h, 0) switches the
+ * recording off (on by default); the actions and everything else the rollout leaves are the same bits either way.
+ *
+ * The value network.  gs_value_mlp_set installs a critic: the reference's `_build_mlp` with a scalar output (IQL's and AWR's value
+ * functions), described by gs_policy_mlp with head = GS_HEAD_LINEAR.  Rules beyond those of gs_policy_mlp / gs_policy_mlp_opts
+ * (GS_E_INVALID with a message; the installed network stays): head = GS_HEAD_LINEAR, dims[n_layers] = 1, stochastic = 0, and
+ * compute = GS_COMPUTE_F32 (the precision of torch critics; obs_shift / obs_scale as for the policy).  gs_policy_mlp_set* keeps
+ * refusing GS_HEAD_LINEAR.  NULL removes the network.  Like the policy it is not environment state.  gs_value_mlp_check: the
+ * rules on the host alone.  gs_value_mlp_eval: values[B] on the observation the environment stands at (the twin of
+ * gs_policy_mlp_eval; GS_E_STATE without a network or before gs_reset).  A row's value depends on that row alone: the same
+ * observation gives the same bits wherever it lies in a batch.
+ *
+ * gs_rollout_evaluate (asynchronous, on the handle's stream, over the LAST rollout; no host synchronisation behind gs_rollout)
+ * computes values[T + 1][B] over obs_seq, terminal_values[k] over terminal_obs in the order of terminal_index, and, t running
+ * from T - 1 down to 0 with every operation IEEE float64 and none contracted,
+ *   done  = terminals[t][b] != 0
+ *   vnext = done ? ((terminals[t][b] & bootstrap_mask) ? terminal_value(t, b) : 0.0) : values[t + 1][b]
+ *   delta = (r' + gamma * vnext) - values[t][b]                  r' = (rewards[t][b] - reward_shift) * reward_scale
+ *   adv   = done ? delta : delta + (gamma * lambda) * adv_next   adv_next = 0 at t = T - 1
+ *   ret   = adv + values[t][b]
+ * so the tail of an unfinished episode bootstraps from values[T].  GS_E_STATE without a rollout or without a value network;
+ * GS_E_INVALID for a wrong struct_size, bootstrap_mask outside 0 .. 3 or a non-finite parameter.
+ * gs_rollout_onpolicy_view: device pointers, valid until the next gs_rollout (consumer_stream as gs_step_device_view; the call
+ * waits for the number of finished episodes).  gs_rollout_onpolicy_download: host copies, any pointer may be NULL.  Both return
+ * GS_E_STATE unless gs_rollout_evaluate has run on the last rollout -- in particular after a further gs_rollout --, except that the
+ * download of log_probs alone needs no evaluation (GS_E_STATE if the last rollout recorded none). */
+enum { GS_HEAD_LINEAR = 2 };      /* gs_policy_mlp.head of a value network: the last layer's output as it is */
+int gs_rollout_set_log_probs(gs_handle* h, int32_t on);
+int gs_value_mlp_check(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim);
+int gs_value_mlp_set(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_opts* o);
+int gs_value_mlp_eval(gs_handle* h, double* values_host /* [B] */);
+typedef struct gs_gae_config {
+  int32_t struct_size;            /* = sizeof(gs_gae_config) */
+  int32_t bootstrap_mask;         /* done-flag bits whose episode end bootstraps from V(terminal observation): bit 0 terminated
+                                     (here: the time limit), bit 1 truncated (too many violations); 0 = the reference's (1 - terminals) */
+  double gamma, lambda;
+  double reward_shift, reward_scale;   /* r' = (r - shift) * scale; 0, 1 = raw */
+} gs_gae_config;
+int gs_rollout_evaluate(gs_handle* h, const gs_gae_config* cfg);
+typedef struct gs_rollout_onpolicy {
+  int32_t T, B, n_terminal, rows_per_tile;   /* rows_per_tile: the rows one workgroup of the value kernel evaluates */
+  const double* log_probs;        /* [T][B], or NULL: the last rollout recorded none */
+  const double* values;           /* [T + 1][B] */
+  const double* terminal_values;  /* [n_terminal], in the order of gs_rollout_device.terminal_index */
+  const double* advantages;       /* [T][B] */
+  const double* returns;          /* [T][B] */
+} gs_rollout_onpolicy;
+int gs_rollout_onpolicy_view(gs_handle* h, gs_rollout_onpolicy* out, void* consumer_stream);
+typedef struct gs_rollout_onpolicy_host {
+  double* log_probs;              /* [T][B] */
+  double* values;                 /* [T + 1][B] */
+  double* terminal_values;        /* [n_terminal] (room for as many as gs_rollout_download reported) */
+  double* advantages;             /* [T][B] */
+  double* returns;                /* [T][B] */
+} gs_rollout_onpolicy_host;
+int gs_rollout_onpolicy_download(gs_handle* h, const gs_rollout_onpolicy_host* out);
+
 /* ---- the device-resident dataset: statistics of the last rollout and normalised minibatches ----------------------------
  * What the reference's GridDataset (algorithms/base.py:180-266) does on the host, done where gs_rollout left the collection:
  * the per-column normalisation statistics over its N = T * B transitions (transition index = t * B + b), and minibatches
