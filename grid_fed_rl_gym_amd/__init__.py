@@ -17,7 +17,8 @@ from .solver import (BatchedNewtonRaphsonSolver, NewtonRaphsonSolver, FastDecoup
                      injections_from_dicts)
 from .env import BatchedGridEnvironment, VectorizedEnvironment, Box
 from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy_data, evaluate_rollout, gae_np, rollout_device, GridDataset,
-                      DeviceGridDataset)
+                      DeviceGridDataset, ConstraintLimits, costs_np, rollout_costs_np, rollout_costs, evaluate_rollout_costs,
+                      constraint_values, collect_constrained_data)
 from .policy import MLPPolicy, MLPValue
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -29,7 +30,9 @@ __all__ = [
     "BatchedNewtonRaphsonSolver", "NewtonRaphsonSolver", "FastDecoupledSolver",
     "BatchedForwardBackwardSweepSolver", "BatchedRobustPowerFlowSolver", "DistributionPowerFlow", "parallel_power_flow_batch",
     "injections_from_dicts", "BatchedGridEnvironment", "VectorizedEnvironment", "Box",
-    "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "MLPValue", "collect_onpolicy_data", "evaluate_rollout", "gae_np", "GridDataset", "DeviceGridDataset", "ShardedGridEnvironment", "LoopbackShards", "shard_range",
+    "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "MLPValue", "collect_onpolicy_data", "evaluate_rollout", "gae_np", "GridDataset", "DeviceGridDataset",
+    "ConstraintLimits", "costs_np", "rollout_costs_np", "rollout_costs", "evaluate_rollout_costs", "constraint_values", "collect_constrained_data",
+    "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",
     "BatchedSafetyChecker", "BatchedSafetyMonitor", "PostStepChecks", "device_quality_score",
     "UnbalancedPowerFlow", "UnbalancedFeederSpec", "UnbalancedSolution", "unbalanced_from_single_phase", "ieee8500_like",

@@ -119,6 +119,58 @@ ONPOLICY_KEYS = ("log_probs", "values", "terminal_values", "advantages", "return
 BOOTSTRAP = {"terminated": 1, "truncated": 2}      # bits of gs_gae_config.bootstrap_mask
 
 
+# constraint costs of a rollout (include/gridstep.h): channels, kinds and the structs of gs_rollout_costs / gs_rollout_evaluate_costs
+COST_CHANNELS = ("voltage", "frequency", "thermal")      # GS_COST_VOLTAGE, GS_COST_FREQUENCY, GS_COST_THERMAL
+COST_KIND = {"excess": 0, "indicator": 1, "count": 2}    # GS_COSTKIND_*
+_d3, _vp3, _dp3 = C.c_double * 3, C.c_void_p * 3, _dp * 3
+
+
+class gs_cost_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32 * 3), ("voltage_limits", C.c_double * 2),
+                ("frequency_limits", C.c_double * 2), ("line_loading_limit", C.c_double)]
+
+
+class gs_cost_gae_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("bootstrap_mask", C.c_int32), ("gamma", _d3), ("lam", _d3), ("cost_shift", _d3),
+                ("cost_scale", _d3)]
+
+
+class gs_rollout_costs_dev(C.Structure):
+    _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("margins", C.c_void_p), ("counts", C.c_void_p), ("costs", C.c_void_p),
+                ("n_violating", C.c_void_p), ("values", _vp3), ("terminal_values", _vp3), ("advantages", _vp3), ("returns", _vp3)]
+
+
+class gs_rollout_costs_host(C.Structure):
+    _fields_ = [("margins", _dp), ("counts", _ip), ("costs", _dp), ("n_violating", C.POINTER(C.c_int64)), ("values", _dp3),
+                ("terminal_values", _dp3), ("advantages", _dp3), ("returns", _dp3)]
+
+
+COST_CRITIC_KEYS = ("values", "terminal_values", "advantages", "returns")      # the per-channel fields of both structs, in order
+
+
+def cost_config(limits=None, kinds="excess", struct_size=None) -> gs_cost_config:
+    """gs_cost_config from ``limits`` -- anything with ``voltage``, ``frequency`` (lo, hi) and ``thermal`` -- and ``kinds``: one name
+    of COST_KIND (or its number) for all channels, or three."""
+    ks = [kinds] * 3 if isinstance(kinds, (str, int, np.integer)) else list(kinds)
+    if len(ks) != 3:
+        raise PowerFlowError(f"kinds: one kind or three, got {len(ks)}")
+    ks = [COST_KIND[k] if isinstance(k, str) else int(k) for k in ks]
+    c = gs_cost_config()
+    c.struct_size = C.sizeof(gs_cost_config) if struct_size is None else int(struct_size)
+    c.kind[:] = ks
+    c.voltage_limits[:] = [float(x) for x in limits.voltage]
+    c.frequency_limits[:] = [float(x) for x in limits.frequency]
+    c.line_loading_limit = float(limits.thermal)
+    return c
+
+
+def cost_config_check(c: gs_cost_config) -> Tuple[int, str]:
+    """gs_cost_config_check: (return code, message) -- the rules of a cost configuration on the host alone (no GPU)."""
+    lib = load()
+    rc = lib.gs_cost_config_check(C.byref(c))
+    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+
+
 class gs_dataset_stats_view(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("rows_per_chunk", C.c_int32), ("n", C.c_int64), ("obs_dim", C.c_int32), ("action_dim", C.c_int32),
                 ("obs_mean", _dp), ("obs_std", _dp), ("act_mean", _dp), ("act_std", _dp), ("reward_mean", _dp), ("reward_std", _dp)]
@@ -209,6 +261,14 @@ SYMBOLS = [
     ("gs_rollout_evaluate", C.c_int, [_H, C.POINTER(gs_gae_config)]),
     ("gs_rollout_onpolicy_view", C.c_int, [_H, C.POINTER(gs_rollout_onpolicy), C.c_void_p]),
     ("gs_rollout_onpolicy_download", C.c_int, [_H, C.POINTER(gs_rollout_onpolicy_host)]),
+    ("gs_cost_config_default", C.c_int, [_H, C.POINTER(gs_cost_config)]),
+    ("gs_cost_config_check", C.c_int, [C.POINTER(gs_cost_config)]),
+    ("gs_rollout_costs", C.c_int, [_H, C.POINTER(gs_cost_config)]),
+    ("gs_costs_eval", C.c_int, [_H, C.POINTER(gs_cost_config), _dp, C.c_int32, _dp, _ip, _dp]),
+    ("gs_cost_value_mlp_set", C.c_int, [_H, C.c_int32, C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts)]),
+    ("gs_rollout_evaluate_costs", C.c_int, [_H, C.POINTER(gs_cost_gae_config)]),
+    ("gs_rollout_costs_view", C.c_int, [_H, C.POINTER(gs_rollout_costs_dev), C.c_void_p]),
+    ("gs_rollout_costs_download", C.c_int, [_H, C.POINTER(gs_rollout_costs_host)]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -1055,6 +1115,86 @@ class Handle:
                 out[k] = np.empty((T + 1, B) if k == "values" else (T, B))
         v = gs_rollout_onpolicy_host(*[_ptr(out.get(k), _dp) for k in ONPOLICY_KEYS])
         self._check(self._lib.gs_rollout_onpolicy_download(self._h, C.byref(v)))
+        return out
+
+    # -- constraint costs of the last rollout: margins, counts, costs, cost critics and cost advantages (include/gridstep.h) ----
+    def cost_config_default(self) -> gs_cost_config:
+        """gs_cost_config_default: the handle's own voltage and frequency limits, 0.8 and the excess kind."""
+        c = gs_cost_config()
+        self._check(self._lib.gs_cost_config_default(self._h, C.byref(c)))
+        return c
+
+    def rollout_costs(self, cfg: Optional[gs_cost_config] = None) -> None:
+        """gs_rollout_costs (asynchronous): margins, counts and costs of every transition of the last rollout; None: the defaults."""
+        self._check(self._lib.gs_rollout_costs(self._h, None if cfg is None else C.byref(cfg)))
+
+    def costs_eval(self, observations, cfg: Optional[gs_cost_config] = None, want=("margins", "counts", "costs")) -> dict:
+        """gs_costs_eval: the same three results, [rows, 3] each, for ``observations`` [rows, obs_dim] on the host."""
+        obs = _f64(observations)
+        if obs.ndim != 2 or obs.shape[1] != self.obs_dim:
+            raise PowerFlowError(f"observations shape {obs.shape} != (rows, {self.obs_dim})")
+        rows = obs.shape[0]
+        out = {k: np.empty((rows, 3), dtype=np.int32 if k == "counts" else np.float64) for k in want}
+        self._check(self._lib.gs_costs_eval(self._h, None if cfg is None else C.byref(cfg), _ptr(obs, _dp) if rows else None, rows,
+                                            _ptr(out.get("margins"), _dp), _ptr(out.get("counts"), _ip), _ptr(out.get("costs"), _dp)))
+        return out
+
+    def set_cost_value(self, channel: int, p: Optional[gs_policy_mlp], opts: Optional[gs_policy_mlp_opts] = None) -> None:
+        """gs_cost_value_mlp_set: install (a copy of) a value network as the cost critic of ``channel``; None removes it."""
+        self._check(self._lib.gs_cost_value_mlp_set(self._h, int(channel), None if p is None else C.byref(p), None if opts is None else C.byref(opts)))
+
+    def rollout_evaluate_costs(self, gamma=0.99, lam=0.95, bootstrap_mask: int = 0, cost_shift=0.0, cost_scale=1.0, struct_size=None) -> None:
+        """gs_rollout_evaluate_costs (asynchronous): values, terminal values, cost advantages and cost returns of every channel that
+        has a critic.  ``gamma``, ``lam``, ``cost_shift``, ``cost_scale``: a scalar for all channels or three."""
+        three = lambda x: _d3(*[float(v) for v in np.broadcast_to(np.asarray(x, dtype=np.float64), (3,))])
+        cfg = gs_cost_gae_config(C.sizeof(gs_cost_gae_config) if struct_size is None else int(struct_size), int(bootstrap_mask), three(gamma),
+                                 three(lam), three(cost_shift), three(cost_scale))
+        self._check(self._lib.gs_rollout_evaluate_costs(self._h, C.byref(cfg)))
+
+    def rollout_costs_view(self, stream=None) -> gs_rollout_costs_dev:
+        """Device pointers of the last rollout's constraint arrays (gs_rollout_costs_view)."""
+        v = gs_rollout_costs_dev()
+        self._check(self._lib.gs_rollout_costs_view(self._h, C.byref(v), _stream_arg(stream)))
+        return v
+
+    def rollout_costs_arrays(self, stream=None) -> dict:
+        """The same as zero-copy ``DeviceArray`` views: ``margins``, ``costs`` (float64) and ``counts`` (int32) [3, T, B], ``n_violating``
+        [3] int64, and per channel c ``values[c]`` [T + 1, B], ``terminal_values[c]`` [n_terminal], ``advantages[c]``, ``returns[c]``
+        [T, B] -- None where the channel had no critic at the last evaluation.  Valid until the next rollout."""
+        v = self.rollout_costs_view(stream)
+        T, B = int(v.T), int(v.B)
+        n = int(self.rollout_device_view().n_terminal)
+        shapes = dict(values=(T + 1, B), terminal_values=(n,), advantages=(T, B), returns=(T, B))
+        out = dict(margins=DeviceArray(v.margins, (3, T, B), "<f8"), counts=DeviceArray(v.counts, (3, T, B), "<i4"),
+                   costs=DeviceArray(v.costs, (3, T, B), "<f8"), n_violating=DeviceArray(v.n_violating, (3,), "<i8"))
+        for k in COST_CRITIC_KEYS:
+            out[k] = [DeviceArray(getattr(v, k)[c], shapes[k], "<f8") if getattr(v, k)[c] else None for c in range(3)]
+        return out
+
+    def rollout_costs_download(self, want=("margins", "counts", "costs", "n_violating"), channels=(), n_terminal: Optional[int] = None) -> dict:
+        """Host copies (gs_rollout_costs_download) of the arrays named in ``want``; the per-channel arrays (``values``,
+        ``terminal_values``, ``advantages``, ``returns``) come as lists of three with None outside ``channels``."""
+        T, B = getattr(self, "_rollout_T", 0), self.B
+        out = {}
+        dtypes = dict(margins=np.float64, counts=np.int32, costs=np.float64)
+        v = gs_rollout_costs_host()
+        for k in want:
+            if k in dtypes:
+                out[k] = np.empty((3, T, B), dtype=dtypes[k])
+                setattr(v, k, _ptr(out[k], _ip if k == "counts" else _dp))
+            elif k == "n_violating":
+                out[k] = np.empty(3, dtype=np.int64)
+                v.n_violating = out[k].ctypes.data_as(C.POINTER(C.c_int64))
+            elif k in COST_CRITIC_KEYS:
+                if k == "terminal_values" and n_terminal is None:
+                    n_terminal = int(self.rollout_device_view().n_terminal)
+                shape = {"values": (T + 1, B), "terminal_values": (n_terminal,)}.get(k, (T, B))
+                out[k] = [np.empty(shape) if c in channels else None for c in range(3)]
+                for c in channels:
+                    getattr(v, k)[c] = _ptr(out[k][c], _dp)
+            else:
+                raise PowerFlowError(f"rollout_costs_download: unknown array {k!r}")
+        self._check(self._lib.gs_rollout_costs_download(self._h, C.byref(v)))
         return out
 
     def rollout_device_view(self) -> gs_rollout_device:

@@ -1,6 +1,7 @@
 // abi_onpolicy.hip -- on-policy rollouts (include/gridstep.h): the value network (gs_value_mlp_*), gs_rollout_evaluate and the
 // views of what it and the policy kernels' log-probability output left.  The value network's buffers and the rollout's on-policy
 // arrays are made here and released here (the log-probabilities are allocated by gs_rollout, abi_rollout.hip, which writes them).
+// The cost critics of abi_costs.hip are value networks too: installed and launched through value_install / launch_value, released here.
 #include <cmath>
 #include <string>
 
@@ -14,6 +15,7 @@ void value_release(gs_handle* h) {
   dev_free(h->val.blob);
   dev_free(h->val.out);
   h->val.set = false;
+  for (gs_handle::Value& v : h->cost_val) { dev_free(v.blob); dev_free(v.out); v.set = false; }
 }
 
 void onpolicy_release(gs_handle* h) {
@@ -23,20 +25,48 @@ void onpolicy_release(gs_handle* h) {
   ro.logp_recorded = false; ro.evaluated_on = 0;
 }
 
-}  // namespace gsi
+// what gs_value_mlp_set and gs_cost_value_mlp_set (abi_costs.hip) share: `p` has passed gs_value_check; NULL removes the network
+int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out) {
+  GS_ENTER(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  dev_free(val.blob);
+  val.set = false;
+  if (!p) return GS_OK;
+  if (want_out && !val.out) HIPCHK(h, hipMalloc((void**)&val.out, (size_t)h->B * sizeof(double)));
+  const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
+  val.lds = gs_val_lds_bytes(im.kb[0]);
+  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_value_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
+  // one allocation: the float image (a multiple of 16 floats), then shift and scale
+  const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
+  HIPCHK(h, hipMalloc((void**)&val.blob, image_bytes + norm_bytes));
+  const float* image = val.blob;
+  const double* norm = (const double*)((const char*)val.blob + image_bytes);
+  HIPCHK(h, hipMemcpy((void*)image, im.blob.data(), image_bytes, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy((void*)norm, im.norm.data(), norm_bytes, hipMemcpyHostToDevice));
+  GsValueArgs& a = val.args;
+  a = GsValueArgs{};
+  a.shift = norm; a.scale = norm + 16 * im.kb[0];
+  a.D = h->obs_dim; a.n_layers = p->n_layers; a.activation = p->activation;
+  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
+  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
+  val.set = true;
+  return GS_OK;
+}
 
 // one launch over `rows` rows of obs (device pointers) on the handle's main stream; rows_dev / scatter_*: GsValueArgs
-static int launch_value(gs_handle* h, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
-                        const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0) {
+int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev,
+                 const int32_t* scatter_idx, double* scatter_out, int scatter_T) {
   if (rows <= 0) return GS_OK;
   if (rows > 0x7fffffffLL - GS_VAL_ROWS) return fail(h, GS_E_INVALID, "%lld rows exceed the value kernel's 32-bit row index", rows);
-  GsValueArgs a = h->val.args;
+  GsValueArgs a = val.args;
   a.obs = obs; a.out = out; a.rows = (int32_t)rows; a.rows_dev = rows_dev;
   a.scatter_idx = scatter_idx; a.scatter_out = scatter_out; a.scatter_T = scatter_T; a.scatter_B = h->B;
-  hipLaunchKernelGGL(gs_k_value_mlp_f32, dim3((unsigned)((rows + GS_VAL_ROWS - 1) / GS_VAL_ROWS)), dim3(64 * GS_POL_WAVES), h->val.lds, h->stream, a);
+  hipLaunchKernelGGL(gs_k_value_mlp_f32, dim3((unsigned)((rows + GS_VAL_ROWS - 1) / GS_VAL_ROWS)), dim3(64 * GS_POL_WAVES), val.lds, h->stream, a);
   HIPCHK(h, hipGetLastError());
   return GS_OK;
 }
+
+}  // namespace gsi
 
 extern "C" {
 
@@ -58,31 +88,7 @@ int gs_value_mlp_set(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_o
     const std::string why = gs_value_check(p, o, h->obs_dim);
     if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
   }
-  GS_ENTER(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  gs_handle::Value& val = h->val;
-  dev_free(val.blob);
-  val.set = false;
-  if (!p) return GS_OK;
-  if (!val.out) HIPCHK(h, hipMalloc((void**)&val.out, (size_t)h->B * sizeof(double)));
-  const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
-  val.lds = gs_val_lds_bytes(im.kb[0]);
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_value_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-  // one allocation: the float image (a multiple of 16 floats), then shift and scale
-  const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
-  HIPCHK(h, hipMalloc((void**)&val.blob, image_bytes + norm_bytes));
-  const float* image = val.blob;
-  const double* norm = (const double*)((const char*)val.blob + image_bytes);
-  HIPCHK(h, hipMemcpy((void*)image, im.blob.data(), image_bytes, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy((void*)norm, im.norm.data(), norm_bytes, hipMemcpyHostToDevice));
-  GsValueArgs& a = val.args;
-  a = GsValueArgs{};
-  a.shift = norm; a.scale = norm + 16 * im.kb[0];
-  a.D = h->obs_dim; a.n_layers = p->n_layers; a.activation = p->activation;
-  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
-  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
-  val.set = true;
-  return GS_OK;
+  return value_install(h, h->val, p, o, true);
 }
 
 int gs_value_mlp_eval(gs_handle* h, double* values_host) {
@@ -90,7 +96,7 @@ int gs_value_mlp_eval(gs_handle* h, double* values_host) {
   if (!h->val.set) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_value_mlp_set");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_reset");
   GS_ENTER(h);
-  int rc = launch_value(h, h->d_obs2[h->obs_cur], h->val.out, h->B);
+  int rc = launch_value(h, h->val, h->d_obs2[h->obs_cur], h->val.out, h->B);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(values_host, h->val.out, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -119,11 +125,11 @@ int gs_rollout_evaluate(gs_handle* h, const gs_gae_config* cfg) {
       return fail(h, GS_E_NOMEM, "on-policy arrays for T = %d do not fit", ro.T_cap);
     }
   }
-  int rc = launch_value(h, ro.obs_seq, ro.values, (long long)((T + 1) * B));
+  int rc = launch_value(h, h->val, ro.obs_seq, ro.values, (long long)((T + 1) * B));
   if (rc) return rc;
   // the terminal rows: launched over the list's capacity, the count read on the device; every value also goes to its (t, b) in
   // `ret`, where gs_k_gae looks for it before it writes the return there
-  if ((rc = launch_value(h, ro.term_obs, ro.term_values, ro.term_cap, ro.term_count, ro.term_idx, ro.ret, (int)T))) return rc;
+  if ((rc = launch_value(h, h->val, ro.term_obs, ro.term_values, ro.term_cap, ro.term_count, ro.term_idx, ro.ret, (int)T))) return rc;
   GsGaeArgs g{ro.values, ro.rew, ro.done, ro.adv, ro.ret, (int32_t)T, h->B, cfg->bootstrap_mask, 0, cfg->gamma, cfg->lambda, cfg->reward_shift, cfg->reward_scale};
   hipLaunchKernelGGL(gs_k_gae, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, g);
   HIPCHK(h, hipGetLastError());

@@ -24,6 +24,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   dev_free(ro.obs_seq); dev_free(ro.act); dev_free(ro.rew); dev_free(ro.done); dev_free(ro.term_idx); dev_free(ro.term_obs);
   if (!keep_term_count) dev_free(ro.term_count);
   onpolicy_release(h);           // (sized by T as well)
+  costs_release(h);
   ro.T_cap = 0;
 }
 

@@ -611,6 +611,27 @@ struct GsDsGatherArgs {
   long long N;
   int32_t n, B, D, A, Ct, Cs, term_cap, normalize, vec2, pad;
 };
+// ---- constraint costs of observation rows (kernels_costs.hip, abi_costs.hip) ----
+// gs_k_costs reads the first 2 n + 2 m + 1 columns of every row: |V| at 2 i, |loading| at 2 n + 2 k + 1, the frequency at 2 n + 2 m.
+// One kernel, three launches: over obs_seq[1 ..] (skip = the done flags: a flagged row belongs to the terminal launch), over the
+// terminal list (rows_dev, scatter_idx: row k's results go to entry t * scatter_B + b) and over a plain matrix (entry = row).
+// Channel c of entry i lies at c * chan_stride + i * row_stride of margins / counts / costs.
+#define GS_COST_ROWS 2                   // rows a group of `lanes` lanes holds in flight
+#define GS_COST_LOADS 4                  // loads per lane, row and pass over the prefix
+struct GsCostArgs {
+  const double* obs;                     // [rows][D]
+  const uint8_t* skip;                   // NULL, or [rows]: != 0 = the row is not evaluated here
+  const int32_t* rows_dev;               // NULL, or the device word holding the number of rows actually there (<= rows)
+  const int32_t* scatter_idx;            // NULL, or [rows][2] (t, b)
+  double* margins; int32_t* counts; double* costs;      // any may be NULL
+  unsigned long long* n_violating;       // NULL, or [3]: += the entries written with margin < 0
+  long long chan_stride;
+  int32_t rows, D, n, m, lanes, pad, row_stride, scatter_T, scatter_B, kind[3];
+  double vlo, vhi, flo, fhi, lim;
+};
+// lanes per row for a prefix of `cols` = 2 n + 2 m columns (the frequency is read on its own): the smallest power of two in 8 .. 64
+// that covers the prefix in one pass of GS_COST_LOADS loads a lane; longer prefixes take several passes on 64 lanes
+inline int gs_cost_lanes(int cols) { int l = 8; while (l < 64 && GS_COST_LOADS * l < cols + 1) l *= 2; return l; }
 #if defined(__HIPCC__)
 // constant ci of an observation (plan.cpp plan_maps: 2 l = P of load l, 2 l + 1 = its Q) as instance b holds it
 __device__ __forceinline__ double gs_pl_const(const double* __restrict__ pl, int n_loads, int b, int ci) {

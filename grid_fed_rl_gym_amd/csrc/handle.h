@@ -98,6 +98,18 @@ struct gs_handle : GsPlan {
   // gs_value_mlp_set: the value network's float32 image and normalisation vectors (one allocation), the values of
   // gs_value_mlp_eval [B], and the argument block of gs_k_value_mlp_f32 with everything but obs / out / rows filled in
   struct Value { bool set = false; float* blob = nullptr; double* out = nullptr; GsValueArgs args{}; int lds = 0; } val;
+  // gs_cost_value_mlp_set: one critic per constraint channel (GS_COST_*), installed like `val` (no `out`: they run over rollouts only)
+  Value cost_val[GS_COST_CHANNELS];
+  // gs_rollout_costs / gs_rollout_evaluate_costs (abi_costs.hip): margins / costs [3][T][B], counts [3][T][B], n_viol [3] of the last
+  // rollout, channel c at c * T * B; computed_on = ro.calls of the rollout they belong to, 0 = none.  values [3][T_cap + 1][B],
+  // term_values [3][term_cap], adv / ret [3][T_cap][B]: the cost critics' arrays, channel c at c * its capacity; evaluated_on as
+  // computed_on, evaluated[c]: channel c had a critic at that evaluation.  All sized by the rollout's capacity and released with it.
+  struct Costs {
+    double* margins = nullptr; int32_t* counts = nullptr; double* costs = nullptr; unsigned long long* n_viol = nullptr;
+    double* values = nullptr; double* term_values = nullptr; double* adv = nullptr; double* ret = nullptr;
+    uint64_t computed_on = 0, evaluated_on = 0; bool evaluated[GS_COST_CHANNELS] = {false, false, false};
+    hipEvent_t ev = nullptr;
+  } cc;
   double* d_cst = nullptr;
   int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
           *map_p = nullptr, *map_q = nullptr, *map_act = nullptr, *map_state = nullptr;
@@ -259,6 +271,14 @@ int rollout_finish(gs_handle* h);      // waits for the last rollout's number of
 // ---- owner of the value network and of the rollout's on-policy arrays (abi_onpolicy.hip) ----
 void value_release(gs_handle* h);
 void onpolicy_release(gs_handle* h);
+// installs `p` (checked by the caller; NULL removes) as `val`; want_out: with the [B] block of gs_value_mlp_eval
+int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out);
+// one launch of `val` over `rows` rows of obs (device pointers) on the handle's main stream; rows_dev / scatter_*: GsValueArgs
+int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
+                 const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0);
+
+// ---- owner of the rollout's constraint arrays and of the cost critics' arrays (abi_costs.hip) ----
+void costs_release(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);

@@ -316,6 +316,17 @@ class BatchedGridEnvironment:
         opts, keep_opts = value.to_opts()
         self._h.set_value(p, opts)          # (raises, and leaves the installed network in place, if the library refuses it)
 
+    def set_cost_value(self, channel, value: Optional[Any]) -> None:
+        """Install an ``MLPValue`` as the cost critic of constraint ``channel`` (0 voltage, 1 frequency, 2 thermal, or the name;
+        gs_cost_value_mlp_set) for ``evaluate_rollout_costs``; None removes it.  Not environment state."""
+        c = _lib.COST_CHANNELS.index(channel) if isinstance(channel, str) else int(channel)
+        if value is None:
+            self._h.set_cost_value(c, None)
+            return
+        p, keep = value.to_struct()
+        opts, keep_opts = value.to_opts()
+        self._h.set_cost_value(c, p, opts)  # (raises, and leaves the installed critic in place, if the library refuses it)
+
     def value_estimates(self) -> np.ndarray:
         """The installed value network's estimates [num_envs] on the observation the environment stands at (gs_value_mlp_eval)."""
         if self._needs_reset:

@@ -14,11 +14,17 @@ normalised there (``gs_dataset_*``, include/gridstep.h), n
 ``evaluate_rollout`` / ``collect_onpolicy_data`` add what a policy-gradient learner needs from a stochastic rollout -- the
 log-probabilities the policy kernels recorded, a value network's estimates over every row, advantages and returns
 (``gs_rollout_evaluate``); ``gae_np`` restates the device's recurrence.
+
+``rollout_costs`` / ``evaluate_rollout_costs`` / ``collect_constrained_data`` add what a CONSTRAINED learner needs (the reference's
+algorithms/safe.py): per transition and per channel (voltage, frequency, thermal) the constraint margin, the violation count and a
+cost, cost critics and cost advantages (``gs_rollout_costs``, ``gs_rollout_evaluate_costs``); ``costs_np`` and
+``rollout_costs_np`` restate the contract.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from types import SimpleNamespace
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -144,6 +150,136 @@ def collect_onpolicy_data(env: BatchedGridEnvironment, policy, value, num_steps:
     o = env.handle.rollout_onpolicy_download(("log_probs", "values", "advantages", "returns"))
     out["log_probs"], out["values"] = o["log_probs"].reshape(T * B), o["values"][:T].reshape(T * B)
     out["advantages"], out["returns"] = o["advantages"].reshape(T * B), o["returns"].reshape(T * B)
+    return out
+
+
+# ---- constraint costs (include/gridstep.h "constraint costs of a rollout") --------------------------------------
+
+@dataclass
+class ConstraintLimits:
+    """The limits of the three constraint channels: ``voltage`` (lo, hi) per unit, ``frequency`` (lo, hi) Hz, ``thermal`` the line
+    loading limit.  ``ConstraintLimits.of(env)``: the environment's own voltage and frequency limits and 0.8, the threshold of the
+    reference's reward (grid_env.py:785-826) and ``thermal_constraint``'s default (safe.py:554)."""
+    voltage: Tuple[float, float] = (0.95, 1.05)
+    frequency: Tuple[float, float] = (59.5, 60.5)
+    thermal: float = 0.8
+
+    @classmethod
+    def of(cls, env, **override) -> "ConstraintLimits":
+        kw = dict(voltage=tuple(env.voltage_limits), frequency=tuple(env.frequency_limits), thermal=0.8)
+        kw.update(override)
+        return cls(**kw)
+
+
+def _nm(spec_or_nm) -> Tuple[int, int]:
+    if hasattr(spec_or_nm, "n") and hasattr(spec_or_nm, "m"):
+        return int(spec_or_nm.n), int(spec_or_nm.m)
+    n, m = spec_or_nm
+    return int(n), int(m)
+
+
+def _kinds(kinds):
+    ks = [kinds] * 3 if isinstance(kinds, (str, int, np.integer)) else list(kinds)
+    if len(ks) != 3:
+        raise ValueError(f"kinds: one kind or three, got {len(ks)}")
+    return [_lib.COST_KIND[k] if isinstance(k, str) else int(k) for k in ks]
+
+
+def costs_np(obs, spec_or_nm, limits: ConstraintLimits, kinds="excess"):
+    """(margins float64, counts int32, costs float64), [..., 3] each, of observation rows ``obs`` [..., obs_dim]: the contract of
+    ``gs_rollout_costs`` (include/gridstep.h) restated in NumPy.  ``spec_or_nm``: a ``FeederSpec`` or (n, m).  Only the first
+    2 n + 2 m + 1 columns are read: |V| at 2 i, the line loading at 2 n + 2 k + 1, the frequency at 2 n + 2 m."""
+    obs = np.asarray(obs, dtype=np.float64)
+    n, m = _nm(spec_or_nm)
+    vm = obs[..., 0:2 * n:2]
+    load = np.abs(obs[..., 2 * n + 1:2 * n + 2 * m:2])
+    f = obs[..., 2 * n + 2 * m]
+    (vlo, vhi), (flo, fhi), lim = limits.voltage, limits.frequency, float(limits.thermal)
+    margins = np.empty(obs.shape[:-1] + (3,))
+    with np.errstate(invalid="ignore"):
+        margins[..., 0] = np.min(np.minimum(vm - vlo, vhi - vm), axis=-1)                       # safe.py:513-522
+        margins[..., 1] = np.minimum(f - flo, fhi - f)                                          # safe.py:534-542
+        margins[..., 2] = lim - np.max(load, axis=-1) if m else lim                             # safe.py:554-561
+        counts = np.stack([np.sum((vm < vlo) | (vm > vhi), axis=-1), ((f < flo) | (f > fhi)).astype(np.int64),   # base.py:153-167
+                           np.sum(load > lim, axis=-1)], axis=-1).astype(np.int32)
+        neg = margins < 0.0
+    by_kind = (np.where(neg, -margins, 0.0),            # excess, safe.py:471 (a NaN margin: 0)
+               np.where(neg, 1.0, 0.0),                 # indicator, safe.py:282
+               counts.astype(np.float64))
+    costs = np.stack([by_kind[k][..., c] for c, k in enumerate(_kinds(kinds))], axis=-1)
+    return margins, counts, costs
+
+
+def rollout_costs_np(next_observations, spec_or_nm, limits: ConstraintLimits, kinds="excess"):
+    """``costs_np`` over a downloaded rollout: ``next_observations`` [T, B, obs_dim] (or [T * B, obs_dim]) as ``rollout_download`` /
+    ``collect_*_data`` return them -- the terminal observation where the transition ended an episode, not the fresh one after the
+    reset.  Returns margins, counts, costs channel-major, [3, T, B] (or [3, T * B]), and n_violating [3] int64."""
+    margins, counts, costs = costs_np(next_observations, spec_or_nm, limits, kinds)
+    cm = lambda a: np.ascontiguousarray(np.moveaxis(a, -1, 0))
+    margins = cm(margins)
+    with np.errstate(invalid="ignore"):
+        n_violating = np.sum(margins.reshape(3, -1) < 0.0, axis=1).astype(np.int64)
+    return margins, cm(counts), cm(costs), n_violating
+
+
+def rollout_costs(env: BatchedGridEnvironment, limits: Optional[ConstraintLimits] = None, kinds="excess", stream=None):
+    """Constraint margins, violation counts and costs of every transition of the environment's LAST rollout, computed on the device
+    (``gs_rollout_costs``: one streaming kernel over the first 2 n + 2 m + 1 columns of ``obs_seq[1:]`` and of the terminal
+    observations).  ``limits``: None = ``ConstraintLimits.of(env)``; ``kinds``: "excess", "indicator" or "count", one or three.
+    Returns an object with ``margins``, ``costs`` (float64), ``counts`` (int32), [3, T, B] zero-copy ``DeviceArray`` views (channel
+    order ``_lib.COST_CHANNELS``), and ``n_violating`` [3] int64; valid until the next rollout.  ``stream``: as ``evaluate_rollout``."""
+    h = env.handle
+    h.rollout_costs(_lib.cost_config(ConstraintLimits.of(env) if limits is None else limits, kinds))
+    a = h.rollout_costs_arrays(stream)
+    return SimpleNamespace(margins=a["margins"], counts=a["counts"], costs=a["costs"], n_violating=a["n_violating"])
+
+
+def evaluate_rollout_costs(env: BatchedGridEnvironment, gamma=0.99, lam=0.95, bootstrap: Sequence[str] = (), cost_shift=0.0, cost_scale=1.0,
+                           stream=None):
+    """Cost values, cost advantages and cost returns of the LAST rollout under the cost critics ``env.set_cost_value`` installed
+    (``gs_rollout_evaluate_costs``, after ``rollout_costs``): per channel the critic over ``obs_seq`` and the terminal observations
+    and the recurrence of ``evaluate_rollout`` with that channel's costs as rewards.  ``gamma``, ``lam``, ``cost_shift``,
+    ``cost_scale``: a scalar or one per channel; ``bootstrap`` is shared.  Returns an object whose ``values``, ``terminal_values``,
+    ``advantages`` and ``returns`` are lists of three ``DeviceArray`` views, None for a channel without a critic."""
+    h = env.handle
+    h.rollout_evaluate_costs(gamma, lam, _bootstrap_mask(bootstrap), cost_shift, cost_scale)
+    a = h.rollout_costs_arrays(stream)
+    return SimpleNamespace(**{k: a[k] for k in _lib.COST_CRITIC_KEYS})
+
+
+def constraint_values(env: BatchedGridEnvironment, observations, limits: Optional[ConstraintLimits] = None, kinds="excess") -> Dict[str, np.ndarray]:
+    """``margins``, ``counts`` and ``costs``, [rows, 3] each, of host ``observations`` [rows, obs_dim] (``gs_costs_eval``): the
+    reference's constraint values (safe.py:26-32, >= 0 is safe) of arbitrary rows, e.g. what ``env.step`` returned."""
+    return env.handle.costs_eval(observations, _lib.cost_config(ConstraintLimits.of(env) if limits is None else limits, kinds))
+
+
+def collect_constrained_data(env: BatchedGridEnvironment, policy, value, cost_values, num_steps: int, seed: int = 0, reset: bool = True,
+                             limits: Optional[ConstraintLimits] = None, kinds="excess", gamma: float = 0.99, lam: float = 0.95,
+                             bootstrap: Sequence[str] = (), reward_shift: float = 0.0, reward_scale: float = 1.0, cost_gamma=0.99,
+                             cost_lam=0.95, cost_shift=0.0, cost_scale=1.0) -> Dict[str, np.ndarray]:
+    """``collect_onpolicy_data`` plus the constraint signals, as host arrays in the same transition order (index = t * B + b):
+    ``constraint_margins`` and ``constraint_costs`` [T * B, 3], and ``cost_advantages`` / ``cost_returns``, dicts from the channel
+    index to [T * B] for the channels with a critic.  ``cost_values``: a dict channel (index or name in ``_lib.COST_CHANNELS``) ->
+    ``MLPValue``, or a sequence of three with None for a channel without one; these replace the installed cost critics."""
+    if isinstance(cost_values, dict):
+        given = {(_lib.COST_CHANNELS.index(c) if isinstance(c, str) else int(c)): v for c, v in cost_values.items()}
+    else:
+        given = {c: v for c, v in enumerate(cost_values)}
+    out = collect_onpolicy_data(env, policy, value, num_steps, seed=seed, reset=reset, gamma=gamma, lam=lam, bootstrap=bootstrap,
+                                reward_shift=reward_shift, reward_scale=reward_scale)
+    h = env.handle
+    for c in range(3):
+        env.set_cost_value(c, given.get(c))
+    critics = tuple(c for c in range(3) if given.get(c) is not None)
+    h.rollout_costs(_lib.cost_config(ConstraintLimits.of(env) if limits is None else limits, kinds))
+    if critics:
+        h.rollout_evaluate_costs(cost_gamma, cost_lam, _bootstrap_mask(bootstrap), cost_shift, cost_scale)
+    T, B = int(num_steps), env.num_envs
+    d = h.rollout_costs_download(("margins", "costs", "advantages", "returns") if critics else ("margins", "costs"), channels=critics)
+    out["constraint_margins"] = np.ascontiguousarray(d["margins"].reshape(3, T * B).T)
+    out["constraint_costs"] = np.ascontiguousarray(d["costs"].reshape(3, T * B).T)
+    out["cost_advantages"] = {c: d["advantages"][c].reshape(T * B) for c in critics}
+    out["cost_returns"] = {c: d["returns"][c].reshape(T * B) for c in critics}
     return out
 
 

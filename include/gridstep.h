@@ -466,6 +466,91 @@ typedef struct gs_rollout_onpolicy_host {
 } gs_rollout_onpolicy_host;
 int gs_rollout_onpolicy_download(gs_handle* h, const gs_rollout_onpolicy_host* out);
 
+/* ---- constraint costs of a rollout: margins, violation counts, costs, cost critics and cost advantages ----
+ * What the reference's constrained learners (algorithms/safe.py: SafeRL, ConstrainedPolicyOptimization) need beside the reward:
+ * a constraint value per transition (>= 0 is safe, safe.py:26-32), violation flags and rates (:282, :74-80) and a penalty on
+ * max(0, -value) (:459-474), computed where the collection lies.  Additive to ABI 2.
+ *
+ * One observation row o is read at the positions of the real layout (grid_env.py:753-783; the reference's own constraint functions
+ * read placeholder positions, safe.py:519): Vm_i = o[2 i], i < n; L_k = |o[2 n + 2 k + 1]|, k < m; f = o[2 n + 2 m]; no other column.
+ * Three channels with the limits (vlo, vhi), (flo, fhi) and lim:
+ *   margin[V] = min_i min(Vm_i - vlo, vhi - Vm_i)   safe.py:513-522        count[V] = #{i : Vm_i < vlo or Vm_i > vhi}   base.py:153-167
+ *   margin[F] = min(f - flo, fhi - f)               safe.py:534-542        count[F] = (f < flo or f > fhi)
+ *   margin[T] = lim - max_k L_k  (m = 0: lim)       safe.py:554-561        count[T] = #{k : L_k > lim}
+ * margins are float64, counts int32.  A NaN among a channel's own inputs makes that channel's margin NaN (as np.min / np.max do) and
+ * counts as nothing (the comparisons are strict); a NaN anywhere else in the row changes nothing.  cost (float64) by the channel's kind:
+ *   GS_COSTKIND_EXCESS     margin < 0 ? -margin : 0.0   (safe.py:471; a NaN margin gives 0)
+ *   GS_COSTKIND_INDICATOR  margin < 0 ? 1.0 : 0.0       (safe.py:282)
+ *   GS_COSTKIND_COUNT      (double)count
+ * Every quantity is a minimum, a maximum, a count or one rounded subtraction: the results do not depend on how the device maps lanes.
+ *
+ * gs_cost_config_default: the handle's own v_min / v_max and f_min / f_max, 0.8 (get_reward's threshold, grid_env.py:785-826, and
+ * thermal_constraint's default) and GS_COSTKIND_EXCESS.  gs_cost_config_check: the rules on the host alone (GS_E_INVALID with a
+ * message: a wrong struct_size, a kind outside 0 .. 2, a non-finite limit, lo > hi).
+ * gs_rollout_costs (asynchronous, on the handle's stream, over the LAST rollout; c == NULL: the default) fills margins, counts and
+ * costs [3][T][B], channel-major, each channel indexed like rewards by t * B + b, and n_violating[3], the number of transitions with
+ * margin < 0.  The row of transition (t, b) is the observation its reward was computed on: obs_seq[t + 1][b] unless
+ * terminals[t][b] != 0, then terminal_obs[k] with terminal_index[k] = (t, b).  GS_E_STATE without a rollout.
+ * gs_costs_eval: the same three results [rows][3] for `rows` observation rows on the host (any output may be NULL); GS_E_INVALID for
+ * rows <= 0 or a NULL obs_host.
+ *
+ * Cost critics.  gs_cost_value_mlp_set installs a value network for one channel exactly as gs_value_mlp_set accepts it
+ * (GS_HEAD_LINEAR, scalar output, GS_COMPUTE_F32; the same rules, GS_E_INVALID also for a channel outside 0 .. 2; NULL removes it; a
+ * refused network leaves the installed one in place).  gs_rollout_evaluate_costs (asynchronous) runs, for every channel that has a
+ * critic, the value kernel over obs_seq and over the terminal observations and the recurrence of gs_rollout_evaluate with
+ * rewards = costs[c] and the channel's own gamma, lambda, cost_shift and cost_scale; the bootstrap mask is shared.  GS_E_STATE
+ * without a rollout, before gs_rollout_costs on the last rollout, or with no cost critic installed; GS_E_INVALID as gs_rollout_evaluate.
+ * gs_rollout_costs_view: device pointers, valid until the next gs_rollout (consumer_stream as gs_step_device_view).  The pointers
+ * of a channel that had no critic at the last evaluation -- or of every channel, before the evaluation -- are NULL.
+ * gs_rollout_costs_download: host copies, any pointer may be NULL; asking for values, terminal_values, advantages or returns of a
+ * channel that was not evaluated on the last rollout is GS_E_STATE.  Both return GS_E_STATE unless gs_rollout_costs has run on the
+ * last rollout -- in particular after a further gs_rollout. */
+enum { GS_COST_VOLTAGE = 0, GS_COST_FREQUENCY = 1, GS_COST_THERMAL = 2, GS_COST_CHANNELS = 3 };
+enum { GS_COSTKIND_EXCESS = 0, GS_COSTKIND_INDICATOR = 1, GS_COSTKIND_COUNT = 2 };
+typedef struct gs_cost_config {
+  int32_t struct_size;            /* = sizeof(gs_cost_config) */
+  int32_t kind[3];                /* GS_COSTKIND_* per channel */
+  double voltage_limits[2];       /* (vlo, vhi), per unit */
+  double frequency_limits[2];     /* (flo, fhi), Hz */
+  double line_loading_limit;      /* lim, |S| / rating */
+} gs_cost_config;
+int gs_cost_config_default(const gs_handle* h, gs_cost_config* out);
+int gs_cost_config_check(const gs_cost_config* c);
+int gs_rollout_costs(gs_handle* h, const gs_cost_config* c);
+int gs_costs_eval(gs_handle* h, const gs_cost_config* c, const double* obs_host /* [rows][obs_dim] */, int32_t rows,
+                  double* margins_host, int32_t* counts_host, double* costs_host /* [rows][3] each */);
+int gs_cost_value_mlp_set(gs_handle* h, int32_t channel, const gs_policy_mlp* p, const gs_policy_mlp_opts* o);
+typedef struct gs_cost_gae_config {
+  int32_t struct_size;            /* = sizeof(gs_cost_gae_config) */
+  int32_t bootstrap_mask;         /* as gs_gae_config, shared by the channels */
+  double gamma[3], lambda[3];
+  double cost_shift[3], cost_scale[3];   /* c' = (cost - shift) * scale; 0, 1 = raw */
+} gs_cost_gae_config;
+int gs_rollout_evaluate_costs(gs_handle* h, const gs_cost_gae_config* c);
+typedef struct gs_rollout_costs_dev {
+  int32_t T, B;
+  const double* margins;          /* [3][T][B] */
+  const int32_t* counts;          /* [3][T][B] */
+  const double* costs;            /* [3][T][B] */
+  const int64_t* n_violating;     /* [3] */
+  const double* values[3];        /* [T + 1][B] per channel, or NULL */
+  const double* terminal_values[3];   /* [n_terminal], in the order of gs_rollout_device.terminal_index */
+  const double* advantages[3];    /* [T][B] */
+  const double* returns[3];       /* [T][B] */
+} gs_rollout_costs_dev;
+int gs_rollout_costs_view(gs_handle* h, gs_rollout_costs_dev* out, void* consumer_stream);
+typedef struct gs_rollout_costs_host {
+  double* margins;                /* [3][T][B] */
+  int32_t* counts;                /* [3][T][B] */
+  double* costs;                  /* [3][T][B] */
+  int64_t* n_violating;           /* [3] */
+  double* values[3];              /* [T + 1][B] */
+  double* terminal_values[3];     /* [n_terminal] (room for as many as gs_rollout_download reported) */
+  double* advantages[3];          /* [T][B] */
+  double* returns[3];             /* [T][B] */
+} gs_rollout_costs_host;
+int gs_rollout_costs_download(gs_handle* h, const gs_rollout_costs_host* out);
+
 /* ---- the device-resident dataset: statistics of the last rollout and normalised minibatches ----------------------------
  * What the reference's GridDataset (algorithms/base.py:180-266) does on the host, done where gs_rollout left the collection:
  * the per-column normalisation statistics over its N = T * B transitions (transition index = t * B + b), and minibatches
