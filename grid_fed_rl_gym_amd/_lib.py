@@ -164,11 +164,21 @@ def cost_config(limits=None, kinds="excess", struct_size=None) -> gs_cost_config
     return c
 
 
+def _host_check(name: str, *args) -> Tuple[int, str]:
+    """(return code, message) of ``name``, one of the library's checks that run on the host alone (no GPU, no handle)."""
+    lib = load()
+    rc = getattr(lib, name)(*args)
+    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+
+
+def _critic_shapes(T: int, B: int, n_terminal: int) -> dict:
+    """The shapes of what a critic leaves over a rollout (COST_CRITIC_KEYS; ONPOLICY_KEYS without ``log_probs``)."""
+    return dict(values=(T + 1, B), terminal_values=(n_terminal,), advantages=(T, B), returns=(T, B))
+
+
 def cost_config_check(c: gs_cost_config) -> Tuple[int, str]:
     """gs_cost_config_check: (return code, message) -- the rules of a cost configuration on the host alone (no GPU)."""
-    lib = load()
-    rc = lib.gs_cost_config_check(C.byref(c))
-    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+    return _host_check("gs_cost_config_check", C.byref(c))
 
 
 class gs_dataset_stats_view(C.Structure):
@@ -531,9 +541,7 @@ def policy_struct(weights, biases, activation="relu", head="gaussian_tanh", stoc
 
 def policy_check(p: gs_policy_mlp, obs_dim: int, action_dim: int) -> Tuple[int, str]:
     """gs_policy_mlp_check: (return code, message) -- the rules of gs_policy_mlp on the host alone (no GPU)."""
-    lib = load()
-    rc = lib.gs_policy_mlp_check(C.byref(p), int(obs_dim), int(action_dim))
-    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+    return _host_check("gs_policy_mlp_check", C.byref(p), int(obs_dim), int(action_dim))
 
 
 def policy_opts(compute="float64", obs_shift=None, obs_scale=None, struct_size=None):
@@ -553,16 +561,12 @@ def policy_opts(compute="float64", obs_shift=None, obs_scale=None, struct_size=N
 
 def policy_check_opts(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int, action_dim: int) -> Tuple[int, str]:
     """gs_policy_mlp_check_opts: (return code, message) -- the rules of gs_policy_mlp and its options on the host alone."""
-    lib = load()
-    rc = lib.gs_policy_mlp_check_opts(C.byref(p), None if o is None else C.byref(o), int(obs_dim), int(action_dim))
-    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+    return _host_check("gs_policy_mlp_check_opts", C.byref(p), None if o is None else C.byref(o), int(obs_dim), int(action_dim))
 
 
 def value_check(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int) -> Tuple[int, str]:
     """gs_value_mlp_check: (return code, message) -- the rules of a value network on the host alone (no GPU)."""
-    lib = load()
-    rc = lib.gs_value_mlp_check(C.byref(p), None if o is None else C.byref(o), int(obs_dim))
-    return rc, ("" if rc == GS_OK else lib.gs_last_error(None).decode())
+    return _host_check("gs_value_mlp_check", C.byref(p), None if o is None else C.byref(o), int(obs_dim))
 
 
 MESH_ITEM_DTYPE = np.dtype([("vk_off", "<i4"), ("vj_off", "<i4"), ("xk_off", "<i4"), ("xj_off", "<i4"), ("flags", "<i4"), ("cq_off", "<i4"),
@@ -678,16 +682,21 @@ class Handle:
     def last_error(self) -> str:
         return self._lib.gs_last_error(self._h).decode()
 
+    def _instance_mask(self, mask) -> Optional[np.ndarray]:
+        """``mask`` (None: every instance) as the uint8 [B] array the per-instance setters pass on."""
+        if mask is None:
+            return None
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        if mk.shape != (self.B,):
+            raise PowerFlowError(f"mask must have shape ({self.B},)")
+        return mk
+
     # -- per-instance line impedances (gs_set_line_impedances / gs_get_line_impedances) --------------------------------------
     def set_line_impedances(self, r: np.ndarray, x: np.ndarray, mask: Optional[np.ndarray] = None) -> None:
         r, x = _f64(r), _f64(x)
         if r.shape != (self.B, self.m) or x.shape != (self.B, self.m):
             raise PowerFlowError(f"line impedances must have shape {(self.B, self.m)}")
-        mk = None
-        if mask is not None:
-            mk = np.ascontiguousarray(mask, dtype=np.uint8)
-            if mk.shape != (self.B,):
-                raise PowerFlowError(f"mask must have shape ({self.B},)")
+        mk = self._instance_mask(mask)
         self._check(self._lib.gs_set_line_impedances(self._h, _ptr(r, _dp), _ptr(x, _dp), None if mk is None else _ptr(mk, _up)))
 
     def get_line_impedances(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -700,11 +709,7 @@ class Handle:
         pl = _f64(load_powers)
         if pl.shape != (self.B, int(self.spec.n_loads)):
             raise PowerFlowError(f"load powers must have shape {(self.B, int(self.spec.n_loads))}")
-        mk = None
-        if mask is not None:
-            mk = np.ascontiguousarray(mask, dtype=np.uint8)
-            if mk.shape != (self.B,):
-                raise PowerFlowError(f"mask must have shape ({self.B},)")
+        mk = self._instance_mask(mask)
         self._check(self._lib.gs_set_load_powers(self._h, _ptr(pl, _dp), None if mk is None else _ptr(mk, _up)))
 
     def get_load_powers(self) -> np.ndarray:
@@ -1105,14 +1110,13 @@ class Handle:
         """Host copies (gs_rollout_onpolicy_download) of the arrays named in ``want``; ``terminal_values`` needs ``n_terminal`` (what
         ``rollout_download`` reported) or asks for it."""
         T, B = getattr(self, "_rollout_T", 0), self.B
-        out = {}
         for k in want:
             if k not in ONPOLICY_KEYS:
                 raise PowerFlowError(f"rollout_onpolicy_download: unknown array {k!r}")
-            if k == "terminal_values":
-                out[k] = np.empty(int(self.rollout_device_view().n_terminal if n_terminal is None else n_terminal))
-            else:
-                out[k] = np.empty((T + 1, B) if k == "values" else (T, B))
+        if "terminal_values" in want and n_terminal is None:
+            n_terminal = int(self.rollout_device_view().n_terminal)
+        shapes = dict(_critic_shapes(T, B, n_terminal), log_probs=(T, B))
+        out = {k: np.empty(shapes[k]) for k in want}
         v = gs_rollout_onpolicy_host(*[_ptr(out.get(k), _dp) for k in ONPOLICY_KEYS])
         self._check(self._lib.gs_rollout_onpolicy_download(self._h, C.byref(v)))
         return out
@@ -1164,7 +1168,7 @@ class Handle:
         v = self.rollout_costs_view(stream)
         T, B = int(v.T), int(v.B)
         n = int(self.rollout_device_view().n_terminal)
-        shapes = dict(values=(T + 1, B), terminal_values=(n,), advantages=(T, B), returns=(T, B))
+        shapes = _critic_shapes(T, B, n)
         out = dict(margins=DeviceArray(v.margins, (3, T, B), "<f8"), counts=DeviceArray(v.counts, (3, T, B), "<i4"),
                    costs=DeviceArray(v.costs, (3, T, B), "<f8"), n_violating=DeviceArray(v.n_violating, (3,), "<i8"))
         for k in COST_CRITIC_KEYS:
@@ -1188,8 +1192,7 @@ class Handle:
             elif k in COST_CRITIC_KEYS:
                 if k == "terminal_values" and n_terminal is None:
                     n_terminal = int(self.rollout_device_view().n_terminal)
-                shape = {"values": (T + 1, B), "terminal_values": (n_terminal,)}.get(k, (T, B))
-                out[k] = [np.empty(shape) if c in channels else None for c in range(3)]
+                out[k] = [np.empty(_critic_shapes(T, B, n_terminal)[k]) if c in channels else None for c in range(3)]
                 for c in channels:
                     getattr(v, k)[c] = _ptr(out[k][c], _dp)
             else:

@@ -108,19 +108,16 @@ int gs_checks_create(gs_handle* h, const gs_checks_config* cfg, gs_checks** out)
   C.row_vm = h->R.VM.base; C.row_qload = h->R.LOAD; C.row_flow = h->R.FLOW.base;
   C.row_cload = cfg->loading_source ? h->R.ENVLOAD.base : h->R.LOAD; C.stride_cload = cfg->loading_source ? 2 : 1;
   C.row_freq = h->R.FREQ; C.row_conv = h->R.CONV; C.row_iters = h->R.ITERS; C.row_maxmis = h->R.MAXMIS;
-  const size_t Bp = h->Bp;
-  bool ok = hipMalloc((void**)&c->prev, (size_t)h->groups * (h->n + 1) * GS_LANES * sizeof(double)) == hipSuccess &&
-            hipMalloc((void**)&c->state, 3 * Bp * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc((void**)&c->out_i, (size_t)GS_CI_COUNT * Bp * sizeof(int32_t)) == hipSuccess &&
-            hipMalloc((void**)&c->out_f, (size_t)GS_CF_COUNT * Bp * sizeof(double)) == hipSuccess &&
-            hipMalloc((void**)&c->bus_mask, std::max<size_t>(1, (size_t)h->groups * h->n * GS_LANES)) == hipSuccess &&
-            hipMalloc((void**)&c->line_mask, std::max<size_t>(1, (size_t)h->groups * h->m * GS_LANES)) == hipSuccess &&
-            hipMalloc((void**)&c->freq, Bp * sizeof(double)) == hipSuccess;
-  ok = ok && hipMemset(c->prev, 0, (size_t)h->groups * (h->n + 1) * GS_LANES * sizeof(double)) == hipSuccess &&
-       hipMemset(c->state, 0, 3 * Bp * sizeof(int32_t)) == hipSuccess && hipMemset(c->out_i, 0, (size_t)GS_CI_COUNT * Bp * sizeof(int32_t)) == hipSuccess &&
-       hipMemset(c->out_f, 0, (size_t)GS_CF_COUNT * Bp * sizeof(double)) == hipSuccess &&
-       hipDeviceSynchronize() == hipSuccess;        // (done before the check kernels, which run on the handle's non-blocking stream)
-  if (!ok) { gs_checks_destroy(c); return fail(h, GS_E_NOMEM, "device allocation for the checks failed"); }
+  const size_t Bp = h->Bp, prev_n = (size_t)h->groups * (h->n + 1) * GS_LANES;
+  int rc = alloc_all(h, "the checks' buffers", c->prev.want(prev_n), c->state.want(3 * Bp), c->out_i.want((size_t)GS_CI_COUNT * Bp),
+                     c->out_f.want((size_t)GS_CF_COUNT * Bp), c->bus_mask.want((size_t)h->groups * h->n * GS_LANES),
+                     c->line_mask.want((size_t)h->groups * h->m * GS_LANES), c->freq.want(Bp));
+  if (rc) { gs_checks_destroy(c); return rc; }
+  const bool ok = hipMemset(c->prev, 0, prev_n * sizeof(double)) == hipSuccess &&
+                  hipMemset(c->state, 0, 3 * Bp * sizeof(int32_t)) == hipSuccess && hipMemset(c->out_i, 0, (size_t)GS_CI_COUNT * Bp * sizeof(int32_t)) == hipSuccess &&
+                  hipMemset(c->out_f, 0, (size_t)GS_CF_COUNT * Bp * sizeof(double)) == hipSuccess &&
+                  hipDeviceSynchronize() == hipSuccess;        // (done before the check kernels, which run on the handle's non-blocking stream)
+  if (!ok) { gs_checks_destroy(c); return fail(h, GS_E_HIP, "zeroing the checks' buffers failed"); }
   *out = c;
   return GS_OK;
 }
@@ -131,8 +128,7 @@ void gs_checks_destroy(gs_checks* c) {
   (void)hipSetDevice(c->h->device);
   (void)hipStreamSynchronize(c->h->stream);
   for (auto& e : c->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  dev_free(c->prev); dev_free(c->state); dev_free(c->out_i); dev_free(c->out_f); dev_free(c->bus_mask); dev_free(c->line_mask); dev_free(c->freq);
-  delete c;
+  delete c;      // (its buffers with it: the device is current and the stream idle)
 }
 
 int gs_checks_set_frequency(gs_checks* c, const double* f) {
@@ -161,8 +157,8 @@ int gs_checks_run(gs_checks* c) {
     e = &c->ev[c->ev_used++];
     HIPCHK(h, hipEventRecord(e->first, h->stream));
   }
-  hipLaunchKernelGGL(gs_k_checks, dim3(h->groups), dim3(1024), 0, h->stream, c->C, h->slab, c->use_freq ? c->freq : (const double*)nullptr,
-                     c->prev, c->state, c->out_i, c->out_f, c->bus_mask, c->line_mask, h->B, h->Bp);
+  hipLaunchKernelGGL(gs_k_checks, dim3(h->groups), dim3(1024), 0, h->stream, c->C, h->slab, c->use_freq ? c->freq.p : (const double*)nullptr,
+                     c->prev.p, c->state.p, c->out_i.p, c->out_f.p, c->bus_mask.p, c->line_mask.p, h->B, h->Bp);
   HIPCHK(h, hipGetLastError());
   if (e) HIPCHK(h, hipEventRecord(e->second, h->stream));
   return GS_OK;
@@ -196,14 +192,14 @@ int gs_checks_reset(gs_checks* c, const uint8_t* mask) {
   if (!c) return fail(nullptr, GS_E_INVALID, "checks object is NULL");
   gs_handle* h = c->h;
   GS_ENTER(h);
-  uint8_t* dmask = nullptr;
+  DevBuf<uint8_t> dmask;
   if (mask) {
-    HIPCHK(h, hipMalloc((void**)&dmask, h->B));
-    if (hipMemcpyAsync(dmask, mask, h->B, hipMemcpyHostToDevice, h->stream) != hipSuccess) { (void)hipFree(dmask); return fail(h, GS_E_HIP, "mask upload failed"); }
+    int rc = dmask.alloc(h, h->B, "the checks' reset mask");
+    if (rc) return rc;
+    if (hipMemcpyAsync(dmask, mask, h->B, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, GS_E_HIP, "mask upload failed");
   }
-  hipLaunchKernelGGL(gs_k_checks_reset, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, c->state, (const uint8_t*)dmask, h->B, h->Bp);
-  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(h->stream);
-  if (dmask) (void)hipFree(dmask);
+  hipLaunchKernelGGL(gs_k_checks_reset, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, c->state.p, (const uint8_t*)dmask.p, h->B, h->Bp);
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(h->stream);      // (before `dmask` goes)
   if (e1 != hipSuccess || e2 != hipSuccess) return fail(h, GS_E_HIP, "checks reset failed");
   return GS_OK;
 }

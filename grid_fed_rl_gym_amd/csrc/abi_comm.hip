@@ -308,12 +308,8 @@ int gs_allgather_obs_view(gs_handle* h, gs_gathered_obs* out, void* consumer_str
   if (!h->d_obs_full) return fail(h, GS_E_STATE, "no communicator on this handle");
   if (h->loop && h->loop->arrived[h->rank]) return fail(h, GS_E_STATE, "the gather of this round is not complete: not every member has called gs_allgather_obs");
   HIPCHK(h, hipSetDevice(h->device));
-  if (consumer_stream) {
-    HIPCHK(h, hipEventRecord(h->ev_full, h->comm_stream));
-    HIPCHK(h, hipStreamWaitEvent(peer_stream(consumer_stream), h->ev_full, 0));
-  } else {
-    HIPCHK(h, hipStreamSynchronize(h->comm_stream));
-  }
+  int rc = publish(h, h->comm_stream, h->ev_full, consumer_stream);
+  if (rc) return rc;
   out->observations = h->d_obs_full; out->rows = (int64_t)h->world * h->B; out->obs_dim = h->obs_dim;
   out->rank = h->rank; out->world = h->world; out->reserved = 0;
   return GS_OK;

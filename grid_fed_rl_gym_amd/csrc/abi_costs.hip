@@ -1,7 +1,7 @@
 // abi_costs.hip -- constraint costs of a rollout (include/gridstep.h): gs_cost_config_*, gs_rollout_costs and
-// gs_costs_eval (gs_k_costs, kernels_costs.hip), the cost critics (gs_cost_value_mlp_set: value networks, installed and launched
-// through abi_onpolicy.hip's helpers), gs_rollout_evaluate_costs and the views of what they left.  The rollout's constraint arrays
-// and the cost critics' arrays are made here and released here (costs_release; the networks themselves go with value_release).
+// gs_costs_eval (gs_k_costs, kernels_costs.hip), the cost critics (gs_cost_value_mlp_set, gs_rollout_evaluate_costs: critics
+// 1 .. 3 of abi_onpolicy.hip's critic track, which owns their networks and arrays) and the views of what they left.  The rollout's
+// constraint arrays are made here and released here (costs_release).
 #include <cmath>
 #include <string>
 
@@ -13,10 +13,9 @@ namespace gsi __attribute__((visibility("hidden"))) {
 
 void costs_release(gs_handle* h) {
   gs_handle::Costs& cs = h->cc;
-  dev_free(cs.margins); dev_free(cs.counts); dev_free(cs.costs); dev_free(cs.n_viol);
-  dev_free(cs.values); dev_free(cs.term_values); dev_free(cs.adv); dev_free(cs.ret);
+  cs.margins.release(); cs.counts.release(); cs.costs.release(); cs.n_viol.release();
   if (cs.ev) { (void)hipEventDestroy(cs.ev); cs.ev = nullptr; }
-  cs.computed_on = cs.evaluated_on = 0;
+  cs.computed_on = 0;
 }
 
 }  // namespace gsi
@@ -102,14 +101,9 @@ int gs_rollout_costs(gs_handle* h, const gs_cost_config* c) {
   GS_ENTER(h);
   gs_handle::Costs& cs = h->cc;
   const size_t B = h->B, T = ro.T, TB = T * B;
-  if (!cs.margins) {         // sized by the rollout's capacity; released with it (costs_release)
+  if (!cs.margins) {         // sized by the rollout's capacity; released with it (costs_release); all four or none
     const size_t cap = (size_t)GS_COST_CHANNELS * ro.T_cap * B;
-    if (hipMalloc((void**)&cs.margins, cap * sizeof(double)) != hipSuccess || hipMalloc((void**)&cs.counts, cap * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&cs.costs, cap * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&cs.n_viol, GS_COST_CHANNELS * sizeof(unsigned long long)) != hipSuccess) {
-      dev_free(cs.margins); dev_free(cs.counts); dev_free(cs.costs); dev_free(cs.n_viol);      // all four or none
-      return fail(h, GS_E_NOMEM, "constraint arrays for T = %d do not fit", ro.T_cap);
-    }
+    if ((rc = alloc_all(h, "the rollout's constraint arrays", cs.margins.want(cap), cs.counts.want(cap), cs.costs.want(cap), cs.n_viol.want(GS_COST_CHANNELS)))) return rc;
   }
   cs.computed_on = 0;        // (until both launches are queued)
   HIPCHK(h, hipMemsetAsync(cs.n_viol, 0, GS_COST_CHANNELS * sizeof(unsigned long long), h->stream));
@@ -143,19 +137,19 @@ int gs_costs_eval(gs_handle* h, const gs_cost_config* c, const double* obs_host,
   GS_ENTER(h);
   const size_t R = (size_t)rows, obs_bytes = R * h->obs_dim * sizeof(double), out8 = R * GS_COST_CHANNELS * sizeof(double);
   // one allocation for the call: the rows, then margins, costs and counts [rows][3]
-  char* buf = nullptr;
-  if (hipMalloc((void**)&buf, obs_bytes + 2 * out8 + out8 / 2) != hipSuccess) return fail(h, GS_E_NOMEM, "gs_costs_eval: %d rows do not fit", rows);
+  DevBuf<char> buf;
+  if ((rc = buf.alloc(h, obs_bytes + 2 * out8 + out8 / 2, "gs_costs_eval's rows"))) return rc;
   GsCostArgs a = cost_args(h, *c);
-  a.obs = (const double*)buf;
+  a.obs = (const double*)buf.p;
   a.margins = (double*)(buf + obs_bytes); a.costs = (double*)(buf + obs_bytes + out8); a.counts = (int32_t*)(buf + obs_bytes + 2 * out8);
   a.chan_stride = 1; a.row_stride = GS_COST_CHANNELS;
   hipError_t e = hipMemcpyAsync(buf, obs_host, obs_bytes, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) { rc = launch_costs(h, a, rows); if (rc) { (void)hipStreamSynchronize(h->stream); (void)hipFree(buf); return rc; } }
-  if (e == hipSuccess && margins_host) e = hipMemcpyAsync(margins_host, a.margins, out8, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && costs_host) e = hipMemcpyAsync(costs_host, a.costs, out8, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && counts_host) e = hipMemcpyAsync(counts_host, a.counts, out8 / 2, hipMemcpyDeviceToHost, h->stream);
-  const hipError_t es = hipStreamSynchronize(h->stream);
-  (void)hipFree(buf);
+  if (e == hipSuccess) rc = launch_costs(h, a, rows);
+  if (e == hipSuccess && !rc && margins_host) e = hipMemcpyAsync(margins_host, a.margins, out8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && !rc && costs_host) e = hipMemcpyAsync(costs_host, a.costs, out8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && !rc && counts_host) e = hipMemcpyAsync(counts_host, a.counts, out8 / 2, hipMemcpyDeviceToHost, h->stream);
+  const hipError_t es = hipStreamSynchronize(h->stream);      // (before `buf` goes)
+  if (rc) return rc;
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail(h, GS_E_HIP, "gs_costs_eval failed: %s", hipGetErrorString(e));
   return GS_OK;
@@ -169,53 +163,32 @@ int gs_cost_value_mlp_set(gs_handle* h, int32_t channel, const gs_policy_mlp* p,
     const std::string why = gs_value_check(p, o, h->obs_dim);
     if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
   }
-  return value_install(h, h->cost_val[channel], p, o, false);
+  return value_install(h, h->critic[1 + channel].net, p, o, false);
 }
 
 int gs_rollout_evaluate_costs(gs_handle* h, const gs_cost_gae_config* cfg) {
   if (!h || !cfg) return fail(h, GS_E_INVALID, "handle / config is NULL");
   if (cfg->struct_size != (int32_t)sizeof(gs_cost_gae_config))
     return fail(h, GS_E_INVALID, "gs_cost_gae_config struct_size %d != %d", cfg->struct_size, (int)sizeof(gs_cost_gae_config));
-  if (cfg->bootstrap_mask < 0 || cfg->bootstrap_mask > 3) return fail(h, GS_E_INVALID, "bootstrap_mask %d outside 0 .. 3", cfg->bootstrap_mask);
+  int rc = GS_OK;
   for (int c = 0; c < GS_COST_CHANNELS; ++c)
-    if (!std::isfinite(cfg->gamma[c]) || !std::isfinite(cfg->lambda[c]) || !std::isfinite(cfg->cost_shift[c]) || !std::isfinite(cfg->cost_scale[c]))
-      return fail(h, GS_E_INVALID, "gamma / lambda / cost_shift / cost_scale must be finite");
+    if ((rc = gae_check(h, cfg->bootstrap_mask, cfg->gamma[c], cfg->lambda[c], cfg->cost_shift[c], cfg->cost_scale[c], "cost"))) return rc;
   gs_handle::Rollout& ro = h->ro;
   gs_handle::Costs& cs = h->cc;
+  gs_handle::Critic* const critic = h->critic + 1;      // [channel]
   if (ro.T <= 0 || ro.calls == 0) return fail(h, GS_E_STATE, "gs_rollout_evaluate_costs: no rollout has been collected on this handle");
   if (!cs.computed_on || cs.computed_on != ro.calls) return fail(h, GS_E_STATE, "gs_rollout_evaluate_costs: gs_rollout_costs has not run on the last rollout");
   bool any = false;
-  for (const gs_handle::Value& v : h->cost_val) any = any || v.set;
+  for (int c = 0; c < GS_COST_CHANNELS; ++c) any = any || critic[c].net.set;
   if (!any) return fail(h, GS_E_STATE, "gs_rollout_evaluate_costs before gs_cost_value_mlp_set");
   GS_ENTER(h);
-  const size_t B = h->B, T = ro.T, TB = T * B;
-  const size_t vcap = (size_t)(ro.T_cap + 1) * B, tcap = (size_t)std::max(ro.term_cap, 1), acap = (size_t)ro.T_cap * B;
-  if (!cs.values) {          // sized by the rollout's capacity; released with it
-    if (hipMalloc((void**)&cs.values, GS_COST_CHANNELS * vcap * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&cs.term_values, GS_COST_CHANNELS * tcap * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&cs.adv, GS_COST_CHANNELS * acap * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&cs.ret, GS_COST_CHANNELS * acap * sizeof(double)) != hipSuccess) {
-      dev_free(cs.values); dev_free(cs.term_values); dev_free(cs.adv); dev_free(cs.ret);      // all four or none
-      return fail(h, GS_E_NOMEM, "cost critic arrays for T = %d do not fit", ro.T_cap);
-    }
-  }
-  cs.evaluated_on = 0;
-  for (int c = 0; c < GS_COST_CHANNELS; ++c) {
-    cs.evaluated[c] = false;
-    const gs_handle::Value& val = h->cost_val[c];
-    if (!val.set) continue;
-    double* values = cs.values + c * vcap; double* ret = cs.ret + c * acap;
-    int rc = launch_value(h, val, ro.obs_seq, values, (long long)((T + 1) * B));
-    if (rc) return rc;
-    // (the terminal values also go to their (t, b) in this channel's `ret`, where gs_k_gae looks for them: gs_rollout_evaluate)
-    if ((rc = launch_value(h, val, ro.term_obs, cs.term_values + c * tcap, ro.term_cap, ro.term_count, ro.term_idx, ret, (int)T))) return rc;
-    GsGaeArgs g{values, cs.costs + c * TB, ro.done, cs.adv + c * acap, ret, (int32_t)T, h->B, cfg->bootstrap_mask, 0,
-                cfg->gamma[c], cfg->lambda[c], cfg->cost_shift[c], cfg->cost_scale[c]};
-    hipLaunchKernelGGL(gs_k_gae, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, g);
-    HIPCHK(h, hipGetLastError());
-    cs.evaluated[c] = true;
-  }
-  cs.evaluated_on = ro.calls;
+  // no channel counts as evaluated until every launch of this call is queued -- one whose critic has been removed never again
+  for (int c = 0; c < GS_COST_CHANNELS; ++c) critic[c].evaluated_on = 0;
+  const size_t TB = (size_t)ro.T * h->B;
+  for (int c = 0; c < GS_COST_CHANNELS; ++c)
+    if (critic[c].net.set && (rc = critic_evaluate(h, critic[c], cs.costs + c * TB, cfg->bootstrap_mask, cfg->gamma[c], cfg->lambda[c],
+                                                   cfg->cost_shift[c], cfg->cost_scale[c]))) return rc;
+  for (int c = 0; c < GS_COST_CHANNELS; ++c) if (critic[c].net.set) critic[c].evaluated_on = ro.calls;
   return GS_OK;
 }
 
@@ -228,22 +201,14 @@ int gs_rollout_costs_view(gs_handle* h, gs_rollout_costs_dev* out, void* consume
   if (!cs.computed_on || cs.computed_on != ro.calls) return fail(h, GS_E_STATE, "gs_rollout_costs has not run on the last rollout");
   int rc = rollout_finish(h);      // (waits for the rollout, not for the costs)
   if (rc) return rc;
-  if (consumer_stream) {
-    if (!cs.ev) HIPCHK(h, hipEventCreateWithFlags(&cs.ev, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(cs.ev, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(peer_stream(consumer_stream), cs.ev, 0));
-  } else {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  if ((rc = publish(h, h->stream, cs.ev, consumer_stream))) return rc;
   *out = gs_rollout_costs_dev{};
   out->T = ro.T; out->B = h->B;
-  out->margins = cs.margins; out->counts = cs.counts; out->costs = cs.costs; out->n_violating = (const int64_t*)cs.n_viol;
-  const bool evaluated = cs.evaluated_on && cs.evaluated_on == ro.calls;
-  const size_t B = h->B, vcap = (size_t)(ro.T_cap + 1) * B, tcap = (size_t)std::max(ro.term_cap, 1), acap = (size_t)ro.T_cap * B;
+  out->margins = cs.margins; out->counts = cs.counts; out->costs = cs.costs; out->n_violating = (const int64_t*)cs.n_viol.p;
   for (int c = 0; c < GS_COST_CHANNELS; ++c) {
-    if (!evaluated || !cs.evaluated[c]) continue;
-    out->values[c] = cs.values + c * vcap; out->terminal_values[c] = cs.term_values + c * tcap;
-    out->advantages[c] = cs.adv + c * acap; out->returns[c] = cs.ret + c * acap;
+    const gs_handle::Critic& k = h->critic[1 + c];
+    if (!critic_current(h, k)) continue;
+    out->values[c] = k.values; out->terminal_values[c] = k.term_values; out->advantages[c] = k.adv; out->returns[c] = k.ret;
   }
   return GS_OK;
 }
@@ -254,25 +219,19 @@ int gs_rollout_costs_download(gs_handle* h, const gs_rollout_costs_host* out) {
   gs_handle::Costs& cs = h->cc;
   if (ro.T <= 0) return fail(h, GS_E_STATE, "no rollout has been collected on this handle");
   if (!cs.computed_on || cs.computed_on != ro.calls) return fail(h, GS_E_STATE, "gs_rollout_costs has not run on the last rollout");
-  const bool evaluated = cs.evaluated_on && cs.evaluated_on == ro.calls;
   for (int c = 0; c < GS_COST_CHANNELS; ++c)
-    if ((out->values[c] || out->terminal_values[c] || out->advantages[c] || out->returns[c]) && !(evaluated && cs.evaluated[c]))
+    if ((out->values[c] || out->terminal_values[c] || out->advantages[c] || out->returns[c]) && !critic_current(h, h->critic[1 + c]))
       return fail(h, GS_E_STATE, "gs_rollout_evaluate_costs has not run on the last rollout with a critic for channel %d", c);
   int rc = rollout_finish(h);
   if (rc) return rc;
-  const size_t B = h->B, TB = (size_t)ro.T * B, TB8 = TB * sizeof(double), B8 = B * sizeof(double);
-  const size_t vcap = (size_t)(ro.T_cap + 1) * B, tcap = (size_t)std::max(ro.term_cap, 1), acap = (size_t)ro.T_cap * B;
+  const size_t TB = (size_t)ro.T * h->B, TB8 = TB * sizeof(double);
   const hipMemcpyKind d2h = hipMemcpyDeviceToHost;
   if (out->margins) HIPCHK(h, hipMemcpyAsync(out->margins, cs.margins, GS_COST_CHANNELS * TB8, d2h, h->stream));
   if (out->counts) HIPCHK(h, hipMemcpyAsync(out->counts, cs.counts, GS_COST_CHANNELS * TB * sizeof(int32_t), d2h, h->stream));
   if (out->costs) HIPCHK(h, hipMemcpyAsync(out->costs, cs.costs, GS_COST_CHANNELS * TB8, d2h, h->stream));
   if (out->n_violating) HIPCHK(h, hipMemcpyAsync(out->n_violating, cs.n_viol, GS_COST_CHANNELS * sizeof(int64_t), d2h, h->stream));
-  for (int c = 0; c < GS_COST_CHANNELS; ++c) {
-    if (out->values[c]) HIPCHK(h, hipMemcpyAsync(out->values[c], cs.values + c * vcap, TB8 + B8, d2h, h->stream));
-    if (out->terminal_values[c] && ro.n_term) HIPCHK(h, hipMemcpyAsync(out->terminal_values[c], cs.term_values + c * tcap, (size_t)ro.n_term * sizeof(double), d2h, h->stream));
-    if (out->advantages[c]) HIPCHK(h, hipMemcpyAsync(out->advantages[c], cs.adv + c * acap, TB8, d2h, h->stream));
-    if (out->returns[c]) HIPCHK(h, hipMemcpyAsync(out->returns[c], cs.ret + c * acap, TB8, d2h, h->stream));
-  }
+  for (int c = 0; c < GS_COST_CHANNELS; ++c)
+    if ((rc = critic_download(h, h->critic[1 + c], out->values[c], out->terminal_values[c], out->advantages[c], out->returns[c]))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return GS_OK;
 }

@@ -12,14 +12,13 @@ namespace gsi __attribute__((visibility("hidden"))) {
 
 void dataset_release(gs_handle* h, bool keep_stats) {
   gs_handle::Dataset& ds = h->ds;
-  dev_free(ds.part); ds.part_doubles = 0;
-  dev_free(ds.map); ds.map_cap = 0;
+  ds.part.release(); ds.map.release();
   ds.built_on = 0;
   if (keep_stats) return;
-  dev_free(ds.stats); ds.have_stats = false;
-  dev_free(ds.idx); ds.idx_cap = 0;
+  ds.stats.release(); ds.have_stats = false;
+  ds.idx.release();
   if (ds.h_idx) { (void)hipHostFree(ds.h_idx); ds.h_idx = nullptr; }
-  for (int k = 0; k < 5; ++k) { dev_free(ds.batch[k]); ds.batch_bytes[k] = 0; }
+  for (DevBuf<char>& b : ds.batch) b.release();
   if (ds.ev_idx) { (void)hipEventDestroy(ds.ev_idx); ds.ev_idx = nullptr; }
   if (ds.ev_batch) { (void)hipEventDestroy(ds.ev_batch); ds.ev_batch = nullptr; }
   ds.idx_pending = false;
@@ -30,10 +29,7 @@ void dataset_release(gs_handle* h, bool keep_stats) {
 static inline int ds_ct(const gs_handle* h) { return h->obs_dim + h->action_dim + 1; }
 static inline int ds_cs(const gs_handle* h) { return (ds_ct(h) + 1) & ~1; }
 
-static int ds_stats_ensure(gs_handle* h) {
-  if (!h->ds.stats) HIPCHK(h, hipMalloc((void**)&h->ds.stats, (size_t)2 * ds_cs(h) * sizeof(double)));
-  return GS_OK;
-}
+static int ds_stats_ensure(gs_handle* h) { return h->ds.stats.grow(h, (size_t)2 * ds_cs(h), "the dataset's statistics"); }
 
 // the dataset is built on the rollout the handle holds now
 static int ds_current(gs_handle* h, const char* who) {
@@ -58,31 +54,20 @@ int gs_dataset_build(gs_handle* h, uint32_t flags) {
   GS_ENTER(h);
   const int D = h->obs_dim, A = h->action_dim, Ct = ds_ct(h);
   // the map: -1, then the rollout's terminal list scattered (the list's length is read on the device: no host round trip)
-  if (ds.map_cap < (size_t)N) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    dev_free(ds.map); ds.map_cap = 0;
-    HIPCHK(h, hipMalloc((void**)&ds.map, (size_t)N * sizeof(int32_t)));
-    ds.map_cap = (size_t)N;
-  }
   ds.built_on = 0;
-  hipLaunchKernelGGL(gs_k_ds_map_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, ds.map, N);
+  int rc = ds.map.grow(h, (size_t)N, "the dataset's terminal map");
+  if (rc) return rc;
+  hipLaunchKernelGGL(gs_k_ds_map_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, ds.map.p, N);
   HIPCHK(h, hipGetLastError());
   if (ro.term_cap > 0) {
-    hipLaunchKernelGGL(gs_k_ds_map_scatter, dim3((unsigned)((ro.term_cap + 255) / 256)), dim3(256), 0, h->stream, ds.map, ro.term_count, ro.term_idx,
+    hipLaunchKernelGGL(gs_k_ds_map_scatter, dim3((unsigned)((ro.term_cap + 255) / 256)), dim3(256), 0, h->stream, ds.map.p, ro.term_count.p, ro.term_idx.p,
                        ro.term_cap, ro.T, h->B);
     HIPCHK(h, hipGetLastError());
   }
   if (!keep) {
-    int rc = ds_stats_ensure(h);
-    if (rc) return rc;
+    if ((rc = ds_stats_ensure(h))) return rc;
     const long long chunks = (N + GS_DS_ROWS_PER_CHUNK - 1) / GS_DS_ROWS_PER_CHUNK;
-    const size_t need = (size_t)chunks * Ct * 2;
-    if (ds.part_doubles < need) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      dev_free(ds.part); ds.part_doubles = 0;
-      HIPCHK(h, hipMalloc((void**)&ds.part, need * sizeof(double)));
-      ds.part_doubles = need;
-    }
+    if ((rc = ds.part.grow(h, (size_t)chunks * Ct * 2, "the dataset's partial statistics"))) return rc;
     GsDsStatArgs S{};
     const auto panels = [](int C) { return C <= 0 ? 0 : ((C & 1) ? (C + 63) / 64 : (C / 2 + 63) / 64); };
     S.m[0] = GsDsMatrix{ro.obs_seq, D, 0, panels(D), 0};
@@ -98,7 +83,7 @@ int gs_dataset_build(gs_handle* h, uint32_t flags) {
       const long long nodes = (chunks + stride - 1) / stride, groups = (nodes + 15) / 16;
       const bool last = groups == 1;
       const long long threads = groups * Ct;
-      hipLaunchKernelGGL(gs_k_ds_merge, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, ds.part, chunks, Ct, stride, N,
+      hipLaunchKernelGGL(gs_k_ds_merge, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, ds.part.p, chunks, Ct, stride, N,
                          S.m[0], S.m[1], S.m[2], last ? ds.stats : (double*)nullptr, last ? ds.stats + ds_cs(h) : (double*)nullptr);
       HIPCHK(h, hipGetLastError());
       if (last) break;
@@ -172,14 +157,15 @@ int gs_dataset_sample(gs_handle* h, int32_t n, const int64_t* indices, uint64_t 
   if ((rc = ds_stats_ensure(h))) return rc;
   const int D = h->obs_dim, A = h->action_dim;
   if (!ds.ev_idx) HIPCHK(h, hipEventCreateWithFlags(&ds.ev_idx, hipEventDisableTiming));
-  if (ds.idx_cap < n) {
+  if (ds.idx.cap < (size_t)n) {      // idx and its page-locked twin grow together: both, or neither is left
     HIPCHK(h, hipStreamSynchronize(h->stream));
     ds.idx_pending = false;
-    dev_free(ds.idx); ds.idx_cap = 0;
     if (ds.h_idx) { (void)hipHostFree(ds.h_idx); ds.h_idx = nullptr; }
-    HIPCHK(h, hipMalloc((void**)&ds.idx, (size_t)n * sizeof(int32_t)));
-    HIPCHK(h, hipHostMalloc((void**)&ds.h_idx, (size_t)n * sizeof(int32_t), hipHostMallocDefault));
-    ds.idx_cap = n;
+    if ((rc = ds.idx.alloc(h, (size_t)n, "the dataset's sample indices"))) return rc;
+    if (hipHostMalloc((void**)&ds.h_idx, (size_t)n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+      ds.h_idx = nullptr; ds.idx.release(); (void)hipGetLastError();
+      return fail(h, GS_E_NOMEM, "the dataset's sample indices: %zu page-locked bytes do not fit", (size_t)n * sizeof(int32_t));
+    }
   }
   // the handle's own output buffers, where the caller gave none (grown before anything of this call is queued)
   const size_t esz = dtype == GS_COMPUTE_F32 ? sizeof(float) : sizeof(double);
@@ -189,14 +175,8 @@ int gs_dataset_sample(gs_handle* h, int32_t n, const int64_t* indices, uint64_t 
   for (int k = 0; k < 5; ++k) {
     dst[k] = *slots[k];
     if (dst[k]) continue;
-    const size_t bytes = (size_t)n * widths[k] * esz;
-    if (ds.batch_bytes[k] < bytes) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      dev_free(ds.batch[k]); ds.batch_bytes[k] = 0;
-      HIPCHK(h, hipMalloc(&ds.batch[k], bytes));
-      ds.batch_bytes[k] = bytes;
-    }
-    dst[k] = ds.batch[k];
+    if ((rc = ds.batch[k].grow(h, (size_t)n * widths[k] * esz, "the dataset's batch"))) return rc;
+    dst[k] = ds.batch[k].p;
   }
   if (indices) {
     if (ds.idx_pending) { HIPCHK(h, hipEventSynchronize(ds.ev_idx)); ds.idx_pending = false; }   // the staging copy of the call before
@@ -205,7 +185,7 @@ int gs_dataset_sample(gs_handle* h, int32_t n, const int64_t* indices, uint64_t 
     HIPCHK(h, hipEventRecord(ds.ev_idx, h->stream));
     ds.idx_pending = true;
   } else {
-    hipLaunchKernelGGL(gs_k_ds_draw, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, h->stream, ds.idx, (int)n, N, seed, draw);
+    hipLaunchKernelGGL(gs_k_ds_draw, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, h->stream, ds.idx.p, (int)n, N, seed, draw);
     HIPCHK(h, hipGetLastError());
   }
   GsDsGatherArgs G{};
@@ -221,13 +201,7 @@ int gs_dataset_sample(gs_handle* h, int32_t n, const int64_t* indices, uint64_t 
   if (dtype == GS_COMPUTE_F32) hipLaunchKernelGGL(gs_k_ds_gather_f32, grid, block, 0, h->stream, G);
   else hipLaunchKernelGGL(gs_k_ds_gather_f64, grid, block, 0, h->stream, G);
   HIPCHK(h, hipGetLastError());
-  if (consumer_stream) {
-    if (!ds.ev_batch) HIPCHK(h, hipEventCreateWithFlags(&ds.ev_batch, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(ds.ev_batch, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(peer_stream(consumer_stream), ds.ev_batch, 0));
-  } else {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  if ((rc = publish(h, h->stream, ds.ev_batch, consumer_stream))) return rc;
   for (int k = 0; k < 5; ++k) *slots[k] = dst[k];
   return GS_OK;
 }

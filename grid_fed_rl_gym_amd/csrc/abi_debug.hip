@@ -174,13 +174,12 @@ int gs_debug_write_rows(gs_handle* h, int32_t which, const double* values) {
   const int C = debug_rows_map(h, which, map);
   if (C <= 0) return GS_OK;
   if ((size_t)h->B * C > h->in_doubles) return fail(h, GS_E_INVALID, "staging buffer too small");
-  int32_t* dmap = nullptr;
-  HIPCHK(h, hipMalloc((void**)&dmap, C * sizeof(int32_t)));
-  int rc = GS_OK;
+  DevBuf<int32_t> dmap;
+  int rc = dmap.alloc(h, C, "the row map");
+  if (rc) return rc;
   if (hipMemcpyAsync(dmap, map.data(), C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, GS_E_HIP, "map upload failed");
   if (!rc) rc = unpack_from_host(h, dmap, C, values);
-  const hipError_t e = hipStreamSynchronize(h->stream);
-  (void)hipFree(dmap);
+  const hipError_t e = hipStreamSynchronize(h->stream);      // (before `dmap` goes)
   if (!rc && e != hipSuccess) rc = fail(h, GS_E_HIP, "row write failed");
   return rc;
 }
@@ -193,13 +192,12 @@ int gs_debug_read_rows(gs_handle* h, int32_t which, double* values) {
   const int C = debug_rows_map(h, which, map);
   if (C <= 0) return GS_OK;
   if ((size_t)h->B * C > h->out_doubles) return fail(h, GS_E_INVALID, "staging buffer too small");
-  int32_t* dmap = nullptr;
-  HIPCHK(h, hipMalloc((void**)&dmap, C * sizeof(int32_t)));
-  int rc = GS_OK;
+  DevBuf<int32_t> dmap;
+  int rc = dmap.alloc(h, C, "the row map");
+  if (rc) return rc;
   if (hipMemcpyAsync(dmap, map.data(), C * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(h, GS_E_HIP, "map upload failed");
   if (!rc) rc = pack_to_host(h, dmap, C, values);
-  (void)hipStreamSynchronize(h->stream);
-  (void)hipFree(dmap);
+  (void)hipStreamSynchronize(h->stream);      // (before `dmap` goes)
   return rc;
 }
 

@@ -1,7 +1,8 @@
-// abi_onpolicy.hip -- on-policy rollouts (include/gridstep.h): the value network (gs_value_mlp_*), gs_rollout_evaluate and the
-// views of what it and the policy kernels' log-probability output left.  The value network's buffers and the rollout's on-policy
-// arrays are made here and released here (the log-probabilities are allocated by gs_rollout, abi_rollout.hip, which writes them).
-// The cost critics of abi_costs.hip are value networks too: installed and launched through value_install / launch_value, released here.
+// abi_onpolicy.hip -- on-policy rollouts (include/gridstep.h): the value network (gs_value_mlp_*), the critic track (a value
+// network's values, advantages and returns over the last rollout: gs_rollout_evaluate here, gs_rollout_evaluate_costs in
+// abi_costs.hip) and the views of what the reward critic and the policy kernels' log-probability output left.  The value networks
+// and every critic's arrays are made here and released here (the log-probabilities are allocated by gs_rollout, abi_rollout.hip,
+// which writes them).
 #include <cmath>
 #include <string>
 
@@ -9,53 +10,9 @@
 
 using namespace gsi;
 
-namespace gsi __attribute__((visibility("hidden"))) {
-
-void value_release(gs_handle* h) {
-  dev_free(h->val.blob);
-  dev_free(h->val.out);
-  h->val.set = false;
-  for (gs_handle::Value& v : h->cost_val) { dev_free(v.blob); dev_free(v.out); v.set = false; }
-}
-
-void onpolicy_release(gs_handle* h) {
-  gs_handle::Rollout& ro = h->ro;
-  dev_free(ro.logp); dev_free(ro.values); dev_free(ro.term_values); dev_free(ro.adv); dev_free(ro.ret);
-  if (ro.ev_eval) { (void)hipEventDestroy(ro.ev_eval); ro.ev_eval = nullptr; }
-  ro.logp_recorded = false; ro.evaluated_on = 0;
-}
-
-// what gs_value_mlp_set and gs_cost_value_mlp_set (abi_costs.hip) share: `p` has passed gs_value_check; NULL removes the network
-int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out) {
-  GS_ENTER(h);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  dev_free(val.blob);
-  val.set = false;
-  if (!p) return GS_OK;
-  if (want_out && !val.out) HIPCHK(h, hipMalloc((void**)&val.out, (size_t)h->B * sizeof(double)));
-  const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
-  val.lds = gs_val_lds_bytes(im.kb[0]);
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_value_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-  // one allocation: the float image (a multiple of 16 floats), then shift and scale
-  const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
-  HIPCHK(h, hipMalloc((void**)&val.blob, image_bytes + norm_bytes));
-  const float* image = val.blob;
-  const double* norm = (const double*)((const char*)val.blob + image_bytes);
-  HIPCHK(h, hipMemcpy((void*)image, im.blob.data(), image_bytes, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy((void*)norm, im.norm.data(), norm_bytes, hipMemcpyHostToDevice));
-  GsValueArgs& a = val.args;
-  a = GsValueArgs{};
-  a.shift = norm; a.scale = norm + 16 * im.kb[0];
-  a.D = h->obs_dim; a.n_layers = p->n_layers; a.activation = p->activation;
-  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
-  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
-  val.set = true;
-  return GS_OK;
-}
-
 // one launch over `rows` rows of obs (device pointers) on the handle's main stream; rows_dev / scatter_*: GsValueArgs
-int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev,
-                 const int32_t* scatter_idx, double* scatter_out, int scatter_T) {
+static int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
+                        const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0) {
   if (rows <= 0) return GS_OK;
   if (rows > 0x7fffffffLL - GS_VAL_ROWS) return fail(h, GS_E_INVALID, "%lld rows exceed the value kernel's 32-bit row index", rows);
   GsValueArgs a = val.args;
@@ -66,10 +23,80 @@ int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, d
   return GS_OK;
 }
 
+namespace gsi __attribute__((visibility("hidden"))) {
+
+void value_release(gs_handle* h) {
+  for (gs_handle::Critic& c : h->critic) { c.net.blob.release(); c.net.out.release(); c.net.set = false; }
+}
+
+void onpolicy_release(gs_handle* h) {
+  h->ro.logp.release();
+  for (gs_handle::Critic& c : h->critic) { c.values.release(); c.term_values.release(); c.adv.release(); c.ret.release(); c.evaluated_on = 0; }
+  if (h->ro.ev_eval) { (void)hipEventDestroy(h->ro.ev_eval); h->ro.ev_eval = nullptr; }
+  h->ro.logp_recorded = false;
+}
+
+// what gs_value_mlp_set and gs_cost_value_mlp_set (abi_costs.hip) share: `p` has passed gs_value_check; NULL removes the network
+int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out) {
+  GS_ENTER(h);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  val.blob.release();
+  val.set = false;
+  if (!p) return GS_OK;
+  int rc = want_out ? val.out.grow(h, (size_t)h->B, "the value network's output") : GS_OK;
+  if (rc) return rc;
+  const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
+  val.lds = gs_val_lds_bytes(im.kb[0]);
+  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_value_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
+  const float* image = nullptr; const double* norm = nullptr;
+  if ((rc = upload_image_f32(h, val.blob, im, &image, &norm))) return rc;
+  GsValueArgs& a = val.args;
+  a = GsValueArgs{};
+  a.shift = norm; a.scale = norm + 16 * im.kb[0];
+  a.D = h->obs_dim; a.n_layers = p->n_layers; a.activation = p->activation;
+  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
+  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
+  val.set = true;
+  return GS_OK;
+}
+
+int gae_check(gs_handle* h, int bootstrap_mask, double gamma, double lambda, double shift, double scale, const char* signal) {
+  if (bootstrap_mask < 0 || bootstrap_mask > 3) return fail(h, GS_E_INVALID, "bootstrap_mask %d outside 0 .. 3", bootstrap_mask);
+  if (!std::isfinite(gamma) || !std::isfinite(lambda) || !std::isfinite(shift) || !std::isfinite(scale))
+    return fail(h, GS_E_INVALID, "gamma / lambda / %s_shift / %s_scale must be finite", signal, signal);
+  return GS_OK;
+}
+
+int critic_evaluate(gs_handle* h, gs_handle::Critic& c, const double* signal, int bootstrap_mask, double gamma, double lambda, double shift, double scale) {
+  gs_handle::Rollout& ro = h->ro;
+  const size_t B = h->B, T = ro.T, cap = ro.T_cap;
+  int rc = GS_OK;
+  // all four or none: a later call must not find `values` and launch on the others
+  if (!c.values && (rc = alloc_all(h, "a critic's arrays over the rollout", c.values.want((cap + 1) * B), c.term_values.want((size_t)ro.term_cap),
+                                   c.adv.want(cap * B), c.ret.want(cap * B)))) return rc;
+  if ((rc = launch_value(h, c.net, ro.obs_seq, c.values, (long long)((T + 1) * B)))) return rc;
+  // the terminal rows: launched over the list's capacity, the count read on the device; every value also goes to its (t, b) in
+  // `ret`, where gs_k_gae looks for it before it writes the return there
+  if ((rc = launch_value(h, c.net, ro.term_obs, c.term_values, ro.term_cap, ro.term_count, ro.term_idx, c.ret, (int)T))) return rc;
+  GsGaeArgs g{c.values, signal, ro.done, c.adv, c.ret, (int32_t)T, h->B, bootstrap_mask, 0, gamma, lambda, shift, scale};
+  hipLaunchKernelGGL(gs_k_gae, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, g);
+  HIPCHK(h, hipGetLastError());
+  return GS_OK;
+}
+
+int critic_download(gs_handle* h, const gs_handle::Critic& c, double* values, double* term_values, double* adv, double* ret) {
+  const gs_handle::Rollout& ro = h->ro;
+  const size_t TB = (size_t)ro.T * h->B * sizeof(double), B8 = (size_t)h->B * sizeof(double);
+  if (values) HIPCHK(h, hipMemcpyAsync(values, c.values, TB + B8, hipMemcpyDeviceToHost, h->stream));
+  if (term_values && ro.n_term) HIPCHK(h, hipMemcpyAsync(term_values, c.term_values, (size_t)ro.n_term * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (adv) HIPCHK(h, hipMemcpyAsync(adv, c.adv, TB, hipMemcpyDeviceToHost, h->stream));
+  if (ret) HIPCHK(h, hipMemcpyAsync(ret, c.ret, TB, hipMemcpyDeviceToHost, h->stream));
+  return GS_OK;
+}
+
 }  // namespace gsi
 
 extern "C" {
-
 int gs_rollout_set_log_probs(gs_handle* h, int32_t on) {
   if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
   h->ro.record_logp = on != 0;
@@ -88,17 +115,18 @@ int gs_value_mlp_set(gs_handle* h, const gs_policy_mlp* p, const gs_policy_mlp_o
     const std::string why = gs_value_check(p, o, h->obs_dim);
     if (!why.empty()) return fail(h, GS_E_INVALID, "%s", why.c_str());
   }
-  return value_install(h, h->val, p, o, true);
+  return value_install(h, h->critic[0].net, p, o, true);
 }
 
 int gs_value_mlp_eval(gs_handle* h, double* values_host) {
   if (!h || !values_host) return fail(h, GS_E_INVALID, "handle / values_host is NULL");
-  if (!h->val.set) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_value_mlp_set");
+  const gs_handle::Value& val = h->critic[0].net;
+  if (!val.set) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_value_mlp_set");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_reset");
   GS_ENTER(h);
-  int rc = launch_value(h, h->val, h->d_obs2[h->obs_cur], h->val.out, h->B);
+  int rc = launch_value(h, val, h->d_obs2[h->obs_cur], val.out, h->B);
   if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(values_host, h->val.out, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(values_host, val.out, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return GS_OK;
 }
@@ -107,53 +135,31 @@ int gs_value_mlp_eval(gs_handle* h, double* values_host) {
 int gs_rollout_evaluate(gs_handle* h, const gs_gae_config* cfg) {
   if (!h || !cfg) return fail(h, GS_E_INVALID, "handle / config is NULL");
   if (cfg->struct_size != (int32_t)sizeof(gs_gae_config)) return fail(h, GS_E_INVALID, "gs_gae_config struct_size %d != %d", cfg->struct_size, (int)sizeof(gs_gae_config));
-  if (cfg->bootstrap_mask < 0 || cfg->bootstrap_mask > 3) return fail(h, GS_E_INVALID, "bootstrap_mask %d outside 0 .. 3", cfg->bootstrap_mask);
-  if (!std::isfinite(cfg->gamma) || !std::isfinite(cfg->lambda) || !std::isfinite(cfg->reward_shift) || !std::isfinite(cfg->reward_scale))
-    return fail(h, GS_E_INVALID, "gamma / lambda / reward_shift / reward_scale must be finite");
-  gs_handle::Rollout& ro = h->ro;
-  if (ro.T <= 0) return fail(h, GS_E_STATE, "gs_rollout_evaluate: no rollout has been collected on this handle");
-  if (!h->val.set) return fail(h, GS_E_STATE, "gs_rollout_evaluate before gs_value_mlp_set");
-  GS_ENTER(h);
-  const size_t B = h->B, T = ro.T;
-  if (!ro.values) {          // sized by the rollout's capacity; released with it (onpolicy_release)
-    if (hipMalloc((void**)&ro.values, (size_t)(ro.T_cap + 1) * B * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&ro.term_values, (size_t)std::max(ro.term_cap, 1) * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&ro.adv, (size_t)ro.T_cap * B * sizeof(double)) != hipSuccess ||
-        hipMalloc((void**)&ro.ret, (size_t)ro.T_cap * B * sizeof(double)) != hipSuccess) {
-      // all four or none: a later call must not find `values` and launch on the others
-      dev_free(ro.values); dev_free(ro.term_values); dev_free(ro.adv); dev_free(ro.ret);
-      return fail(h, GS_E_NOMEM, "on-policy arrays for T = %d do not fit", ro.T_cap);
-    }
-  }
-  int rc = launch_value(h, h->val, ro.obs_seq, ro.values, (long long)((T + 1) * B));
+  int rc = gae_check(h, cfg->bootstrap_mask, cfg->gamma, cfg->lambda, cfg->reward_shift, cfg->reward_scale, "reward");
   if (rc) return rc;
-  // the terminal rows: launched over the list's capacity, the count read on the device; every value also goes to its (t, b) in
-  // `ret`, where gs_k_gae looks for it before it writes the return there
-  if ((rc = launch_value(h, h->val, ro.term_obs, ro.term_values, ro.term_cap, ro.term_count, ro.term_idx, ro.ret, (int)T))) return rc;
-  GsGaeArgs g{ro.values, ro.rew, ro.done, ro.adv, ro.ret, (int32_t)T, h->B, cfg->bootstrap_mask, 0, cfg->gamma, cfg->lambda, cfg->reward_shift, cfg->reward_scale};
-  hipLaunchKernelGGL(gs_k_gae, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, g);
-  HIPCHK(h, hipGetLastError());
-  ro.evaluated_on = ro.calls;
+  gs_handle::Rollout& ro = h->ro;
+  gs_handle::Critic& c = h->critic[0];
+  if (ro.T <= 0) return fail(h, GS_E_STATE, "gs_rollout_evaluate: no rollout has been collected on this handle");
+  if (!c.net.set) return fail(h, GS_E_STATE, "gs_rollout_evaluate before gs_value_mlp_set");
+  GS_ENTER(h);
+  c.evaluated_on = 0;        // (until every launch is queued)
+  if ((rc = critic_evaluate(h, c, ro.rew, cfg->bootstrap_mask, cfg->gamma, cfg->lambda, cfg->reward_shift, cfg->reward_scale))) return rc;
+  c.evaluated_on = ro.calls;
   return GS_OK;
 }
 
 int gs_rollout_onpolicy_view(gs_handle* h, gs_rollout_onpolicy* out, void* consumer_stream) {
   if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
   gs_handle::Rollout& ro = h->ro;
+  const gs_handle::Critic& c = h->critic[0];
   if (ro.T <= 0) return fail(h, GS_E_STATE, "no rollout has been collected on this handle");
-  if (!ro.evaluated_on || ro.evaluated_on != ro.calls) return fail(h, GS_E_STATE, "gs_rollout_evaluate has not run on the last rollout");
+  if (!critic_current(h, c)) return fail(h, GS_E_STATE, "gs_rollout_evaluate has not run on the last rollout");
   int rc = rollout_finish(h);      // (waits for the rollout, not for the evaluation)
   if (rc) return rc;
-  if (consumer_stream) {
-    if (!ro.ev_eval) HIPCHK(h, hipEventCreateWithFlags(&ro.ev_eval, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(ro.ev_eval, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(peer_stream(consumer_stream), ro.ev_eval, 0));
-  } else {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  if ((rc = publish(h, h->stream, ro.ev_eval, consumer_stream))) return rc;
   out->T = ro.T; out->B = h->B; out->n_terminal = ro.n_term; out->rows_per_tile = GS_VAL_ROWS;
-  out->log_probs = ro.logp_recorded ? ro.logp : nullptr;
-  out->values = ro.values; out->terminal_values = ro.term_values; out->advantages = ro.adv; out->returns = ro.ret;
+  out->log_probs = ro.logp_recorded ? ro.logp.p : nullptr;
+  out->values = c.values; out->terminal_values = c.term_values; out->advantages = c.adv; out->returns = c.ret;
   return GS_OK;
 }
 
@@ -161,18 +167,13 @@ int gs_rollout_onpolicy_download(gs_handle* h, const gs_rollout_onpolicy_host* o
   if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
   gs_handle::Rollout& ro = h->ro;
   if (ro.T <= 0) return fail(h, GS_E_STATE, "no rollout has been collected on this handle");
-  const bool evaluated = ro.evaluated_on && ro.evaluated_on == ro.calls;
-  if ((out->values || out->terminal_values || out->advantages || out->returns) && !evaluated)
+  if ((out->values || out->terminal_values || out->advantages || out->returns) && !critic_current(h, h->critic[0]))
     return fail(h, GS_E_STATE, "gs_rollout_evaluate has not run on the last rollout");
   if (out->log_probs && !ro.logp_recorded) return fail(h, GS_E_STATE, "the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
   int rc = rollout_finish(h);
   if (rc) return rc;
-  const size_t TB = (size_t)ro.T * h->B * sizeof(double), B8 = (size_t)h->B * sizeof(double);
-  if (out->log_probs) HIPCHK(h, hipMemcpyAsync(out->log_probs, ro.logp, TB, hipMemcpyDeviceToHost, h->stream));
-  if (out->values) HIPCHK(h, hipMemcpyAsync(out->values, ro.values, TB + B8, hipMemcpyDeviceToHost, h->stream));
-  if (out->terminal_values && ro.n_term) HIPCHK(h, hipMemcpyAsync(out->terminal_values, ro.term_values, (size_t)ro.n_term * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->advantages) HIPCHK(h, hipMemcpyAsync(out->advantages, ro.adv, TB, hipMemcpyDeviceToHost, h->stream));
-  if (out->returns) HIPCHK(h, hipMemcpyAsync(out->returns, ro.ret, TB, hipMemcpyDeviceToHost, h->stream));
+  if (out->log_probs) HIPCHK(h, hipMemcpyAsync(out->log_probs, ro.logp, (size_t)ro.T * h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if ((rc = critic_download(h, h->critic[0], out->values, out->terminal_values, out->advantages, out->returns))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return GS_OK;
 }

@@ -13,19 +13,31 @@ namespace gsi __attribute__((visibility("hidden"))) {
 
 // the installed policy's image and the action block of gs_policy_mlp_eval (made by gs_policy_mlp_set_opts)
 void policy_release(gs_handle* h) {
-  dev_free(h->pol.blob);
-  dev_free(h->pol.act);
+  h->pol.blob.release();
+  h->pol.act.release();
   h->pol.set = false;
 }
 
-// the rollout's buffers (made by rollout_ensure); keep_term_count: all but the 4-byte counter, which does not depend on T
+int upload_image_f32(gs_handle* h, DevBuf<char>& blob, const GsPolicyImageF32& im, const float** image, const double** norm) {
+  // one allocation: the float image (a multiple of 16 floats), then shift and scale
+  const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
+  int rc = blob.alloc(h, image_bytes + norm_bytes, "the network's float32 image");
+  if (rc) return rc;
+  HIPCHK(h, hipMemcpy(blob, im.blob.data(), image_bytes, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(blob + image_bytes, im.norm.data(), norm_bytes, hipMemcpyHostToDevice));
+  *image = (const float*)blob.p; *norm = (const double*)(blob + image_bytes);
+  return GS_OK;
+}
+
+// the rollout's buffers (made by rollout_ensure); keep_term_count: all but the 4-byte counter, which does not depend on T.
+// The handle then holds no rollout: every gate on ro.T refuses until gs_rollout has collected one again.
 void rollout_release(gs_handle* h, bool keep_term_count) {
   gs_handle::Rollout& ro = h->ro;
-  dev_free(ro.obs_seq); dev_free(ro.act); dev_free(ro.rew); dev_free(ro.done); dev_free(ro.term_idx); dev_free(ro.term_obs);
-  if (!keep_term_count) dev_free(ro.term_count);
+  ro.obs_seq.release(); ro.act.release(); ro.rew.release(); ro.done.release(); ro.term_idx.release(); ro.term_obs.release();
+  if (!keep_term_count) ro.term_count.release();
   onpolicy_release(h);           // (sized by T as well)
   costs_release(h);
-  ro.T_cap = 0;
+  ro.T_cap = 0; ro.T = 0; ro.n_term = -1;
 }
 
 }  // namespace gsi
@@ -54,21 +66,17 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
   GS_ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   gs_handle::Policy& pol = h->pol;
-  dev_free(pol.blob);
+  pol.blob.release();
   pol.set = false;
   if (!p) return GS_OK;
-  if (!pol.act) HIPCHK(h, hipMalloc((void**)&pol.act, (size_t)h->B * h->action_dim * sizeof(double)));
+  int rc = pol.act.grow(h, (size_t)h->B * h->action_dim, "the policy's actions");
+  if (rc) return rc;
   if (gs_policy_is_f32(o)) {
     const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
     pol.lds32 = p->stochastic ? gs_pol32_lds_bytes(im.kb[0], h->action_dim) : gs_pol32_lds_bytes(im.kb[0]);
     HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL32_LDS_MAX));
-    // one allocation: the float image (a multiple of 16 floats), then shift and scale
-    const size_t image_bytes = im.blob.size() * sizeof(float), norm_bytes = im.norm.size() * sizeof(double);
-    HIPCHK(h, hipMalloc((void**)&pol.blob, image_bytes + norm_bytes));
-    const float* image = (const float*)pol.blob;
-    const double* norm = (const double*)((const char*)pol.blob + image_bytes);
-    HIPCHK(h, hipMemcpy((void*)image, im.blob.data(), image_bytes, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy((void*)norm, im.norm.data(), norm_bytes, hipMemcpyHostToDevice));
+    const float* image = nullptr; const double* norm = nullptr;
+    if ((rc = upload_image_f32(h, pol.blob, im, &image, &norm))) return rc;
     GsPolicyArgsF32& a = pol.args32;
     a = GsPolicyArgsF32{};
     a.shift = norm; a.scale = norm + 16 * im.kb[0];
@@ -82,13 +90,14 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
   const GsPolicyImage im = gs_policy_pack(*p);
   pol.lds64 = p->stochastic ? gs_pol_lds_bytes(h->action_dim) : GS_POL_LDS_BYTES;
   HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, GS_POL_LDS_MAX));
-  HIPCHK(h, hipMalloc((void**)&pol.blob, im.blob.size() * sizeof(double)));
-  HIPCHK(h, hipMemcpy(pol.blob, im.blob.data(), im.blob.size() * sizeof(double), hipMemcpyHostToDevice));
+  if ((rc = pol.blob.alloc(h, im.blob.size() * sizeof(double), "the policy's image"))) return rc;
+  double* const image = (double*)pol.blob.p;
+  HIPCHK(h, hipMemcpy(image, im.blob.data(), im.blob.size() * sizeof(double), hipMemcpyHostToDevice));
   GsPolicyArgs& a = pol.args;
   a = GsPolicyArgs{};
   a.B = h->B; a.D = h->obs_dim; a.A = h->action_dim; a.n_layers = p->n_layers; a.activation = p->activation; a.head = p->head;
   a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance; a.logp_behind = gs_pol_logp_behind(h->action_dim);
-  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayer{pol.blob + im.w_off[l], pol.blob + im.b_off[l], im.kb[l], im.nt[l]};
+  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayer{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
   pol.compute = GS_COMPUTE_F64;
   pol.set = true;
   return GS_OK;
@@ -140,21 +149,18 @@ static int rollout_ensure(gs_handle* h, int T) {
   // since its last reset, grid_env.py:604) plus once for an episode that was already under way
   const int min_ep = std::max(1, std::min(h->cfg.episode_length, 11));
   const size_t cap = B * ((size_t)T / min_ep + 1);
-  if (!ro.term_count) HIPCHK(h, hipMalloc((void**)&ro.term_count, sizeof(int32_t)));
-  if (hipMalloc((void**)&ro.obs_seq, (size_t)(T + 1) * B * D * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&ro.act, (size_t)T * B * A * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&ro.rew, (size_t)T * B * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&ro.done, (size_t)T * B) != hipSuccess ||
-      hipMalloc((void**)&ro.term_idx, cap * 2 * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc((void**)&ro.term_obs, cap * D * sizeof(double)) != hipSuccess)
-    return fail(h, GS_E_NOMEM, "rollout buffers for T = %d (%.1f MB per step) do not fit", T, (double)B * D * 8e-6);
+  int rc = ro.term_count.grow(h, 1, "the rollout's terminal counter");
+  if (rc) return rc;
+  // all or none; until gs_rollout sets ro.T again the handle holds no rollout (rollout_release)
+  if ((rc = alloc_all(h, "the rollout's buffers", ro.obs_seq.want((size_t)(T + 1) * B * D), ro.act.want((size_t)T * B * A), ro.rew.want((size_t)T * B),
+                      ro.done.want((size_t)T * B), ro.term_idx.want(cap * 2), ro.term_obs.want(cap * D)))) return rc;
   ro.T_cap = T; ro.term_cap = (int)std::min<size_t>(cap, 0x7fffffff);
   // the constant columns of every slot, once: the step kernels write only the columns that change
   const long long rows = (long long)(T + 1) * B;
   const int w = h->obs_skip1 - h->obs_skip0;
   if (w > 0) {
     const long long total = rows * w;
-    hipLaunchKernelGGL(gs_k_fill_const_columns, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ro.obs_seq, rows,
+    hipLaunchKernelGGL(gs_k_fill_const_columns, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ro.obs_seq.p, rows,
                        h->obs_dim, h->obs_skip0, h->obs_skip1, h->map_obs, h->d_cst);
     HIPCHK(h, hipGetLastError());
   }
@@ -172,18 +178,18 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   if (rc) return rc;
   gs_handle::Rollout& ro = h->ro;
   const size_t B = h->B, D = h->obs_dim, A = h->action_dim;
-  ro.T = T; ro.n_term = -1;
   // a stochastic policy's log-probabilities are recorded with its actions (on-policy rollouts, abi_onpolicy.hip)
   const bool stochastic = policy == GS_POLICY_MLP && (h->pol.compute == GS_COMPUTE_F32 ? h->pol.args32.stochastic : h->pol.args.stochastic);
   ro.logp_recorded = stochastic && ro.record_logp;
-  if (ro.logp_recorded && !ro.logp) HIPCHK(h, hipMalloc((void**)&ro.logp, (size_t)ro.T_cap * B * sizeof(double)));
+  if (ro.logp_recorded && (rc = ro.logp.grow(h, (size_t)ro.T_cap * B, "the rollout's log-probabilities"))) { ro.logp_recorded = false; return rc; }
+  ro.T = T; ro.n_term = -1;
   HIPCHK(h, hipMemsetAsync(ro.term_count, 0, sizeof(int32_t), h->stream));
   if (A > 0) {
     if (policy == GS_POLICY_UPLOADED) {
       HIPCHK(h, hipMemcpyAsync(ro.act, actions, (size_t)T * B * A * sizeof(double), hipMemcpyHostToDevice, h->stream));
     } else if (policy == GS_POLICY_RANDOM) {
       const long long total = (long long)T * B * ((A + 3) / 4);
-      hipLaunchKernelGGL(gs_k_rollout_actions, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ro.act, (int)T, (int)B, (int)A,
+      hipLaunchKernelGGL(gs_k_rollout_actions, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, ro.act.p, (int)T, (int)B, (int)A,
                          policy_seed, h->EC.first_instance, 0u);
       HIPCHK(h, hipGetLastError());
     }

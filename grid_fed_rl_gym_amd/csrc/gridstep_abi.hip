@@ -96,7 +96,7 @@ GsFusedChecks fused_checks_args(gs_handle* h) {
   if (h->fused) {
     gs_checks* c = h->fused;
     f.C = c->C; f.prev = c->prev; f.state = c->state; f.out_i = c->out_i; f.out_f = c->out_f;
-    f.bus_mask = c->want_masks ? c->bus_mask : nullptr; f.line_mask = c->want_masks ? c->line_mask : nullptr;
+    f.bus_mask = c->want_masks ? c->bus_mask.p : nullptr; f.line_mask = c->want_masks ? c->line_mask.p : nullptr;
     f.enabled = 1; f.Bp = h->Bp;
   }
   return f;
@@ -585,7 +585,7 @@ void gs_destroy(gs_handle* h) {
   for (auto& t : h->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   if (h->span_a) { (void)hipEventDestroy(h->span_a); (void)hipEventDestroy(h->span_b); }
   for (void* p : h->allocs) (void)hipFree(p);
-  dev_free(h->d_actions);
+  h->d_actions.release();
   policy_release(h);
   value_release(h);
   rollout_release(h);
@@ -918,13 +918,8 @@ int gs_step_device_view(gs_handle* h, gs_step_device_out* out, void* consumer_st
   hipLaunchKernelGGL(gs_k_scalars, dim3(h->groups), dim3(64), 0, h->stream, h->rows_f, (int)SF_COUNT, h->rows_i,
                      (int)SI_COUNT, h->rows_u, (int)SU_COUNT, h->R.total, h->slab, h->sc_f, h->sc_i, h->sc_u, h->Bp, (uint32_t*)nullptr, 0);
   HIPCHK(h, hipGetLastError());
-  if (consumer_stream) {
-    if (!h->ev_peer2) HIPCHK(h, hipEventCreateWithFlags(&h->ev_peer2, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(h->ev_peer2, h->stream));
-    HIPCHK(h, hipStreamWaitEvent(peer_stream(consumer_stream), h->ev_peer2, 0));
-  } else {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+  int rc = publish(h, h->stream, h->ev_peer2, consumer_stream);
+  if (rc) return rc;
   out->observations = h->d_obs2[h->obs_cur];
   out->reward = h->sc_f + (size_t)SF_REWARD * h->Bp;
   out->terminated = h->sc_u + (size_t)SU_TERM * h->Bp;
@@ -933,22 +928,25 @@ int gs_step_device_view(gs_handle* h, gs_step_device_out* out, void* consumer_st
   return GS_OK;
 }
 
+// doubles that one batch of gs_upload_actions takes in d_actions
+static size_t action_batch(const gs_handle* h) { return (size_t)h->B * std::max(h->action_dim, 1); }
+
 int gs_upload_actions(gs_handle* h, const double* actions, int32_t n_batches) {
   if (!h || !actions || n_batches <= 0) return fail(h, GS_E_INVALID, "bad arguments");
   GS_ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  dev_free(h->d_actions);
-  const size_t bytes = (size_t)n_batches * h->B * std::max(h->action_dim, 1) * sizeof(double);
-  HIPCHK(h, hipMalloc((void**)&h->d_actions, bytes));
+  // (always a fresh allocation of exactly n_batches batches: gs_step_device counts them by the buffer's capacity)
+  int rc = h->d_actions.alloc(h, action_batch(h) * n_batches, "the uploaded actions");
+  if (rc) return rc;
   HIPCHK(h, hipMemcpy(h->d_actions, actions, (size_t)n_batches * h->B * h->action_dim * sizeof(double), hipMemcpyHostToDevice));
-  h->n_action_batches = n_batches;
   return GS_OK;
 }
 
 int gs_step_device(gs_handle* h, int32_t k) {
   if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_step_device before gs_reset");
-  if (k < 0 || k >= h->n_action_batches) return fail(h, GS_E_INVALID, "action batch %d not uploaded (have %d)", k, h->n_action_batches);
+  const int have = (int)(h->d_actions.cap / action_batch(h));      // (0 without an upload, and after one that failed)
+  if (k < 0 || k >= have) return fail(h, GS_E_INVALID, "action batch %d not uploaded (have %d)", k, have);
   HIPCHK(h, hipSetDevice(h->device));
   return step_kernels(h, h->d_actions + (size_t)k * h->B * h->action_dim);
 }

@@ -1,6 +1,6 @@
 // handle.h -- what the translation units of the C ABI's host side share (host only, internal): the handle and the checks object,
-// error reporting, the stream join every entry point starts with, the handle's allocator, launch timing, and the helpers of
-// gridstep_abi.hip that the other files call.
+// error reporting, the stream join every entry point starts with, the handle's allocator, the owner of every other device buffer
+// (DevBuf), the hand-over of a view to a consumer's stream (publish), launch timing, and the helpers that cross files.
 // Which file owns what: DESIGN.md section 1, "File map of the ABI's host side".
 //
 // Whatever has external linkage here lives in namespace gsi, which is hidden: libgridstep.so exports the C ABI and nothing else.
@@ -20,14 +20,58 @@
 #include "plan.h"
 #include "policy.h"
 
-struct GsLoopComm;      // abi_comm.hip
+// (also on the handle's parts that own a DevBuf and on gs_checks: their destructors are not part of the library's surface)
+#define GS_HIDDEN __attribute__((visibility("hidden")))
 
-namespace gsi __attribute__((visibility("hidden"))) {
+struct GsLoopComm;      // abi_comm.hip
+struct gs_handle;
+
+namespace gsi GS_HIDDEN {
 
 typedef void* gs_ncclComm_t;
 struct TimedLaunch { int kid; hipEvent_t a, b; };
 
+// the message as the library's last error (gs_last_error; gridstep_abi.hip holds it) and, with a handle, as the handle's
+int fail(gs_handle* h, int code, const char* fmt, ...);
+
+// A hipMalloc of its own (what does NOT go through dev_alloc): the pointer WITH its capacity in elements, 0 exactly when the pointer
+// is NULL.  Reads like the pointer.  Freed by release() or at scope exit; a handle's members are released by their owners
+// (*_release, called by gs_destroy with the device current and the streams idle), so their destructors find nothing left.
+template <typename X>
+struct DevBuf {
+  X* p = nullptr; size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  operator X*() const { return p; }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  // `count` elements (at least one) in place of what it held; GS_E_NOMEM naming `what` leaves it empty and HIP's last error clear
+  int alloc(gs_handle* h, size_t count, const char* what) {
+    release();
+    count = std::max<size_t>(count, 1);
+    if (hipMalloc((void**)&p, count * sizeof(X)) != hipSuccess) {
+      p = nullptr; (void)hipGetLastError();
+      return fail(h, GS_E_NOMEM, "%s: %zu bytes do not fit on the device", what, count * sizeof(X));
+    }
+    cap = count;
+    return GS_OK;
+  }
+  int grow(gs_handle* h, size_t count, const char* what);      // nothing if it holds `count`; else waits for the handle's stream, then alloc
+  struct Want { DevBuf& b; size_t count; };
+  Want want(size_t count) { return Want{*this, count}; }
+};
+// several buffers or none: alloc_all(h, what, a.want(n), b.want(m), ...)
+template <typename... W>
+int alloc_all(gs_handle* h, const char* what, W... w) {
+  int rc = GS_OK;
+  ((rc = rc ? rc : w.b.alloc(h, w.count, what)), ...);
+  if (rc) (w.b.release(), ...);
+  return rc;
+}
+
 }  // namespace gsi
+using gsi::DevBuf;
 
 // A handle is its plan (plan.h: members, rows, launch shapes, host tables) and the device state built from it.
 struct gs_handle : GsPlan {
@@ -64,51 +108,45 @@ struct gs_handle : GsPlan {
   std::vector<const double*> bound_obs;
   float* d_obs32 = nullptr;                // float32 copy of the observation block (gs_step_f32 / gs_download_step_f32), on first use
   hipEvent_t ev_scalars = nullptr;
-  double* d_actions = nullptr; int n_action_batches = 0;
+  DevBuf<double> d_actions;                // gs_upload_actions: [batches][B][max(action_dim, 1)]
   // gs_rollout: [T + 1][B][obs_dim] observation sequence, [T][B][A] actions, [T][B] rewards / done flags, and the side
   // list of terminal observations (the rows the in-place resets replaced)
-  struct Rollout {
+  struct GS_HIDDEN Rollout {
     int T_cap = 0, T = 0, term_cap = 0; uint64_t calls = 0;
-    double* obs_seq = nullptr; double* act = nullptr; double* rew = nullptr; uint8_t* done = nullptr;
-    int32_t* term_count = nullptr; int32_t* term_idx = nullptr; double* term_obs = nullptr;
+    DevBuf<double> obs_seq, act, rew, term_obs; DevBuf<uint8_t> done; DevBuf<int32_t> term_count, term_idx;
     int32_t n_term = 0;
-    // on-policy data of the last rollout (abi_onpolicy.hip): logp [T][B] (recorded: by the last rollout); values [T + 1][B],
-    // term_values [term_cap], adv / ret [T][B], made by gs_rollout_evaluate; evaluated_on = `calls` of the rollout they belong to
+    // logp [T][B]: the log-probabilities of the last rollout's actions (recorded: by the last rollout); abi_onpolicy.hip
     bool record_logp = true, logp_recorded = false;
-    double* logp = nullptr; double* values = nullptr; double* term_values = nullptr; double* adv = nullptr; double* ret = nullptr;
-    uint64_t evaluated_on = 0; hipEvent_t ev_eval = nullptr;
+    DevBuf<double> logp; hipEvent_t ev_eval = nullptr;
   } ro;
   // gs_dataset_*: the dataset over the last rollout (abi_dataset.hip).  built_on = ro.calls of the rollout the map (and, unless
   // the statistics were installed or kept, the statistics) was built on, 0 = none; stats = mean[Ct] then std[Ct] at stride Cs
   // (Ct = obs_dim + action_dim + 1, Cs = Ct rounded up to even) on the device; part = the chunks' partial results; idx / h_idx =
   // the sample indices on the device / their page-locked staging copy; batch[k] = the handle's own buffer for output k
-  struct Dataset {
+  struct GS_HIDDEN Dataset {
     uint64_t built_on = 0; long long N = 0; bool have_stats = false;
-    double* stats = nullptr; double* part = nullptr; size_t part_doubles = 0;
-    int32_t* map = nullptr; size_t map_cap = 0;
-    int32_t* idx = nullptr; int32_t* h_idx = nullptr; int idx_cap = 0; hipEvent_t ev_idx = nullptr; bool idx_pending = false;
-    void* batch[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t batch_bytes[5] = {0, 0, 0, 0, 0};
-    hipEvent_t ev_batch = nullptr;
+    DevBuf<double> stats, part; DevBuf<int32_t> map;
+    DevBuf<int32_t> idx; int32_t* h_idx = nullptr; hipEvent_t ev_idx = nullptr; bool idx_pending = false;      // (h_idx: idx.cap entries)
+    DevBuf<char> batch[5]; hipEvent_t ev_batch = nullptr;
   } ds;
   // gs_policy_mlp_set: the policy's packed weights and biases (one allocation), the actions of gs_policy_mlp_eval [B][A], and the
   // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
   // compute: GS_COMPUTE_*; with GS_COMPUTE_F32 `blob` holds the float32 image and the normalisation vectors, and args32 is the
   // argument block of gs_k_policy_mlp_f32 (kernels_policy_f32.hip)
-  struct Policy { bool set = false; double* blob = nullptr; double* act = nullptr; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0, lds64 = GS_POL_LDS_BYTES; } pol;
-  // gs_value_mlp_set: the value network's float32 image and normalisation vectors (one allocation), the values of
-  // gs_value_mlp_eval [B], and the argument block of gs_k_value_mlp_f32 with everything but obs / out / rows filled in
-  struct Value { bool set = false; float* blob = nullptr; double* out = nullptr; GsValueArgs args{}; int lds = 0; } val;
-  // gs_cost_value_mlp_set: one critic per constraint channel (GS_COST_*), installed like `val` (no `out`: they run over rollouts only)
-  Value cost_val[GS_COST_CHANNELS];
-  // gs_rollout_costs / gs_rollout_evaluate_costs (abi_costs.hip): margins / costs [3][T][B], counts [3][T][B], n_viol [3] of the last
-  // rollout, channel c at c * T * B; computed_on = ro.calls of the rollout they belong to, 0 = none.  values [3][T_cap + 1][B],
-  // term_values [3][term_cap], adv / ret [3][T_cap][B]: the cost critics' arrays, channel c at c * its capacity; evaluated_on as
-  // computed_on, evaluated[c]: channel c had a critic at that evaluation.  All sized by the rollout's capacity and released with it.
-  struct Costs {
-    double* margins = nullptr; int32_t* counts = nullptr; double* costs = nullptr; unsigned long long* n_viol = nullptr;
-    double* values = nullptr; double* term_values = nullptr; double* adv = nullptr; double* ret = nullptr;
-    uint64_t computed_on = 0, evaluated_on = 0; bool evaluated[GS_COST_CHANNELS] = {false, false, false};
-    hipEvent_t ev = nullptr;
+  struct GS_HIDDEN Policy { bool set = false; DevBuf<char> blob; DevBuf<double> act; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0, lds64 = GS_POL_LDS_BYTES; } pol;
+  // a value network: its float32 image and normalisation vectors (one allocation), the values of gs_value_mlp_eval [B] (the reward
+  // critic's only), and the argument block of gs_k_value_mlp_f32 with everything but obs / out / rows filled in
+  struct GS_HIDDEN Value { bool set = false; DevBuf<char> blob; DevBuf<double> out; GsValueArgs args{}; int lds = 0; };
+  // A critic over rollouts (abi_onpolicy.hip): its network and what critic_evaluate made of the last rollout -- values [T_cap + 1][B],
+  // term_values [term_cap], adv / ret [T_cap][B], made on first use (all four or none), sized by the rollout's capacity and released
+  // with it; evaluated_on = ro.calls of the rollout they belong to, 0 = none.  critic[0]: the reward critic (gs_value_mlp_set,
+  // gs_rollout_evaluate); critic[1 + c]: the critic of constraint channel c (gs_cost_value_mlp_set, gs_rollout_evaluate_costs)
+  struct GS_HIDDEN Critic { Value net; DevBuf<double> values, term_values, adv, ret; uint64_t evaluated_on = 0; } critic[1 + GS_COST_CHANNELS];
+  // gs_rollout_costs (abi_costs.hip): margins / costs [3][T][B], counts [3][T][B], n_viol [3] of the last rollout, channel c at
+  // c * T * B; computed_on = ro.calls of the rollout they belong to, 0 = none.  Sized by the rollout's capacity and released with it.
+  struct GS_HIDDEN Costs {
+    DevBuf<double> margins, costs; DevBuf<int32_t> counts; DevBuf<unsigned long long> n_viol;
+    uint64_t computed_on = 0; hipEvent_t ev = nullptr;
   } cc;
   double* d_cst = nullptr;
   int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
@@ -146,19 +184,16 @@ struct gs_handle : GsPlan {
 };
 
 // ---- post-step checks -------------------------------------------------------------------------------
-struct gs_checks {
+struct GS_HIDDEN gs_checks {
   gs_handle* h = nullptr;
   GsChecksCfg C{};
-  double* prev = nullptr; int32_t* state = nullptr; int32_t* out_i = nullptr; double* out_f = nullptr;
-  uint8_t *bus_mask = nullptr, *line_mask = nullptr; double* freq = nullptr; bool use_freq = false, want_masks = true;
+  DevBuf<double> prev, out_f, freq; DevBuf<int32_t> state, out_i; DevBuf<uint8_t> bus_mask, line_mask;      // (go with `delete`: gs_checks_destroy)
+  bool use_freq = false, want_masks = true;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t ev_used = 0;
 };
 
-namespace gsi __attribute__((visibility("hidden"))) {
-
-// the message as the library's last error (gs_last_error; gridstep_abi.hip holds it) and, with a handle, as the handle's
-int fail(gs_handle* h, int code, const char* fmt, ...);
+namespace gsi GS_HIDDEN {
 
 // A peer's stream as it crosses the C ABI: NULL = none; hipStreamLegacy (1) = the legacy default stream, i.e. handle 0
 static inline hipStream_t peer_stream(void* s) { return s == (void*)hipStreamLegacy ? (hipStream_t)nullptr : (hipStream_t)s; }
@@ -222,11 +257,28 @@ inline int upload_map(gs_handle* h, int32_t** p, const std::vector<int32_t>& v) 
   return rc;
 }
 
-// What did NOT go through dev_alloc (whose allocations live as long as the handle and go with it) is a hipMalloc of its own, owned
-// by whoever made it: freed with this, which leaves the pointer NULL
+// What did NOT go through dev_alloc (whose allocations live as long as the handle and go with it) is a hipMalloc of its own: a
+// DevBuf, or (the communicator's buffers, abi_comm.hip) a plain pointer freed with this, which leaves it NULL
 template <typename X>
 void dev_free(X*& p) {
   if (p) { (void)hipFree(p); p = nullptr; }
+}
+
+template <typename X>
+int DevBuf<X>::grow(gs_handle* h, size_t count, const char* what) {
+  if (p && count <= cap) return GS_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // (what is queued may still read the old allocation)
+  return alloc(h, count, what);
+}
+
+// Hands what `producer` has queued so far to a consumer: with a consumer's stream that stream waits, on the device, for an event
+// recorded now (`ev`: created on first use, destroyed by its owner); without one the host waits
+static inline int publish(gs_handle* h, hipStream_t producer, hipEvent_t& ev, void* consumer_stream) {
+  if (!consumer_stream) { HIPCHK(h, hipStreamSynchronize(producer)); return GS_OK; }
+  if (!ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  HIPCHK(h, hipEventRecord(ev, producer));
+  HIPCHK(h, hipStreamWaitEvent(peer_stream(consumer_stream), ev, 0));
+  return GS_OK;
 }
 
 // ---- timing wrapper -------------------------------------------------------------------------
@@ -265,19 +317,26 @@ int step_kernels(gs_handle* h, const double* d_actions, double* obs_out = nullpt
 
 // ---- owners of what gs_destroy does not free itself (abi_rollout.hip) ----
 void policy_release(gs_handle* h);
+// the float32 image of an MLP as one allocation (image, then shift and scale) in `blob`; *image / *norm: where the two parts lie
+int upload_image_f32(gs_handle* h, DevBuf<char>& blob, const GsPolicyImageF32& im, const float** image, const double** norm);
 void rollout_release(gs_handle* h, bool keep_term_count = false);
 int rollout_finish(gs_handle* h);      // waits for the last rollout's number of finished episodes (ro.n_term); GS_E_STATE without one
 
-// ---- owner of the value network and of the rollout's on-policy arrays (abi_onpolicy.hip) ----
+// ---- owner of the value networks and of the critics' arrays over the rollout (abi_onpolicy.hip) ----
 void value_release(gs_handle* h);
 void onpolicy_release(gs_handle* h);
 // installs `p` (checked by the caller; NULL removes) as `val`; want_out: with the [B] block of gs_value_mlp_eval
 int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out);
-// one launch of `val` over `rows` rows of obs (device pointers) on the handle's main stream; rows_dev / scatter_*: GsValueArgs
-int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
-                 const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0);
+// what gs_gae_config and gs_cost_gae_config (per channel) must satisfy; signal: "reward" / "cost", for the message
+int gae_check(gs_handle* h, int bootstrap_mask, double gamma, double lambda, double shift, double scale, const char* signal);
+// values, terminal values, advantages and returns of `c` over the last rollout, from signal[T][B] (device); queued, not stamped
+int critic_evaluate(gs_handle* h, gs_handle::Critic& c, const double* signal, int bootstrap_mask, double gamma, double lambda, double shift, double scale);
+// critic_evaluate has run for `c` on the rollout the handle holds
+static inline bool critic_current(const gs_handle* h, const gs_handle::Critic& c) { return c.evaluated_on && c.evaluated_on == h->ro.calls; }
+// queues the copies of c's arrays over the last rollout to these host pointers (NULL: not wanted)
+int critic_download(gs_handle* h, const gs_handle::Critic& c, double* values, double* term_values, double* adv, double* ret);
 
-// ---- owner of the rollout's constraint arrays and of the cost critics' arrays (abi_costs.hip) ----
+// ---- owner of the rollout's constraint arrays (abi_costs.hip) ----
 void costs_release(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
