@@ -18,7 +18,8 @@ from .solver import (BatchedNewtonRaphsonSolver, NewtonRaphsonSolver, FastDecoup
 from .env import BatchedGridEnvironment, VectorizedEnvironment, Box
 from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy_data, evaluate_rollout, gae_np, rollout_device, GridDataset,
                       DeviceGridDataset, ConstraintLimits, costs_np, rollout_costs_np, rollout_costs, evaluate_rollout_costs,
-                      constraint_values, collect_constrained_data)
+                      constraint_values, collect_constrained_data, episodes_np, rollout_episodes, EpisodeRecords, EpisodeMonitor,
+                      evaluate_policy)
 from .policy import MLPPolicy, MLPValue
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -32,6 +33,7 @@ __all__ = [
     "injections_from_dicts", "BatchedGridEnvironment", "VectorizedEnvironment", "Box",
     "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "MLPValue", "collect_onpolicy_data", "evaluate_rollout", "gae_np", "GridDataset", "DeviceGridDataset",
     "ConstraintLimits", "costs_np", "rollout_costs_np", "rollout_costs", "evaluate_rollout_costs", "constraint_values", "collect_constrained_data",
+    "episodes_np", "rollout_episodes", "EpisodeRecords", "EpisodeMonitor", "evaluate_policy",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",
     "BatchedSafetyChecker", "BatchedSafetyMonitor", "PostStepChecks", "device_quality_score",

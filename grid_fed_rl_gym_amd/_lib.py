@@ -181,6 +181,46 @@ def cost_config_check(c: gs_cost_config) -> Tuple[int, str]:
     return _host_check("gs_cost_config_check", C.byref(c))
 
 
+# episode accounting over rollouts (include/gridstep.h): start modes, the record flags' bits and the structs of gs_rollout_episodes
+EPISODES_START = {"continue": 0, "fresh": 1, "unknown": 2}      # GS_EPISODES_*
+GS_EPISODE_TERMINATED, GS_EPISODE_TRUNCATED, GS_EPISODE_PARTIAL = 1, 2, 4
+_i64_3 = C.c_int64 * 3
+
+
+class gs_episode_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("start", C.c_int32), ("with_costs", C.c_int32), ("reserved", C.c_int32),
+                ("success_return", C.c_double)]
+
+
+class gs_episode_stats(C.Structure):
+    _fields_ = [("count", C.c_int64), ("count_partial", C.c_int64), ("return_mean", C.c_double), ("return_std", C.c_double),
+                ("return_min", C.c_double), ("return_max", C.c_double), ("length_mean", C.c_double), ("length_min", C.c_double),
+                ("length_max", C.c_double), ("cost_mean", _d3), ("violating", _i64_3), ("n_success", C.c_int64)]
+
+
+# the list arrays and the carries of both structs, in order, with their dtypes; the last three of each group exist with costs only
+EPISODE_LIST_KEYS = (("episode_index", np.int32), ("episode_return", np.float64), ("episode_length", np.int32), ("episode_ordinal", np.int32),
+                     ("episode_flags", np.int32), ("episode_cost", np.float64), ("episode_violating", np.int32), ("episode_any_violating", np.int32))
+EPISODE_CARRY_KEYS = (("ep_return", np.float64), ("ep_length", np.int32), ("ep_ordinal", np.int32), ("ep_partial", np.uint8),
+                      ("ep_cost", np.float64), ("ep_violating", np.int32), ("ep_any_violating", np.int32))
+
+
+class gs_rollout_episodes_dev(C.Structure):
+    _fields_ = ([("n_episodes", C.c_int32), ("B", C.c_int32), ("with_costs", C.c_int32), ("cost_stride", C.c_int32)] +
+                [(k, C.c_void_p) for k, _ in EPISODE_LIST_KEYS] + [("stats", C.c_void_p)] + [(k, C.c_void_p) for k, _ in EPISODE_CARRY_KEYS])
+
+
+class gs_rollout_episodes_host(C.Structure):
+    _fields_ = ([("n_episodes", C.c_void_p)] + [(k, C.c_void_p) for k, _ in EPISODE_LIST_KEYS] + [("stats", C.c_void_p)] +
+                [(k, C.c_void_p) for k, _ in EPISODE_CARRY_KEYS])
+
+
+def episode_config(start="continue", costs: bool = False, success_return: float = -1000.0, struct_size=None) -> gs_episode_config:
+    """gs_episode_config; ``start``: a name of EPISODES_START or its number."""
+    return gs_episode_config(C.sizeof(gs_episode_config) if struct_size is None else int(struct_size),
+                             EPISODES_START[start] if isinstance(start, str) else int(start), int(bool(costs)), 0, float(success_return))
+
+
 class gs_dataset_stats_view(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("rows_per_chunk", C.c_int32), ("n", C.c_int64), ("obs_dim", C.c_int32), ("action_dim", C.c_int32),
                 ("obs_mean", _dp), ("obs_std", _dp), ("act_mean", _dp), ("act_std", _dp), ("reward_mean", _dp), ("reward_std", _dp)]
@@ -279,6 +319,10 @@ SYMBOLS = [
     ("gs_rollout_evaluate_costs", C.c_int, [_H, C.POINTER(gs_cost_gae_config)]),
     ("gs_rollout_costs_view", C.c_int, [_H, C.POINTER(gs_rollout_costs_dev), C.c_void_p]),
     ("gs_rollout_costs_download", C.c_int, [_H, C.POINTER(gs_rollout_costs_host)]),
+    ("gs_rollout_episodes", C.c_int, [_H, C.POINTER(gs_episode_config)]),
+    ("gs_rollout_episodes_view", C.c_int, [_H, C.POINTER(gs_rollout_episodes_dev), C.c_void_p]),
+    ("gs_rollout_episodes_download", C.c_int, [_H, C.POINTER(gs_rollout_episodes_host)]),
+    ("gs_episodes_clear", C.c_int, [_H]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -1198,6 +1242,74 @@ class Handle:
             else:
                 raise PowerFlowError(f"rollout_costs_download: unknown array {k!r}")
         self._check(self._lib.gs_rollout_costs_download(self._h, C.byref(v)))
+        return out
+
+    # -- episode accounting: the episodes the last rollout finished and the carries of the open ones (include/gridstep.h) ---------
+    def rollout_episodes(self, cfg: Optional[gs_episode_config] = None) -> None:
+        """gs_rollout_episodes (asynchronous): the episode list, the statistics and the carries over the last rollout; None:
+        continue, no costs, -1000."""
+        self._check(self._lib.gs_rollout_episodes(self._h, None if cfg is None else C.byref(cfg)))
+
+    def episodes_clear(self) -> None:
+        """gs_episodes_clear: drop the episode track."""
+        self._check(self._lib.gs_episodes_clear(self._h))
+
+    def rollout_episodes_view(self, stream=None) -> gs_rollout_episodes_dev:
+        """Device pointers of what gs_rollout_episodes left (gs_rollout_episodes_view)."""
+        v = gs_rollout_episodes_dev()
+        self._check(self._lib.gs_rollout_episodes_view(self._h, C.byref(v), _stream_arg(stream)))
+        return v
+
+    def rollout_episodes_arrays(self, stream=None) -> dict:
+        """The same as zero-copy ``DeviceArray`` views: the list arrays of EPISODE_LIST_KEYS ([n_episodes]; ``episode_index``
+        [n_episodes, 2]; ``episode_cost`` / ``episode_violating`` lists of three [n_episodes], one per channel), the carries of
+        EPISODE_CARRY_KEYS ([B]; ``ep_cost`` / ``ep_violating`` [3, B]) -- the cost arrays None without costs -- and ``n_episodes``."""
+        v = self.rollout_episodes_view(stream)
+        n, B, stride = int(v.n_episodes), int(v.B), int(v.cost_stride)
+        out = dict(n_episodes=n, with_costs=bool(v.with_costs))
+        for k, dt in EPISODE_LIST_KEYS:
+            ptr, ts, size = getattr(v, k), np.dtype(dt).str, np.dtype(dt).itemsize
+            if not ptr:
+                out[k] = None
+            elif k in ("episode_cost", "episode_violating"):
+                out[k] = [DeviceArray(ptr + c * stride * size, (n,), ts) for c in range(3)]
+            else:
+                out[k] = DeviceArray(ptr, (n, 2) if k == "episode_index" else (n,), ts)
+        for k, dt in EPISODE_CARRY_KEYS:
+            ptr = getattr(v, k)
+            out[k] = DeviceArray(ptr, (3, B) if k in ("ep_cost", "ep_violating") else (B,), np.dtype(dt).str) if ptr else None
+        return out
+
+    def rollout_episodes_download(self, want=None, n_episodes: Optional[int] = None) -> dict:
+        """Host copies (gs_rollout_episodes_download) of the arrays named in ``want`` (None: every list array and carry the last
+        accounting made, and ``stats``): names of EPISODE_LIST_KEYS / EPISODE_CARRY_KEYS and "stats" (a ``gs_episode_stats``).
+        Always carries ``n_episodes``."""
+        if n_episodes is None:
+            n_episodes = int(self.rollout_device_view().n_terminal)
+        n, B = int(n_episodes), self.B
+        cost_keys = ("episode_cost", "episode_violating", "episode_any_violating", "ep_cost", "ep_violating", "ep_any_violating")
+        if want is None:
+            with_costs = bool(self.rollout_episodes_view().with_costs)
+            want = [k for k, _ in EPISODE_LIST_KEYS + EPISODE_CARRY_KEYS if with_costs or k not in cost_keys] + ["stats"]
+        shapes = dict(episode_index=(n, 2), episode_cost=(3, n), episode_violating=(3, n), ep_cost=(3, B), ep_violating=(3, B))
+        dtypes = dict(EPISODE_LIST_KEYS + EPISODE_CARRY_KEYS)
+        v = gs_rollout_episodes_host()
+        out = {}
+        for k in want:
+            if k == "stats":
+                out[k] = gs_episode_stats()
+                v.stats = C.addressof(out[k])
+            elif k in dtypes:
+                out[k] = np.empty(shapes.get(k, (n,) if k.startswith("episode_") else (B,)), dtype=dtypes[k])
+                setattr(v, k, out[k].ctypes.data)
+            else:
+                raise PowerFlowError(f"rollout_episodes_download: unknown array {k!r}")
+        cnt = C.c_int32(0)
+        v.n_episodes = C.addressof(cnt)
+        self._check(self._lib.gs_rollout_episodes_download(self._h, C.byref(v)))
+        if int(cnt.value) != n:
+            raise PowerFlowError(f"rollout_episodes_download: the rollout finished {cnt.value} episodes, not {n}")
+        out["n_episodes"] = n
         return out
 
     def rollout_device_view(self) -> gs_rollout_device:

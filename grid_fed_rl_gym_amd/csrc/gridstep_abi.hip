@@ -700,6 +700,7 @@ int gs_upload_injections(gs_handle* h, const double* P_spec, const double* Q_spe
   if (!h || !P_spec) return fail(h, GS_E_INVALID, "handle / P_spec is NULL");
   if (h->pz) return fail(h, GS_E_STATE, "%s", kPzNoSolve);
   GS_ENTER(h);
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   int rc = unpack_from_host(h, h->map_p, h->n, P_spec);
   if (rc) return rc;
   if (Q_spec) {
@@ -718,6 +719,7 @@ int gs_solve_device(gs_handle* h) {
   if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
   if (h->pz) return fail(h, GS_E_STATE, "%s", kPzNoSolve);
   GS_ENTER(h);
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   h->rows_stale = false;            // the solve writes every result row
   return launch_solve(h);
 }
@@ -752,6 +754,7 @@ int gs_solve(gs_handle* h, const double* P_spec, const double* Q_spec, const gs_
 int gs_reset(gs_handle* h, const uint64_t* seeds, const uint8_t* mask, double* obs_out) {
   if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
   GS_ENTER(h);
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   { int rc0 = ensure_rows(h); if (rc0) return rc0; }      // a masked reset leaves the other instances' rows as they are: they must be current
   if (seeds) HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, (size_t)h->B * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
   if (mask) HIPCHK(h, hipMemcpyAsync(h->d_mask, mask, (size_t)h->B, hipMemcpyHostToDevice, h->stream));
@@ -879,6 +882,7 @@ int gs_step(gs_handle* h, const double* actions, double* obs, double* reward, ui
   if (!h || (!actions && h->action_dim > 0)) return fail(h, GS_E_INVALID, "handle / actions is NULL");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_step before gs_reset");
   GS_ENTER(h);
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   if (h->action_dim > 0)
     HIPCHK(h, hipMemcpyAsync(h->d_in, actions, (size_t)h->B * h->action_dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
   int rc = step_kernels(h, h->d_in);
@@ -891,6 +895,7 @@ int gs_step_f32(gs_handle* h, const double* actions, float* obs, double* reward,
   if (!h || (!actions && h->action_dim > 0) || !obs) return fail(h, GS_E_INVALID, "handle / actions / obs is NULL");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_step_f32 before gs_reset");
   GS_ENTER(h);
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   if (h->action_dim > 0)
     HIPCHK(h, hipMemcpyAsync(h->d_in, actions, (size_t)h->B * h->action_dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
   int rc = step_kernels(h, h->d_in);
@@ -902,6 +907,7 @@ int gs_step_device_ptr(gs_handle* h, const double* d_actions, void* producer_str
   if (!h || (!d_actions && h->action_dim > 0)) return fail(h, GS_E_INVALID, "handle / d_actions is NULL");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_step_device_ptr before gs_reset");
   HIPCHK(h, hipSetDevice(h->device));
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   if (producer_stream) {             // the step waits, on the device, for what the producer has queued so far
     if (!h->ev_peer) HIPCHK(h, hipEventCreateWithFlags(&h->ev_peer, hipEventDisableTiming));
     HIPCHK(h, hipEventRecord(h->ev_peer, peer_stream(producer_stream)));
@@ -948,6 +954,7 @@ int gs_step_device(gs_handle* h, int32_t k) {
   const int have = (int)(h->d_actions.cap / action_batch(h));      // (0 without an upload, and after one that failed)
   if (k < 0 || k >= have) return fail(h, GS_E_INVALID, "action batch %d not uploaded (have %d)", k, have);
   HIPCHK(h, hipSetDevice(h->device));
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   return step_kernels(h, h->d_actions + (size_t)k * h->B * h->action_dim);
 }
 
@@ -963,6 +970,7 @@ int gs_get_state(gs_handle* h, double* state) {
 int gs_set_state(gs_handle* h, const double* state) {
   if (!h || !state) return fail(h, GS_E_INVALID, "handle / state is NULL");
   GS_ENTER(h);
+  h->env_moves += 1;          // (episode accounting: the environment moves outside gs_rollout)
   h->rows_stale = false;            // the checkpoint carries every result row
   int rc = unpack_from_host(h, h->map_state, h->state_dim, state);
   if (rc) return rc;

@@ -632,6 +632,32 @@ struct GsCostArgs {
 // lanes per row for a prefix of `cols` = 2 n + 2 m columns (the frequency is read on its own): the smallest power of two in 8 .. 64
 // that covers the prefix in one pass of GS_COST_LOADS loads a lane; longer prefixes take several passes on 64 lanes
 inline int gs_cost_lanes(int cols) { int l = 8; while (l < 64 && GS_COST_LOADS * l < cols + 1) l *= 2; return l; }
+// ---- episode accounting over the last rollout (kernels_episodes.hip, abi_episodes.hip) ----
+// Four launches: gs_k_ep_count (seg[b] = the episodes instance b finished), gs_k_ep_offsets (seg -> its exclusive prefix sum in
+// place, the total to n_ep), gs_k_ep_accumulate (the recurrence of include/gridstep.h; instance b's records from seg[b] on) and
+// gs_k_ep_stats (one workgroup over the list).  GsEpisodeStats is gs_episode_stats as the kernels write it.
+#define GS_EP_SCAN_THREADS 1024          // the offset pass's one workgroup: a chunk of B per trip
+#define GS_EP_STAT_THREADS 1024          // the statistics pass's one workgroup
+#define GS_EP_CONTINUE 0                 // GS_EPISODES_CONTINUE, GS_EPISODES_UNKNOWN and GS_EPISODE_PARTIAL of include/gridstep.h, which the
+#define GS_EP_UNKNOWN 2                  // kernels do not include (abi_episodes.hip asserts that they agree)
+#define GS_EP_PARTIAL 4
+struct GsEpisodeStats {
+  long long count, count_partial;
+  double ret_mean, ret_std, ret_min, ret_max, len_mean, len_min, len_max, cost_mean[3];
+  long long violating[3], n_success;
+};
+struct GsEpisodeArgs {
+  const double* rew; const uint8_t* done;         // [T][B]
+  const double* costs; const double* margins;     // [3][T][B], channel c at c * chan_stride; NULL without costs
+  long long chan_stride;
+  int32_t T, B, cap, start;                       // cap: entries the list holds; start: GS_EPISODES_*
+  double* c_ret; int32_t* c_len; int32_t* c_ord; uint32_t* c_partial;      // carries [B] (c_partial: B bytes, stored four at a time)
+  double* c_cost; int32_t* c_viol; int32_t* c_anyv;                         // [3][B], [3][B], [B]; NULL without costs
+  int32_t* seg; int32_t* n_ep;
+  int32_t* e_idx; double* e_ret; int32_t* e_len; int32_t* e_ord; int32_t* e_flags;      // the list
+  double* e_cost; int32_t* e_viol; int32_t* e_anyv;                         // channel c at c * cap; NULL without costs
+  GsEpisodeStats* stats; double success_return;
+};
 #if defined(__HIPCC__)
 // constant ci of an observation (plan.cpp plan_maps: 2 l = P of load l, 2 l + 1 = its Q) as instance b holds it
 __device__ __forceinline__ double gs_pl_const(const double* __restrict__ pl, int n_loads, int b, int ci) {

@@ -148,6 +148,20 @@ struct gs_handle : GsPlan {
     DevBuf<double> margins, costs; DevBuf<int32_t> counts; DevBuf<unsigned long long> n_viol;
     uint64_t computed_on = 0; hipEvent_t ev = nullptr;
   } cc;
+  // gs_rollout_episodes (abi_episodes.hip): the per-instance carries of the open episodes ([B]; cost / viol [3][B]; partial: B bytes
+  // in whole words), the episode list of the last accounted rollout (cap entries, the rollout's term_cap; cost / viol channel c at
+  // c * cap), seg [B] (counts, then offsets), n_ep [1] and the statistics.  live: a track exists (gs_episodes_clear ends it);
+  // accounted_on = ro.calls of the rollout the list belongs to, 0 = none; moves_at = env_moves when that rollout was accounted.
+  // The carries are made on first use (all or none) and live until the track is cleared; the list goes with the rollout's buffers.
+  struct GS_HIDDEN EpisodeTrack {
+    DevBuf<double> c_ret, c_cost; DevBuf<int32_t> c_len, c_ord, c_viol, c_anyv, seg, n_ep; DevBuf<uint32_t> c_partial;
+    DevBuf<double> e_ret, e_cost; DevBuf<int32_t> e_idx, e_len, e_ord, e_flags, e_viol, e_anyv; DevBuf<GsEpisodeStats> stats;
+    size_t cap = 0; bool live = false; int with_costs = 0;
+    uint64_t accounted_on = 0, moves_at = 0; hipEvent_t ev = nullptr;
+  } ep;
+  // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count
+  // themselves here: gs_rollout_episodes(GS_EPISODES_CONTINUE) refuses to carry an episode across one
+  uint64_t env_moves = 0;
   double* d_cst = nullptr;
   int32_t *map_obs = nullptr, *map_vm = nullptr, *map_va = nullptr, *map_flow = nullptr, *map_load = nullptr,
           *map_p = nullptr, *map_q = nullptr, *map_act = nullptr, *map_state = nullptr;
@@ -338,6 +352,9 @@ int critic_download(gs_handle* h, const gs_handle::Critic& c, double* values, do
 
 // ---- owner of the rollout's constraint arrays (abi_costs.hip) ----
 void costs_release(gs_handle* h);
+
+// ---- owner of the episode track (abi_episodes.hip); keep_carries: only the list, which is sized by the rollout's capacity, goes ----
+void episodes_release(gs_handle* h, bool keep_carries = false);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);

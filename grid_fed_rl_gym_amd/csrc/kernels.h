@@ -52,6 +52,11 @@ __global__ void gs_k_policy_mlp_f32(GsPolicyArgsF32 P);
 __global__ void gs_k_value_mlp_f32(GsValueArgs P);
 __global__ void gs_k_gae(GsGaeArgs G);
 __global__ void gs_k_costs(GsCostArgs A);
+__global__ void gs_k_ep_count(GsEpisodeArgs E);
+__global__ void gs_k_ep_offsets(GsEpisodeArgs E);
+__global__ void gs_k_ep_accumulate(GsEpisodeArgs E);
+__global__ void gs_k_ep_accumulate_costs(GsEpisodeArgs E);
+__global__ void gs_k_ep_stats(GsEpisodeArgs E);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

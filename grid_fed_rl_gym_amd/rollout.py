@@ -19,6 +19,10 @@ log-probabilities the policy kernels recorded, a value network's estimates over 
 algorithms/safe.py): per transition and per channel (voltage, frequency, thermal) the constraint margin, the violation count and a
 cost, cost critics and cost advantages (``gs_rollout_costs``, ``gs_rollout_evaluate_costs``); ``costs_np`` and
 ``rollout_costs_np`` restate the contract.
+
+``rollout_episodes`` / ``EpisodeMonitor`` / ``evaluate_policy`` keep the books per EPISODE (``gs_rollout_episodes``; DESIGN.md section
+17): the returns, lengths and episodic costs of the episodes a rollout finished, with per-instance carries on the device so that an
+episode that straddles rollouts is one episode; ``episodes_np`` restates the contract.
 """
 from __future__ import annotations
 
@@ -281,6 +285,264 @@ def collect_constrained_data(env: BatchedGridEnvironment, policy, value, cost_va
     out["cost_advantages"] = {c: d["advantages"][c].reshape(T * B) for c in critics}
     out["cost_returns"] = {c: d["returns"][c].reshape(T * B) for c in critics}
     return out
+
+
+# ---- episode accounting (include/gridstep.h "episode accounting") -------------------------------------------------
+
+def _success_floor(success_return) -> float:
+    f = float(success_return)
+    if np.isnan(f) or f == np.inf:
+        raise ValueError("success_return must be finite or -inf")
+    return f
+
+
+def _episode_stats_np(rec: dict, with_costs: bool, success_return: float) -> SimpleNamespace:
+    """``gs_episode_stats`` of a record list, in NumPy (np.mean / np.std: the device's own order is DESIGN.md section 17's)."""
+    full = (rec["episode_flags"] & _lib.GS_EPISODE_PARTIAL) == 0
+    ret, length = rec["episode_return"][full], rec["episode_length"][full]
+    n = int(full.sum())
+    nan = float("nan")
+    clean = rec["episode_any_violating"][full] == 0 if with_costs else np.ones(n, dtype=bool)
+    return SimpleNamespace(
+        count=n, count_partial=int(len(full) - n),
+        return_mean=float(np.mean(ret)) if n else nan, return_std=float(np.std(ret)) if n else nan,
+        return_min=float(np.min(ret)) if n else nan, return_max=float(np.max(ret)) if n else nan,
+        length_mean=float(np.mean(length)) if n else nan, length_min=float(np.min(length)) if n else nan,
+        length_max=float(np.max(length)) if n else nan,
+        cost_mean=np.array([float(np.mean(rec["episode_cost"][c][full])) if n and with_costs else nan for c in range(3)]),
+        violating=np.array([int(rec["episode_violating"][c][full].sum()) if with_costs else 0 for c in range(3)], dtype=np.int64),
+        n_success=int(np.sum(clean & (ret > success_return))))
+
+
+def episodes_np(rewards, terminals, costs=None, margins=None, carry=None, start="fresh", success_return: float = -1000.0):
+    """(records, stats, carry): the contract of ``gs_rollout_episodes`` (include/gridstep.h) restated in NumPy, operation by operation.
+    ``rewards`` [T, B] float64 and ``terminals`` [T, B] uint8 done flags of one rollout; with ``costs`` and ``margins`` [3, T, B]
+    (``rollout_costs``) the episodic costs and violating steps as well.  Per instance, t = 0 .. T-1 in order: ``ret = ret + r``, one
+    rounded float64 addition per step; ``len += 1``; ``cost[c] = cost[c] + costs[c, t, b]``; a step violates channel c where
+    ``margins[c, t, b] < 0`` (a NaN margin counts as nothing); where ``terminals[t, b] != 0`` a record is filed and the carries start
+    again from zero with ``ordinal + 1``.  ``start``: "fresh" (zero carries, nothing partial), "unknown" (zero carries, every instance's
+    open episode partial) or "continue" (``carry`` as a previous call returned it).
+    ``records``: a dict of ``episode_index`` [n, 2] (t_end, b), ``episode_return``, ``episode_length``, ``episode_ordinal``,
+    ``episode_flags`` (the done flag's bits 0, 1; 4 = partial) and with costs ``episode_cost`` / ``episode_violating`` [3, n] and
+    ``episode_any_violating`` [n], sorted by (b, t_end).  ``stats``: the fields of ``gs_episode_stats`` over the complete records.
+    ``carry``: ``ep_return``, ``ep_length``, ``ep_ordinal``, ``ep_partial`` [B] and with costs ``ep_cost`` / ``ep_violating`` [3, B],
+    ``ep_any_violating`` [B]."""
+    floor = _success_floor(success_return)
+    rewards = np.asarray(rewards, dtype=np.float64)
+    terminals = np.asarray(terminals).astype(np.uint8)
+    T, B = rewards.shape
+    with_costs = costs is not None
+    if with_costs != (margins is not None):
+        raise ValueError("episodes_np: costs and margins go together")
+    if start not in _lib.EPISODES_START:
+        raise ValueError(f"episodes_np: start {start!r} is none of {sorted(_lib.EPISODES_START)}")
+    if start == "continue":
+        if carry is None:
+            raise ValueError("episodes_np: start='continue' needs the carry of the previous call")
+        if with_costs != ("ep_cost" in carry):
+            raise ValueError("episodes_np: the carry was made with costs " + ("off" if with_costs else "on"))
+        ret, length, ordinal = carry["ep_return"].astype(np.float64), carry["ep_length"].astype(np.int32), carry["ep_ordinal"].astype(np.int32)
+        partial = carry["ep_partial"].astype(np.uint8)
+        if with_costs:
+            cost, viol, anyv = carry["ep_cost"].astype(np.float64), carry["ep_violating"].astype(np.int32), carry["ep_any_violating"].astype(np.int32)
+    else:
+        ret, length, ordinal = np.zeros(B), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        partial = np.full(B, 1 if start == "unknown" else 0, dtype=np.uint8)
+        cost, viol, anyv = np.zeros((3, B)), np.zeros((3, B), dtype=np.int32), np.zeros(B, dtype=np.int32)
+    if with_costs:
+        costs, margins = np.asarray(costs, dtype=np.float64).reshape(3, T, B), np.asarray(margins, dtype=np.float64).reshape(3, T, B)
+    filed = {k: [] for k in ("t", "b", "ret", "len", "ord", "flags", "cost", "viol", "anyv")}
+    for t in range(T):
+        ret = ret + rewards[t]
+        length = length + 1
+        if with_costs:
+            cost = cost + costs[:, t]
+            with np.errstate(invalid="ignore"):
+                bad = margins[:, t] < 0.0
+            viol = viol + bad
+            anyv = anyv + bad.any(axis=0)
+        done = np.nonzero(terminals[t] != 0)[0]
+        if len(done):
+            filed["t"].append(np.full(len(done), t, dtype=np.int32)); filed["b"].append(done.astype(np.int32))
+            filed["ret"].append(ret[done]); filed["len"].append(length[done]); filed["ord"].append(ordinal[done])
+            filed["flags"].append((terminals[t, done] & 3).astype(np.int32) | np.where(partial[done] != 0, _lib.GS_EPISODE_PARTIAL, 0).astype(np.int32))
+            if with_costs:
+                filed["cost"].append(cost[:, done]); filed["viol"].append(viol[:, done]); filed["anyv"].append(anyv[done])
+                cost[:, done] = 0.0; viol[:, done] = 0; anyv[done] = 0
+            ret[done] = 0.0; length[done] = 0; ordinal[done] += 1; partial[done] = 0
+    cat = lambda k, dt, axis=0, empty=(0,): np.concatenate(filed[k], axis=axis).astype(dt) if filed[k] else np.zeros(empty, dtype=dt)
+    t_end, b_of = cat("t", np.int32), cat("b", np.int32)
+    order = np.lexsort((t_end, b_of))        # by b, then t_end
+    rec = dict(episode_index=np.stack([t_end, b_of], axis=1)[order].astype(np.int32), episode_return=cat("ret", np.float64)[order],
+               episode_length=cat("len", np.int32)[order], episode_ordinal=cat("ord", np.int32)[order], episode_flags=cat("flags", np.int32)[order])
+    new_carry = dict(ep_return=ret, ep_length=length.astype(np.int32), ep_ordinal=ordinal.astype(np.int32), ep_partial=partial)
+    if with_costs:
+        rec.update(episode_cost=cat("cost", np.float64, 1, (3, 0))[:, order], episode_violating=cat("viol", np.int32, 1, (3, 0))[:, order],
+                   episode_any_violating=cat("anyv", np.int32)[order])
+        new_carry.update(ep_cost=cost, ep_violating=viol.astype(np.int32), ep_any_violating=anyv.astype(np.int32))
+    return rec, _episode_stats_np(rec, with_costs, floor), new_carry
+
+
+class EpisodeRecords:
+    """What ``rollout_episodes`` left on the device: the list arrays (``episode_index`` [n, 2] (t_end, b), ``episode_return``,
+    ``episode_length``, ``episode_ordinal``, ``episode_flags`` [n]; with costs ``episode_cost`` and ``episode_violating``, lists of
+    three [n] per channel, and ``episode_any_violating``) and the carries (``ep_return``, ``ep_length``, ``ep_ordinal``,
+    ``ep_partial`` [B]; with costs ``ep_cost``, ``ep_violating`` [3, B], ``ep_any_violating``) as zero-copy ``DeviceArray`` views
+    (``torch.as_tensor(x, device="cuda")``; None where there are no costs); ``n_episodes``; and ``stats``, a host object with the
+    fields of ``gs_episode_stats``.  The list is valid until the next rollout or accounting.  ``download()``: host copies, the cost
+    arrays [3, n]."""
+
+    def __init__(self, handle, arrays: dict, stats) -> None:
+        self._handle = handle
+        self.n_episodes, self.with_costs = arrays["n_episodes"], arrays["with_costs"]
+        for k, _ in _lib.EPISODE_LIST_KEYS + _lib.EPISODE_CARRY_KEYS:
+            setattr(self, k, arrays[k])
+        self.stats = stats
+
+    def download(self, want=None) -> dict:
+        return self._handle.rollout_episodes_download(want, n_episodes=self.n_episodes)
+
+
+def _stats_object(s) -> SimpleNamespace:
+    """A ``gs_episode_stats`` as a plain host object (``cost_mean`` float64 [3], ``violating`` int64 [3])."""
+    return SimpleNamespace(count=int(s.count), count_partial=int(s.count_partial), return_mean=float(s.return_mean), return_std=float(s.return_std),
+                           return_min=float(s.return_min), return_max=float(s.return_max), length_mean=float(s.length_mean),
+                           length_min=float(s.length_min), length_max=float(s.length_max), cost_mean=np.array(list(s.cost_mean), dtype=np.float64),
+                           violating=np.array(list(s.violating), dtype=np.int64), n_success=int(s.n_success))
+
+
+def rollout_episodes(env: BatchedGridEnvironment, start: str = "continue", costs: bool = False, success_return: float = -1000.0,
+                     stream=None) -> EpisodeRecords:
+    """The episodes the environment's LAST rollout finished -- return, length, ordinal, end flags and, with ``costs`` (after
+    ``rollout_costs``), episodic cost and violating steps per channel -- and the carries of the episodes still open, computed on the
+    device (``gs_rollout_episodes``).  An episode that straddles rollouts is one episode: ``start="continue"`` takes the carries the
+    previous accounted rollout left; "fresh" states that ``env.reset()`` came directly before the rollout; "unknown" marks every
+    instance's open episode partial (left out of ``stats``).  ``success_return``: an episode succeeds with no violating step and a
+    return above it (the reference's -1000; -inf: no floor).  ``stream``: as ``evaluate_rollout``."""
+    h = env.handle
+    h.rollout_episodes(_lib.episode_config(start, costs, _success_floor(success_return)))
+    arrays = h.rollout_episodes_arrays(stream)
+    stats = h.rollout_episodes_download(("stats",), n_episodes=arrays["n_episodes"])["stats"]
+    return EpisodeRecords(h, arrays, _stats_object(stats))
+
+
+class EpisodeMonitor:
+    """A learning curve over device rollouts: after every rollout ``update()`` accounts its episodes on the device
+    (``rollout_episodes``) and merges the rollout's statistics into running ones on the host -- Chan's merge on (count, mean, M2) --
+    and keeps the last ``window`` complete returns and lengths.  ``after_reset()`` tells it that ``env.reset()`` came before the
+    next rollout ("fresh"); otherwise it continues, and before its first rollout it assumes nothing ("unknown": the open episodes
+    are partial and left out).  Reports ``count``, ``mean_return``, ``std_return``, ``min_return``, ``max_return``, ``mean_length``,
+    ``mean_cost`` [3], ``violating`` [3], ``success_rate``; ``window_mean_return`` / ``window_mean_length`` over the window."""
+
+    def __init__(self, env: Optional[BatchedGridEnvironment] = None, window: int = 100) -> None:
+        from collections import deque
+        self.env, self._start = env, "unknown"
+        self.returns, self.lengths = deque(maxlen=int(window)), deque(maxlen=int(window))
+        self.count, self.count_partial, self._mean, self._m2 = 0, 0, 0.0, 0.0
+        self.min_return, self.max_return = float("nan"), float("nan")
+        self._length_total, self._cost_mean, self._cost_count = 0, np.zeros(3), 0
+        self.violating, self.n_success = np.zeros(3, dtype=np.int64), 0
+
+    def after_reset(self) -> None:
+        self._start = "fresh"
+
+    def update(self, costs: bool = False, success_return: float = -1000.0, stream=None) -> EpisodeRecords:
+        rec = rollout_episodes(self.env, self._start, costs, success_return, stream)
+        self._start = "continue"
+        returns = lengths = None
+        if rec.n_episodes:
+            d = rec.download(("episode_return", "episode_length", "episode_flags"))
+            full = (d["episode_flags"] & _lib.GS_EPISODE_PARTIAL) == 0
+            returns, lengths = d["episode_return"][full], d["episode_length"][full]
+        self.merge(rec.stats, returns, lengths, with_costs=costs)
+        return rec
+
+    def merge(self, stats, returns=None, lengths=None, with_costs: Optional[bool] = None) -> None:
+        """Merge one rollout's statistics (an object with the fields of ``gs_episode_stats``); ``returns`` / ``lengths``: its
+        complete episodes, for the window."""
+        self.count_partial += int(stats.count_partial)
+        nb = int(stats.count)
+        if returns is not None:
+            self.returns.extend(float(x) for x in returns); self.lengths.extend(int(x) for x in lengths)
+        if nb == 0:
+            return
+        na, n = self.count, self.count + nb
+        mb, m2b = float(stats.return_mean), float(stats.return_std) ** 2 * nb
+        delta = mb - self._mean
+        self._mean = self._mean + delta * (nb / n) if na else mb
+        self._m2 = self._m2 + m2b + delta * delta * (na * nb / n) if na else m2b
+        self.min_return = float(stats.return_min) if na == 0 else min(self.min_return, float(stats.return_min))
+        self.max_return = float(stats.return_max) if na == 0 else max(self.max_return, float(stats.return_max))
+        self._length_total += int(round(float(stats.length_mean) * nb))
+        self.count = n
+        self.n_success += int(stats.n_success)
+        cost_mean = np.asarray(stats.cost_mean, dtype=np.float64)
+        if with_costs is None:
+            with_costs = not np.isnan(cost_mean).all()
+        if with_costs:
+            nc = self._cost_count + nb
+            self._cost_mean = self._cost_mean + (cost_mean - self._cost_mean) * (nb / nc)
+            self._cost_count = nc
+            self.violating = self.violating + np.asarray(stats.violating, dtype=np.int64)
+
+    mean_return = property(lambda self: self._mean if self.count else float("nan"))
+    std_return = property(lambda self: float(np.sqrt(self._m2 / self.count)) if self.count else float("nan"))
+    mean_length = property(lambda self: self._length_total / self.count if self.count else float("nan"))
+    mean_cost = property(lambda self: self._cost_mean.copy() if self._cost_count else np.full(3, np.nan))
+    success_rate = property(lambda self: self.n_success / self.count if self.count else float("nan"))
+    window_mean_return = property(lambda self: float(np.mean(self.returns)) if self.returns else float("nan"))
+    window_mean_length = property(lambda self: float(np.mean(self.lengths)) if self.lengths else float("nan"))
+
+
+def evaluate_policy(env: BatchedGridEnvironment, policy, episodes_per_instance: int = 1, deterministic: bool = True, seed: int = 0,
+                    limits: Optional[ConstraintLimits] = None, kinds="excess", success_return: float = -1000.0,
+                    max_steps: Optional[int] = None, rollout_steps: Optional[int] = None) -> Dict[str, object]:
+    """The reference's ``BenchmarkSuite._run_evaluation`` (benchmarking/benchmark_suite.py:360-429), batched and on the device:
+    ``env.reset(seed=seed)``, then rollouts of ``rollout_steps`` steps (default: min(episode_length, 32)) under ``policy`` (an
+    ``MLPPolicy``; ``stochastic = not deterministic``), rollout r with the noise seed ``seed + r``, each followed by ``rollout_costs``
+    (where ``limits`` is given) and ``rollout_episodes``, until every instance has finished ``episodes_per_instance`` episodes.
+    Only an instance's first ``episodes_per_instance`` episodes count, so instances with short episodes are not over-represented.
+    Raises ``PowerFlowError`` where that would take more than ``max_steps`` steps per instance (default: ``episodes_per_instance *
+    episode_length`` rounded up to whole rollouts -- no episode outlives the time limit).
+    Returns the reference's keys: ``episode_returns`` (float64 [B * episodes_per_instance], rollout by rollout and within one by
+    (instance, end step)), ``mean_return``, ``std_return`` (np.std), ``safety_violations`` (steps violating any channel, None
+    without ``limits``), ``success_rate`` (no violating step -- vacuous without ``limits`` -- and return > ``success_return``),
+    ``mean_cost`` (mean episodic cost per channel [3], None without ``limits``); plus ``episode_lengths``, ``episodes`` and ``steps``."""
+    K, B = int(episodes_per_instance), env.num_envs
+    if K < 1:
+        raise ValueError("evaluate_policy: episodes_per_instance >= 1")
+    floor = _success_floor(success_return)
+    T = int(rollout_steps) if rollout_steps else max(1, min(env.episode_length, 32))
+    if max_steps is None:
+        max_steps = -(-K * env.episode_length // T) * T
+    with_costs = limits is not None
+    env.reset(seed=seed)
+    env.set_policy(policy, stochastic=not deterministic)
+    h = env.handle
+    returns, lengths, costs, anyv = [], [], [], []
+    steps, r = 0, 0
+    while True:
+        if steps + T > int(max_steps):
+            raise PowerFlowError(f"evaluate_policy: not every instance finished {K} episode(s) within max_steps = {max_steps} steps")
+        h.rollout(T, "mlp", seed=seed + r)
+        if with_costs:
+            h.rollout_costs(_lib.cost_config(limits, kinds))
+        h.rollout_episodes(_lib.episode_config("fresh" if r == 0 else "continue", with_costs, floor))
+        want = ["episode_return", "episode_length", "episode_ordinal", "ep_ordinal"] + (["episode_cost", "episode_any_violating"] if with_costs else [])
+        d = h.rollout_episodes_download(want)
+        keep = d["episode_ordinal"] < K
+        returns.append(d["episode_return"][keep]); lengths.append(d["episode_length"][keep])
+        if with_costs:
+            costs.append(d["episode_cost"][:, keep]); anyv.append(d["episode_any_violating"][keep])
+        steps += T; r += 1
+        if int(d["ep_ordinal"].min()) >= K:
+            break
+    returns, lengths = np.concatenate(returns), np.concatenate(lengths)
+    clean = np.concatenate(anyv) == 0 if with_costs else np.ones(len(returns), dtype=bool)
+    return dict(episode_returns=returns, episode_lengths=lengths, mean_return=float(np.mean(returns)), std_return=float(np.std(returns)),
+                safety_violations=int(np.concatenate(anyv).sum()) if with_costs else None,
+                success_rate=float(np.sum(clean & (returns > floor)) / len(returns)),
+                mean_cost=np.mean(np.concatenate(costs, axis=1), axis=1) if with_costs else None, episodes=int(len(returns)), steps=int(steps))
 
 
 class GridDataset:

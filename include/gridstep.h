@@ -551,6 +551,105 @@ typedef struct gs_rollout_costs_host {
 } gs_rollout_costs_host;
 int gs_rollout_costs_download(gs_handle* h, const gs_rollout_costs_host* out);
 
+/* ---- episode accounting: returns, lengths and episodic costs of the episodes a rollout finished ----------
+ * What the reference's evaluation loop (benchmarking/benchmark_suite.py:360-429) keeps per episode -- `episode_return += reward`
+ * until done, the steps, the violating steps -- kept per instance on the device ACROSS rollouts, so that an episode that straddles
+ * a rollout boundary is one episode.  Additive to ABI 2.
+ *
+ * Per-instance carries (device arrays of the handle's episode track): ep_return[B] float64, ep_length[B], ep_ordinal[B] int32 (the
+ * episodes the instance has finished since the track started), ep_partial[B] uint8 (the open episode's start was not seen), and with
+ * costs ep_cost[3][B] float64, ep_violating[3][B], ep_any_violating[B] int32.
+ * gs_rollout_episodes (asynchronous, on the handle's stream, over the LAST rollout) runs, per instance b and t = 0 .. T-1 in order,
+ *   ret = ret + rewards[t][b]          one rounded float64 addition per step, never contracted or reassociated
+ *   len = len + 1
+ *   with costs, per channel c:  cost[c] = cost[c] + costs[c][t][b];  viol[c] += margins[c][t][b] < 0  (a NaN margin counts as nothing);
+ *                               any += (margins[c][t][b] < 0 for some c)
+ *   terminals[t][b] != 0:  file the record (t, b, ret, len, ordinal, flags, cost, viol, any), flags = (terminals[t][b] & 3) |
+ *                          (partial ? GS_EPISODE_PARTIAL : 0); then ret = 0, len = 0, cost = viol = any = 0, ordinal += 1, partial = 0
+ * and stores the carries.  The records of the rollout form a list of n_episodes == n_terminal entries sorted by (b, t_end):
+ * instance-major, chronological within an instance; every record's place follows from a prefix sum of the instances' counts, no
+ * atomic decides it.  cfg == NULL: GS_EPISODES_CONTINUE, no costs, success_return = -1000.
+ *
+ * start.  GS_EPISODES_FRESH: the caller states that every instance stood at the start of an episode when the last rollout began
+ * (gs_reset came directly before it); the carries start from zero and nothing is partial.  GS_EPISODES_UNKNOWN: the carries start
+ * from zero and every instance's open episode is partial: its record covers the seen part only.  GS_EPISODES_CONTINUE: the carries
+ * are those the previous accounted rollout left.
+ *
+ * gs_episode_stats, over the rollout's COMPLETE episodes (those without GS_EPISODE_PARTIAL): count and count_partial; mean,
+ * population standard deviation (np.std), minimum and maximum of the return; mean, minimum and maximum of the length; with costs
+ * the mean cost and the total of violating steps per channel; n_success = the complete episodes with return > success_return and
+ * (with costs) no step violating in any channel.  One workgroup reduces the list in a fixed order (DESIGN.md section 17 states the
+ * order and its error bound): no floating-point atomics, the same list gives the same bits.  count == 0: the means, the standard
+ * deviation and the extremes are NaN, the counts 0.  Without costs cost_mean is NaN and violating 0.
+ *
+ * GS_E_STATE (with a message; nothing launched, the carries untouched): no rollout yet; the last rollout was already accounted;
+ * CONTINUE without a track, or when the rollout before the last one was not accounted, or when the environment was moved outside
+ * gs_rollout since the accounted one (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*), or with a with_costs
+ * other than the track was started with; with_costs before gs_rollout_costs on the last rollout.  GS_E_INVALID: a wrong
+ * struct_size, an unknown start, a success_return that is NaN or +inf (-inf: no floor on the return).
+ * gs_rollout_episodes_view: device pointers, the list valid until the next gs_rollout_episodes or gs_rollout, the carries until
+ * gs_episodes_clear (consumer_stream as gs_step_device_view; the call waits for the number of finished episodes).  Channel c of
+ * episode_cost / episode_violating lies at c * cost_stride; all three cost pointers and the cost carries are NULL without costs.
+ * gs_rollout_episodes_download: host copies, any pointer may be NULL; episode_cost / episode_violating packed [3][n_episodes].
+ * Both return GS_E_STATE unless gs_rollout_episodes has run on the last rollout.  gs_episodes_clear drops the track. */
+enum { GS_EPISODES_CONTINUE = 0, GS_EPISODES_FRESH = 1, GS_EPISODES_UNKNOWN = 2 };
+enum { GS_EPISODE_TERMINATED = 1, GS_EPISODE_TRUNCATED = 2, GS_EPISODE_PARTIAL = 4 };   /* bits 0, 1: the done flag's own */
+typedef struct gs_episode_config {
+  int32_t struct_size, start;        /* = sizeof(gs_episode_config); GS_EPISODES_* */
+  int32_t with_costs, reserved;      /* != 0: also accumulate gs_rollout_costs' costs and violating steps */
+  double success_return;             /* an episode succeeds with no violating step and return > this (reference: -1000) */
+} gs_episode_config;
+typedef struct gs_episode_stats {
+  int64_t count, count_partial;
+  double return_mean, return_std, return_min, return_max;
+  double length_mean, length_min, length_max;
+  double cost_mean[3];
+  int64_t violating[3];
+  int64_t n_success;
+} gs_episode_stats;
+typedef struct gs_rollout_episodes_dev {
+  int32_t n_episodes, B, with_costs, cost_stride;
+  const int32_t* episode_index;          /* [n_episodes][2] (t_end, b) */
+  const double* episode_return;          /* [n_episodes] */
+  const int32_t* episode_length;         /* [n_episodes] */
+  const int32_t* episode_ordinal;        /* [n_episodes] */
+  const int32_t* episode_flags;          /* [n_episodes] GS_EPISODE_* */
+  const double* episode_cost;            /* channel c at c * cost_stride, or NULL */
+  const int32_t* episode_violating;      /* channel c at c * cost_stride, or NULL */
+  const int32_t* episode_any_violating;  /* [n_episodes], or NULL */
+  const gs_episode_stats* stats;
+  const double* ep_return;               /* [B] */
+  const int32_t* ep_length;              /* [B] */
+  const int32_t* ep_ordinal;             /* [B] */
+  const uint8_t* ep_partial;             /* [B] */
+  const double* ep_cost;                 /* [3][B], or NULL */
+  const int32_t* ep_violating;           /* [3][B], or NULL */
+  const int32_t* ep_any_violating;       /* [B], or NULL */
+} gs_rollout_episodes_dev;
+typedef struct gs_rollout_episodes_host {
+  int32_t* n_episodes;                   /* [1] */
+  int32_t* episode_index;                /* [n_episodes][2] (room for as many as gs_rollout_download reported) */
+  double* episode_return;
+  int32_t* episode_length;
+  int32_t* episode_ordinal;
+  int32_t* episode_flags;
+  double* episode_cost;                  /* [3][n_episodes] */
+  int32_t* episode_violating;            /* [3][n_episodes] */
+  int32_t* episode_any_violating;
+  gs_episode_stats* stats;
+  double* ep_return;                     /* [B] */
+  int32_t* ep_length;
+  int32_t* ep_ordinal;
+  uint8_t* ep_partial;
+  double* ep_cost;                       /* [3][B] */
+  int32_t* ep_violating;                 /* [3][B] */
+  int32_t* ep_any_violating;
+} gs_rollout_episodes_host;
+int gs_rollout_episodes(gs_handle* h, const gs_episode_config* cfg);
+int gs_rollout_episodes_view(gs_handle* h, gs_rollout_episodes_dev* out, void* consumer_stream);
+int gs_rollout_episodes_download(gs_handle* h, const gs_rollout_episodes_host* out);
+int gs_episodes_clear(gs_handle* h);
+
 /* ---- the device-resident dataset: statistics of the last rollout and normalised minibatches ----------------------------
  * What the reference's GridDataset (algorithms/base.py:180-266) does on the host, done where gs_rollout left the collection:
  * the per-column normalisation statistics over its N = T * B transitions (transition index = t * B + b), and minibatches
