@@ -19,7 +19,7 @@ from .env import BatchedGridEnvironment, VectorizedEnvironment, Box
 from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy_data, evaluate_rollout, gae_np, rollout_device, GridDataset,
                       DeviceGridDataset, ConstraintLimits, costs_np, rollout_costs_np, rollout_costs, evaluate_rollout_costs,
                       constraint_values, collect_constrained_data, episodes_np, rollout_episodes, EpisodeRecords, EpisodeMonitor,
-                      evaluate_policy)
+                      evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches)
 from .policy import MLPPolicy, MLPValue
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -34,6 +34,7 @@ __all__ = [
     "collect_random_data", "collect_policy_data", "rollout_device", "MLPPolicy", "MLPValue", "collect_onpolicy_data", "evaluate_rollout", "gae_np", "GridDataset", "DeviceGridDataset",
     "ConstraintLimits", "costs_np", "rollout_costs_np", "rollout_costs", "evaluate_rollout_costs", "constraint_values", "collect_constrained_data",
     "episodes_np", "rollout_episodes", "EpisodeRecords", "EpisodeMonitor", "evaluate_policy",
+    "permutation_np", "onpolicy_batch_np", "OnPolicyBatches",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",
     "BatchedSafetyChecker", "BatchedSafetyMonitor", "PostStepChecks", "device_quality_score",

@@ -235,6 +235,42 @@ GS_DATASET_KEEP_STATS = 1
 DATASET_KEYS = ("observations", "actions", "rewards", "next_observations", "terminals")      # gs_dataset_batch's fields, in order
 
 
+# on-policy minibatch epochs (include/gridstep.h): advantage normalisations, the field bits and the structs of gs_onpolicy_*
+ADV_NORM = {"none": 0, "rollout": 1, "minibatch": 2}      # GS_ADVNORM_*
+# the fields of gs_onpolicy_batch_out, in order, with their GS_ONPOLICY_* bit
+ONPOLICY_BATCH_FIELDS = (("observations", 1), ("actions", 2), ("log_probs", 4), ("advantages", 8), ("returns", 16), ("values", 32),
+                         ("cost_advantages", 64), ("cost_returns", 128), ("indices", 256))
+GS_ONPOLICY_ALL_FIELDS = 511
+
+
+class gs_onpolicy_batch_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("adv_norm", C.c_int32), ("dtype", C.c_int32), ("fields", C.c_uint32), ("lam", _d3),
+                ("adv_eps", C.c_double), ("obs_shift", _dp), ("obs_scale", _dp)]
+
+
+class gs_onpolicy_stats_out(C.Structure):
+    _fields_ = [("n", C.c_int64), ("adv_mean", C.c_double), ("adv_std", C.c_double)]
+
+
+class gs_onpolicy_batch_out(C.Structure):
+    _fields_ = [("observations", C.c_void_p), ("actions", C.c_void_p), ("log_probs", C.c_void_p), ("advantages", C.c_void_p),
+                ("returns", C.c_void_p), ("values", C.c_void_p), ("cost_advantages", _vp3), ("cost_returns", _vp3),
+                ("indices", C.c_void_p), ("adv_stats", C.c_void_p)]
+
+
+def onpolicy_fields(fields) -> int:
+    """The GS_ONPOLICY_* mask of ``fields``: None (all), the mask itself, or names of ONPOLICY_BATCH_FIELDS."""
+    if fields is None:
+        return GS_ONPOLICY_ALL_FIELDS
+    if isinstance(fields, (int, np.integer)):
+        return int(fields)
+    bits = dict(ONPOLICY_BATCH_FIELDS)
+    unknown = [k for k in fields if k not in bits]
+    if unknown:
+        raise PowerFlowError(f"on-policy batch: unknown field(s) {unknown}; any of {[k for k, _ in ONPOLICY_BATCH_FIELDS]}")
+    return sum(bits[k] for k in set(fields))
+
+
 # every symbol include/gridstep.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = [
@@ -323,6 +359,9 @@ SYMBOLS = [
     ("gs_rollout_episodes_view", C.c_int, [_H, C.POINTER(gs_rollout_episodes_dev), C.c_void_p]),
     ("gs_rollout_episodes_download", C.c_int, [_H, C.POINTER(gs_rollout_episodes_host)]),
     ("gs_episodes_clear", C.c_int, [_H]),
+    ("gs_onpolicy_prepare", C.c_int, [_H, C.POINTER(gs_onpolicy_batch_config)]),
+    ("gs_onpolicy_stats", C.c_int, [_H, C.POINTER(gs_onpolicy_stats_out)]),
+    ("gs_onpolicy_batch", C.c_int, [_H, C.c_uint64, C.c_uint32, C.c_int64, C.c_int32, C.POINTER(gs_onpolicy_batch_out), C.c_void_p]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -1311,6 +1350,71 @@ class Handle:
             raise PowerFlowError(f"rollout_episodes_download: the rollout finished {cnt.value} episodes, not {n}")
         out["n_episodes"] = n
         return out
+
+    # -- on-policy minibatch epochs over the last rollout (gs_onpolicy_*) --------------------------------------------------------
+    def onpolicy_prepare(self, adv_norm="rollout", dtype=np.float32, fields=None, lambdas=(0.0, 0.0, 0.0), adv_eps: float = 1e-8,
+                         obs_shift=None, obs_scale=None, struct_size=None) -> None:
+        """gs_onpolicy_prepare (asynchronous): the combined advantage of the last rollout and its statistics, and the observation
+        normalisation ``(x - obs_shift) * obs_scale`` of the minibatches.  ``adv_norm``: a name of ADV_NORM or its number; ``dtype``:
+        float64 / float32 (or the GS_COMPUTE_* number); ``fields``: ``onpolicy_fields``; ``lambdas``: one multiplier per channel."""
+        if isinstance(dtype, (int, np.integer)):
+            compute = int(dtype)
+        else:
+            dt = np.dtype(dtype)
+            if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+                raise PowerFlowError(f"onpolicy_prepare: dtype {dt} (float64 or float32)")
+            compute = 1 if dt == np.dtype(np.float32) else 0
+        shift = None if obs_shift is None else _f64(obs_shift).reshape(-1)
+        scale = None if obs_scale is None else _f64(obs_scale).reshape(-1)
+        for v in (shift, scale):
+            if v is not None and v.shape != (self.obs_dim,):
+                raise PowerFlowError(f"onpolicy_prepare: obs_shift / obs_scale shape {v.shape} != ({self.obs_dim},)")
+        cfg = gs_onpolicy_batch_config(C.sizeof(gs_onpolicy_batch_config) if struct_size is None else int(struct_size),
+                                       ADV_NORM[adv_norm] if isinstance(adv_norm, str) else int(adv_norm), compute, onpolicy_fields(fields),
+                                       _d3(*[float(x) for x in lambdas]), float(adv_eps), _ptr(shift, _dp), _ptr(scale, _dp))
+        self._check(self._lib.gs_onpolicy_prepare(self._h, C.byref(cfg)))
+        self._opb = (compute, int(cfg.fields))
+
+    def onpolicy_stats(self) -> dict:
+        """gs_onpolicy_stats: ``n`` and the combined advantage's ``adv_mean`` and raw ``adv_std`` over the rollout (waits for the prepare)."""
+        o = gs_onpolicy_stats_out()
+        self._check(self._lib.gs_onpolicy_stats(self._h, C.byref(o)))
+        return dict(n=int(o.n), adv_mean=float(o.adv_mean), adv_std=float(o.adv_std))
+
+    def onpolicy_batch(self, seed: int, epoch: int, first: int, n: int, out=None, stream=None) -> dict:
+        """gs_onpolicy_batch: positions ``first .. first + n - 1`` of the epoch's permutation as zero-copy ``DeviceArray`` views keyed
+        by the prepared fields (``cost_advantages`` / ``cost_returns``: lists of three, None for a channel that is not gathered), plus
+        ``adv_stats`` [2] float64 with the advantages.  ``out``: the caller's device arrays per key (lists of three for the cost
+        fields), the handle's own buffers -- valid until the next call -- for the rest; ``stream``: the consumer's stream."""
+        compute, fields = getattr(self, "_opb", (1, 0))
+        dt = np.dtype(np.float32 if compute == 1 else np.float64)
+        n = int(n)
+        shapes = dict(observations=(n, self.obs_dim), actions=(n, self.action_dim))
+        types = dict(indices=np.dtype(np.int32), adv_stats=np.dtype(np.float64))
+        shape = lambda k: (2,) if k == "adv_stats" else shapes.get(k, (n,))
+        b = gs_onpolicy_batch_out()
+        for k, x in (out or {}).items():
+            if k in ("cost_advantages", "cost_returns"):
+                for c in range(3):
+                    if x[c] is not None:
+                        getattr(b, k)[c] = _device_address_of(x[c], (n,), dt)
+            elif k in dict(ONPOLICY_BATCH_FIELDS) or k == "adv_stats":
+                setattr(b, k, _device_address_of(x, shape(k), types.get(k, dt)))
+            else:
+                raise PowerFlowError(f"onpolicy_batch: unknown output {k!r}")
+        self._check(self._lib.gs_onpolicy_batch(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(epoch) & 0xFFFFFFFF),
+                                                int(first), n, C.byref(b), _stream_arg(stream)))
+        res = {}
+        for k, bit in ONPOLICY_BATCH_FIELDS:
+            if not fields & bit:
+                continue
+            if k in ("cost_advantages", "cost_returns"):
+                res[k] = [DeviceArray(getattr(b, k)[c], (n,), dt.str) if getattr(b, k)[c] else None for c in range(3)]
+            else:
+                res[k] = DeviceArray(getattr(b, k), shape(k), types.get(k, dt).str)
+        if fields & 8:
+            res["adv_stats"] = DeviceArray(b.adv_stats, (2,), "<f8")
+        return res
 
     def rollout_device_view(self) -> gs_rollout_device:
         """Device pointers of the last rollout (gs_rollout_device_view) for a consumer that stays on the GPU."""

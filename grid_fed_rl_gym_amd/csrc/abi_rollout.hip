@@ -38,6 +38,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   onpolicy_release(h);           // (sized by T as well)
   costs_release(h);
   episodes_release(h, keep_term_count);      // (the list is sized by the capacity; the carries outlive a longer rollout)
+  batches_release(h);
   ro.T_cap = 0; ro.T = 0; ro.n_term = -1;
 }
 

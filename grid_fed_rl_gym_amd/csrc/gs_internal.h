@@ -658,6 +658,45 @@ struct GsEpisodeArgs {
   double* e_cost; int32_t* e_viol; int32_t* e_anyv;                         // channel c at c * cap; NULL without costs
   GsEpisodeStats* stats; double success_return;
 };
+// ---- on-policy minibatch epochs over the last rollout (kernels_batches.hip, abi_batches.hip) ----
+// gs_onpolicy_prepare: gs_k_opb_combine (comb[j] = adv[j] - sum lambda[c] * cadv[c][j]), then the dataset's gs_k_ds_chunk_stats /
+// gs_k_ds_merge over comb as an [N][1] matrix.  gs_onpolicy_batch: gs_k_opb_index (the permutation walk per position: idx[i], and
+// stage[i] = comb[idx[i]]), in minibatch mode gs_k_opb_mbstats (one workgroup over stage), then gs_k_opb_gather_f64 / _f32.
+#define GS_OPB_STAT_THREADS 1024         // the minibatch statistics' one workgroup (the order of gs_k_ep_stats)
+#define GS_OPB_WAVES 4                   // wavefronts per workgroup of the gather
+#define GS_OPB_SAMPLES 1                 // samples per wavefront (2, their loads in flight together, measured slower: DESIGN.md section 18)
+#define GS_OPB_PASSES 6                  // column pairs (columns, where obs_dim is odd) a lane holds shift and scale for at a time
+#define GS_OPB_SCALARS 10                // log_probs, advantages, returns, values, cost_advantages[3], cost_returns[3]: lane k gathers scalar k
+#define GS_OPB_SC_ADV 1
+#define GS_OPB_NORM_NONE 0               // GS_ADVNORM_* of include/gridstep.h, which the kernels do not include (abi_batches.hip
+#define GS_OPB_NORM_ROLLOUT 1            // asserts that they agree)
+#define GS_OPB_NORM_MINIBATCH 2
+struct GsOpbCombineArgs {
+  const double* adv; const double* cadv[3];       // [N]; cadv[c] NULL where lambda[c] == 0
+  double lambda[3];
+  double* comb; long long N;
+};
+struct GsOpbIndexArgs {
+  const double* comb;                    // [N], or NULL: nothing staged
+  const double* roll_stats;              // (mean, std) over N
+  int32_t* idx; double* stage;           // [n]
+  double* adv_stats;                     // [2], or NULL; written here unless adv_norm is MINIBATCH (gs_k_opb_mbstats writes it then)
+  uint32_t seed_lo, seed_hi, epoch; int32_t half_bits;
+  long long N, first;
+  int32_t n, adv_norm;
+};
+struct GsOpbGatherArgs {
+  const int32_t* idx;                    // [n]
+  const double* obs_seq; const double* act;
+  const double* shift; const double* scale;       // [obs_dim] each, or both NULL: raw rows
+  void* out_obs; void* out_act;          // NULL: not wanted
+  const double* sc_src[GS_OPB_SCALARS]; void* sc_dst[GS_OPB_SCALARS];      // scalar k: dst[i] = src[j]; NULL: not wanted
+  const double* stage;                   // [n] comb[idx[i]]: what the advantage is taken from (sc_src[GS_OPB_SC_ADV] only marks it wanted)
+  const double* adv_stats;               // (mean, raw std) to normalise with
+  double adv_eps;
+  long long N;
+  int32_t n, D, A, adv_norm, vec2, pad;
+};
 #if defined(__HIPCC__)
 // constant ci of an observation (plan.cpp plan_maps: 2 l = P of load l, 2 l + 1 = its Q) as instance b holds it
 __device__ __forceinline__ double gs_pl_const(const double* __restrict__ pl, int n_loads, int b, int ci) {

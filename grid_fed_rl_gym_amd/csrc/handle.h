@@ -159,6 +159,16 @@ struct gs_handle : GsPlan {
     size_t cap = 0; bool live = false; int with_costs = 0;
     uint64_t accounted_on = 0, moves_at = 0; hipEvent_t ev = nullptr;
   } ep;
+  // gs_onpolicy_* (abi_batches.hip): comb [T_cap][B] the combined advantage of the last prepared rollout, part the chunks' partial
+  // results, stats (mean, std) of comb, norm = shift then scale at stride Ds (obs_dim rounded up to even) with h_norm its host
+  // staging copy (ev_norm: read); idx / stage / adv_stats / field[k] = the handle's own buffers of a minibatch.  prepared_on = ro.calls of the rollout
+  // prepare ran on, 0 = none; cfg = what it was given (the host pointers dropped), chan = bit c: cost channel c is gathered.  Made
+  // on first use, released with the rollout's buffers.
+  struct GS_HIDDEN OnPolicyBatches {
+    uint64_t prepared_on = 0; long long N = 0; gs_onpolicy_batch_config cfg{}; bool have_norm = false; int chan = 0;
+    DevBuf<double> comb, part, stats, norm, stage, adv_stats; std::vector<double> h_norm;
+    DevBuf<int32_t> idx; DevBuf<char> field[2 + GS_OPB_SCALARS]; hipEvent_t ev = nullptr, ev_norm = nullptr; bool norm_pending = false;
+  } opb;
   // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count
   // themselves here: gs_rollout_episodes(GS_EPISODES_CONTINUE) refuses to carry an episode across one
   uint64_t env_moves = 0;
@@ -355,6 +365,9 @@ void costs_release(gs_handle* h);
 
 // ---- owner of the episode track (abi_episodes.hip); keep_carries: only the list, which is sized by the rollout's capacity, goes ----
 void episodes_release(gs_handle* h, bool keep_carries = false);
+
+// ---- owner of the on-policy minibatch buffers (abi_batches.hip) ----
+void batches_release(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);

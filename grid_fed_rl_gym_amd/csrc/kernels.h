@@ -57,6 +57,11 @@ __global__ void gs_k_ep_offsets(GsEpisodeArgs E);
 __global__ void gs_k_ep_accumulate(GsEpisodeArgs E);
 __global__ void gs_k_ep_accumulate_costs(GsEpisodeArgs E);
 __global__ void gs_k_ep_stats(GsEpisodeArgs E);
+__global__ void gs_k_opb_combine(GsOpbCombineArgs A);
+__global__ void gs_k_opb_index(GsOpbIndexArgs A);
+__global__ void gs_k_opb_mbstats(const double* __restrict__ stage, int n, double* __restrict__ adv_stats);
+__global__ void gs_k_opb_gather_f64(GsOpbGatherArgs G);
+__global__ void gs_k_opb_gather_f32(GsOpbGatherArgs G);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

@@ -23,6 +23,10 @@ cost, cost critics and cost advantages (``gs_rollout_costs``, ``gs_rollout_evalu
 ``rollout_episodes`` / ``EpisodeMonitor`` / ``evaluate_policy`` keep the books per EPISODE (``gs_rollout_episodes``; DESIGN.md section
 17): the returns, lengths and episodic costs of the episodes a rollout finished, with per-instance carries on the device so that an
 episode that straddles rollouts is one episode; ``episodes_np`` restates the contract.
+
+``OnPolicyBatches`` turns the evaluated rollout into EPOCHS of minibatches for a clipped-surrogate learner (``gs_onpolicy_*``; DESIGN.md
+section 18): a keyed permutation evaluated on the device, one gather per minibatch with the observations in the policy's
+normalisation and the (Lagrangian) advantage normalised; ``permutation_np`` and ``onpolicy_batch_np`` restate the contract.
 """
 from __future__ import annotations
 
@@ -670,3 +674,161 @@ class DeviceGridDataset:
 
     def denormalize_observation(self, obs):
         return obs * self.obs_std + self.obs_mean if self.normalize else obs
+
+
+# ---- on-policy minibatch epochs (include/gridstep.h "on-policy minibatch epochs") --------------------------------
+
+def permutation_np(seed: int, epoch, N: int, positions=None) -> np.ndarray:
+    """perm(seed, epoch) of [0, N) as ``gs_onpolicy_batch`` evaluates it per position (include/gridstep.h), int64 [N]: a four-round
+    Feistel network over [0, 2^(2 h)), h the smallest integer >= 1 with 2^(2 h) >= N, its round function word 0 of Philox-4x32 keyed
+    by ``seed`` with counter (R, round, epoch, 'PERM'); values that land at or above N walk on through the network until they come
+    back below it.  ``positions``: only these positions of the permutation (it is stateless per position); ``epoch`` may be an
+    array [E] of epochs, the result then being [E, positions].  Pure NumPy, no device."""
+    seed, N = int(seed) & 0xFFFFFFFFFFFFFFFF, int(N)
+    if not 0 < N < 2 ** 31:
+        raise ValueError(f"permutation_np: N = {N} outside (0, 2^31)")
+    pos = np.arange(N, dtype=np.int64) if positions is None else np.asarray(positions, dtype=np.int64).reshape(-1)
+    if pos.size and (pos.min() < 0 or pos.max() >= N):
+        raise ValueError(f"permutation_np: positions outside [0, {N})")
+    ep = np.asarray(epoch, dtype=np.int64) & _M32
+    shape = pos.shape if ep.ndim == 0 else (ep.size, pos.size)
+    x = np.broadcast_to(pos.astype(np.uint64), shape).reshape(-1).copy()
+    e = np.broadcast_to(ep.astype(np.uint64).reshape(-1, 1), (ep.size, pos.size)).reshape(-1)
+    h = 1
+    while (1 << (2 * h)) < N:
+        h += 1
+    mask, hb = np.uint64((1 << h) - 1), np.uint64(h)
+
+    def one_pass(x, e):
+        L, R = x >> hb, x & mask
+        for rnd in range(4):
+            w = _philox4x32(R, np.full(x.shape, rnd, dtype=np.uint64), e, np.full(x.shape, 0x5045524D, dtype=np.uint64), seed & _M32, seed >> 32)[0]
+            L, R = R, L ^ (w & mask)
+        return (L << hb) | R
+
+    y = one_pass(x, e)
+    while True:
+        out = np.nonzero(y >= np.uint64(N))[0]
+        if out.size == 0:
+            return y.astype(np.int64).reshape(shape)
+        y[out] = one_pass(y[out], e[out])
+
+
+def onpolicy_batch_np(indices, observations, actions, log_probs, advantages, returns, values, cost_advantages=None, cost_returns=None,
+                      lambdas=(0.0, 0.0, 0.0), adv_norm="rollout", adv_stats=None, adv_eps: float = 1e-8, dtype=np.float32, obs_shift=None,
+                      obs_scale=None) -> Dict[str, object]:
+    """The minibatch ``gs_onpolicy_batch`` leaves for the transitions ``indices`` (j = t * B + b), restated from downloaded arrays
+    operation by operation: ``observations`` [N, obs_dim] (``obs_seq[:T]``), ``actions`` [N, A], ``log_probs`` (or None), ``advantages``,
+    ``returns``, ``values`` [N] (``values[:T]``), ``cost_advantages`` / ``cost_returns`` sequences of three [N] arrays or None per
+    channel.  ``adv_stats``: the (mean, raw std) the advantages are normalised with, as the device reported them -- the rollout's
+    (``OnPolicyBatches.stats``) for "rollout", the batch's ``adv_stats`` for "minibatch"; unused for "none".  Everything is computed in
+    float64 and rounded once to ``dtype``."""
+    j = np.asarray(indices, dtype=np.int64)
+    dt = np.dtype(dtype)
+    flat = lambda a: np.asarray(a, dtype=np.float64).reshape(-1)
+    cadv = [None] * 3 if cost_advantages is None else list(cost_advantages)
+    cret = [None] * 3 if cost_returns is None else list(cost_returns)
+    comb = flat(advantages)[j]
+    for c in range(3):
+        if float(lambdas[c]) != 0.0:
+            comb = comb - float(lambdas[c]) * flat(cadv[c])[j]          # the product rounded, then the difference
+    mode = _lib.ADV_NORM[adv_norm] if isinstance(adv_norm, str) else int(adv_norm)
+    stats = np.array([np.nan, np.nan])
+    if mode != 0:
+        stats = np.asarray(adv_stats, dtype=np.float64).reshape(2)
+        comb = (comb - stats[0]) / (stats[1] + float(adv_eps))
+    obs = np.asarray(observations, dtype=np.float64)
+    obs = obs.reshape(-1, obs.shape[-1])[j]
+    if obs_shift is not None:
+        obs = (obs - np.asarray(obs_shift, dtype=np.float64)) * np.asarray(obs_scale, dtype=np.float64)
+    act = np.asarray(actions, dtype=np.float64)
+    out = dict(observations=obs.astype(dt), actions=act.reshape(-1, act.shape[-1])[j].astype(dt),
+               log_probs=None if log_probs is None else flat(log_probs)[j].astype(dt), advantages=comb.astype(dt),
+               returns=flat(returns)[j].astype(dt), values=flat(values)[j].astype(dt),
+               cost_advantages=[None if a is None else flat(a)[j].astype(dt) for a in cadv],
+               cost_returns=[None if a is None else flat(a)[j].astype(dt) for a in cret],
+               indices=j.astype(np.int32), adv_stats=stats)
+    return out
+
+
+class OnPolicyBatches:
+    """Epochs of minibatches over the environment's LAST evaluated rollout, on the device (``gs_onpolicy_*``): every transition exactly
+    once per epoch in the order of ``permutation_np(seed, epoch, N)``, each minibatch one gather that leaves what a clipped-surrogate
+    step reads -- observations in the policy's normalisation, actions, old log-probabilities, the (Lagrangian) advantage normalised
+    over the rollout or the minibatch, returns, values, cost advantages and returns -- in ``dtype``.
+
+    ``policy``: an ``MLPPolicy`` (or ``MLPValue``) whose ``obs_mean`` and ``1 / obs_std`` normalise the observations, or give
+    ``obs_mean`` / ``obs_std`` directly; neither: raw observations.  ``lambdas``: {channel name or index: multiplier}, the advantage
+    becoming ``adv - sum_c lambda_c cost_adv_c``.  ``fields``: names of ``_lib.ONPOLICY_BATCH_FIELDS`` (None: all but the cost fields,
+    which join when a multiplier is given).  ``prepare()`` after every ``evaluate_rollout`` / ``evaluate_rollout_costs``; then
+    ``for batch in batches.epoch(e): ...`` yields dicts of zero-copy ``DeviceArray`` views valid until the next one."""
+
+    def __init__(self, env, minibatch: int, policy=None, obs_mean=None, obs_std=None, lambdas=None, adv_norm: str = "rollout",
+                 dtype=np.float32, fields=None, seed: int = 0, adv_eps: float = 1e-8) -> None:
+        self.minibatch = int(minibatch)
+        if self.minibatch <= 0:
+            raise ValueError(f"OnPolicyBatches: minibatch = {minibatch} must be positive")
+        if adv_norm not in _lib.ADV_NORM:
+            raise ValueError(f"OnPolicyBatches: adv_norm {adv_norm!r}; one of {sorted(_lib.ADV_NORM)}")
+        if policy is not None and (obs_mean is not None or obs_std is not None):
+            raise ValueError("OnPolicyBatches: either a policy or obs_mean / obs_std")
+        if policy is not None:
+            obs_mean, obs_std = policy.obs_mean, policy.obs_std
+        if (obs_mean is None) != (obs_std is None):
+            raise ValueError("OnPolicyBatches: obs_mean and obs_std go together")
+        self.obs_shift = None if obs_mean is None else np.array(obs_mean, dtype=np.float64).reshape(-1)
+        self.obs_scale = None if obs_std is None else 1.0 / np.array(obs_std, dtype=np.float64).reshape(-1)
+        self.lambdas = [0.0, 0.0, 0.0]
+        self.set_lambdas(lambdas or {})
+        if fields is None:
+            fields = ["observations", "actions", "log_probs", "advantages", "returns", "values", "indices"]
+            if any(x != 0.0 for x in self.lambdas):
+                fields += ["cost_advantages", "cost_returns"]
+        self.fields = _lib.onpolicy_fields(fields)
+        self.env, self.adv_norm, self.dtype, self.seed, self.adv_eps = env, adv_norm, np.dtype(dtype), int(seed), float(adv_eps)
+        self.size = 0
+
+    def set_lambdas(self, lambdas) -> None:
+        """New multipliers {channel name or index: value} (the others keep theirs); they count from the next ``prepare()``."""
+        for name, value in dict(lambdas).items():
+            if isinstance(name, str):
+                if name not in _lib.COST_CHANNELS:
+                    raise ValueError(f"OnPolicyBatches: unknown cost channel {name!r}; one of {_lib.COST_CHANNELS}")
+                c = _lib.COST_CHANNELS.index(name)
+            else:
+                c = int(name)
+                if not 0 <= c < 3:
+                    raise ValueError(f"OnPolicyBatches: cost channel {c} outside 0 .. 2")
+            self.lambdas[c] = float(value)
+
+    def prepare(self, stream=None) -> None:
+        """Combine and reduce the advantages of the environment's last rollout (``gs_onpolicy_prepare``, asynchronous).  ``stream``
+        is accepted for symmetry with the evaluation calls: every batch is handed to its consumer's stream by ``epoch``."""
+        h = self.env.handle
+        h.onpolicy_prepare(self.adv_norm, self.dtype, self.fields, self.lambdas, self.adv_eps, self.obs_shift, self.obs_scale)
+        self.size = int(getattr(h, "_rollout_T", 0)) * int(self.env.num_envs)
+
+    def prepared(self, stream=None) -> "OnPolicyBatches":
+        """``prepare()``, returning the object: ``for batch in OnPolicyBatches(env, 4096).prepared().epoch(0): ...``"""
+        self.prepare(stream)
+        return self
+
+    @property
+    def stats(self) -> SimpleNamespace:
+        """``n``, ``adv_mean`` and the raw ``adv_std`` of the combined advantage over the rollout (host copies; waits for ``prepare``)."""
+        return SimpleNamespace(**self.env.handle.onpolicy_stats())
+
+    def __len__(self) -> int:
+        return -(-self.size // self.minibatch)
+
+    def bounds(self):
+        """(first, n) of every minibatch of an epoch; the last one is ragged."""
+        return [(k, min(self.minibatch, self.size - k)) for k in range(0, self.size, self.minibatch)]
+
+    def epoch(self, e: int, out=None, stream=None):
+        """The minibatches of epoch ``e``, in order.  ``out``: the caller's device arrays per key, used by every full-size batch (the
+        ragged one goes to the handle's own buffers); ``stream``: the consumer's stream handle."""
+        if self.size <= 0:
+            raise PowerFlowError("OnPolicyBatches: prepare() first")
+        for first, n in self.bounds():
+            yield self.env.handle.onpolicy_batch(self.seed, e, first, n, out=out if n == self.minibatch else None, stream=stream)

@@ -710,6 +710,85 @@ typedef struct gs_dataset_batch {
 int gs_dataset_sample(gs_handle* h, int32_t n, const int64_t* indices, uint64_t seed, uint64_t draw, int32_t dtype, int32_t normalize,
                       gs_dataset_batch* out, void* consumer_stream);
 
+/* ---- on-policy minibatch epochs: a keyed permutation of the last rollout and one gather per minibatch ----
+ * What a clipped-surrogate (PPO) learner does first with an evaluated rollout -- shuffle its N = T * B transitions, visit every one
+ * exactly once per epoch in minibatches, normalise observations and advantages -- done where the collection lies.  gs_dataset_sample
+ * draws WITH replacement (the reference's offline GridDataset); this visits without.  Additive to ABI 2.
+ *
+ * The epoch permutation perm(seed, epoch) of [0, N), N < 2^31, is a stateless keyed bijection evaluated per position (no stored
+ * permutation, no sort).  h = the smallest integer >= 1 with 2^(2 h) >= N, m = 2^h - 1.  One PASS over a value x < 2^(2 h):
+ *   L = x >> h, R = x & m;  for round = 0, 1, 2, 3:  (L, R) <- (R, L ^ (w & m)),
+ *   w = word 0 of Philox-4x32-10 with counter (R, round, epoch, 'PERM' = 0x5045524D) and key (seed low word, seed high word);
+ *   the result is (L << h) | R
+ * -- a four-round Feistel network, a bijection of [0, 2^(2 h)).  perm[x] = the first of pass(x), pass(pass(x)), ... below N (cycle
+ * walking: x < N lies on a cycle of the bijection, so the walk returns below N at the latest at x itself).  epoch is a uint32, seed a
+ * uint64.
+ *
+ * gs_onpolicy_prepare (asynchronous, on the handle's stream, over the LAST rollout) combines the advantage per transition in float64,
+ * nothing contracted:  comb = advantages;  for c = 0, 1, 2 with lambda[c] != 0:  comb = comb - lambda[c] * cost_advantages[c]  (the
+ * product rounded, then the difference); reduces mean and population standard deviation of comb over N in the fixed tree of
+ * gs_dataset_build (no atomics: a second call gives the same bits); and uploads obs_shift / obs_scale.  With every lambda 0 and no
+ * cost field asked for it needs nothing of gs_rollout_costs.
+ *   GS_E_STATE (with a message): gs_rollout_evaluate has not run on the last rollout; lambda[c] != 0 or a cost field asked for while
+ *     gs_rollout_evaluate_costs left channel c unevaluated on the last rollout (a cost field needs at least one evaluated channel and
+ *     covers every evaluated one); GS_ONPOLICY_LOG_PROBS on a rollout that recorded none.
+ *   GS_E_INVALID: a wrong struct_size; an unknown adv_norm, dtype or field bit; a non-finite lambda, adv_eps, shift or scale;
+ *     adv_eps < 0; exactly one of obs_shift and obs_scale; N >= 2^31.
+ * gs_onpolicy_stats: host copies of N and of the combined advantage's mean and RAW standard deviation; waits for the prepare.
+ *
+ * gs_onpolicy_batch: the minibatch of positions first .. first + n - 1 of perm(seed, epoch), row-major arrays of cfg.dtype.  Sample
+ * i is transition j = perm[first + i] = t * B + b:
+ *   observations [n][obs_dim]   (obs_seq[t][b] - obs_shift) * obs_scale in float64, subtraction then multiplication, not contracted
+ *                               (the formula of the float32 policy and value kernels); the raw row without shift / scale
+ *   actions [n][action_dim], log_probs [n], returns [n]   as stored;   values [n] = values[t][b]
+ *   advantages [n]              GS_ADVNORM_NONE: comb[j];  GS_ADVNORM_ROLLOUT: (comb[j] - mean_N) / (std_N + adv_eps);
+ *                               GS_ADVNORM_MINIBATCH: the same with mean and population standard deviation of the minibatch's n values
+ *   cost_advantages[c] [n], cost_returns[c] [n]   per evaluated channel (the pointers of the others are left alone)
+ *   indices [n]                 int32 j
+ *   adv_stats [2]               float64 (mean, raw std) the advantages were normalised with, NaN for GS_ADVNORM_NONE; written with
+ *                               GS_ONPOLICY_ADVANTAGES
+ * every value computed in float64 and rounded ONCE to float32 for GS_COMPUTE_F32.  The minibatch statistics are reduced by one
+ * workgroup of 1024 threads in the fixed order of the episode statistics (thread i over entries i, i + 1024, ...; a butterfly over
+ * the threads; a second pass for the squared deviations; DESIGN.md sections 17 and 18).
+ * out: each pointer of a field in cfg.fields is the caller's device memory, or NULL for a buffer of the handle's, whose address is
+ * written back and stays valid until the next gs_onpolicy_batch, gs_onpolicy_prepare or gs_rollout; the pointer of a field not in
+ * cfg.fields is left alone.  consumer_stream: as gs_dataset_sample.  GS_E_INVALID (before any launch) for n <= 0, first < 0 or
+ * first + n > N; GS_E_STATE unless gs_onpolicy_prepare has run on the last rollout. */
+enum { GS_ADVNORM_NONE = 0, GS_ADVNORM_ROLLOUT = 1, GS_ADVNORM_MINIBATCH = 2 };
+enum { GS_ONPOLICY_OBSERVATIONS = 1, GS_ONPOLICY_ACTIONS = 2, GS_ONPOLICY_LOG_PROBS = 4, GS_ONPOLICY_ADVANTAGES = 8,
+       GS_ONPOLICY_RETURNS = 16, GS_ONPOLICY_VALUES = 32, GS_ONPOLICY_COST_ADVANTAGES = 64, GS_ONPOLICY_COST_RETURNS = 128,
+       GS_ONPOLICY_INDICES = 256, GS_ONPOLICY_ALL_FIELDS = 511 };
+typedef struct gs_onpolicy_batch_config {
+  int32_t struct_size;            /* = sizeof(gs_onpolicy_batch_config) */
+  int32_t adv_norm;               /* GS_ADVNORM_* */
+  int32_t dtype;                  /* GS_COMPUTE_F64 / GS_COMPUTE_F32 */
+  uint32_t fields;                /* GS_ONPOLICY_* bits */
+  double lambda[3];               /* the multiplier of each cost channel */
+  double adv_eps;                 /* 1e-8 is the usual choice */
+  const double* obs_shift;        /* host [obs_dim], or NULL */
+  const double* obs_scale;        /* host [obs_dim], or NULL: both or neither */
+} gs_onpolicy_batch_config;
+typedef struct gs_onpolicy_stats_out {
+  int64_t n;                      /* N = T * B */
+  double adv_mean, adv_std;       /* of the combined advantage over N; the raw standard deviation */
+} gs_onpolicy_stats_out;
+typedef struct gs_onpolicy_batch_out {
+  void* observations;
+  void* actions;
+  void* log_probs;
+  void* advantages;
+  void* returns;
+  void* values;
+  void* cost_advantages[3];
+  void* cost_returns[3];
+  int32_t* indices;
+  double* adv_stats;
+} gs_onpolicy_batch_out;
+int gs_onpolicy_prepare(gs_handle* h, const gs_onpolicy_batch_config* cfg);
+int gs_onpolicy_stats(gs_handle* h, gs_onpolicy_stats_out* out);
+int gs_onpolicy_batch(gs_handle* h, uint64_t seed, uint32_t epoch, int64_t first, int32_t n, gs_onpolicy_batch_out* out,
+                      void* consumer_stream);
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
