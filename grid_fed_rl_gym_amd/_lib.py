@@ -271,6 +271,51 @@ def onpolicy_fields(fields) -> int:
     return sum(bits[k] for k in set(fields))
 
 
+# the learner (include/gridstep.h "the learner"): GS_LEARNER_*, and the structs of gs_learner_*
+GS_LEARNER_POLICY, GS_LEARNER_VALUE, GS_LEARNER_COST_VALUE = 0, 1, 2
+LEARNER_STATS = ("loss", "surrogate", "entropy", "approx_kl", "clip_fraction", "value_loss", "grad_norm", "step")
+
+
+class gs_learner_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("max_grad_norm", C.c_double), ("clip", C.c_double), ("ent_coef", C.c_double)]
+
+
+class gs_learner_stats_out(C.Structure):
+    _fields_ = [(k, C.c_double) for k in LEARNER_STATS]
+
+
+class gs_learner_info_out(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("activation", C.c_int32), ("dims", C.c_int32 * 5), ("rows_per_segment", C.c_int32),
+                ("param_count", C.c_int64), ("step", C.c_int64)]
+
+
+class gs_learner_view_out(C.Structure):
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("log_probs_new", C.c_void_p), ("ratio", C.c_void_p), ("clipped", C.c_void_p),
+                ("loss_terms", C.c_void_p), ("entropy_terms", C.c_void_p)]
+
+
+def learner_net(net) -> int:
+    """The GS_LEARNER_* number of ``net``: "policy", "value", a cost channel's name (``COST_CHANNELS``) or the number itself."""
+    if isinstance(net, (int, np.integer)) and not isinstance(net, bool):
+        if not 0 <= int(net) < 2 + len(COST_CHANNELS):
+            raise ValueError(f"learner: net {int(net)} outside 0 .. {1 + len(COST_CHANNELS)}")
+        return int(net)
+    if net == "policy":
+        return GS_LEARNER_POLICY
+    if net == "value":
+        return GS_LEARNER_VALUE
+    if net in COST_CHANNELS:
+        return GS_LEARNER_COST_VALUE + COST_CHANNELS.index(net)
+    raise ValueError(f"learner: unknown network {net!r}; 'policy', 'value' or one of {COST_CHANNELS}")
+
+
+def learner_config(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=0.2, ent_coef=0.0, max_grad_norm=0.0,
+                   struct_size=None) -> gs_learner_config:
+    return gs_learner_config(C.sizeof(gs_learner_config) if struct_size is None else int(struct_size), 0, float(lr), float(betas[0]),
+                             float(betas[1]), float(eps), float(weight_decay), float(max_grad_norm), float(clip), float(ent_coef))
+
+
 # every symbol include/gridstep.h declares: (name, restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = [
@@ -362,6 +407,12 @@ SYMBOLS = [
     ("gs_onpolicy_prepare", C.c_int, [_H, C.POINTER(gs_onpolicy_batch_config)]),
     ("gs_onpolicy_stats", C.c_int, [_H, C.POINTER(gs_onpolicy_stats_out)]),
     ("gs_onpolicy_batch", C.c_int, [_H, C.c_uint64, C.c_uint32, C.c_int64, C.c_int32, C.POINTER(gs_onpolicy_batch_out), C.c_void_p]),
+    ("gs_learner_create", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_config)]),
+    ("gs_learner_step", C.c_int, [_H, C.c_int32, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.c_void_p]),
+    ("gs_learner_stats", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_stats_out)]),
+    ("gs_learner_info", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_info_out)]),
+    ("gs_learner_download", C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gs_learner_view", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_view_out), C.c_void_p]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -1415,6 +1466,63 @@ class Handle:
         if fields & 8:
             res["adv_stats"] = DeviceArray(b.adv_stats, (2,), "<f8")
         return res
+
+    # -- the learner (gs_learner_*) ----------------------------------------------------------------------------------------------
+    def learner_create(self, net, cfg: gs_learner_config) -> None:
+        """gs_learner_create: the installed network ``net`` (``learner_net``) becomes trainable; Adam starts from zero."""
+        self._check(self._lib.gs_learner_create(self._h, learner_net(net), C.byref(cfg)))
+
+    def learner_step(self, net, batch: dict, n: Optional[int] = None, stream=None) -> None:
+        """gs_learner_step (asynchronous): one update of ``net`` on ``batch``, a dict of ``onpolicy_batch``'s (device arrays or
+        addresses per key; the cost fields lists of three).  ``n``: the samples, by default the length of ``observations``."""
+        b = gs_onpolicy_batch_out()
+        addr = lambda x: None if x is None else int(x) if isinstance(x, (int, np.integer)) else int(x.__cuda_array_interface__["data"][0]) if hasattr(x, "__cuda_array_interface__") else int(x.data_ptr())
+        for k, x in batch.items():
+            if k in ("cost_advantages", "cost_returns"):
+                for c in range(3):
+                    getattr(b, k)[c] = addr(x[c])
+            elif k in dict(ONPOLICY_BATCH_FIELDS) or k == "adv_stats":
+                setattr(b, k, addr(x))
+        if n is None:
+            obs = batch.get("observations")
+            n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
+        self._check(self._lib.gs_learner_step(self._h, learner_net(net), C.byref(b), int(n), _stream_arg(stream)))
+
+    def learner_stats(self, net) -> dict:
+        """gs_learner_stats: the last step's ``LEARNER_STATS`` as floats (waits for the step); ``step`` an int."""
+        o = gs_learner_stats_out()
+        self._check(self._lib.gs_learner_stats(self._h, learner_net(net), C.byref(o)))
+        out = {k: float(getattr(o, k)) for k in LEARNER_STATS}
+        out["step"] = int(o.step)
+        return out
+
+    def learner_info(self, net) -> dict:
+        """gs_learner_info: ``dims`` (the layers' widths), ``activation`` (its name), ``param_count``, ``step``, ``rows_per_segment``."""
+        o = gs_learner_info_out()
+        self._check(self._lib.gs_learner_info(self._h, learner_net(net), C.byref(o)))
+        names = {v: k for k, v in ACTIVATION.items()}
+        return dict(dims=[int(o.dims[l]) for l in range(o.n_layers + 1)], activation=names[int(o.activation)], param_count=int(o.param_count),
+                    step=int(o.step), rows_per_segment=int(o.rows_per_segment))
+
+    def learner_download(self, net, want=("params", "grads", "m", "v")) -> dict:
+        """gs_learner_download: flat float32 host copies [param_count], in torch order, of the arrays named in ``want``."""
+        P = self.learner_info(net)["param_count"]
+        out = {k: np.empty(P, dtype=np.float32) for k in want}
+        unknown = set(out) - {"params", "grads", "m", "v"}
+        if unknown:
+            raise PowerFlowError(f"learner_download: unknown array(s) {sorted(unknown)}")
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        self._check(self._lib.gs_learner_download(self._h, learner_net(net), ptr("params"), ptr("grads"), ptr("m"), ptr("v")))
+        return out
+
+    def learner_view(self, net, stream=None) -> dict:
+        """gs_learner_view: the last step's per-sample arrays as zero-copy ``DeviceArray`` views (None where ``net`` has none)."""
+        o = gs_learner_view_out()
+        self._check(self._lib.gs_learner_view(self._h, learner_net(net), C.byref(o), _stream_arg(stream)))
+        n = int(o.n)
+        arr = lambda p, ts: DeviceArray(p, (n,), ts) if p else None
+        return dict(log_probs_new=arr(o.log_probs_new, "<f8"), ratio=arr(o.ratio, "<f8"), clipped=arr(o.clipped, "<i4"),
+                    loss_terms=arr(o.loss_terms, "<f8"), entropy_terms=arr(o.entropy_terms, "<f8"))
 
     def rollout_device_view(self) -> gs_rollout_device:
         """Device pointers of the last rollout (gs_rollout_device_view) for a consumer that stays on the GPU."""

@@ -1,0 +1,302 @@
+// abi_learner.hip -- the learner (include/gridstep.h "the learner"): gs_learner_create snapshots an installed
+// network into master parameters, gs_learner_step queues one update on the minibatch gs_onpolicy_batch left (the kernels of
+// kernels_train.hip), gs_learner_stats / _info / _download / _view read what it left.  The learners' buffers are made here and
+// released here: parameters with the learner (learner_drop), what is sized by n with the rollout's buffers (learner_scratch_release).
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "handle.h"
+
+using namespace gsi;
+
+static_assert(sizeof(gs_learner_config) == 72, "gs_learner_config: two int32, eight doubles");
+static_assert(GS_POLICY_MAX_LAYERS == 4, "gs_learner_info_out::dims holds five widths");
+
+namespace gsi __attribute__((visibility("hidden"))) {
+
+static void learner_scratch_release_one(gs_handle::Learner& L) {
+  L.lp_new.release(); L.ratio.release(); L.term0.release(); L.term1.release(); L.clipped.release();
+  L.n_last = 0;
+}
+
+void learner_drop(gs_handle* h, int k) {
+  gs_handle::Learner& L = h->learner[k];
+  if (L.live) (void)hipStreamSynchronize(h->stream);      // (a queued step still reads and writes the parameters)
+  L.params.release(); L.grad.release(); L.m.release(); L.v.release(); L.wt.release(); L.stats.release(); L.blocksum.release();
+  learner_scratch_release_one(L);
+  if (L.ev) { (void)hipEventDestroy(L.ev); L.ev = nullptr; }
+  L.live = false; L.steps = 0;
+}
+
+void learner_scratch_release(gs_handle* h) {
+  for (gs_handle::Learner& L : h->learner) learner_scratch_release_one(L);
+  h->tr.acts.release(); h->tr.deltas.release(); h->tr.partial.release();
+}
+
+void learner_release(gs_handle* h) {
+  for (int k = 0; k < 2 + GS_COST_CHANNELS; ++k) learner_drop(h, k);
+  learner_scratch_release(h);
+}
+
+}  // namespace gsi
+
+namespace {
+
+const char* net_name(int net) {
+  static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2"};
+  return names[net];
+}
+
+bool net_ok(int net) { return net >= 0 && net < 2 + GS_COST_CHANNELS; }
+
+// the installed network `net` trains: its layers, widths, activation and host normalisation; false: not installed
+struct Installed { const GsPolicyLayerF32* L; const int32_t* dims; int n_layers, activation; const std::vector<double>* norm; const DevBuf<char>* blob; };
+bool installed(gs_handle* h, int net, Installed& I) {
+  if (net == GS_LEARNER_POLICY) {
+    const gs_handle::Policy& p = h->pol;
+    if (!p.set || p.compute != GS_COMPUTE_F32) return false;
+    I = Installed{p.args32.L, p.dims, p.args32.n_layers, p.args32.activation, &p.h_norm, &p.blob};
+    return true;
+  }
+  const gs_handle::Value& v = h->critic[net - 1].net;
+  if (!v.set) return false;
+  I = Installed{v.args.L, v.dims, v.args.n_layers, v.args.activation, &v.h_norm, &v.blob};
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
+  if (!h || !cfg) return fail(h, GS_E_INVALID, "handle / config is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_create: unknown net %d", net);
+  if (cfg->struct_size != (int32_t)sizeof(gs_learner_config))
+    return fail(h, GS_E_INVALID, "gs_learner_config struct_size %d != %d", cfg->struct_size, (int)sizeof(gs_learner_config));
+  const double vals[] = {cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->max_grad_norm};
+  for (double x : vals)
+    if (!std::isfinite(x) || x < 0.0) return fail(h, GS_E_INVALID, "gs_learner_config: lr, beta1, beta2, eps, weight_decay and max_grad_norm must be finite and >= 0");
+  if (cfg->beta1 >= 1.0 || cfg->beta2 >= 1.0) return fail(h, GS_E_INVALID, "gs_learner_config: beta1 and beta2 must lie in [0, 1)");
+  if (net == GS_LEARNER_POLICY && (!std::isfinite(cfg->clip) || cfg->clip < 0.0 || !std::isfinite(cfg->ent_coef)))
+    return fail(h, GS_E_INVALID, "gs_learner_config: clip must be finite and >= 0, ent_coef finite");
+  Installed I{};
+  if (!installed(h, net, I))
+    return fail(h, GS_E_STATE, "gs_learner_create: %s is not installed%s", net_name(net), net == GS_LEARNER_POLICY ? " with GS_COMPUTE_F32" : "");
+  if (net == GS_LEARNER_POLICY && h->pol.args32.head != GS_HEAD_GAUSSIAN_TANH)
+    return fail(h, GS_E_STATE, "gs_learner_create: the policy needs the Gaussian head (GS_HEAD_GAUSSIAN_TANH)");
+  GS_ENTER(h);
+  learner_drop(h, net);
+  gs_handle::Learner& Ln = h->learner[net];
+  GsTrainNet& N = Ln.net;
+  N = GsTrainNet{};
+  N.n_layers = I.n_layers; N.activation = I.activation;
+  int stride = 0; long long P = 0; size_t wt_floats = 0;
+  size_t wt_off[GS_POLICY_MAX_LAYERS] = {};
+  for (int l = 0; l <= I.n_layers; ++l) N.dims[l] = I.dims[l];
+  for (int l = 0; l < I.n_layers; ++l) {
+    N.L[l] = I.L[l];
+    N.col_off[l] = stride; stride += 16 * I.L[l].nt;
+    N.p_off[l] = (int32_t)P; P += (long long)N.dims[l + 1] * (N.dims[l] + 1);
+    if (l) { wt_off[l] = wt_floats; wt_floats += (size_t)I.L[l].kb * I.L[l].nt * 256; }
+  }
+  N.row_stride = stride; N.P = (int32_t)P;
+  Ln.A = net == GS_LEARNER_POLICY ? h->action_dim : 0;
+  int rc = alloc_all(h, "the learner's parameters", Ln.params.want((size_t)P), Ln.grad.want((size_t)P), Ln.m.want((size_t)P), Ln.v.want((size_t)P),
+                     Ln.wt.want(wt_floats), Ln.stats.want(GS_TR_STAT_COUNT),
+                     Ln.blocksum.want((size_t)((P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD))));
+  if (rc) return rc;
+  // the installed image, unpacked into torch order (the image holds float32 values: the snapshot is exact), and its transposes
+  const float* const image = (const float*)I.blob->p;
+  size_t image_floats = 0;
+  for (int l = 0; l < I.n_layers; ++l) image_floats = std::max(image_floats, (size_t)(I.L[l].b - image) + 16 * (size_t)I.L[l].nt);
+  std::vector<float> img(image_floats), flat((size_t)P), wt(std::max<size_t>(wt_floats, 1), 0.0f);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(img.data(), image, image_floats * sizeof(float), hipMemcpyDeviceToHost));
+  for (int l = 0; l < I.n_layers; ++l) {
+    const int n_out = N.dims[l + 1], n_in = N.dims[l], kb = I.L[l].kb, nt = I.L[l].nt;
+    const float* w = img.data() + (I.L[l].w - image);
+    const float* b = img.data() + (I.L[l].b - image);
+    float* dst = flat.data() + N.p_off[l];
+    for (int o = 0; o < n_out; ++o)
+      for (int k = 0; k < n_in; ++k) {
+        const float x = w[(((size_t)(o >> 4) * kb + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (o & 15)) * 4 + (k & 3)];
+        dst[(size_t)o * n_in + k] = x;
+        if (l) wt[wt_off[l] + (((size_t)(k >> 4) * nt + (o >> 4)) * 64 + ((o & 15) >> 2) * 16 + (k & 15)) * 4 + (o & 3)] = x;
+      }
+    for (int o = 0; o < n_out; ++o) dst[(size_t)n_out * n_in + o] = b[o];
+    if (l) N.T[l] = GsPolicyLayerF32{Ln.wt.p + wt_off[l], nullptr, nt, kb};
+  }
+  HIPCHK(h, hipMemcpy(Ln.params, flat.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice));
+  if (wt_floats) HIPCHK(h, hipMemcpy(Ln.wt, wt.data(), wt_floats * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemset(Ln.grad, 0, (size_t)P * sizeof(float)));
+  HIPCHK(h, hipMemset(Ln.m, 0, (size_t)P * sizeof(float)));
+  HIPCHK(h, hipMemset(Ln.v, 0, (size_t)P * sizeof(float)));
+  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_train_forward, hipFuncAttributeMaxDynamicSharedMemorySize, GS_TR_LDS_MAX));
+  Ln.cfg = *cfg; Ln.steps = 0; Ln.n_last = 0;
+  Ln.live = true;
+  return GS_OK;
+}
+
+int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, void* consumer_stream) {
+  if (!h || !batch) return fail(h, GS_E_INVALID, "handle / batch is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_step: unknown net %d", net);
+  if (n <= 0 || n > (1 << 24)) return fail(h, GS_E_INVALID, "gs_learner_step: n = %d outside 1 .. 2^24", n);
+  gs_handle::Learner& Ln = h->learner[net];
+  Installed I{};
+  if (!Ln.live || !installed(h, net, I)) return fail(h, GS_E_STATE, "gs_learner_step: no learner for %s (gs_learner_create after the network was installed)", net_name(net));
+  const gs_handle::OnPolicyBatches& ob = h->opb;
+  const gs_handle::Rollout& ro = h->ro;
+  if (!ob.prepared_on || ob.prepared_on != ro.calls) return fail(h, GS_E_STATE, "gs_learner_step: gs_onpolicy_prepare has not run on the last rollout");
+  if (ob.cfg.dtype != GS_COMPUTE_F32) return fail(h, GS_E_STATE, "gs_learner_step: the minibatches must be prepared with dtype GS_COMPUTE_F32");
+  const int D = h->obs_dim, D16 = 16 * I.L[0].kb;
+  const size_t Ds = (size_t)((D + 1) & ~1);
+  for (int c = 0; c < D; ++c) {
+    const double shift = ob.have_norm ? ob.h_norm[c] : 0.0, scale = ob.have_norm ? ob.h_norm[Ds + c] : 1.0;
+    if (memcmp(&shift, &(*I.norm)[c], sizeof(double)) || memcmp(&scale, &(*I.norm)[D16 + c], sizeof(double)))
+      return fail(h, GS_E_STATE, "gs_learner_step: the minibatches' obs_shift / obs_scale differ from the normalisation of %s (column %d)", net_name(net), c);
+  }
+  const bool policy = net == GS_LEARNER_POLICY;
+  const void* target = policy ? batch->advantages : net == GS_LEARNER_VALUE ? batch->returns : batch->cost_returns[net - GS_LEARNER_COST_VALUE];
+  if (policy && !ro.logp_recorded) return fail(h, GS_E_STATE, "gs_learner_step: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
+  if (!batch->observations || !target || (policy && !batch->indices))
+    return fail(h, GS_E_INVALID, "gs_learner_step: the batch lacks %s", !batch->observations ? "observations" : !target ? (policy ? "advantages" : "returns") : "indices");
+  GS_ENTER(h);
+  int rc = GS_OK;
+  const GsTrainNet& N = Ln.net;
+  const int segments = (n + GS_TR_SEG - 1) / GS_TR_SEG;
+  gs_handle::TrainScratch& tr = h->tr;
+  if ((rc = tr.acts.grow(h, (size_t)n * N.row_stride, "the learner's saved activations"))) return rc;
+  if ((rc = tr.deltas.grow(h, (size_t)n * N.row_stride, "the learner's backward pass"))) return rc;
+  if ((rc = tr.partial.grow(h, (size_t)segments * N.P, "the learner's partial gradients"))) return rc;
+  if ((rc = Ln.term0.grow(h, (size_t)n, "the learner's loss terms"))) return rc;
+  if (policy) {
+    if ((rc = Ln.term1.grow(h, (size_t)n, "the learner's entropy terms"))) return rc;
+    if ((rc = Ln.lp_new.grow(h, (size_t)n, "the learner's log-probabilities"))) return rc;
+    if ((rc = Ln.ratio.grow(h, (size_t)n, "the learner's ratios"))) return rc;
+    if ((rc = Ln.clipped.grow(h, (size_t)n, "the learner's clip flags"))) return rc;
+  }
+  Ln.n_last = 0;           // (until every launch is queued)
+  const int last = N.n_layers - 1, tiles = (n + GS_TR_ROWS - 1) / GS_TR_ROWS;
+  const gs_learner_config& cfg = Ln.cfg;
+
+  GsTrainFwdArgs F{};
+  F.N = N; F.obs = (const float*)batch->observations; F.acts = tr.acts; F.n = n; F.D = D;
+  F.obs_stride = gs_val_obs_stride(N.L[0].kb); F.panel_kb = gs_val_panel_kb(N.L[0].kb);
+  hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(N.L[0].kb), h->stream, F);
+  HIPCHK(h, hipGetLastError());
+
+  GsTrainHeadArgs H{};
+  H.pre = tr.acts + N.col_off[last]; H.ghead = tr.deltas + N.col_off[last];
+  H.n = n; H.row_stride = N.row_stride; H.width16 = 16 * N.L[last].nt; H.A = Ln.A;
+  H.term0 = Ln.term0;
+  if (policy) {
+    H.idx = batch->indices; H.act = ro.act; H.logp = ro.logp; H.adv = (const float*)target; H.N = ob.N;
+    H.clip = cfg.clip; H.ent_coef = cfg.ent_coef;
+    H.lp_new = Ln.lp_new; H.ratio = Ln.ratio; H.clipped = Ln.clipped; H.term1 = Ln.term1;
+  } else {
+    H.ret = (const float*)target;
+  }
+  hipLaunchKernelGGL(gs_k_train_head, dim3((n + 63) / 64), dim3(64), 0, h->stream, H);
+  HIPCHK(h, hipGetLastError());
+
+  if (last > 0) {
+    GsTrainBwdArgs B{};
+    B.N = N; B.acts = tr.acts; B.deltas = tr.deltas; B.n = n;
+    hipLaunchKernelGGL(gs_k_train_bwd_data, dim3(tiles), dim3(64 * GS_POL_WAVES), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+  }
+
+  GsTrainGradArgs G{};
+  G.N = N; G.obs = F.obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
+  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
+  int blocks = 0;
+  for (int l = 0; l <= last; ++l) {
+    G.blk0[l] = blocks;
+    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
+    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
+  }
+  G.blk0[last + 1] = blocks;
+  hipLaunchKernelGGL(gs_k_train_grad, dim3(blocks, segments), dim3(64), 0, h->stream, G);
+  HIPCHK(h, hipGetLastError());
+
+  const int red_blocks = (N.P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD);
+  GsTrainReduceArgs R{tr.partial, Ln.grad, Ln.blocksum, N.P, segments};
+  hipLaunchKernelGGL(gs_k_train_reduce, dim3(red_blocks), dim3(GS_TR_RED_THREADS), 0, h->stream, R);
+  HIPCHK(h, hipGetLastError());
+
+  GsTrainStatArgs S{};
+  S.term0 = Ln.term0; S.term1 = Ln.term1; S.lp_new = Ln.lp_new; S.logp = ro.logp; S.idx = batch->indices; S.clipped = Ln.clipped;
+  S.blocksum = Ln.blocksum; S.stats = Ln.stats; S.N = ob.N; S.n = n; S.blocks = red_blocks; S.policy = policy; S.ent_coef = cfg.ent_coef;
+  hipLaunchKernelGGL(gs_k_train_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, S);
+  HIPCHK(h, hipGetLastError());
+
+  const double t = (double)(Ln.steps + 1);
+  GsTrainAdamArgs A{};
+  A.N = N; A.params = Ln.params; A.grad = Ln.grad; A.m = Ln.m; A.v = Ln.v; A.stats = Ln.stats; A.max_grad_norm = cfg.max_grad_norm;
+  A.wd = (float)cfg.weight_decay; A.b1 = (float)cfg.beta1; A.omb1 = (float)(1.0 - cfg.beta1); A.b2 = (float)cfg.beta2; A.omb2 = (float)(1.0 - cfg.beta2);
+  A.bc2s = (float)std::sqrt(1.0 - std::pow(cfg.beta2, t)); A.eps = (float)cfg.eps; A.step = (float)(cfg.lr / (1.0 - std::pow(cfg.beta1, t)));
+  hipLaunchKernelGGL(gs_k_train_adam, dim3((N.P + 255) / 256), dim3(256), 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  Ln.steps += 1; Ln.n_last = n;
+  return publish(h, h->stream, Ln.ev, consumer_stream);
+}
+
+int gs_learner_stats(gs_handle* h, int32_t net, gs_learner_stats_out* out) {
+  if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_stats: unknown net %d", net);
+  gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live || !Ln.steps) return fail(h, GS_E_STATE, "gs_learner_stats: %s has taken no step", net_name(net));
+  GS_ENTER(h);
+  double st[GS_TR_STAT_COUNT];
+  HIPCHK(h, hipMemcpyAsync(st, Ln.stats, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  out->loss = st[GS_TR_STAT_LOSS]; out->surrogate = st[GS_TR_STAT_SURR]; out->entropy = st[GS_TR_STAT_ENT]; out->approx_kl = st[GS_TR_STAT_KL];
+  out->clip_fraction = st[GS_TR_STAT_CLIPFRAC]; out->value_loss = st[GS_TR_STAT_VLOSS]; out->grad_norm = st[GS_TR_STAT_GNORM];
+  out->step = (double)Ln.steps;
+  return GS_OK;
+}
+
+int gs_learner_info(gs_handle* h, int32_t net, gs_learner_info_out* out) {
+  if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_info: unknown net %d", net);
+  const gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_info: no learner for %s", net_name(net));
+  *out = gs_learner_info_out{};
+  out->n_layers = Ln.net.n_layers; out->activation = Ln.net.activation;
+  for (int l = 0; l <= Ln.net.n_layers; ++l) out->dims[l] = Ln.net.dims[l];
+  out->rows_per_segment = GS_TR_SEG; out->param_count = Ln.net.P; out->step = (int64_t)Ln.steps;
+  return GS_OK;
+}
+
+int gs_learner_download(gs_handle* h, int32_t net, float* params, float* grads, float* m, float* v) {
+  if (!h) return fail(h, GS_E_INVALID, "handle is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_download: unknown net %d", net);
+  const gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_download: no learner for %s", net_name(net));
+  GS_ENTER(h);
+  const size_t bytes = (size_t)Ln.net.P * sizeof(float);
+  if (params) HIPCHK(h, hipMemcpyAsync(params, Ln.params, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (grads) HIPCHK(h, hipMemcpyAsync(grads, Ln.grad, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (m) HIPCHK(h, hipMemcpyAsync(m, Ln.m, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (v) HIPCHK(h, hipMemcpyAsync(v, Ln.v, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return GS_OK;
+}
+
+int gs_learner_view(gs_handle* h, int32_t net, gs_learner_view_out* out, void* consumer_stream) {
+  if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_view: unknown net %d", net);
+  gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live || !Ln.n_last) return fail(h, GS_E_STATE, "gs_learner_view: %s holds no step's arrays", net_name(net));
+  GS_ENTER(h);
+  int rc = publish(h, h->stream, Ln.ev, consumer_stream);
+  if (rc) return rc;
+  const bool policy = net == GS_LEARNER_POLICY;
+  *out = gs_learner_view_out{};
+  out->n = Ln.n_last; out->loss_terms = Ln.term0;
+  if (policy) { out->log_probs_new = Ln.lp_new; out->ratio = Ln.ratio; out->clipped = Ln.clipped; out->entropy_terms = Ln.term1; }
+  return GS_OK;
+}
+
+}  // extern "C"

@@ -40,6 +40,8 @@ void onpolicy_release(gs_handle* h) {
 int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out) {
   GS_ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int k = 0; k <= GS_COST_CHANNELS; ++k)
+    if (&h->critic[k].net == &val) learner_drop(h, 1 + k);      // (a learner trains the network it was created on)
   val.blob.release();
   val.set = false;
   if (!p) return GS_OK;
@@ -56,6 +58,8 @@ int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, c
   a.D = h->obs_dim; a.n_layers = p->n_layers; a.activation = p->activation;
   a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
   for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
+  for (int l = 0; l <= p->n_layers; ++l) val.dims[l] = p->dims[l];
+  val.h_norm = im.norm;
   val.set = true;
   return GS_OK;
 }

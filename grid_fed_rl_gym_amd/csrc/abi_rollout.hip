@@ -39,6 +39,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   costs_release(h);
   episodes_release(h, keep_term_count);      // (the list is sized by the capacity; the carries outlive a longer rollout)
   batches_release(h);
+  learner_scratch_release(h);
   ro.T_cap = 0; ro.T = 0; ro.n_term = -1;
 }
 
@@ -68,6 +69,7 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
   GS_ENTER(h);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   gs_handle::Policy& pol = h->pol;
+  learner_drop(h, 0);              // (a learner trains the network it was created on)
   pol.blob.release();
   pol.set = false;
   if (!p) return GS_OK;
@@ -85,6 +87,8 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
     a.B = h->B; a.D = h->obs_dim; a.A = h->action_dim; a.n_layers = p->n_layers; a.activation = p->activation; a.head = p->head;
     a.stochastic = p->stochastic; a.first_instance = h->EC.first_instance; a.obs_stride = gs_pol32_obs_stride(im.kb[0]);
     for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
+    for (int l = 0; l <= p->n_layers; ++l) pol.dims[l] = p->dims[l];
+    pol.h_norm = im.norm;
     pol.compute = GS_COMPUTE_F32;
     pol.set = true;
     return GS_OK;

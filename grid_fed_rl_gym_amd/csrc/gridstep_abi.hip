@@ -586,6 +586,7 @@ void gs_destroy(gs_handle* h) {
   if (h->span_a) { (void)hipEventDestroy(h->span_a); (void)hipEventDestroy(h->span_b); }
   for (void* p : h->allocs) (void)hipFree(p);
   h->d_actions.release();
+  learner_release(h);
   policy_release(h);
   value_release(h);
   rollout_release(h);

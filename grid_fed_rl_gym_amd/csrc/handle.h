@@ -19,6 +19,7 @@
 #include "topology.h"
 #include "plan.h"
 #include "policy.h"
+#include "train.h"
 
 // (also on the handle's parts that own a DevBuf and on gs_checks: their destructors are not part of the library's surface)
 #define GS_HIDDEN __attribute__((visibility("hidden")))
@@ -133,10 +134,14 @@ struct gs_handle : GsPlan {
   // argument block of gs_k_policy_mlp with everything but obs / act / t / seed filled in.  Not environment state.
   // compute: GS_COMPUTE_*; with GS_COMPUTE_F32 `blob` holds the float32 image and the normalisation vectors, and args32 is the
   // argument block of gs_k_policy_mlp_f32 (kernels_policy_f32.hip)
-  struct GS_HIDDEN Policy { bool set = false; DevBuf<char> blob; DevBuf<double> act; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0, lds64 = GS_POL_LDS_BYTES; } pol;
+  // dims / h_norm (float32 path): the layers' widths and the host copy of shift then scale ([16 kb_0] each), for the learner
+  struct GS_HIDDEN Policy { bool set = false; DevBuf<char> blob; DevBuf<double> act; GsPolicyArgs args{}; int compute = GS_COMPUTE_F64; GsPolicyArgsF32 args32{}; int lds32 = 0, lds64 = GS_POL_LDS_BYTES;
+                            int32_t dims[GS_POLICY_MAX_LAYERS + 1] = {}; std::vector<double> h_norm; } pol;
   // a value network: its float32 image and normalisation vectors (one allocation), the values of gs_value_mlp_eval [B] (the reward
   // critic's only), and the argument block of gs_k_value_mlp_f32 with everything but obs / out / rows filled in
-  struct GS_HIDDEN Value { bool set = false; DevBuf<char> blob; DevBuf<double> out; GsValueArgs args{}; int lds = 0; };
+  // (dims / h_norm: as the policy's)
+  struct GS_HIDDEN Value { bool set = false; DevBuf<char> blob; DevBuf<double> out; GsValueArgs args{}; int lds = 0;
+                           int32_t dims[GS_POLICY_MAX_LAYERS + 1] = {}; std::vector<double> h_norm; };
   // A critic over rollouts (abi_onpolicy.hip): its network and what critic_evaluate made of the last rollout -- values [T_cap + 1][B],
   // term_values [term_cap], adv / ret [T_cap][B], made on first use (all four or none), sized by the rollout's capacity and released
   // with it; evaluated_on = ro.calls of the rollout they belong to, 0 = none.  critic[0]: the reward critic (gs_value_mlp_set,
@@ -169,6 +174,18 @@ struct gs_handle : GsPlan {
     DevBuf<double> comb, part, stats, norm, stage, adv_stats; std::vector<double> h_norm;
     DevBuf<int32_t> idx; DevBuf<char> field[2 + GS_OPB_SCALARS]; hipEvent_t ev = nullptr, ev_norm = nullptr; bool norm_pending = false;
   } opb;
+  // gs_learner_* (abi_learner.hip).  learner[0]: the policy's, learner[1 + k]: critic[k]'s.  live: created and
+  // the network not installed again since.  net: the kernels' description (forward image = the installed network's, T = wt);
+  // params / grad / m / v [P] in torch order; steps: Adam's t.  Per-sample arrays of the last step (n_last samples; 0: none) and
+  // stats / blocksum: scratch, grown to the largest n seen and released with the rollout's buffers, like tr (acts / deltas
+  // [n][row_stride], partial [segments][P]), which every learner of the handle shares.
+  struct GS_HIDDEN Learner {
+    bool live = false; gs_learner_config cfg{}; uint64_t steps = 0; GsTrainNet net{}; int A = 0;
+    DevBuf<float> params, grad, m, v, wt;
+    DevBuf<double> lp_new, ratio, term0, term1, stats, blocksum; DevBuf<int32_t> clipped; int n_last = 0;
+    hipEvent_t ev = nullptr;
+  } learner[2 + GS_COST_CHANNELS];
+  struct GS_HIDDEN TrainScratch { DevBuf<float> acts, deltas, partial; } tr;
   // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count
   // themselves here: gs_rollout_episodes(GS_EPISODES_CONTINUE) refuses to carry an episode across one
   uint64_t env_moves = 0;
@@ -368,6 +385,12 @@ void episodes_release(gs_handle* h, bool keep_carries = false);
 
 // ---- owner of the on-policy minibatch buffers (abi_batches.hip) ----
 void batches_release(gs_handle* h);
+
+// ---- owner of the learners (abi_learner.hip).  learner_drop: learner `k` (0 the policy's, 1 + c critic c's) ends, its parameters go
+// (every *_set* entry calls it for its network); learner_scratch_release: what is sized by n; learner_release: everything ----
+void learner_drop(gs_handle* h, int k);
+void learner_scratch_release(gs_handle* h);
+void learner_release(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);

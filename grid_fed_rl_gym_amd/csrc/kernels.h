@@ -7,6 +7,7 @@
 #include "gs_internal.h"
 #include "members.h"
 #include "policy.h"
+#include "train.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -62,6 +63,13 @@ __global__ void gs_k_opb_index(GsOpbIndexArgs A);
 __global__ void gs_k_opb_mbstats(const double* __restrict__ stage, int n, double* __restrict__ adv_stats);
 __global__ void gs_k_opb_gather_f64(GsOpbGatherArgs G);
 __global__ void gs_k_opb_gather_f32(GsOpbGatherArgs G);
+__global__ void gs_k_train_forward(GsTrainFwdArgs P);
+__global__ void gs_k_train_head(GsTrainHeadArgs H);
+__global__ void gs_k_train_bwd_data(GsTrainBwdArgs P);
+__global__ void gs_k_train_grad(GsTrainGradArgs P);
+__global__ void gs_k_train_reduce(GsTrainReduceArgs A);
+__global__ void gs_k_train_stats(GsTrainStatArgs S);
+__global__ void gs_k_train_adam(GsTrainAdamArgs A);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

@@ -284,15 +284,25 @@ class BatchedGridEnvironment:
         ``stochastic``: sample tanh(mean + std * eps) instead of tanh(mean) (Gaussian head only).  None removes it.  Not
         environment state: reset() and set_state() leave it alone.  ``policy.compute`` picks the kernel: "float64" (the
         default; normalisation folded into the first layer) or "float32" (gs_policy_mlp_set_opts with GS_COMPUTE_F32: the
-        normalisation as a float64 stage of its own, float32 layers, float64 head)."""
+        normalisation as a float64 stage of its own, float32 layers, float64 head).  The device holds a COPY: once a
+        ``DeviceLearner`` has stepped, ``policy`` no longer describes the installed network (``DeviceLearner.policy()`` does)."""
         if policy is None:
             self._h.set_policy(None)
             self._policy_compute = None
+            self._installed_nets().pop("policy", None)
             return
         p, keep = policy.to_struct(stochastic=stochastic)
         opts, keep_opts = policy.to_opts()
         self._h.set_policy(p, opts)         # (raises, and leaves the installed policy in place, if the library refuses it)
         self._policy_compute = policy.compute
+        self._installed_nets()["policy"] = dict(obs_mean=policy.obs_mean, obs_std=policy.obs_std, head=policy.head, compute=policy.compute)
+
+    def _installed_nets(self) -> dict:
+        """What ``DeviceLearner`` needs to rebuild an installed network from the device's parameters: per network ("policy",
+        "value", a cost channel's index) the observation normalisation it was installed with (and the policy's head)."""
+        if not hasattr(self, "_nets"):
+            self._nets = {}
+        return self._nets
 
     @property
     def policy_compute(self) -> Optional[str]:
@@ -311,10 +321,12 @@ class BatchedGridEnvironment:
         it.  Like the policy it is not environment state."""
         if value is None:
             self._h.set_value(None)
+            self._installed_nets().pop("value", None)
             return
         p, keep = value.to_struct()
         opts, keep_opts = value.to_opts()
         self._h.set_value(p, opts)          # (raises, and leaves the installed network in place, if the library refuses it)
+        self._installed_nets()["value"] = dict(obs_mean=value.obs_mean, obs_std=value.obs_std)
 
     def set_cost_value(self, channel, value: Optional[Any]) -> None:
         """Install an ``MLPValue`` as the cost critic of constraint ``channel`` (0 voltage, 1 frequency, 2 thermal, or the name;
@@ -322,10 +334,12 @@ class BatchedGridEnvironment:
         c = _lib.COST_CHANNELS.index(channel) if isinstance(channel, str) else int(channel)
         if value is None:
             self._h.set_cost_value(c, None)
+            self._installed_nets().pop(c, None)
             return
         p, keep = value.to_struct()
         opts, keep_opts = value.to_opts()
         self._h.set_cost_value(c, p, opts)  # (raises, and leaves the installed critic in place, if the library refuses it)
+        self._installed_nets()[c] = dict(obs_mean=value.obs_mean, obs_std=value.obs_std)
 
     def value_estimates(self) -> np.ndarray:
         """The installed value network's estimates [num_envs] on the observation the environment stands at (gs_value_mlp_eval)."""

@@ -789,6 +789,95 @@ int gs_onpolicy_stats(gs_handle* h, gs_onpolicy_stats_out* out);
 int gs_onpolicy_batch(gs_handle* h, uint64_t seed, uint32_t epoch, int64_t first, int32_t n, gs_onpolicy_batch_out* out,
                       void* consumer_stream);
 
+/* ---- the learner: one clipped-surrogate (PPO) or critic update per minibatch, where the networks lie ----
+ * The networks that gs_policy_mlp_set_opts, gs_value_mlp_set and gs_cost_value_mlp_set installed become trainable in place: one
+ * gs_learner_step per network and minibatch runs the forward pass with saved activations, the loss and its gradient at the head, the
+ * backward pass, a deterministic gradient reduction and Adam, which also rewrites the packed image the rollout and critic kernels
+ * read -- the next gs_rollout acts with the updated policy and no weight crosses the host.  Additive to ABI 2.
+ *
+ * net: GS_LEARNER_POLICY, GS_LEARNER_VALUE (the reward critic) or GS_LEARNER_COST_VALUE + c (the critic of cost channel c).
+ * gs_learner_create snapshots the installed network's float32 weights and biases as the master parameters -- P float32 values, flat
+ * in torch order: W_0 row-major [out][in], b_0, W_1, b_1, ... -- and zeroes Adam's m, v and step count.  GS_E_STATE: the network is
+ * not installed, or the policy is not GS_COMPUTE_F32 with GS_HEAD_GAUSSIAN_TANH.  GS_E_INVALID: a wrong struct_size, an unknown
+ * net, or a hyper-parameter that is not finite or outside lr >= 0, 0 <= beta1 < 1, 0 <= beta2 < 1, eps >= 0, weight_decay >= 0,
+ * max_grad_norm >= 0 (0: no clipping), clip >= 0.  Creating again starts afresh from the installed image (which holds the trained
+ * parameters).  Installing a network again with a *_set* entry drops that network's learner: a step is GS_E_STATE until
+ * gs_learner_create has run again.
+ *
+ * gs_learner_step (asynchronous, on the handle's stream): one update on the minibatch of n samples that gs_onpolicy_batch just left
+ * in `batch`.  It needs gs_onpolicy_prepare on the last rollout with dtype GS_COMPUTE_F32 and with obs_shift / obs_scale bit-equal,
+ * compared on the host, to the network's own normalisation (none given: the network's must be shift 0, scale 1); GS_E_STATE
+ * otherwise, and for the policy also when the last rollout recorded no log-probabilities.  The policy reads observations [n][obs_dim]
+ * (float32, normalised), advantages [n] and indices [n] of `batch`, and THROUGH the indices the rollout's float64 actions and
+ * log-probabilities: a float32 copy of a saturated action loses 1 - a^2, and importance ratios of up to 5.5 at unchanged
+ * parameters were measured with it.  A critic reads observations and returns (cost_returns[c]).  A missing pointer or n <= 0 (or more
+ * than 2^24 samples) is GS_E_INVALID.  Every check runs before anything is launched.  consumer_stream: as gs_onpolicy_batch.
+ *
+ * The loss.  Layers in float32 (float32 products and sums on the matrix cores, float32 activations), the head in float64 on the
+ * float32 pre-head values (mean_k | log_std_k), its gradient rounded once to float32, the backward pass in float32.
+ *   policy, sample i with stored action a (float64), old log-probability lp_old and advantage A:
+ *     ls_k = clamp(log_std_k, -20, 2);  x_k = atanh(clamp(a_k, -(1 - 1e-7), 1 - 1e-7));  e_k = (x_k - mean_k) exp(-ls_k)
+ *     lp = sum_k (((-0.5 e_k) e_k - ls_k) - 0.5 log(2 pi)) - log((1 - a_k a_k) + 1e-6)      in action order from k = 0
+ *     r = exp(lp - lp_old);   s_i = min(r A, clamp(r, 1 - clip, 1 + clip) A);   h_i = sum_k (ls_k + 0.5 log(2 pi e))
+ *     L = -(1/n) sum_i s_i - ent_coef (1/n) sum_i h_i
+ *     clipped_i = (A > 0 and r > 1 + clip) or (A < 0 and r < 1 - clip);   dL/dlp = 0 if clipped_i, else -(r A) / n
+ *     dL/dmean_k = dL/dlp  e_k exp(-ls_k)
+ *     dL/dlog_std_k = dL/dlp (e_k e_k - 1) - ent_coef / n   where -20 <= log_std_k <= 2, and 0 outside (as torch.clamp)
+ *   critic:  L = (1/n) sum_i (v_i - ret_i)^2,   dL/dv_i = 2 (v_i - ret_i) / n
+ *   hidden layers: delta_l = (delta_{l+1} W_{l+1}) * act'(y_l), act' from the saved output y: relu y > 0, tanh 1 - y^2, elu
+ *     y > 0 ? 1 : y + 1;  dW_l = delta_l^T a_{l-1},  db_l = the column sums of delta_l.
+ * Determinism.  dW and db are summed over segments of rows_per_segment rows (a compile-time constant): within a segment in an order
+ * fixed by the layer's shape, the segments' partial results in ascending order; no floating-point atomics.  The gradient's bits are
+ * a function of the parameters, the minibatch's contents and n alone.  grad_norm = sqrt of the float64 sum of the squares of the
+ * float32 gradient, in a fixed tree (four per thread in order, a butterfly over 256 threads; then ONE workgroup of 1024 threads
+ * over those sums in the order of gs_episode_stats).
+ * Adam, per parameter p with gradient g, all float32, every operation rounded, nothing contracted (t = the step's number from 1):
+ *     max_grad_norm > 0:   g = g * float32(min(1, max_grad_norm / (grad_norm + 1e-6)))        the scale computed in float64
+ *     weight_decay != 0:   g = g + wd * p
+ *     m = b1 * m + omb1 * g;   v = b2 * v + (omb2 * g) * g;   denom = sqrt(v) / bc2s + eps;   p = p - step * (m / denom)
+ *   with the scalars computed on the host in float64 and rounded ONCE to float32: wd = weight_decay, b1 = beta1, omb1 = 1 - beta1,
+ *   b2 = beta2, omb2 = 1 - beta2, bc2s = sqrt(1 - beta2^t), eps, step = lr / (1 - beta1^t).  That is torch.optim.Adam with
+ *   weight_decay as L2 on the gradient, behind torch.nn.utils.clip_grad_norm_.  The same thread stores p into the master
+ *   parameters, the installed image and (layers >= 1) the transposed image of the backward pass; padding stays zero.
+ *
+ * gs_learner_stats waits for the step: loss = L; policy: surrogate = (1/n) sum s_i, entropy = (1/n) sum h_i, approx_kl = (1/n)
+ * sum (lp_old - lp), clip_fraction = (1/n) sum clipped_i, value_loss NaN; critic: value_loss = L, the four policy figures NaN;
+ * grad_norm (before clipping); step = the steps taken.  Reduced by ONE workgroup in the order of gs_episode_stats.  GS_E_STATE
+ * before the first step.  gs_learner_info: the network's shape (any time after create).  gs_learner_download: host float32 copies
+ * [param_count], any pointer may be NULL (grads: the last step's, before clipping and weight decay).  gs_learner_view: device
+ * pointers of the last step's per-sample arrays, valid until the learner's next step or the next gs_rollout that grows the
+ * rollout's buffers; consumer_stream as gs_onpolicy_batch. */
+enum { GS_LEARNER_POLICY = 0, GS_LEARNER_VALUE = 1, GS_LEARNER_COST_VALUE = 2 /* + channel */ };
+typedef struct gs_learner_config {
+  int32_t struct_size;            /* = sizeof(gs_learner_config) */
+  int32_t reserved;
+  double lr, beta1, beta2, eps, weight_decay, max_grad_norm;
+  double clip, ent_coef;          /* the policy's; ignored for a critic */
+} gs_learner_config;
+typedef struct gs_learner_stats_out {
+  double loss, surrogate, entropy, approx_kl, clip_fraction, value_loss, grad_norm, step;
+} gs_learner_stats_out;
+typedef struct gs_learner_info_out {
+  int32_t n_layers, activation;   /* GS_ACT_* */
+  int32_t dims[5];                /* widths, dims[0] = obs_dim */
+  int32_t rows_per_segment;
+  int64_t param_count, step;
+} gs_learner_info_out;
+typedef struct gs_learner_view_out {
+  int32_t n, reserved;
+  const double* log_probs_new;    /* [n]; NULL for a critic, like ratio, clipped and entropy_terms */
+  const double* ratio;            /* [n] */
+  const int32_t* clipped;         /* [n] */
+  const double* loss_terms;       /* [n] policy: s_i; critic: (v_i - ret_i)^2 */
+  const double* entropy_terms;    /* [n] h_i */
+} gs_learner_view_out;
+int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg);
+int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, void* consumer_stream);
+int gs_learner_stats(gs_handle* h, int32_t net, gs_learner_stats_out* out);
+int gs_learner_info(gs_handle* h, int32_t net, gs_learner_info_out* out);
+int gs_learner_download(gs_handle* h, int32_t net, float* params, float* grads, float* m, float* v);
+int gs_learner_view(gs_handle* h, int32_t net, gs_learner_view_out* out, void* consumer_stream);
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
