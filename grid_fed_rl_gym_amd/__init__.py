@@ -22,6 +22,7 @@ from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy
                       evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches)
 from .policy import MLPPolicy, MLPValue
 from .learner import DeviceLearner, ppo_grad_np, value_grad_np, adam_np, split_parameters
+from .federated import FederatedLearners, fedavg_np, fed_noise_np, filter_outliers_np, gaussian_sigma
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
 from .feeders import feeder_from_dict, feeder_to_dict, network_dict_normalized
@@ -37,6 +38,7 @@ __all__ = [
     "episodes_np", "rollout_episodes", "EpisodeRecords", "EpisodeMonitor", "evaluate_policy",
     "permutation_np", "onpolicy_batch_np", "OnPolicyBatches",
     "DeviceLearner", "ppo_grad_np", "value_grad_np", "adam_np", "split_parameters",
+    "FederatedLearners", "fedavg_np", "fed_noise_np", "filter_outliers_np", "gaussian_sigma",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",
     "BatchedSafetyChecker", "BatchedSafetyMonitor", "PostStepChecks", "device_quality_score",

@@ -295,6 +295,28 @@ class gs_learner_view_out(C.Structure):
                 ("loss_terms", C.c_void_p), ("entropy_terms", C.c_void_p)]
 
 
+# the federation (include/gridstep.h "the federation"): the structs of gs_fed_*
+GS_FED_MAX_CLIENTS = 32
+_FED = C.c_void_p
+
+
+class gs_fed_info_out(C.Structure):
+    _fields_ = [("n_clients", C.c_int32), ("net", C.c_int32), ("param_count", C.c_int64), ("rounds", C.c_int64), ("block_params", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class gs_fed_round(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_participants", C.c_int32), ("participants", C.POINTER(C.c_int32)), ("weights", C.POINTER(C.c_double)),
+                ("clip_norm", C.c_double), ("noise_std", C.c_double), ("server_lr", C.c_double), ("seed", C.c_uint64), ("round", C.c_uint32),
+                ("reset_moments", C.c_int32)]
+
+
+class gs_fed_stats_out(C.Structure):
+    _fields_ = [("norm", C.c_double * GS_FED_MAX_CLIENTS), ("clip_scale", C.c_double * GS_FED_MAX_CLIENTS),
+                ("coefficient", C.c_double * GS_FED_MAX_CLIENTS), ("noise_std", C.c_double), ("rounds", C.c_int64), ("round", C.c_uint32),
+                ("n", C.c_int32)]
+
+
 def learner_net(net) -> int:
     """The GS_LEARNER_* number of ``net``: "policy", "value", a cost channel's name (``COST_CHANNELS``) or the number itself."""
     if isinstance(net, (int, np.integer)) and not isinstance(net, bool):
@@ -413,6 +435,14 @@ SYMBOLS = [
     ("gs_learner_info", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_info_out)]),
     ("gs_learner_download", C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gs_learner_view", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_view_out), C.c_void_p]),
+    ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
+    ("gs_fed_destroy", C.c_int, [_FED]),
+    ("gs_fed_info", C.c_int, [_FED, C.POINTER(gs_fed_info_out)]),
+    ("gs_fed_set_global", C.c_int, [_FED, C.c_void_p]),
+    ("gs_fed_measure", C.c_int, [_FED, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double)]),
+    ("gs_fed_aggregate", C.c_int, [_FED, C.POINTER(gs_fed_round)]),
+    ("gs_fed_stats", C.c_int, [_FED, C.POINTER(gs_fed_stats_out)]),
+    ("gs_fed_download", C.c_int, [_FED, C.c_void_p]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 

@@ -134,6 +134,7 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
   HIPCHK(h, hipMemset(Ln.v, 0, (size_t)P * sizeof(float)));
   HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_train_forward, hipFuncAttributeMaxDynamicSharedMemorySize, GS_TR_LDS_MAX));
   Ln.cfg = *cfg; Ln.steps = 0; Ln.n_last = 0;
+  Ln.gen += 1;             // (a federation created on the learner before this one refuses it: abi_fed.hip)
   Ln.live = true;
   return GS_OK;
 }

@@ -573,6 +573,7 @@ void gs_destroy(gs_handle* h) {
   if (h->stream2) (void)hipStreamSynchronize(h->stream2);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
+  fed_detach(h);                  // federations this handle is a client of refuse every further call
   (void)gs_comm_destroy(h);       // the communicator and its buffers, if the handle has one
   if (h->stream2) { (void)hipStreamDestroy(h->stream2); (void)hipEventDestroy(h->ev_fork); (void)hipEventDestroy(h->ev_join); }
   if (h->ev_peer) (void)hipEventDestroy(h->ev_peer);

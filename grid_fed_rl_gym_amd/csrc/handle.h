@@ -178,14 +178,17 @@ struct gs_handle : GsPlan {
   // the network not installed again since.  net: the kernels' description (forward image = the installed network's, T = wt);
   // params / grad / m / v [P] in torch order; steps: Adam's t.  Per-sample arrays of the last step (n_last samples; 0: none) and
   // stats / blocksum: scratch, grown to the largest n seen and released with the rollout's buffers, like tr (acts / deltas
-  // [n][row_stride], partial [segments][P]), which every learner of the handle shares.
+  // [n][row_stride], partial [segments][P]), which every learner of the handle shares.  gen: advanced by every gs_learner_create (a
+  // federation remembers it: abi_fed.hip).
   struct GS_HIDDEN Learner {
-    bool live = false; gs_learner_config cfg{}; uint64_t steps = 0; GsTrainNet net{}; int A = 0;
+    bool live = false; gs_learner_config cfg{}; uint64_t steps = 0, gen = 0; GsTrainNet net{}; int A = 0;
     DevBuf<float> params, grad, m, v, wt;
     DevBuf<double> lp_new, ratio, term0, term1, stats, blocksum; DevBuf<int32_t> clipped; int n_last = 0;
     hipEvent_t ev = nullptr;
   } learner[2 + GS_COST_CHANNELS];
   struct GS_HIDDEN TrainScratch { DevBuf<float> acts, deltas, partial; } tr;
+  // gs_fed_* (abi_fed.hip): the federations this handle is a client of; gs_destroy detaches them (fed_detach)
+  std::vector<gs_fed*> feds;
   // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count
   // themselves here: gs_rollout_episodes(GS_EPISODES_CONTINUE) refuses to carry an episode across one
   uint64_t env_moves = 0;
@@ -391,6 +394,9 @@ void batches_release(gs_handle* h);
 void learner_drop(gs_handle* h, int k);
 void learner_scratch_release(gs_handle* h);
 void learner_release(gs_handle* h);
+
+// ---- the federations of a handle that is being destroyed lose it (abi_fed.hip) ----
+void fed_detach(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);

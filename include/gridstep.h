@@ -878,6 +878,101 @@ int gs_learner_info(gs_handle* h, int32_t net, gs_learner_info_out* out);
 int gs_learner_download(gs_handle* h, int32_t net, float* params, float* grads, float* m, float* v);
 int gs_learner_view(gs_handle* h, int32_t net, gs_learner_view_out* out, void* consumer_stream);
 
+/* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
+ * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
+ * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
+ * the new global parameters into EVERY client's master parameters, forward image and transposed image -- on the device, no weight
+ * on the host, Adam's moments and step counts kept.  Additive to ABI 2.
+ *
+ * gs_fed_create: 1 <= n_clients <= GS_FED_MAX_CLIENTS distinct handles on one device, else GS_E_INVALID.  Every client must hold a
+ * live learner for `net` (GS_E_STATE).  All clients must agree in layer count, widths and activation, and their networks'
+ * observation normalisation (the handles' host copies) must be bit-equal: GS_E_INVALID otherwise -- an average of weights behind
+ * different normalisations is not an average of functions.  The global parameters g are float32 [P] in torch order (as the
+ * learner's), owned by the federation and snapshotted from client 0's master parameters.  NO client is written by create.
+ * gs_fed_set_global is the explicit broadcast: g (params != NULL: taken from the host first) goes, bit for bit, into every
+ * client's master parameters and images; moments and step counts are left alone.
+ *
+ * Lifetime.  The federation keeps the handles, never their buffers, and remembers the generation of each client's learner (every
+ * gs_learner_create advances it).  A client whose learner was dropped (its network installed again) or created again since
+ * gs_fed_create, or that was gs_destroy'ed, makes every call below GS_E_STATE, the message naming the client; only gs_fed_destroy
+ * still succeeds (it may run before or after the clients' gs_destroy).  Every check runs before anything is launched: a refused
+ * call changes nothing.
+ *
+ * Streams.  The federation has a stream of its own.  A call that reads or writes the clients (set_global, measure, aggregate)
+ * first makes that stream wait for an event recorded on every client's stream -- queued learner steps finish first -- and
+ * (set_global, aggregate) afterwards makes every client's stream wait for the federation's event: the client's next
+ * gs_learner_step, gs_rollout or network installation is ordered after the round without a host wait.  Only gs_fed_measure,
+ * gs_fed_stats and gs_fed_download wait on the host (set_global with host parameters waits for its own previous upload only).
+ *
+ * Arithmetic: float64 on the float32 values, every product and sum rounded, nothing contracted.  The participants (indices into
+ * the clients, each at most once, 1 <= n <= n_clients) are taken in the order of the list; p_k: participant k's master parameters.
+ *     d_k[j] = (double)p_k[j] - (double)g[j]
+ *     G_ik   = sum_j d_i[j] d_k[j]                       norm_k = sqrt(G_kk)
+ *     c_k    = clip_norm > 0 ? min(1, clip_norm / (norm_k + 1e-6)) : 1              (the form of Adam's clip)
+ *     u_k    = server_lr * (w_k / W),  W = w_0 + w_1 + ... in list order            (host, float64)
+ *     a_k    = u_k * c_k                                                            (device)
+ *     s[j]   = ((0 + a_0 d_0[j]) + a_1 d_1[j]) + ...                                (ascending k)
+ *     g'[j]  = (float)( ((double)g[j] + s[j]) + noise_std * z[j] )                  (the noise term only when noise_std > 0)
+ *   z[j] = component j & 3 of the four normals of one Philox4x32-10 call with counter (j >> 2, round, net, 'FEDN' = 0x4645444E)
+ *   and key `seed`, by the recipe of the environment's load noise: every output word w is a uniform (w + 1/2) 2^-32, words (0, 1)
+ *   and (2, 3) are one Box-Muller pair each -- sqrt(-2 log u_a) cos(2 pi u_b), then the sine.
+ *   The order of a sum G_ik: a workgroup of 256 threads takes 1024 consecutive parameters, thread t the parameters base + t,
+ *   base + 256 + t, base + 512 + t, base + 768 + t in that order; the 256 sums go through the butterfly of the learner's gradient
+ *   norm (xor 32, 16, ..., 1 within a wavefront, then xor 2, 1 over the four wavefronts).  ONE workgroup of 1024 threads per
+ *   entry then adds the workgroups' sums, thread t those of workgroups t, t + 1024, ..., and the same butterfly over 16 wavefronts
+ *   (the order of gs_episode_stats).  No floating-point atomics: the bits of G are a function of the parameters alone, G is
+ *   symmetric bit for bit, and gs_fed_aggregate -- which computes the diagonal only, with the same kernels -- finds the norms
+ *   that gs_fed_measure reports as sqrt(G_kk), bit for bit.
+ *   Consequences: clients all equal to g give g' == g bit for bit (a parameter -0 becomes +0).  ONE participant with weight 1,
+ *   server_lr 1, no clip and no noise makes g' the participant's parameters bit for bit wherever p - g is exact in float64 (the
+ *   exponents of p[j] and g[j] less than 29 apart) -- in general g + (p - g) is p to within 2^-52 of the larger of the two.
+ *
+ * gs_fed_aggregate (asynchronous) runs one round: one thread per parameter computes g'[j] and stores it into g and, for ALL
+ * n_clients clients -- a client that sat the round out starts its next one from the global model -- into the master parameters,
+ * the client's slot of the forward image and (layers >= 1) of the transposed image; padding is never written and stays zero.
+ * reset_moments != 0: the same thread zeroes every client's m and v, and the clients' step counts become 0; otherwise Adam's
+ * state is left as it is.  GS_E_INVALID: a wrong struct_size, n_participants < 1, a participant out of range or named twice,
+ * a weight that is not finite or negative, weights that sum to 0, or a clip_norm, noise_std or server_lr that is not finite or
+ * below 0.
+ * gs_fed_measure: the Gram matrix [n][n] (row-major, host) of the listed participants' updates; changes nothing.
+ * gs_fed_stats: the last round's figures (GS_E_STATE before the first round).  gs_fed_download: g, host float32 [param_count].
+ * gs_fed_info: the shape.  gs_fed_destroy: waits for the federation's stream and frees what it owns; the clients stay as they are. */
+typedef struct gs_fed gs_fed;
+enum { GS_FED_MAX_CLIENTS = 32 };
+typedef struct gs_fed_info_out {
+  int32_t n_clients, net;
+  int64_t param_count, rounds;     /* rounds: gs_fed_aggregate calls that ran */
+  int32_t block_params;            /* parameters per workgroup of the reductions (1024) */
+  int32_t reserved;
+} gs_fed_info_out;
+typedef struct gs_fed_round {
+  int32_t struct_size;             /* = sizeof(gs_fed_round) */
+  int32_t n_participants;
+  const int32_t* participants;     /* [n] indices into the clients */
+  const double* weights;           /* [n] the reference's num_samples */
+  double clip_norm, noise_std, server_lr;      /* clip_norm 0: no clipping; noise_std 0: no noise */
+  uint64_t seed;
+  uint32_t round;
+  int32_t reset_moments;
+} gs_fed_round;
+typedef struct gs_fed_stats_out {
+  double norm[GS_FED_MAX_CLIENTS];             /* per participant, in list order: norm_k, c_k, a_k */
+  double clip_scale[GS_FED_MAX_CLIENTS];
+  double coefficient[GS_FED_MAX_CLIENTS];
+  double noise_std;
+  int64_t rounds;
+  uint32_t round;
+  int32_t n;
+} gs_fed_stats_out;
+int gs_fed_create(gs_handle* const* clients, int32_t n_clients, int32_t net, gs_fed** out);
+int gs_fed_destroy(gs_fed* f);
+int gs_fed_info(gs_fed* f, gs_fed_info_out* out);
+int gs_fed_set_global(gs_fed* f, const float* params);
+int gs_fed_measure(gs_fed* f, const int32_t* participants, int32_t n, double* gram);
+int gs_fed_aggregate(gs_fed* f, const gs_fed_round* r);
+int gs_fed_stats(gs_fed* f, gs_fed_stats_out* out);
+int gs_fed_download(gs_fed* f, float* global_params);
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
