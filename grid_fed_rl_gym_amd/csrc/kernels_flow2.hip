@@ -22,6 +22,16 @@
 //  * cross-wave maxima / counts are LDS integer atomics on the bit patterns (exact, order-independent); only the two
 //    floating-point SUMS (losses, voltage deviation) keep per-wave partials added in wave order.
 //
+// The budget of the default member (gs_k_step_fbs_flow2h on the 123-bus feeder; DESIGN.md section 9 item 5 has the table).
+// Counted in the gfx950 assembly: a sweep is ~400 vector instructions per wave, 189 of them FP64 (47 per bus); the epilogue's
+// line phase 4 passes x ~60 (37 FP64), its bus phase 4 x ~140 (82 FP64), wave 0's scalar tail ~300 dependent ones on 16 useful
+// lanes; 127 registers of 128; 47 KB of code.  A wave-wide FP64 instruction holds its SIMD for 4 cycles, rsq / rcp for 16.
+// Measured (phase stamps): the launch is ONE workgroup's chain of 68-70 k cycles (every workgroup is resident, two per CU); lines
+// ~5 k, buses ~4 k, tail 5.1 k against the other waves' 2.4 k.  The line and bus phases are bound by ISSUE: four waves share a
+// SIMD and fill each other's waits (4 waves x 4 passes x ~240 cycles = 3.8 k of the line phase's 5 k) -- asking for every pass's
+// records at once moved nothing and its 4 KB of code slowed every phase (the instruction cache serves two CUs).  Only wave 0's
+// tail is a chain that nothing fills: see TAIL_BATCH.  Code size is a budget here like the registers.
+//
 // Reference arithmetic restated (paths relative to /root/reference/grid_fed_rl/environments/): as kernels_solve.hip:
 // mismatch power_flow.py:150-171, line flows / losses :329-358 / :198-200, env step grid_env.py:410-619.
 // The sweep itself is the one of fbs_loop_flow (kernels_solve.hip): same per-bus operations in the same order.
@@ -1715,12 +1725,47 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
   if (st_lane) {
     ROW(R.LOSSES) = losses; ROW(R.MAXMIS) = st.mm; ROW(R.ITERS) = (double)st.iters; ROW(R.CONV) = (double)st.conv; ROW(R.STATUS) = (double)st.status;
   }
+  // From here on the workgroup is this one wave and a chain of dependent operations: an LDS operand read where it is used is a
+  // round trip nothing else fills (16 of them on the 123-bus feeder's 5 generators and 3 batteries).  TAIL_BATCH: the observation
+  // columns that do not wait for the chain -- renewable powers, battery state (grid_env.py:773-781) -- go out first, one
+  // generator / battery per sub-group (every sub-group of wave 0 holds the instance: HV stores per instruction), and the operands
+  // of the sums are read TAIL_Q at a time.  Each value is still formed by the same additions in the same order.  For the sweep
+  // members with more than one bus per sub-group, without the checks: the small members keep the plain loops (with the two or
+  // three devices of a 13-bus feeder the batches' set-up costs more than the round trips it saves: +1.5 % on a step of the
+  // 13-bus Newton-Raphson benchmark), and in the Newton-Raphson members and the forms with the checks the batches' registers
+  // came out as 1 to 14 more spilled ones at the members' caps.
+  constexpr bool TAIL_BATCH = SOLVER == F2_FBS && NI > 1 && !CHK;
+  constexpr int TAIL_Q = 4;
+  if constexpr (TAIL_BATCH) {
+    if (PA.out != nullptr && valid) {
+      double* o = PA.out + (size_t)b * PA.obs_dim;
+      const int c_g = 2 * n + 2 * m + 1 + 2 * nl_, c_b = c_g + ng;
+      for (int gi = hv; gi < ng; gi += HV) o[c_g + gi] = env_lds[(F.env_genp + gi) * IW + l];
+      for (int q = hv; q < nb; q += HV) { o[c_b + 2 * q] = env_lds[(F.env_soc + q) * IW + l]; o[c_b + 2 * q + 1] = env_lds[(F.env_batp + q) * IW + l]; }
+    }
+  }
   const double dt = E.timestep;
   double total_gen = 0.0, total_curt = 0.0;                            // grid_env.py:744-751, 807-816
-  for (int gi = 0; gi < ng; ++gi) {
-    const double p = env_lds[(F.env_genp + gi) * IW + l];
-    total_gen += p;
-    total_curt += p * (1.0 - env_lds[(F.env_curt + gi) * IW + l]);
+  if constexpr (TAIL_BATCH) {
+#pragma unroll 1
+    for (int g0 = 0; g0 < ng; g0 += TAIL_Q) {
+      double gp[TAIL_Q], gc[TAIL_Q];
+#pragma unroll
+      for (int q = 0; q < TAIL_Q; ++q) {
+        const int gi = g0 + q < ng ? g0 + q : ng - 1;
+        gp[q] = env_lds[(F.env_genp + gi) * IW + l]; gc[q] = env_lds[(F.env_curt + gi) * IW + l];
+      }
+#pragma unroll
+      for (int q = 0; q < TAIL_Q; ++q) {
+        if (g0 + q < ng) { total_gen += gp[q]; total_curt += gp[q] * (1.0 - gc[q]); }
+      }
+    }
+  } else {
+    for (int gi = 0; gi < ng; ++gi) {
+      const double p = env_lds[(F.env_genp + gi) * IW + l];
+      total_gen += p;
+      total_curt += p * (1.0 - env_lds[(F.env_curt + gi) * IW + l]);
+    }
   }
   const double totloss = totloss0 + gs_div_by(losses * dt, 3600.0, 1.0 / 3600.0);      // grid_env.py:739
   double load_sum = total_load;                                        // sum(load.active_power), grid_env.py:744
@@ -1735,9 +1780,22 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
   reward -= (double)(over * 50);
   reward -= totloss * 0.1;
   reward += (total_gen - total_curt) * 1e-5;
-  for (int q = 0; q < nb; ++q) {
-    const double soc = env_lds[(F.env_soc + q) * IW + l];
-    reward += (soc >= 0.2 && soc <= 0.8) ? 1.0 : -5.0;
+  if constexpr (TAIL_BATCH) {
+#pragma unroll 1
+    for (int q0 = 0; q0 < nb; q0 += TAIL_Q) {
+      double soc[TAIL_Q];
+#pragma unroll
+      for (int q = 0; q < TAIL_Q; ++q) soc[q] = env_lds[(F.env_soc + (q0 + q < nb ? q0 + q : nb - 1)) * IW + l];
+#pragma unroll
+      for (int q = 0; q < TAIL_Q; ++q) {
+        if (q0 + q < nb) reward += (soc[q] >= 0.2 && soc[q] <= 0.8) ? 1.0 : -5.0;
+      }
+    }
+  } else {
+    for (int q = 0; q < nb; ++q) {
+      const double soc = env_lds[(F.env_soc + q) * IW + l];
+      reward += (soc >= 0.2 && soc <= 0.8) ? 1.0 : -5.0;
+    }
   }
   const int vhigh = vflags & 1, vlow = (vflags >> 1) & 1, fhigh = f > E.f_max, flow_ = f < E.f_min;
   double viol = viol0, trunc = 0.0;
@@ -1757,13 +1815,16 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
       RS.done[(size_t)RS.t * B + b] = (uint8_t)((step0 >= (double)E.episode_length ? 1 : 0) | (trunc != 0.0 ? 2 : 0));
     }
     // the observation columns that are neither bus nor line pairs: frequency, renewable powers, battery state
-    // (grid_env.py:766, 773-781); the static load columns in between are written at reset and never change
+    // (grid_env.py:766, 773-781; TAIL_BATCH: the last two went out above); the static load columns in between are written
+    // at reset and never change
     if (PA.out != nullptr && valid) {
       double* o = PA.out + (size_t)b * PA.obs_dim;
       const int c_f = 2 * n + 2 * m, c_g = c_f + 1 + 2 * nl_, c_b = c_g + ng;
       o[c_f] = f;
-      for (int gi = 0; gi < ng; ++gi) o[c_g + gi] = env_lds[(F.env_genp + gi) * IW + l];
-      for (int q = 0; q < nb; ++q) { o[c_b + 2 * q] = env_lds[(F.env_soc + q) * IW + l]; o[c_b + 2 * q + 1] = env_lds[(F.env_batp + q) * IW + l]; }
+      if constexpr (!TAIL_BATCH) {
+        for (int gi = 0; gi < ng; ++gi) o[c_g + gi] = env_lds[(F.env_genp + gi) * IW + l];
+        for (int q = 0; q < nb; ++q) { o[c_b + 2 * q] = env_lds[(F.env_soc + q) * IW + l]; o[c_b + 2 * q + 1] = env_lds[(F.env_batp + q) * IW + l]; }
+      }
     }
   }
   if (chk && st_lane && b < (int)FC.Bp && valid) {
