@@ -21,7 +21,7 @@ from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy
                       constraint_values, collect_constrained_data, episodes_np, rollout_episodes, EpisodeRecords, EpisodeMonitor,
                       evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches)
 from .policy import MLPPolicy, MLPValue
-from .learner import DeviceLearner, ppo_grad_np, value_grad_np, adam_np, split_parameters
+from .learner import DeviceLearner, ppo_grad_np, value_grad_np, awr_grad_np, expectile_grad_np, adam_np, split_parameters
 from .federated import FederatedLearners, fedavg_np, fed_noise_np, filter_outliers_np, gaussian_sigma
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -37,7 +37,7 @@ __all__ = [
     "ConstraintLimits", "costs_np", "rollout_costs_np", "rollout_costs", "evaluate_rollout_costs", "constraint_values", "collect_constrained_data",
     "episodes_np", "rollout_episodes", "EpisodeRecords", "EpisodeMonitor", "evaluate_policy",
     "permutation_np", "onpolicy_batch_np", "OnPolicyBatches",
-    "DeviceLearner", "ppo_grad_np", "value_grad_np", "adam_np", "split_parameters",
+    "DeviceLearner", "ppo_grad_np", "value_grad_np", "awr_grad_np", "expectile_grad_np", "adam_np", "split_parameters",
     "FederatedLearners", "fedavg_np", "fed_noise_np", "filter_outliers_np", "gaussian_sigma",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",

@@ -295,6 +295,26 @@ class gs_learner_view_out(C.Structure):
                 ("loss_terms", C.c_void_p), ("entropy_terms", C.c_void_p)]
 
 
+# the learner's loss (include/gridstep.h "the learner's loss"): GS_LOSS_* and the struct of gs_learner_set_loss / _get_loss
+GS_LOSS_DEFAULT, GS_LOSS_AWR, GS_LOSS_EXPECTILE = 0, 1, 2
+LOSS_KINDS = {"default": GS_LOSS_DEFAULT, "awr": GS_LOSS_AWR, "expectile": GS_LOSS_EXPECTILE}
+
+
+class gs_learner_loss(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("temperature", C.c_double), ("weight_max", C.c_double),
+                ("expectile", C.c_double)]
+
+
+def learner_loss(kind="default", temperature=1.0, weight_max=20.0, expectile=0.7, struct_size=None) -> gs_learner_loss:
+    """A ``gs_learner_loss``: ``kind`` a name of ``LOSS_KINDS`` or a GS_LOSS_* number."""
+    if isinstance(kind, str):
+        if kind not in LOSS_KINDS:
+            raise ValueError(f"learner loss: unknown kind {kind!r}; one of {sorted(LOSS_KINDS)}")
+        kind = LOSS_KINDS[kind]
+    return gs_learner_loss(C.sizeof(gs_learner_loss) if struct_size is None else int(struct_size), int(kind), float(temperature),
+                           float(weight_max), float(expectile))
+
+
 # the federation (include/gridstep.h "the federation"): the structs of gs_fed_*
 GS_FED_MAX_CLIENTS = 32
 _FED = C.c_void_p
@@ -435,6 +455,8 @@ SYMBOLS = [
     ("gs_learner_info", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_info_out)]),
     ("gs_learner_download", C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gs_learner_view", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_view_out), C.c_void_p]),
+    ("gs_learner_set_loss", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_loss)]),
+    ("gs_learner_get_loss", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_loss)]),
     ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
     ("gs_fed_destroy", C.c_int, [_FED]),
     ("gs_fed_info", C.c_int, [_FED, C.POINTER(gs_fed_info_out)]),
@@ -1553,6 +1575,17 @@ class Handle:
         arr = lambda p, ts: DeviceArray(p, (n,), ts) if p else None
         return dict(log_probs_new=arr(o.log_probs_new, "<f8"), ratio=arr(o.ratio, "<f8"), clipped=arr(o.clipped, "<i4"),
                     loss_terms=arr(o.loss_terms, "<f8"), entropy_terms=arr(o.entropy_terms, "<f8"))
+
+    def learner_set_loss(self, net, loss: gs_learner_loss) -> None:
+        """gs_learner_set_loss: ``loss`` (``learner_loss``) applies from the next step of ``net``; Adam's state stays."""
+        self._check(self._lib.gs_learner_set_loss(self._h, learner_net(net), C.byref(loss)))
+
+    def learner_get_loss(self, net) -> dict:
+        """gs_learner_get_loss: ``kind`` (a name of ``LOSS_KINDS``), ``temperature``, ``weight_max`` and ``expectile`` in force."""
+        o = gs_learner_loss()
+        self._check(self._lib.gs_learner_get_loss(self._h, learner_net(net), C.byref(o)))
+        names = {v: k for k, v in LOSS_KINDS.items()}
+        return dict(kind=names[int(o.kind)], temperature=float(o.temperature), weight_max=float(o.weight_max), expectile=float(o.expectile))
 
     def rollout_device_view(self) -> gs_rollout_device:
         """Device pointers of the last rollout (gs_rollout_device_view) for a consumer that stays on the GPU."""

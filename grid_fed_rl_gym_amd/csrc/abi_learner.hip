@@ -1,6 +1,7 @@
 // abi_learner.hip -- the learner (include/gridstep.h "the learner"): gs_learner_create snapshots an installed
 // network into master parameters, gs_learner_step queues one update on the minibatch gs_onpolicy_batch left (the kernels of
-// kernels_train.hip), gs_learner_stats / _info / _download / _view read what it left.  The learners' buffers are made here and
+// kernels_train.hip; with gs_learner_set_loss the head and its statistics are those of kernels_train_offline.hip, DESIGN.md section
+// 21), gs_learner_stats / _info / _download / _view read what it left.  The learners' buffers are made here and
 // released here: parameters with the learner (learner_drop), what is sized by n with the rollout's buffers (learner_scratch_release).
 #include <cmath>
 #include <cstring>
@@ -11,6 +12,7 @@
 using namespace gsi;
 
 static_assert(sizeof(gs_learner_config) == 72, "gs_learner_config: two int32, eight doubles");
+static_assert(sizeof(gs_learner_loss) == 32, "gs_learner_loss: two int32, three doubles");
 static_assert(GS_POLICY_MAX_LAYERS == 4, "gs_learner_info_out::dims holds five widths");
 
 namespace gsi __attribute__((visibility("hidden"))) {
@@ -26,7 +28,7 @@ void learner_drop(gs_handle* h, int k) {
   L.params.release(); L.grad.release(); L.m.release(); L.v.release(); L.wt.release(); L.stats.release(); L.blocksum.release();
   learner_scratch_release_one(L);
   if (L.ev) { (void)hipEventDestroy(L.ev); L.ev = nullptr; }
-  L.live = false; L.steps = 0;
+  L.live = false; L.steps = 0; L.loss = gs_learner_loss{};
 }
 
 void learner_scratch_release(gs_handle* h) {
@@ -133,7 +135,7 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
   HIPCHK(h, hipMemset(Ln.m, 0, (size_t)P * sizeof(float)));
   HIPCHK(h, hipMemset(Ln.v, 0, (size_t)P * sizeof(float)));
   HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_train_forward, hipFuncAttributeMaxDynamicSharedMemorySize, GS_TR_LDS_MAX));
-  Ln.cfg = *cfg; Ln.steps = 0; Ln.n_last = 0;
+  Ln.cfg = *cfg; Ln.steps = 0; Ln.n_last = 0; Ln.loss = gs_learner_loss{};      // (GS_LOSS_DEFAULT)
   Ln.gen += 1;             // (a federation created on the learner before this one refuses it: abi_fed.hip)
   Ln.live = true;
   return GS_OK;
@@ -159,7 +161,8 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   }
   const bool policy = net == GS_LEARNER_POLICY;
   const void* target = policy ? batch->advantages : net == GS_LEARNER_VALUE ? batch->returns : batch->cost_returns[net - GS_LEARNER_COST_VALUE];
-  if (policy && !ro.logp_recorded) return fail(h, GS_E_STATE, "gs_learner_step: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
+  const int loss = Ln.loss.kind;
+  if (policy && loss == GS_LOSS_DEFAULT && !ro.logp_recorded) return fail(h, GS_E_STATE, "gs_learner_step: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
   if (!batch->observations || !target || (policy && !batch->indices))
     return fail(h, GS_E_INVALID, "gs_learner_step: the batch lacks %s", !batch->observations ? "observations" : !target ? (policy ? "advantages" : "returns") : "indices");
   GS_ENTER(h);
@@ -198,7 +201,21 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   } else {
     H.ret = (const float*)target;
   }
-  hipLaunchKernelGGL(gs_k_train_head, dim3((n + 63) / 64), dim3(64), 0, h->stream, H);
+  if (loss == GS_LOSS_AWR) {                 // (the heads of kernels_train_offline.hip: the same grid, the same arrays)
+    GsTrainAwrHeadArgs W{};
+    W.pre = H.pre; W.ghead = H.ghead; W.n = n; W.row_stride = H.row_stride; W.width16 = H.width16; W.A = H.A;
+    W.idx = H.idx; W.act = H.act; W.adv = H.adv; W.N = H.N;
+    W.temperature = Ln.loss.temperature; W.weight_max = Ln.loss.weight_max; W.ent_coef = cfg.ent_coef;
+    W.lp_new = Ln.lp_new; W.weight = Ln.ratio; W.capped = Ln.clipped; W.term0 = Ln.term0; W.term1 = Ln.term1;
+    hipLaunchKernelGGL(gs_k_train_head_awr, dim3((n + 63) / 64), dim3(64), 0, h->stream, W);
+  } else if (loss == GS_LOSS_EXPECTILE) {
+    GsTrainExpectileArgs E{};
+    E.pre = H.pre; E.ghead = H.ghead; E.ret = H.ret; E.term0 = Ln.term0; E.n = n; E.row_stride = H.row_stride; E.width16 = H.width16;
+    E.tau = Ln.loss.expectile;
+    hipLaunchKernelGGL(gs_k_train_head_expectile, dim3((n + 63) / 64), dim3(64), 0, h->stream, E);
+  } else {
+    hipLaunchKernelGGL(gs_k_train_head, dim3((n + 63) / 64), dim3(64), 0, h->stream, H);
+  }
   HIPCHK(h, hipGetLastError());
 
   if (last > 0) {
@@ -229,7 +246,14 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   GsTrainStatArgs S{};
   S.term0 = Ln.term0; S.term1 = Ln.term1; S.lp_new = Ln.lp_new; S.logp = ro.logp; S.idx = batch->indices; S.clipped = Ln.clipped;
   S.blocksum = Ln.blocksum; S.stats = Ln.stats; S.N = ob.N; S.n = n; S.blocks = red_blocks; S.policy = policy; S.ent_coef = cfg.ent_coef;
-  hipLaunchKernelGGL(gs_k_train_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, S);
+  if (loss == GS_LOSS_AWR) {
+    GsTrainAwrStatArgs W{};
+    W.term0 = S.term0; W.term1 = S.term1; W.lp_new = S.lp_new; W.logp = ro.logp_recorded ? ro.logp.p : nullptr; W.idx = S.idx; W.capped = S.clipped;
+    W.blocksum = S.blocksum; W.stats = S.stats; W.N = S.N; W.n = n; W.blocks = red_blocks; W.ent_coef = cfg.ent_coef;
+    hipLaunchKernelGGL(gs_k_train_stats_awr, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, W);
+  } else {                                   // (an expectile critic: a critic's sum of term0)
+    hipLaunchKernelGGL(gs_k_train_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, S);
+  }
   HIPCHK(h, hipGetLastError());
 
   const double t = (double)(Ln.steps + 1);
@@ -297,6 +321,39 @@ int gs_learner_view(gs_handle* h, int32_t net, gs_learner_view_out* out, void* c
   *out = gs_learner_view_out{};
   out->n = Ln.n_last; out->loss_terms = Ln.term0;
   if (policy) { out->log_probs_new = Ln.lp_new; out->ratio = Ln.ratio; out->clipped = Ln.clipped; out->entropy_terms = Ln.term1; }
+  return GS_OK;
+}
+
+// ---- the learner's loss (include/gridstep.h "the learner's loss"): host state only, read by the next step ----
+int gs_learner_set_loss(gs_handle* h, int32_t net, const gs_learner_loss* loss) {
+  if (!h || !loss) return fail(h, GS_E_INVALID, "handle / loss is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_set_loss: unknown net %d", net);
+  if (loss->struct_size != (int32_t)sizeof(gs_learner_loss))
+    return fail(h, GS_E_INVALID, "gs_learner_loss struct_size %d != %d", loss->struct_size, (int)sizeof(gs_learner_loss));
+  const bool policy = net == GS_LEARNER_POLICY;
+  if (loss->kind != GS_LOSS_DEFAULT && loss->kind != GS_LOSS_AWR && loss->kind != GS_LOSS_EXPECTILE)
+    return fail(h, GS_E_INVALID, "gs_learner_set_loss: unknown kind %d", loss->kind);
+  if (loss->kind == GS_LOSS_AWR && !policy) return fail(h, GS_E_INVALID, "gs_learner_set_loss: GS_LOSS_AWR is the policy's loss, not %s's", net_name(net));
+  if (loss->kind == GS_LOSS_EXPECTILE && policy) return fail(h, GS_E_INVALID, "gs_learner_set_loss: GS_LOSS_EXPECTILE is a critic's loss, not the policy's");
+  if (std::isnan(loss->temperature) || std::isnan(loss->weight_max) || std::isnan(loss->expectile))
+    return fail(h, GS_E_INVALID, "gs_learner_loss: temperature, weight_max or expectile is NaN");
+  if (loss->kind == GS_LOSS_AWR && (!(loss->temperature > 0.0) || !(loss->weight_max > 0.0)))
+    return fail(h, GS_E_INVALID, "gs_learner_loss: GS_LOSS_AWR needs temperature > 0 and weight_max > 0 (+inf allowed)");
+  if (loss->kind == GS_LOSS_EXPECTILE && !(loss->expectile > 0.0 && loss->expectile < 1.0))
+    return fail(h, GS_E_INVALID, "gs_learner_loss: GS_LOSS_EXPECTILE needs 0 < expectile < 1");
+  gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_set_loss: no learner for %s", net_name(net));
+  Ln.loss = *loss;        // (a queued step took its arguments by value: it keeps the loss it was queued with)
+  return GS_OK;
+}
+
+int gs_learner_get_loss(gs_handle* h, int32_t net, gs_learner_loss* out) {
+  if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_get_loss: unknown net %d", net);
+  const gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_get_loss: no learner for %s", net_name(net));
+  *out = Ln.loss;
+  out->struct_size = (int32_t)sizeof(gs_learner_loss);
   return GS_OK;
 }
 

@@ -182,6 +182,7 @@ struct gs_handle : GsPlan {
   // federation remembers it: abi_fed.hip).
   struct GS_HIDDEN Learner {
     bool live = false; gs_learner_config cfg{}; uint64_t steps = 0, gen = 0; GsTrainNet net{}; int A = 0;
+    gs_learner_loss loss{};      // gs_learner_set_loss; GS_LOSS_DEFAULT from gs_learner_create and after learner_drop
     DevBuf<float> params, grad, m, v, wt;
     DevBuf<double> lp_new, ratio, term0, term1, stats, blocksum; DevBuf<int32_t> clipped; int n_last = 0;
     hipEvent_t ev = nullptr;

@@ -70,6 +70,9 @@ __global__ void gs_k_train_grad(GsTrainGradArgs P);
 __global__ void gs_k_train_reduce(GsTrainReduceArgs A);
 __global__ void gs_k_train_stats(GsTrainStatArgs S);
 __global__ void gs_k_train_adam(GsTrainAdamArgs A);
+__global__ void gs_k_train_head_awr(GsTrainAwrHeadArgs H);
+__global__ void gs_k_train_head_expectile(GsTrainExpectileArgs H);
+__global__ void gs_k_train_stats_awr(GsTrainAwrStatArgs S);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

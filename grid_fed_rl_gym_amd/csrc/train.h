@@ -92,6 +92,35 @@ struct GsTrainStatArgs {
   double ent_coef;
 };
 
+// ---- the heads of kernels_train_offline.hip (include/gridstep.h "the learner's loss") ----
+// gs_k_train_head_awr: GsTrainHeadArgs' policy part without the rollout's log-probabilities and the clip
+struct GsTrainAwrHeadArgs {
+  const float* pre; float* ghead;        // as GsTrainHeadArgs
+  int32_t n, row_stride, width16, A;
+  const int32_t* idx; const double* act; const float* adv;
+  long long N;
+  double temperature, weight_max, ent_coef;
+  double* lp_new; double* weight; int32_t* capped;
+  double* term0;         // w_i lp
+  double* term1;         // sum_k (ls_k + 0.5 log(2 pi e))
+};
+
+// gs_k_train_head_expectile: a critic's head, term0 = q_i (v - ret)^2
+struct GsTrainExpectileArgs {
+  const float* pre; float* ghead; const float* ret; double* term0;
+  int32_t n, row_stride, width16, reserved;
+  double tau;
+};
+
+// gs_k_train_stats_awr: GsTrainStatArgs for a policy whose rollout may hold no log-probabilities (logp NULL: approx_kl NaN)
+struct GsTrainAwrStatArgs {
+  const double* term0; const double* term1; const double* lp_new; const double* logp; const int32_t* idx; const int32_t* capped;
+  const double* blocksum; double* stats;
+  long long N;
+  int32_t n, blocks;
+  double ent_coef;
+};
+
 struct GsTrainAdamArgs {
   GsTrainNet N;
   float* params; const float* grad; float* m; float* v;

@@ -4,7 +4,7 @@ network, one clipped-surrogate (PPO) or critic update on a minibatch of ``OnPoli
 pass, a deterministic gradient reduction and Adam, which also rewrites the image the rollout and critic kernels read: the next
 ``rollout_device(policy="mlp")`` acts with the updated policy and no weight crosses the host.
 
-``ppo_grad_np``, ``value_grad_np`` and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
+``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np`` and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
 """
 from __future__ import annotations
 
@@ -66,23 +66,12 @@ def _backward(rounded, acts, ghead, activation: str):
     return grads
 
 
-def ppo_grad_np(policy_layers, obs_n, actions, lp_old, adv, clip: float, ent_coef: float, exact: bool = False, clipped=None,
-                activation: str = "relu") -> Dict[str, Any]:
-    """The clipped-surrogate loss of include/gridstep.h and its gradient, as ``gs_learner_step`` computes them for the policy.
-    ``policy_layers``: [(W [out, in], b [out])], the last of width 2 A (mean | log_std); ``obs_n`` [n, obs_dim] the NORMALISED
-    observations (rounded to float32); ``actions`` [n, A] and ``lp_old`` [n] float64 as the rollout stored them; ``adv`` [n].
-    Layers in float32 -- or, with ``exact``, the same float32-rounded operands in float64 throughout (what the float32 result is
-    measured against, the ``pre_head_np`` pattern); the head in float64 either way, its gradient rounded once to float32 unless
-    ``exact``.  ``clipped``: flags [n] to use in place of the ones this evaluation finds (a sample whose ratio lies at a rounding
-    from 1 +- clip).  Returns ``grads`` [(dW, db)], ``log_probs_new``, ``ratio``, ``clipped``, ``surrogate_terms``,
-    ``entropy_terms`` [n], ``log_std_outside`` [n, A] (the clamp is active), and the scalars ``loss``, ``surrogate``,
-    ``entropy``, ``approx_kl``, ``clip_fraction``."""
-    rounded, acts = _forward(policy_layers, obs_n, activation, exact)
-    out = acts[-1].astype(np.float64)
+def _gaussian_head(out: np.ndarray, actions):
+    """The Gaussian head of include/gridstep.h in float64 on the pre-head values ``out`` [n, 2 A] (mean | log_std) and the stored
+    actions: ``inside`` [n, A] (the clamp of log_std is inactive), ``inv`` = exp(-ls), ``e``, and per sample the log-probability
+    ``lp`` and the entropy ``ent``, summed in action order from k = 0."""
     n, A = out.shape[0], out.shape[1] // 2
     a = np.asarray(actions, dtype=np.float64).reshape(n, A)
-    lp_old = np.asarray(lp_old, dtype=np.float64).reshape(n)
-    adv = np.asarray(adv).astype(np.float64).reshape(n)
     mean, lsr = out[:, :A], out[:, A:]
     inside = (lsr >= LOG_STD_MIN) & (lsr <= LOG_STD_MAX)
     ls = np.clip(lsr, LOG_STD_MIN, LOG_STD_MAX)
@@ -96,16 +85,41 @@ def ppo_grad_np(policy_layers, obs_n, actions, lp_old, adv, clip: float, ent_coe
     for k in range(1, A):
         lp += terms[:, k]
         ent += ls[:, k] + HALF_LOG_2PIE
+    return inside, inv, e, lp, ent
+
+
+def _head_grad(dlp: np.ndarray, inside, inv, e, ent_coef: float, n: int, exact: bool) -> np.ndarray:
+    """dL / d(mean | log_std) [n, 2 A] from dL/dlp [n]: the clamp rule, - ent_coef / n, one rounding to float32 unless ``exact``"""
+    gmean = dlp[:, None] * (e * inv)
+    gls = np.where(inside, dlp[:, None] * (e * e - 1.0) - ent_coef / n, 0.0)
+    ghead = np.concatenate([gmean, gls], axis=1)
+    return ghead if exact else ghead.astype(np.float32)
+
+
+def ppo_grad_np(policy_layers, obs_n, actions, lp_old, adv, clip: float, ent_coef: float, exact: bool = False, clipped=None,
+                activation: str = "relu") -> Dict[str, Any]:
+    """The clipped-surrogate loss of include/gridstep.h and its gradient, as ``gs_learner_step`` computes them for the policy.
+    ``policy_layers``: [(W [out, in], b [out])], the last of width 2 A (mean | log_std); ``obs_n`` [n, obs_dim] the NORMALISED
+    observations (rounded to float32); ``actions`` [n, A] and ``lp_old`` [n] float64 as the rollout stored them; ``adv`` [n].
+    Layers in float32 -- or, with ``exact``, the same float32-rounded operands in float64 throughout (what the float32 result is
+    measured against, the ``pre_head_np`` pattern); the head in float64 either way, its gradient rounded once to float32 unless
+    ``exact``.  ``clipped``: flags [n] to use in place of the ones this evaluation finds (a sample whose ratio lies at a rounding
+    from 1 +- clip).  Returns ``grads`` [(dW, db)], ``log_probs_new``, ``ratio``, ``clipped``, ``surrogate_terms``,
+    ``entropy_terms`` [n], ``log_std_outside`` [n, A] (the clamp is active), and the scalars ``loss``, ``surrogate``,
+    ``entropy``, ``approx_kl``, ``clip_fraction``."""
+    rounded, acts = _forward(policy_layers, obs_n, activation, exact)
+    out = acts[-1].astype(np.float64)
+    n = out.shape[0]
+    inside, inv, e, lp, ent = _gaussian_head(out, actions)
+    lp_old = np.asarray(lp_old, dtype=np.float64).reshape(n)
+    adv = np.asarray(adv).astype(np.float64).reshape(n)
     r = np.exp(lp - lp_old)
     lo, hi = 1.0 - clip, 1.0 + clip
     surr = np.minimum(r * adv, np.clip(r, lo, hi) * adv)
     found = ((adv > 0.0) & (r > hi)) | ((adv < 0.0) & (r < lo))
     flags = found if clipped is None else np.asarray(clipped).reshape(n).astype(bool)
     dlp = np.where(flags, 0.0, -((r * adv) / n))
-    gmean = dlp[:, None] * (e * inv)
-    gls = np.where(inside, dlp[:, None] * (e * e - 1.0) - ent_coef / n, 0.0)
-    ghead = np.concatenate([gmean, gls], axis=1)
-    ghead = ghead if exact else ghead.astype(np.float32)
+    ghead = _head_grad(dlp, inside, inv, e, ent_coef, n, exact)
     surrogate, entropy = math.fsum(surr) / n, math.fsum(ent) / n
     return dict(grads=_backward(rounded, acts, ghead, activation), log_probs_new=lp, ratio=r, clipped=found.astype(np.int32),
                 surrogate_terms=surr, entropy_terms=ent, log_std_outside=~inside, loss=-surrogate - ent_coef * entropy,
@@ -123,6 +137,68 @@ def value_grad_np(value_layers, obs_n, returns, exact: bool = False, activation:
     ghead = ((2.0 * d) / n)[:, None]
     ghead = ghead if exact else ghead.astype(np.float32)
     return dict(grads=_backward(rounded, acts, ghead, activation), values=v, loss_terms=d * d, loss=math.fsum(d * d) / n)
+
+
+def awr_grad_np(policy_layers, obs_n, actions, adv, temperature: float, weight_max: float, ent_coef: float, exact: bool = False,
+                capped=None, activation: str = "relu", lp_old=None) -> Dict[str, Any]:
+    """The advantage-weighted log-likelihood of include/gridstep.h ("the learner's loss") and its gradient, as ``gs_learner_step``
+    computes them under GS_LOSS_AWR: ``w = fmin(exp(adv / temperature), weight_max)`` times the log-probability of the STORED
+    action; both may be ``inf`` (unit weights, no cap: behaviour cloning).  Arguments as ``ppo_grad_np``; ``capped``: flags [n] to
+    use in place of the ones this evaluation finds (a sample whose weight lies at a rounding from ``weight_max``: a flagged sample
+    takes ``weight_max`` in the gradient, an unflagged one ``exp(adv / temperature)``); ``lp_old`` [n]: the rollout's
+    log-probabilities where it recorded any, for ``approx_kl`` alone.  Returns ``grads`` [(dW, db)], ``log_probs_new``, ``weights``,
+    ``capped``, ``loss_terms`` (w lp), ``entropy_terms`` [n], ``log_std_outside`` [n, A] and the scalars ``loss``, ``surrogate``,
+    ``entropy``, ``approx_kl`` (NaN without ``lp_old``) and ``clip_fraction`` (the capped share)."""
+    temperature, weight_max = _awr_check(temperature, weight_max)
+    rounded, acts = _forward(policy_layers, obs_n, activation, exact)
+    out = acts[-1].astype(np.float64)
+    n = out.shape[0]
+    inside, inv, e, lp, ent = _gaussian_head(out, actions)
+    adv = np.asarray(adv).astype(np.float64).reshape(n)
+    with np.errstate(over="ignore"):
+        u = np.exp(adv / temperature)
+    w = np.fmin(u, weight_max)
+    found = u > weight_max
+    w_grad = w if capped is None else np.where(np.asarray(capped).reshape(n).astype(bool), weight_max, u)
+    dlp = -(w_grad / n)
+    ghead = _head_grad(dlp, inside, inv, e, ent_coef, n, exact)
+    terms = w * lp
+    surrogate, entropy = math.fsum(terms) / n, math.fsum(ent) / n
+    kl = float("nan") if lp_old is None else math.fsum(np.asarray(lp_old, dtype=np.float64).reshape(n) - lp) / n
+    return dict(grads=_backward(rounded, acts, ghead, activation), log_probs_new=lp, weights=w, capped=found.astype(np.int32),
+                loss_terms=terms, entropy_terms=ent, log_std_outside=~inside, loss=-surrogate - ent_coef * entropy,
+                surrogate=surrogate, entropy=entropy, approx_kl=kl, clip_fraction=float(np.count_nonzero(found)) / n)
+
+
+def expectile_grad_np(value_layers, obs_n, returns, expectile: float, exact: bool = False, activation: str = "relu") -> Dict[str, Any]:
+    """The expectile regression ``mean q (v - ret)^2``, ``q = expectile`` where ``v < ret`` and ``1 - expectile`` elsewhere, and its
+    gradient, as ``gs_learner_step`` computes them under GS_LOSS_EXPECTILE; arguments and results as ``value_grad_np``, plus
+    ``below`` [n] (``v < ret``).  At 0.5 the head gradient is exactly half of ``value_grad_np``'s."""
+    tau = _expectile_check(expectile)
+    rounded, acts = _forward(value_layers, obs_n, activation, exact)
+    v = acts[-1].astype(np.float64)[:, 0]
+    n = v.shape[0]
+    d = v - np.asarray(returns).astype(np.float64).reshape(n)
+    q = np.where(d < 0.0, tau, 1.0 - tau)
+    ghead = (q * ((2.0 * d) / n))[:, None]
+    ghead = ghead if exact else ghead.astype(np.float32)
+    terms = q * (d * d)
+    return dict(grads=_backward(rounded, acts, ghead, activation), values=v, below=d < 0.0, loss_terms=terms, loss=math.fsum(terms) / n)
+
+
+def _awr_check(temperature, weight_max) -> Tuple[float, float]:
+    temperature, weight_max = float(temperature), float(weight_max)
+    for k, x in (("temperature", temperature), ("weight_max", weight_max)):
+        if math.isnan(x) or not x > 0.0:
+            raise ValueError(f"{k} = {x} must be > 0 (inf allowed)")
+    return temperature, weight_max
+
+
+def _expectile_check(expectile) -> float:
+    tau = float(expectile)
+    if not 0.0 < tau < 1.0:
+        raise ValueError(f"expectile = {expectile} must lie in (0, 1)")
+    return tau
 
 
 def adam_np(p, g, m, v, t: int, cfg, grad_norm: float):
@@ -164,7 +240,10 @@ class DeviceLearner:
     """Adam on the networks installed on ``env``'s device handle.  ``nets``: "policy" (a float32 Gaussian policy of
     ``env.set_policy``), "value" (``env.set_value``) and cost critics by channel name, as in ``env.set_cost_value``.  The
     hyper-parameters are torch's (``weight_decay``: L2 added to the gradient; ``max_grad_norm`` 0: no clipping); ``clip`` and
-    ``ent_coef`` are the policy's.  Creating the learner snapshots each network's installed weights as float32 master parameters and
+    ``ent_coef`` are the policy's.  ``policy_loss``: "ppo" (the clipped surrogate), "awr" (the advantage-weighted log-likelihood of
+    the stored actions, weights ``fmin(exp(A / temperature), weight_max)``; it needs no recorded log-probabilities, so a random-
+    or uploaded-action rollout trains the policy) or "bc" (AWR with both ``inf``: behaviour cloning).  ``value_loss``: "mse" or
+    "expectile" (IQL's value loss at ``expectile``), for every critic named.  Creating the learner snapshots each network's installed weights as float32 master parameters and
     zeroes Adam's state; installing a network again ends its learner (create a new ``DeviceLearner``).
 
     ``step(batch)``: one ``gs_learner_step`` per network on a dict of ``OnPolicyBatches.epoch`` (prepared with float32 and the
@@ -172,7 +251,9 @@ class DeviceLearner:
     from no longer describe them: ``policy()`` / ``value(net)`` rebuild current ones from the device's parameters."""
 
     def __init__(self, env, nets: Sequence[str] = ("policy", "value"), lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0, clip: float = 0.2, ent_coef: float = 0.0, max_grad_norm: float = 0.0) -> None:
+                 eps: float = 1e-8, weight_decay: float = 0.0, clip: float = 0.2, ent_coef: float = 0.0, max_grad_norm: float = 0.0,
+                 policy_loss: str = "ppo", temperature: float = 1.0, weight_max: float = 20.0, value_loss: str = "mse",
+                 expectile: float = 0.7) -> None:
         if isinstance(nets, str):
             nets = (nets,)
         self.nets = tuple(nets)
@@ -191,12 +272,57 @@ class DeviceLearner:
             raise ValueError(f"DeviceLearner: betas = {tuple(betas)} must lie in [0, 1)")
         if not math.isfinite(float(ent_coef)):
             raise ValueError(f"DeviceLearner: ent_coef = {ent_coef} must be finite")
+        self._loss_struct(_lib.GS_LEARNER_POLICY, policy_loss, temperature, weight_max, expectile)      # (ValueError also for a
+        self._loss_struct(_lib.GS_LEARNER_VALUE, value_loss, temperature, weight_max, expectile)        # network not in `nets`)
+        losses = {k: self._loss_struct(k, policy_loss if k == _lib.GS_LEARNER_POLICY else value_loss, temperature, weight_max, expectile)
+                  for k in self._ids}
         self.env = env
         self.config = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                            clip=float(clip), ent_coef=float(ent_coef), max_grad_norm=float(max_grad_norm))
         cfg = _lib.learner_config(**self.config)
         for net in self._ids:
             env.handle.learner_create(net, cfg)
+            if losses[net].kind != _lib.GS_LOSS_DEFAULT:      # (a learner left at "ppo" / "mse" never calls the entry)
+                env.handle.learner_set_loss(net, losses[net])
+
+    @staticmethod
+    def _loss_struct(k: int, loss: str, temperature, weight_max, expectile) -> "_lib.gs_learner_loss":
+        """The ``gs_learner_loss`` of network number ``k`` for the loss named ``loss``; ValueError for what the ABI would refuse."""
+        policy = k == _lib.GS_LEARNER_POLICY
+        names = ("ppo", "awr", "bc") if policy else ("mse", "expectile")
+        if loss not in names:
+            raise ValueError(f"DeviceLearner: {'policy_loss' if policy else 'value_loss'} = {loss!r} must be one of {names}")
+        if loss == "bc":
+            return _lib.learner_loss("awr", math.inf, math.inf, 0.0)
+        if loss == "awr":
+            temperature, weight_max = _awr_check(temperature, weight_max)
+            return _lib.learner_loss("awr", temperature, weight_max, 0.0)
+        if loss == "expectile":
+            return _lib.learner_loss("expectile", 0.0, 0.0, _expectile_check(expectile))
+        return _lib.learner_loss("default", 0.0, 0.0, 0.0)
+
+    def set_loss(self, net="policy", loss: Optional[str] = None, temperature: float = 1.0, weight_max: float = 20.0,
+                 expectile: float = 0.7) -> None:
+        """Another loss for ``net`` from its next step (``gs_learner_set_loss``): the policy's "ppo", "awr" (``temperature``,
+        ``weight_max``) or "bc"; a critic's "mse" or "expectile" (``expectile``).  Adam's moments and step count stay, and a
+        ``FederatedLearners`` on the learner stays valid."""
+        k = self._id(net)
+        if loss is None:
+            raise ValueError("DeviceLearner.set_loss: name the loss")
+        self.env.handle.learner_set_loss(k, self._loss_struct(k, loss, temperature, weight_max, expectile))
+
+    def loss(self, net="policy") -> dict:
+        """The loss of ``net`` in force: ``name`` ("ppo", "awr", "bc", "mse" or "expectile") and ``gs_learner_get_loss``'s ``kind``,
+        ``temperature``, ``weight_max`` and ``expectile``."""
+        k = self._id(net)
+        out = self.env.handle.learner_get_loss(k)
+        if out["kind"] == "default":
+            out["name"] = "ppo" if k == _lib.GS_LEARNER_POLICY else "mse"
+        elif out["kind"] == "awr":
+            out["name"] = "bc" if math.isinf(out["temperature"]) and math.isinf(out["weight_max"]) else "awr"
+        else:
+            out["name"] = "expectile"
+        return out
 
     def _id(self, net) -> int:
         k = _lib.learner_net(net)
@@ -262,6 +388,8 @@ class DeviceLearner:
 
     def views(self, net="policy", stream=None) -> dict:
         """The last step's per-sample arrays as zero-copy ``DeviceArray`` views: ``log_probs_new``, ``ratio`` (float64), ``clipped``
-        (int32), ``loss_terms`` and ``entropy_terms`` (float64) [n]; None where the network has none (a critic has ``loss_terms``)."""
+        (int32), ``loss_terms`` and ``entropy_terms`` (float64) [n]; None where the network has none (a critic has ``loss_terms``).
+        Under "awr" / "bc" ``ratio`` holds the weights, ``clipped`` the cap flags and ``loss_terms`` weight x log-probability; under
+        "expectile" ``loss_terms`` holds q (v - ret)^2."""
         k = self._id(net)
         return self.env.handle.learner_view(k, stream)

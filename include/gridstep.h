@@ -878,6 +878,54 @@ int gs_learner_info(gs_handle* h, int32_t net, gs_learner_info_out* out);
 int gs_learner_download(gs_handle* h, int32_t net, float* params, float* grads, float* m, float* v);
 int gs_learner_view(gs_handle* h, int32_t net, gs_learner_view_out* out, void* consumer_stream);
 
+/* ---- the learner's loss: advantage-weighted log-likelihood and expectile regression ----
+ * The two in-sample losses of offline RL, as other heads behind the learner's unchanged matrix kernels.  Additive to ABI 2;
+ * gs_learner_config is as it was.  A learner has ONE loss: GS_LOSS_DEFAULT (the policy's clipped surrogate, a critic's mean squared
+ * error: everything "the learner" states), GS_LOSS_AWR (the policy only) or GS_LOSS_EXPECTILE (critics only).
+ *
+ * gs_learner_set_loss applies from the learner's next gs_learner_step.  It touches neither the parameters nor Adam's m, v and step
+ * count nor the learner's generation number: a federation on the learner stays valid.  gs_learner_create resets the loss to
+ * GS_LOSS_DEFAULT, and a *_set* entry that drops the learner drops its loss with it.  gs_learner_get_loss: the loss in force
+ * (struct_size is written; fields the kind does not use hold what was last given, 0 after gs_learner_create).
+ * GS_E_STATE: no live learner for `net`.  GS_E_INVALID, before anything changes: a wrong struct_size, an unknown net or kind,
+ * GS_LOSS_AWR on a critic, GS_LOSS_EXPECTILE on the policy, NaN in any field, and for the kind's own fields temperature <= 0,
+ * weight_max <= 0 (+inf is allowed for both) or expectile outside (0, 1).  Fields the kind does not use are otherwise ignored.
+ *
+ * GS_LOSS_AWR.  Sample i has the stored float64 action a, read through `indices` as the clipped surrogate reads it, and the batch's
+ * float32 advantage A under whichever adv_norm the minibatches were prepared with.  ls_k, x_k, e_k, lp and h_i are the formulas of
+ * "the learner", in the same order, nothing contracted.  In float64:
+ *     u_i = exp(A / temperature);   w_i = fmin(u_i, weight_max);   capped_i = u_i > weight_max;   s_i = w_i lp
+ *     L = -(1/n) sum_i s_i - ent_coef (1/n) sum_i h_i;      dL/dlp = -(w_i (1/n))
+ *     dL/dmean_k and dL/dlog_std_k from dL/dlp as in "the learner": the clamp rule, - ent_coef / n, one rounding to float32.
+ *   A / +inf = 0, so temperature = +inf gives w_i = 1 exactly: with weight_max = +inf that is behaviour cloning, L = -mean lp.  The
+ *   weight is a constant of the gradient (no derivative through A).  ent_coef is gs_learner_config's; clip is ignored.  The rollout's
+ *   log-probabilities are NOT read for the gradient: the step's refusal of a rollout that recorded none holds for GS_LOSS_DEFAULT
+ *   only, so a random-action or uploaded-action rollout trains the policy.
+ *   gs_learner_stats: surrogate = (1/n) sum s_i, entropy as before, clip_fraction = (1/n) sum capped_i, approx_kl = (1/n) sum
+ *   (lp_old - lp) when the last rollout recorded log-probabilities and NaN otherwise, value_loss NaN.  gs_learner_view: ratio holds
+ *   w_i, clipped holds capped_i, loss_terms holds s_i.
+ *   Deviation from the reference: its AWR.update and IQL._update_actor weight the log-probability of an action freshly SAMPLED from
+ *   the current policy (_get_action_and_log_prob(states)), not of the dataset's action.  This is the published algorithm, which
+ *   weights the stored action's log-probability.
+ * GS_LOSS_EXPECTILE (IQL's value loss), in float64 on the float32 value v_i and return ret_i:
+ *     d = v_i - ret_i   (the reference's diff is -d);   q_i = (d < 0) ? tau : 1 - tau;   term0_i = q_i (d d)
+ *     L = (1/n) sum_i term0_i;      dL/dv_i = q_i ((2.0 d) (1/n)), rounded once to float32
+ *   At tau = 0.5 every head gradient is exactly half of the mean squared error's (a product with 0.5 is exact away from underflow),
+ *   and so is the loss.  gs_learner_stats: loss = value_loss = L; gs_learner_view: loss_terms holds term0_i.
+ * Both reduce their statistics in the order of gs_learner_stats, ONE workgroup of 1024 threads.  Everything else of a step -- forward
+ * pass, backward pass, gradient reduction, Adam, determinism -- is "the learner"'s, by the same kernels. */
+enum { GS_LOSS_DEFAULT = 0,       /* policy: clipped surrogate; critic: mean squared error */
+       GS_LOSS_AWR = 1,           /* policy only */
+       GS_LOSS_EXPECTILE = 2 };   /* critics only */
+typedef struct gs_learner_loss {
+  int32_t struct_size, kind;      /* = sizeof(gs_learner_loss); GS_LOSS_* */
+  double temperature;             /* AWR: > 0, +inf allowed (unit weights: behaviour cloning) */
+  double weight_max;              /* AWR: > 0, +inf allowed (no cap) */
+  double expectile;               /* EXPECTILE: 0 < tau < 1 */
+} gs_learner_loss;
+int gs_learner_set_loss(gs_handle* h, int32_t net, const gs_learner_loss* loss);
+int gs_learner_get_loss(gs_handle* h, int32_t net, gs_learner_loss* out);
+
 /* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
  * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
  * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
