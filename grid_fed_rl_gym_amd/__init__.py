@@ -19,8 +19,9 @@ from .env import BatchedGridEnvironment, VectorizedEnvironment, Box
 from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy_data, evaluate_rollout, gae_np, rollout_device, GridDataset,
                       DeviceGridDataset, ConstraintLimits, costs_np, rollout_costs_np, rollout_costs, evaluate_rollout_costs,
                       constraint_values, collect_constrained_data, episodes_np, rollout_episodes, EpisodeRecords, EpisodeMonitor,
-                      evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches)
-from .policy import MLPPolicy, MLPValue
+                      evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches, evaluate_rollout_q, q_rollout_np, td_target_np,
+                      q_combine_np, polyak_np)
+from .policy import MLPPolicy, MLPValue, MLPQ
 from .learner import DeviceLearner, ppo_grad_np, value_grad_np, awr_grad_np, expectile_grad_np, adam_np, split_parameters
 from .federated import FederatedLearners, fedavg_np, fed_noise_np, filter_outliers_np, gaussian_sigma
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
@@ -37,6 +38,7 @@ __all__ = [
     "ConstraintLimits", "costs_np", "rollout_costs_np", "rollout_costs", "evaluate_rollout_costs", "constraint_values", "collect_constrained_data",
     "episodes_np", "rollout_episodes", "EpisodeRecords", "EpisodeMonitor", "evaluate_policy",
     "permutation_np", "onpolicy_batch_np", "OnPolicyBatches",
+    "MLPQ", "evaluate_rollout_q", "q_rollout_np", "td_target_np", "q_combine_np", "polyak_np",
     "DeviceLearner", "ppo_grad_np", "value_grad_np", "awr_grad_np", "expectile_grad_np", "adam_np", "split_parameters",
     "FederatedLearners", "fedavg_np", "fed_noise_np", "filter_outliers_np", "gaussian_sigma",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",

@@ -315,6 +315,39 @@ def learner_loss(kind="default", temperature=1.0, weight_max=20.0, expectile=0.7
                            float(weight_max), float(expectile))
 
 
+# state-action critics (include/gridstep.h "state-action critics"): GS_LEARNER_Q, GS_SIGNAL_* and the structs of gs_rollout_*_q
+GS_LEARNER_Q = 5            # + which
+GS_SIGNAL_BATCH, GS_SIGNAL_Q = 0, 1
+SIGNALS = {"batch": GS_SIGNAL_BATCH, "q": GS_SIGNAL_Q}
+Q_NETS = ("q1", "q2")       # the names of GS_LEARNER_Q + 0 and + 1
+
+
+class gs_q_eval_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("bootstrap_mask", C.c_int32), ("gamma", C.c_double), ("reward_shift", C.c_double),
+                ("reward_scale", C.c_double)]
+
+
+class gs_rollout_q(C.Structure):
+    _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("installed", C.c_int32), ("rows_per_tile", C.c_int32),
+                ("q", (C.c_void_p * 2) * 2), ("q_min", C.c_void_p * 2), ("q_adv", C.c_void_p), ("td_target", C.c_void_p)]
+
+
+class gs_rollout_q_host(C.Structure):
+    _fields_ = [("q", (_dp * 2) * 2), ("q_min", _dp * 2), ("q_adv", _dp), ("td_target", _dp)]
+
+
+Q_SOURCES = ("online", "target")      # the first index of gs_rollout_q.q and of q_min
+
+
+def q_which(which) -> int:
+    """0 or 1 from a twin's number or its name in ``Q_NETS``."""
+    if which in Q_NETS:
+        return Q_NETS.index(which)
+    if isinstance(which, (int, np.integer)) and not isinstance(which, bool) and 0 <= int(which) <= 1:
+        return int(which)
+    raise ValueError(f"Q network: which = {which!r} must be 0, 1 or one of {Q_NETS}")
+
+
 # the federation (include/gridstep.h "the federation"): the structs of gs_fed_*
 GS_FED_MAX_CLIENTS = 32
 _FED = C.c_void_p
@@ -338,7 +371,8 @@ class gs_fed_stats_out(C.Structure):
 
 
 def learner_net(net) -> int:
-    """The GS_LEARNER_* number of ``net``: "policy", "value", a cost channel's name (``COST_CHANNELS``) or the number itself."""
+    """The GS_LEARNER_* number of ``net``: "policy", "value", a cost channel's name (``COST_CHANNELS``), a twin Q network's name
+    (``Q_NETS``), or the number itself for the policy and the state critics (the Q networks go by name)."""
     if isinstance(net, (int, np.integer)) and not isinstance(net, bool):
         if not 0 <= int(net) < 2 + len(COST_CHANNELS):
             raise ValueError(f"learner: net {int(net)} outside 0 .. {1 + len(COST_CHANNELS)}")
@@ -349,7 +383,16 @@ def learner_net(net) -> int:
         return GS_LEARNER_VALUE
     if net in COST_CHANNELS:
         return GS_LEARNER_COST_VALUE + COST_CHANNELS.index(net)
-    raise ValueError(f"learner: unknown network {net!r}; 'policy', 'value' or one of {COST_CHANNELS}")
+    if net in Q_NETS:
+        return GS_LEARNER_Q + Q_NETS.index(net)
+    raise ValueError(f"learner: unknown network {net!r}; 'policy', 'value' or one of {COST_CHANNELS + Q_NETS}")
+
+
+def _net_number(net) -> int:
+    """``learner_net`` for the ``Handle``'s methods, which also take the numbers ``learner_net`` gave for the Q networks' names"""
+    if isinstance(net, (int, np.integer)) and not isinstance(net, bool) and GS_LEARNER_Q <= int(net) < GS_LEARNER_Q + len(Q_NETS):
+        return int(net)
+    return learner_net(net)
 
 
 def learner_config(lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=0.2, ent_coef=0.0, max_grad_norm=0.0,
@@ -457,6 +500,15 @@ SYMBOLS = [
     ("gs_learner_view", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_view_out), C.c_void_p]),
     ("gs_learner_set_loss", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_loss)]),
     ("gs_learner_get_loss", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_loss)]),
+    ("gs_q_mlp_check", C.c_int, [C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts), C.c_int32, C.c_int32]),
+    ("gs_q_mlp_set", C.c_int, [_H, C.c_int32, C.POINTER(gs_policy_mlp), C.POINTER(gs_policy_mlp_opts)]),
+    ("gs_rollout_evaluate_q", C.c_int, [_H, C.POINTER(gs_q_eval_config)]),
+    ("gs_rollout_q_view", C.c_int, [_H, C.POINTER(gs_rollout_q), C.c_void_p]),
+    ("gs_rollout_q_download", C.c_int, [_H, C.POINTER(gs_rollout_q_host)]),
+    ("gs_learner_set_signal", C.c_int, [_H, C.c_int32, C.c_int32]),
+    ("gs_learner_get_signal", C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32)]),
+    ("gs_q_target_update", C.c_int, [_H, C.c_double]),
+    ("gs_q_target_download", C.c_int, [_H, C.c_int32, C.c_void_p]),
     ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
     ("gs_fed_destroy", C.c_int, [_FED]),
     ("gs_fed_info", C.c_int, [_FED, C.POINTER(gs_fed_info_out)]),
@@ -748,6 +800,11 @@ def policy_opts(compute="float64", obs_shift=None, obs_scale=None, struct_size=N
 def policy_check_opts(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int, action_dim: int) -> Tuple[int, str]:
     """gs_policy_mlp_check_opts: (return code, message) -- the rules of gs_policy_mlp and its options on the host alone."""
     return _host_check("gs_policy_mlp_check_opts", C.byref(p), None if o is None else C.byref(o), int(obs_dim), int(action_dim))
+
+
+def q_check(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int, action_dim: int) -> Tuple[int, str]:
+    """(return code, message) of gs_q_mlp_check: the rules of ``gs_q_mlp_set`` on the host alone."""
+    return _host_check("gs_q_mlp_check", C.byref(p), None if o is None else C.byref(o), int(obs_dim), int(action_dim))
 
 
 def value_check(p: gs_policy_mlp, o: Optional[gs_policy_mlp_opts], obs_dim: int) -> Tuple[int, str]:
@@ -1522,7 +1579,7 @@ class Handle:
     # -- the learner (gs_learner_*) ----------------------------------------------------------------------------------------------
     def learner_create(self, net, cfg: gs_learner_config) -> None:
         """gs_learner_create: the installed network ``net`` (``learner_net``) becomes trainable; Adam starts from zero."""
-        self._check(self._lib.gs_learner_create(self._h, learner_net(net), C.byref(cfg)))
+        self._check(self._lib.gs_learner_create(self._h, _net_number(net), C.byref(cfg)))
 
     def learner_step(self, net, batch: dict, n: Optional[int] = None, stream=None) -> None:
         """gs_learner_step (asynchronous): one update of ``net`` on ``batch``, a dict of ``onpolicy_batch``'s (device arrays or
@@ -1538,12 +1595,12 @@ class Handle:
         if n is None:
             obs = batch.get("observations")
             n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
-        self._check(self._lib.gs_learner_step(self._h, learner_net(net), C.byref(b), int(n), _stream_arg(stream)))
+        self._check(self._lib.gs_learner_step(self._h, _net_number(net), C.byref(b), int(n), _stream_arg(stream)))
 
     def learner_stats(self, net) -> dict:
         """gs_learner_stats: the last step's ``LEARNER_STATS`` as floats (waits for the step); ``step`` an int."""
         o = gs_learner_stats_out()
-        self._check(self._lib.gs_learner_stats(self._h, learner_net(net), C.byref(o)))
+        self._check(self._lib.gs_learner_stats(self._h, _net_number(net), C.byref(o)))
         out = {k: float(getattr(o, k)) for k in LEARNER_STATS}
         out["step"] = int(o.step)
         return out
@@ -1551,7 +1608,7 @@ class Handle:
     def learner_info(self, net) -> dict:
         """gs_learner_info: ``dims`` (the layers' widths), ``activation`` (its name), ``param_count``, ``step``, ``rows_per_segment``."""
         o = gs_learner_info_out()
-        self._check(self._lib.gs_learner_info(self._h, learner_net(net), C.byref(o)))
+        self._check(self._lib.gs_learner_info(self._h, _net_number(net), C.byref(o)))
         names = {v: k for k, v in ACTIVATION.items()}
         return dict(dims=[int(o.dims[l]) for l in range(o.n_layers + 1)], activation=names[int(o.activation)], param_count=int(o.param_count),
                     step=int(o.step), rows_per_segment=int(o.rows_per_segment))
@@ -1564,13 +1621,13 @@ class Handle:
         if unknown:
             raise PowerFlowError(f"learner_download: unknown array(s) {sorted(unknown)}")
         ptr = lambda k: out[k].ctypes.data if k in out else None
-        self._check(self._lib.gs_learner_download(self._h, learner_net(net), ptr("params"), ptr("grads"), ptr("m"), ptr("v")))
+        self._check(self._lib.gs_learner_download(self._h, _net_number(net), ptr("params"), ptr("grads"), ptr("m"), ptr("v")))
         return out
 
     def learner_view(self, net, stream=None) -> dict:
         """gs_learner_view: the last step's per-sample arrays as zero-copy ``DeviceArray`` views (None where ``net`` has none)."""
         o = gs_learner_view_out()
-        self._check(self._lib.gs_learner_view(self._h, learner_net(net), C.byref(o), _stream_arg(stream)))
+        self._check(self._lib.gs_learner_view(self._h, _net_number(net), C.byref(o), _stream_arg(stream)))
         n = int(o.n)
         arr = lambda p, ts: DeviceArray(p, (n,), ts) if p else None
         return dict(log_probs_new=arr(o.log_probs_new, "<f8"), ratio=arr(o.ratio, "<f8"), clipped=arr(o.clipped, "<i4"),
@@ -1578,14 +1635,87 @@ class Handle:
 
     def learner_set_loss(self, net, loss: gs_learner_loss) -> None:
         """gs_learner_set_loss: ``loss`` (``learner_loss``) applies from the next step of ``net``; Adam's state stays."""
-        self._check(self._lib.gs_learner_set_loss(self._h, learner_net(net), C.byref(loss)))
+        self._check(self._lib.gs_learner_set_loss(self._h, _net_number(net), C.byref(loss)))
 
     def learner_get_loss(self, net) -> dict:
         """gs_learner_get_loss: ``kind`` (a name of ``LOSS_KINDS``), ``temperature``, ``weight_max`` and ``expectile`` in force."""
         o = gs_learner_loss()
-        self._check(self._lib.gs_learner_get_loss(self._h, learner_net(net), C.byref(o)))
+        self._check(self._lib.gs_learner_get_loss(self._h, _net_number(net), C.byref(o)))
         names = {v: k for k, v in LOSS_KINDS.items()}
         return dict(kind=names[int(o.kind)], temperature=float(o.temperature), weight_max=float(o.weight_max), expectile=float(o.expectile))
+
+    # -- state-action critics (gs_q_*, gs_rollout_*_q, gs_learner_*_signal) ---------------------------------------------------------
+    def set_q(self, which, p: Optional[gs_policy_mlp], opts: Optional[gs_policy_mlp_opts] = None) -> None:
+        """gs_q_mlp_set: install (a copy of) twin ``which`` (0 / 1 / "q1" / "q2") and its target image; None removes it."""
+        self._check(self._lib.gs_q_mlp_set(self._h, q_which(which), None if p is None else C.byref(p), None if opts is None else C.byref(opts)))
+
+    def rollout_evaluate_q(self, gamma: float = 0.99, bootstrap_mask: int = 0, reward_shift: float = 0.0, reward_scale: float = 1.0,
+                           struct_size=None) -> None:
+        """gs_rollout_evaluate_q (asynchronous): the twins' values under both images, their minimum, q_adv and td_target."""
+        cfg = gs_q_eval_config(C.sizeof(gs_q_eval_config) if struct_size is None else int(struct_size), int(bootstrap_mask), float(gamma),
+                               float(reward_shift), float(reward_scale))
+        self._check(self._lib.gs_rollout_evaluate_q(self._h, C.byref(cfg)))
+
+    def rollout_q_arrays(self, stream=None) -> dict:
+        """gs_rollout_q_view as zero-copy ``DeviceArray`` views, [T, B] float64 each: ``q`` {"online" / "target": [twin 0, twin 1]}
+        (None for a twin that is not installed), ``q_min`` {"online" / "target"}, ``q_adv``, ``td_target``; plus ``installed`` (a
+        tuple of the installed twins' numbers) and ``rows_per_tile``.  Valid until the next rollout."""
+        v = gs_rollout_q()
+        self._check(self._lib.gs_rollout_q_view(self._h, C.byref(v), _stream_arg(stream)))
+        T, B = int(v.T), int(v.B)
+        arr = lambda p: DeviceArray(p, (T, B), "<f8") if p else None
+        return dict(q={name: [arr(v.q[s][w]) for w in range(2)] for s, name in enumerate(Q_SOURCES)},
+                    q_min={name: arr(v.q_min[s]) for s, name in enumerate(Q_SOURCES)}, q_adv=arr(v.q_adv), td_target=arr(v.td_target),
+                    installed=tuple(w for w in range(2) if v.installed >> w & 1), rows_per_tile=int(v.rows_per_tile))
+
+    def rollout_q_download(self, want=("q", "q_min", "q_adv", "td_target")) -> dict:
+        """gs_rollout_q_download: host copies [T, B] of what ``want`` names -- ``q`` and ``q_min`` as dicts like ``rollout_q_arrays``'s
+        (``q`` holds both twins' arrays; a twin that is not installed is left as NaN)."""
+        T, B = getattr(self, "_rollout_T", 0), self.B
+        unknown = set(want) - {"q", "q_min", "q_adv", "td_target"}
+        if unknown:
+            raise PowerFlowError(f"rollout_q_download: unknown array(s) {sorted(unknown)}")
+        o = gs_rollout_q_host()
+        out: dict = {}
+        if "q" in want:
+            out["q"] = {name: [np.full((T, B), np.nan) for _ in range(2)] for name in Q_SOURCES}
+            for s, name in enumerate(Q_SOURCES):
+                for w in range(2):
+                    o.q[s][w] = _ptr(out["q"][name][w], _dp)
+        if "q_min" in want:
+            out["q_min"] = {name: np.empty((T, B)) for name in Q_SOURCES}
+            for s, name in enumerate(Q_SOURCES):
+                o.q_min[s] = _ptr(out["q_min"][name], _dp)
+        for k in ("q_adv", "td_target"):
+            if k in want:
+                out[k] = np.empty((T, B))
+                setattr(o, k, _ptr(out[k], _dp))
+        self._check(self._lib.gs_rollout_q_download(self._h, C.byref(o)))
+        return out
+
+    def learner_set_signal(self, net, signal) -> None:
+        """gs_learner_set_signal: "batch" or "q" (``SIGNALS``, or the number) from the next step of ``net``."""
+        if isinstance(signal, str):
+            if signal not in SIGNALS:
+                raise ValueError(f"learner signal: unknown signal {signal!r}; one of {sorted(SIGNALS)}")
+            signal = SIGNALS[signal]
+        self._check(self._lib.gs_learner_set_signal(self._h, _net_number(net), int(signal)))
+
+    def learner_get_signal(self, net) -> str:
+        """gs_learner_get_signal: the name of the signal in force."""
+        o = C.c_int32(0)
+        self._check(self._lib.gs_learner_get_signal(self._h, _net_number(net), C.byref(o)))
+        return {v: k for k, v in SIGNALS.items()}[int(o.value)]
+
+    def q_target_update(self, tau: float = 0.005) -> None:
+        """gs_q_target_update (asynchronous): every installed twin's target image moves by ``tau`` towards its online image."""
+        self._check(self._lib.gs_q_target_update(self._h, float(tau)))
+
+    def q_target_download(self, which, param_count: int) -> np.ndarray:
+        """gs_q_target_download: the target's parameters, float32 [param_count], flat in torch order."""
+        out = np.empty(int(param_count), dtype=np.float32)
+        self._check(self._lib.gs_q_target_download(self._h, q_which(which), out.ctypes.data))
+        return out
 
     def rollout_device_view(self) -> gs_rollout_device:
         """Device pointers of the last rollout (gs_rollout_device_view) for a consumer that stays on the GPU."""

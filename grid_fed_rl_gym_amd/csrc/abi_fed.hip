@@ -33,11 +33,14 @@ struct GS_HIDDEN gs_fed {
 namespace {
 
 const char* net_name(int net) {
-  static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2"};
+  static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2",
+                                 "Q network 0", "Q network 1"};
   return names[net];
 }
 
-const std::vector<double>& norm_of(const gs_handle* h, int net) { return net == GS_LEARNER_POLICY ? h->pol.h_norm : h->critic[net - 1].net.h_norm; }
+const std::vector<double>& norm_of(const gs_handle* h, int net) {
+  return net == GS_LEARNER_POLICY ? h->pol.h_norm : net >= GS_LEARNER_Q ? h->qnet[net - GS_LEARNER_Q].net.h_norm : h->critic[net - 1].net.h_norm;
+}
 
 GsFedClient client_of(gs_handle::Learner& L) {
   GsFedClient c{};
@@ -161,7 +164,7 @@ int gs_fed_create(gs_handle* const* clients, int32_t n_clients, int32_t net, gs_
   if (!clients || !out) return fail(nullptr, GS_E_INVALID, "gs_fed_create: clients / out is NULL");
   *out = nullptr;
   if (n_clients < 1 || n_clients > GS_FED_MAX_CLIENTS) return fail(nullptr, GS_E_INVALID, "gs_fed_create: %d clients outside 1 .. %d", n_clients, (int)GS_FED_MAX_CLIENTS);
-  if (net < 0 || net >= 2 + GS_COST_CHANNELS) return fail(nullptr, GS_E_INVALID, "gs_fed_create: unknown net %d", net);
+  if (net < 0 || net >= GS_LEARNER_COUNT) return fail(nullptr, GS_E_INVALID, "gs_fed_create: unknown net %d", net);
   for (int k = 0; k < n_clients; ++k) {
     if (!clients[k]) return fail(nullptr, GS_E_INVALID, "gs_fed_create: client %d is NULL", k);
     for (int i = 0; i < k; ++i)

@@ -1,7 +1,8 @@
 // abi_learner.hip -- the learner (include/gridstep.h "the learner"): gs_learner_create snapshots an installed
 // network into master parameters, gs_learner_step queues one update on the minibatch gs_onpolicy_batch left (the kernels of
 // kernels_train.hip; with gs_learner_set_loss the head and its statistics are those of kernels_train_offline.hip, DESIGN.md section
-// 21), gs_learner_stats / _info / _download / _view read what it left.  The learners' buffers are made here and
+// 21; a Q learner's input rows and targets, and the heads' Q-based signals of gs_learner_set_signal, are gathered first by
+// gs_k_q_gather of kernels_q.hip, section 22), gs_learner_stats / _info / _download / _view read what it left.  The learners' buffers are made here and
 // released here: parameters with the learner (learner_drop), what is sized by n with the rollout's buffers (learner_scratch_release).
 #include <cmath>
 #include <cstring>
@@ -28,16 +29,16 @@ void learner_drop(gs_handle* h, int k) {
   L.params.release(); L.grad.release(); L.m.release(); L.v.release(); L.wt.release(); L.stats.release(); L.blocksum.release();
   learner_scratch_release_one(L);
   if (L.ev) { (void)hipEventDestroy(L.ev); L.ev = nullptr; }
-  L.live = false; L.steps = 0; L.loss = gs_learner_loss{};
+  L.live = false; L.steps = 0; L.loss = gs_learner_loss{}; L.signal = GS_SIGNAL_BATCH;
 }
 
 void learner_scratch_release(gs_handle* h) {
   for (gs_handle::Learner& L : h->learner) learner_scratch_release_one(L);
-  h->tr.acts.release(); h->tr.deltas.release(); h->tr.partial.release();
+  h->tr.acts.release(); h->tr.deltas.release(); h->tr.partial.release(); h->tr.qsa.release(); h->tr.qy.release();
 }
 
 void learner_release(gs_handle* h) {
-  for (int k = 0; k < 2 + GS_COST_CHANNELS; ++k) learner_drop(h, k);
+  for (int k = 0; k < GS_LEARNER_COUNT; ++k) learner_drop(h, k);
   learner_scratch_release(h);
 }
 
@@ -46,11 +47,13 @@ void learner_release(gs_handle* h) {
 namespace {
 
 const char* net_name(int net) {
-  static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2"};
+  static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2",
+                                 "Q network 0", "Q network 1"};
   return names[net];
 }
 
-bool net_ok(int net) { return net >= 0 && net < 2 + GS_COST_CHANNELS; }
+bool net_ok(int net) { return net >= 0 && net < GS_LEARNER_COUNT; }
+bool net_is_q(int net) { return net >= GS_LEARNER_Q; }
 
 // the installed network `net` trains: its layers, widths, activation and host normalisation; false: not installed
 struct Installed { const GsPolicyLayerF32* L; const int32_t* dims; int n_layers, activation; const std::vector<double>* norm; const DevBuf<char>* blob; };
@@ -61,7 +64,7 @@ bool installed(gs_handle* h, int net, Installed& I) {
     I = Installed{p.args32.L, p.dims, p.args32.n_layers, p.args32.activation, &p.h_norm, &p.blob};
     return true;
   }
-  const gs_handle::Value& v = h->critic[net - 1].net;
+  const gs_handle::Value& v = net_is_q(net) ? h->qnet[net - GS_LEARNER_Q].net : h->critic[net - 1].net;
   if (!v.set) return false;
   I = Installed{v.args.L, v.dims, v.args.n_layers, v.args.activation, &v.h_norm, &v.blob};
   return true;
@@ -136,6 +139,7 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
   HIPCHK(h, hipMemset(Ln.v, 0, (size_t)P * sizeof(float)));
   HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_train_forward, hipFuncAttributeMaxDynamicSharedMemorySize, GS_TR_LDS_MAX));
   Ln.cfg = *cfg; Ln.steps = 0; Ln.n_last = 0; Ln.loss = gs_learner_loss{};      // (GS_LOSS_DEFAULT)
+  Ln.signal = GS_SIGNAL_BATCH;
   Ln.gen += 1;             // (a federation created on the learner before this one refuses it: abi_fed.hip)
   Ln.live = true;
   return GS_OK;
@@ -159,12 +163,16 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
     if (memcmp(&shift, &(*I.norm)[c], sizeof(double)) || memcmp(&scale, &(*I.norm)[D16 + c], sizeof(double)))
       return fail(h, GS_E_STATE, "gs_learner_step: the minibatches' obs_shift / obs_scale differ from the normalisation of %s (column %d)", net_name(net), c);
   }
-  const bool policy = net == GS_LEARNER_POLICY;
-  const void* target = policy ? batch->advantages : net == GS_LEARNER_VALUE ? batch->returns : batch->cost_returns[net - GS_LEARNER_COST_VALUE];
+  const bool policy = net == GS_LEARNER_POLICY, qnet = net_is_q(net);
+  // what the head regresses on or weights with: a field of the batch, or (a Q learner, GS_SIGNAL_Q) an array of gs_rollout_evaluate_q
+  // gathered through the indices into tr.qy
+  const bool gathered = qnet || Ln.signal == GS_SIGNAL_Q;
+  const void* target = gathered ? nullptr : policy ? batch->advantages : net == GS_LEARNER_VALUE ? batch->returns : batch->cost_returns[net - GS_LEARNER_COST_VALUE];
+  if (gathered && !q_current(h)) return fail(h, GS_E_STATE, "gs_learner_step: gs_rollout_evaluate_q has not run on the last rollout (%s reads its arrays)", net_name(net));
   const int loss = Ln.loss.kind;
   if (policy && loss == GS_LOSS_DEFAULT && !ro.logp_recorded) return fail(h, GS_E_STATE, "gs_learner_step: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
-  if (!batch->observations || !target || (policy && !batch->indices))
-    return fail(h, GS_E_INVALID, "gs_learner_step: the batch lacks %s", !batch->observations ? "observations" : !target ? (policy ? "advantages" : "returns") : "indices");
+  if (!batch->observations || (!gathered && !target) || ((policy || gathered) && !batch->indices))
+    return fail(h, GS_E_INVALID, "gs_learner_step: the batch lacks %s", !batch->observations ? "observations" : (!gathered && !target) ? (policy ? "advantages" : "returns") : "indices");
   GS_ENTER(h);
   int rc = GS_OK;
   const GsTrainNet& N = Ln.net;
@@ -180,12 +188,27 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
     if ((rc = Ln.ratio.grow(h, (size_t)n, "the learner's ratios"))) return rc;
     if ((rc = Ln.clipped.grow(h, (size_t)n, "the learner's clip flags"))) return rc;
   }
+  const int Din = qnet ? D + h->action_dim : D;      // the width of an input row
+  if (gathered && (rc = tr.qy.grow(h, (size_t)n, "the learner's gathered targets"))) return rc;
+  if (qnet && (rc = tr.qsa.grow(h, (size_t)n * Din, "the Q learner's input rows"))) return rc;
   Ln.n_last = 0;           // (until every launch is queued)
   const int last = N.n_layers - 1, tiles = (n + GS_TR_ROWS - 1) / GS_TR_ROWS;
   const gs_learner_config& cfg = Ln.cfg;
 
+  if (gathered) {
+    const size_t cap = (size_t)ro.T_cap * h->B;
+    GsQGatherArgs Q{};
+    Q.idx = batch->indices; Q.y = tr.qy; Q.N = ob.N; Q.n = n;
+    Q.src = qnet ? h->qt.td.p : policy ? h->qt.q_adv.p : h->qt.q_min.p + cap;      // td_target; q_adv; q_min[target]
+    if (qnet) { Q.obs = (const float*)batch->observations; Q.act = ro.act; Q.sa = tr.qsa; Q.D = D; Q.DA = Din; }
+    const long long total = (long long)n * (qnet ? Din : 1);
+    hipLaunchKernelGGL(gs_k_q_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, Q);
+    HIPCHK(h, hipGetLastError());
+    target = tr.qy.p;
+  }
+
   GsTrainFwdArgs F{};
-  F.N = N; F.obs = (const float*)batch->observations; F.acts = tr.acts; F.n = n; F.D = D;
+  F.N = N; F.obs = qnet ? tr.qsa.p : (const float*)batch->observations; F.acts = tr.acts; F.n = n; F.D = Din;
   F.obs_stride = gs_val_obs_stride(N.L[0].kb); F.panel_kb = gs_val_panel_kb(N.L[0].kb);
   hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(N.L[0].kb), h->stream, F);
   HIPCHK(h, hipGetLastError());
@@ -226,7 +249,7 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   }
 
   GsTrainGradArgs G{};
-  G.N = N; G.obs = F.obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
+  G.N = N; G.obs = F.obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = Din;
   const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
   int blocks = 0;
   for (int l = 0; l <= last; ++l) {
@@ -344,6 +367,28 @@ int gs_learner_set_loss(gs_handle* h, int32_t net, const gs_learner_loss* loss) 
   gs_handle::Learner& Ln = h->learner[net];
   if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_set_loss: no learner for %s", net_name(net));
   Ln.loss = *loss;        // (a queued step took its arguments by value: it keeps the loss it was queued with)
+  return GS_OK;
+}
+
+// ---- the signal of the policy's and the reward critic's heads (include/gridstep.h "state-action critics"): host state, as the loss ----
+int gs_learner_set_signal(gs_handle* h, int32_t net, int32_t signal) {
+  if (!h) return fail(nullptr, GS_E_INVALID, "handle is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_set_signal: unknown net %d", net);
+  if (signal != GS_SIGNAL_BATCH && signal != GS_SIGNAL_Q) return fail(h, GS_E_INVALID, "gs_learner_set_signal: unknown signal %d", signal);
+  if (signal == GS_SIGNAL_Q && net != GS_LEARNER_POLICY && net != GS_LEARNER_VALUE)
+    return fail(h, GS_E_INVALID, "gs_learner_set_signal: GS_SIGNAL_Q is the policy's and the value network's, not %s's", net_name(net));
+  gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_set_signal: no learner for %s", net_name(net));
+  Ln.signal = signal;     // (a queued step took its pointers by value: it keeps the signal it was queued with)
+  return GS_OK;
+}
+
+int gs_learner_get_signal(gs_handle* h, int32_t net, int32_t* signal) {
+  if (!h || !signal) return fail(h, GS_E_INVALID, "handle / signal is NULL");
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_get_signal: unknown net %d", net);
+  const gs_handle::Learner& Ln = h->learner[net];
+  if (!Ln.live) return fail(h, GS_E_STATE, "gs_learner_get_signal: no learner for %s", net_name(net));
+  *signal = Ln.signal;
   return GS_OK;
 }
 

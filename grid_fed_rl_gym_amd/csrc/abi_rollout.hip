@@ -37,6 +37,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   if (!keep_term_count) ro.term_count.release();
   onpolicy_release(h);           // (sized by T as well)
   costs_release(h);
+  q_rollout_release(h);
   episodes_release(h, keep_term_count);      // (the list is sized by the capacity; the carries outlive a longer rollout)
   batches_release(h);
   learner_scratch_release(h);

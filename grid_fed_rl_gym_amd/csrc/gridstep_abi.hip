@@ -590,6 +590,7 @@ void gs_destroy(gs_handle* h) {
   learner_release(h);
   policy_release(h);
   value_release(h);
+  q_release(h);
   rollout_release(h);
   dataset_release(h);
   if (h->h_pin) (void)hipHostFree(h->h_pin);

@@ -20,9 +20,13 @@
 #include "plan.h"
 #include "policy.h"
 #include "train.h"
+#include "q.h"
 
 // (also on the handle's parts that own a DevBuf and on gs_checks: their destructors are not part of the library's surface)
 #define GS_HIDDEN __attribute__((visibility("hidden")))
+
+constexpr int GS_LEARNER_COUNT = 2 + GS_COST_CHANNELS + 2;      // the policy, the reward critic, the cost critics, the twin Q networks
+static_assert(GS_LEARNER_Q == 2 + GS_COST_CHANNELS, "the Q learners follow the cost critics'");
 
 struct GsLoopComm;      // abi_comm.hip
 struct gs_handle;
@@ -186,8 +190,17 @@ struct gs_handle : GsPlan {
     DevBuf<float> params, grad, m, v, wt;
     DevBuf<double> lp_new, ratio, term0, term1, stats, blocksum; DevBuf<int32_t> clipped; int n_last = 0;
     hipEvent_t ev = nullptr;
-  } learner[2 + GS_COST_CHANNELS];
-  struct GS_HIDDEN TrainScratch { DevBuf<float> acts, deltas, partial; } tr;
+    int signal = GS_SIGNAL_BATCH;      // gs_learner_set_signal; reset like `loss`
+  } learner[GS_LEARNER_COUNT];
+  // (qsa [n][obs_dim + A], qy [n]: the Q learner's input rows and targets, and the Q-based signals; abi_learner.hip)
+  struct GS_HIDDEN TrainScratch { DevBuf<float> acts, deltas, partial, qsa, qy; } tr;
+  // gs_q_* (abi_q.hip).  qnet[which]: a twin -- the network (blob = the ONLINE image and the normalisation; args
+  // unused but for L, n_layers and activation), its target image (image_floats floats, laid out as the online one: TL points into
+  // it) and the argument block of gs_k_q_mlp_f32 on the online image.  learner[GS_LEARNER_Q + which] trains it.
+  struct GS_HIDDEN QNet { Value net; DevBuf<float> target; size_t image_floats = 0; GsPolicyLayerF32 TL[GS_POLICY_MAX_LAYERS] = {}; GsQArgs qargs{}; } qnet[2];
+  // what gs_rollout_evaluate_q made of the last rollout: q [src][which][T_cap][B], q_min [src][T_cap][B], q_adv, td [T_cap][B]; made
+  // on first use (all or none), released with the rollout's buffers; evaluated_on = ro.calls of the rollout they belong to, 0 = none
+  struct GS_HIDDEN QTrack { DevBuf<double> q, q_min, q_adv, td; uint64_t evaluated_on = 0; hipEvent_t ev = nullptr; } qt;
   // gs_fed_* (abi_fed.hip): the federations this handle is a client of; gs_destroy detaches them (fed_detach)
   std::vector<gs_fed*> feds;
   // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count
@@ -390,11 +403,16 @@ void episodes_release(gs_handle* h, bool keep_carries = false);
 // ---- owner of the on-policy minibatch buffers (abi_batches.hip) ----
 void batches_release(gs_handle* h);
 
-// ---- owner of the learners (abi_learner.hip).  learner_drop: learner `k` (0 the policy's, 1 + c critic c's) ends, its parameters go
+// ---- owner of the learners (abi_learner.hip).  learner_drop: learner `k` (0 the policy's, 1 + c critic c's, GS_LEARNER_Q + w twin w's) ends, its parameters go
 // (every *_set* entry calls it for its network); learner_scratch_release: what is sized by n; learner_release: everything ----
 void learner_drop(gs_handle* h, int k);
 void learner_scratch_release(gs_handle* h);
 void learner_release(gs_handle* h);
+
+// ---- owner of the Q networks, their targets and their arrays over the rollout (abi_q.hip) ----
+void q_release(gs_handle* h);              // everything
+void q_rollout_release(gs_handle* h);      // what is sized by the rollout's capacity
+static inline bool q_current(const gs_handle* h) { return h->qt.evaluated_on && h->qt.evaluated_on == h->ro.calls; }
 
 // ---- the federations of a handle that is being destroyed lose it (abi_fed.hip) ----
 void fed_detach(gs_handle* h);

@@ -8,6 +8,7 @@
 #include "members.h"
 #include "policy.h"
 #include "train.h"
+#include "q.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -73,6 +74,11 @@ __global__ void gs_k_train_adam(GsTrainAdamArgs A);
 __global__ void gs_k_train_head_awr(GsTrainAwrHeadArgs H);
 __global__ void gs_k_train_head_expectile(GsTrainExpectileArgs H);
 __global__ void gs_k_train_stats_awr(GsTrainAwrStatArgs S);
+__global__ void gs_k_q_mlp_f32(GsQArgs P);
+__global__ void gs_k_q_combine(GsQCombineArgs C);
+__global__ void gs_k_q_td(GsQTdArgs G);
+__global__ void gs_k_q_gather(GsQGatherArgs G);
+__global__ void gs_k_q_polyak(GsQPolyakArgs A);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

@@ -341,6 +341,20 @@ class BatchedGridEnvironment:
         self._h.set_cost_value(c, p, opts)  # (raises, and leaves the installed critic in place, if the library refuses it)
         self._installed_nets()[c] = dict(obs_mean=value.obs_mean, obs_std=value.obs_std)
 
+    def set_q(self, which, q: Optional[Any]) -> None:
+        """Install an ``MLPQ`` as twin ``which`` (0 / 1 or "q1" / "q2"; gs_q_mlp_set) for ``evaluate_rollout_q`` and the Q learners;
+        the device also keeps a second copy of its image, the target network (``DeviceLearner.update_targets``).  None removes it.  Not
+        environment state."""
+        w = _lib.q_which(which)
+        if q is None:
+            self._h.set_q(w, None)
+            self._installed_nets().pop(_lib.Q_NETS[w], None)
+            return
+        p, keep = q.to_struct()
+        opts, keep_opts = q.to_opts()
+        self._h.set_q(w, p, opts)           # (raises, and leaves the installed network in place, if the library refuses it)
+        self._installed_nets()[_lib.Q_NETS[w]] = dict(obs_mean=q.obs_mean, obs_std=q.obs_std, obs_dim=q.obs_dim)
+
     def value_estimates(self) -> np.ndarray:
         """The installed value network's estimates [num_envs] on the observation the environment stands at (gs_value_mlp_eval)."""
         if self._needs_reset:

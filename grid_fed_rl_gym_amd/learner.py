@@ -14,7 +14,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .policy import HALF_LOG_2PI, LOG_STD_MAX, LOG_STD_MIN, MLPPolicy, MLPValue
+from .policy import HALF_LOG_2PI, LOG_STD_MAX, LOG_STD_MIN, MLPPolicy, MLPQ, MLPValue
 
 HALF_LOG_2PIE = HALF_LOG_2PI + 0.5      # 0.5 * log(2 pi e): a unit Gaussian's entropy
 
@@ -246,6 +246,13 @@ class DeviceLearner:
     "expectile" (IQL's value loss at ``expectile``), for every critic named.  Creating the learner snapshots each network's installed weights as float32 master parameters and
     zeroes Adam's state; installing a network again ends its learner (create a new ``DeviceLearner``).
 
+    State-action critics: "q1" and "q2" name the twin Q networks of ``env.set_q``; their step regresses
+    Q(s, a) on the one-step TD target of the last ``evaluate_rollout_q`` (``q_loss``: "mse" or "expectile") over the batch's
+    observations and, through its indices, the rollout's stored actions.  ``advantage_source="q"``: the policy's head weights with
+    ``q_adv = min(Q1, Q2) - V`` of that evaluation instead of the batch's advantages; ``value_target="q"``: the reward critic
+    regresses on the target networks' ``min(Q1, Q2)`` instead of the batch's returns -- with ``policy_loss="awr"`` and
+    ``value_loss="expectile"`` that is IQL.  ``update_targets(tau)`` moves the target networks.
+
     ``step(batch)``: one ``gs_learner_step`` per network on a dict of ``OnPolicyBatches.epoch`` (prepared with float32 and the
     networks' own observation normalisation).  After a step the ``MLPPolicy`` / ``MLPValue`` objects the networks were installed
     from no longer describe them: ``policy()`` / ``value(net)`` rebuild current ones from the device's parameters."""
@@ -253,7 +260,7 @@ class DeviceLearner:
     def __init__(self, env, nets: Sequence[str] = ("policy", "value"), lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0, clip: float = 0.2, ent_coef: float = 0.0, max_grad_norm: float = 0.0,
                  policy_loss: str = "ppo", temperature: float = 1.0, weight_max: float = 20.0, value_loss: str = "mse",
-                 expectile: float = 0.7) -> None:
+                 expectile: float = 0.7, q_loss: str = "mse", advantage_source: str = "batch", value_target: str = "batch") -> None:
         if isinstance(nets, str):
             nets = (nets,)
         self.nets = tuple(nets)
@@ -274,8 +281,18 @@ class DeviceLearner:
             raise ValueError(f"DeviceLearner: ent_coef = {ent_coef} must be finite")
         self._loss_struct(_lib.GS_LEARNER_POLICY, policy_loss, temperature, weight_max, expectile)      # (ValueError also for a
         self._loss_struct(_lib.GS_LEARNER_VALUE, value_loss, temperature, weight_max, expectile)        # network not in `nets`)
-        losses = {k: self._loss_struct(k, policy_loss if k == _lib.GS_LEARNER_POLICY else value_loss, temperature, weight_max, expectile)
-                  for k in self._ids}
+        self._loss_struct(_lib.GS_LEARNER_Q, q_loss, temperature, weight_max, expectile, what="q_loss")
+        losses = {k: self._loss_struct(k, policy_loss if k == _lib.GS_LEARNER_POLICY else q_loss if k >= _lib.GS_LEARNER_Q else value_loss,
+                                       temperature, weight_max, expectile) for k in self._ids}
+        signals = {}
+        for what, source, k in (("advantage_source", advantage_source, _lib.GS_LEARNER_POLICY), ("value_target", value_target, _lib.GS_LEARNER_VALUE)):
+            if source not in _lib.SIGNALS:
+                raise ValueError(f"DeviceLearner: {what} = {source!r} must be one of {sorted(_lib.SIGNALS)}")
+            if source == "q":
+                if k not in self._ids:
+                    raise ValueError(f"DeviceLearner: {what} = 'q' needs {'policy' if k == _lib.GS_LEARNER_POLICY else 'value'!r} among nets {self.nets}")
+                signals[k] = source
+        self.advantage_source, self.value_target = advantage_source, value_target
         self.env = env
         self.config = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                            clip=float(clip), ent_coef=float(ent_coef), max_grad_norm=float(max_grad_norm))
@@ -284,14 +301,16 @@ class DeviceLearner:
             env.handle.learner_create(net, cfg)
             if losses[net].kind != _lib.GS_LOSS_DEFAULT:      # (a learner left at "ppo" / "mse" never calls the entry)
                 env.handle.learner_set_loss(net, losses[net])
+            if net in signals:                                # (a learner left at "batch" never calls the entry)
+                env.handle.learner_set_signal(net, signals[net])
 
     @staticmethod
-    def _loss_struct(k: int, loss: str, temperature, weight_max, expectile) -> "_lib.gs_learner_loss":
+    def _loss_struct(k: int, loss: str, temperature, weight_max, expectile, what: Optional[str] = None) -> "_lib.gs_learner_loss":
         """The ``gs_learner_loss`` of network number ``k`` for the loss named ``loss``; ValueError for what the ABI would refuse."""
         policy = k == _lib.GS_LEARNER_POLICY
         names = ("ppo", "awr", "bc") if policy else ("mse", "expectile")
         if loss not in names:
-            raise ValueError(f"DeviceLearner: {'policy_loss' if policy else 'value_loss'} = {loss!r} must be one of {names}")
+            raise ValueError(f"DeviceLearner: {what or ('policy_loss' if policy else 'value_loss')} = {loss!r} must be one of {names}")
         if loss == "bc":
             return _lib.learner_loss("awr", math.inf, math.inf, 0.0)
         if loss == "awr":
@@ -325,7 +344,7 @@ class DeviceLearner:
         return out
 
     def _id(self, net) -> int:
-        k = _lib.learner_net(net)
+        k = _lib._net_number(net)
         if k not in self._ids:
             raise ValueError(f"DeviceLearner: {net!r} is not one of this learner's networks {self.nets}")
         return k
@@ -362,10 +381,11 @@ class DeviceLearner:
         return split_parameters(self.env.handle.learner_download(k, ("grads",))["grads"], self.env.handle.learner_info(k)["dims"])
 
     def _meta(self, k: int) -> dict:
-        key = "policy" if k == _lib.GS_LEARNER_POLICY else "value" if k == _lib.GS_LEARNER_VALUE else k - _lib.GS_LEARNER_COST_VALUE
+        key = ("policy" if k == _lib.GS_LEARNER_POLICY else "value" if k == _lib.GS_LEARNER_VALUE else _lib.Q_NETS[k - _lib.GS_LEARNER_Q]
+               if k >= _lib.GS_LEARNER_Q else k - _lib.GS_LEARNER_COST_VALUE)
         meta = self.env._installed_nets().get(key)
         if meta is None:
-            raise _lib.PowerFlowError("DeviceLearner: the network was not installed through this environment (set_policy / set_value / set_cost_value)")
+            raise _lib.PowerFlowError("DeviceLearner: the network was not installed through this environment (set_policy / set_value / set_cost_value / set_q)")
         return meta
 
     def policy(self) -> MLPPolicy:
@@ -380,11 +400,53 @@ class DeviceLearner:
     def value(self, net="value") -> MLPValue:
         """A current ``MLPValue`` of the reward critic or of a cost critic, as ``policy()``."""
         k = self._id(net)
-        if k == _lib.GS_LEARNER_POLICY:
-            raise ValueError("DeviceLearner.value: the policy is no critic (policy())")
+        if k == _lib.GS_LEARNER_POLICY or k >= _lib.GS_LEARNER_Q:
+            raise ValueError("DeviceLearner.value: a state critic is meant (policy() / q(which) for the others)")
         meta = self._meta(k)
         W, b = self.parameters(k)
         return MLPValue(W, b, activation=self.env.handle.learner_info(k)["activation"], obs_mean=meta["obs_mean"], obs_std=meta["obs_std"])
+
+    def set_signal(self, net, source: str) -> None:
+        """"batch" or "q" for the policy's advantages / the reward critic's regression target, from the next step
+        (``gs_learner_set_signal``); Adam's state stays."""
+        k = self._id(net)
+        if source not in _lib.SIGNALS:
+            raise ValueError(f"DeviceLearner.set_signal: source = {source!r} must be one of {sorted(_lib.SIGNALS)}")
+        if source == "q" and k not in (_lib.GS_LEARNER_POLICY, _lib.GS_LEARNER_VALUE):
+            raise ValueError("DeviceLearner.set_signal: 'q' is for the policy and the reward critic")
+        self.env.handle.learner_set_signal(k, source)
+        if k == _lib.GS_LEARNER_POLICY:
+            self.advantage_source = source
+        else:
+            self.value_target = source
+
+    def signal(self, net) -> str:
+        return self.env.handle.learner_get_signal(self._id(net))
+
+    def update_targets(self, tau: float = 0.005) -> None:
+        """The target networks of every installed twin move towards the online ones, ``t = tau p + (1 - tau) t`` in float32 on the
+        device (``gs_q_target_update``, asynchronous; ``polyak_np`` restates it)."""
+        tau = float(tau)
+        if not (math.isfinite(tau) and 0.0 <= tau <= 1.0):
+            raise ValueError(f"DeviceLearner.update_targets: tau = {tau} must lie in [0, 1]")
+        self.env.handle.q_target_update(tau)
+
+    def _q_object(self, k: int, flat) -> MLPQ:
+        meta = self._meta(k)
+        info = self.env.handle.learner_info(k)
+        W, b = split_parameters(flat, info["dims"])
+        return MLPQ(W, b, meta["obs_dim"], activation=info["activation"], obs_mean=meta["obs_mean"], obs_std=meta["obs_std"])
+
+    def q(self, which) -> MLPQ:
+        """A current ``MLPQ`` of twin ``which`` (0 / 1 / "q1" / "q2") from the device's master parameters, as ``policy()``."""
+        k = self._id(_lib.Q_NETS[_lib.q_which(which)])
+        return self._q_object(k, self.env.handle.learner_download(k, ("params",))["params"])
+
+    def target_q(self, which) -> MLPQ:
+        """The TARGET network of twin ``which`` as an ``MLPQ`` (``gs_q_target_download``)."""
+        w = _lib.q_which(which)
+        k = self._id(_lib.Q_NETS[w])
+        return self._q_object(k, self.env.handle.q_target_download(w, self.env.handle.learner_info(k)["param_count"]))
 
     def views(self, net="policy", stream=None) -> dict:
         """The last step's per-sample arrays as zero-copy ``DeviceArray`` views: ``log_probs_new``, ``ratio`` (float64), ``clipped``

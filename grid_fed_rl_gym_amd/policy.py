@@ -252,3 +252,97 @@ class MLPValue:
         normalised observations, float32 products, sums and activations); with ``exact`` the same rounded operands evaluated
         in float64 throughout (what the float32 result is measured against)."""
         return self._net.pre_head_np(obs, "float32", exact).astype(np.float64)[..., 0]
+
+
+class MLPQ:
+    """A state-action critic Q(s, a) for ``env.set_q`` / ``evaluate_rollout_q``: the reference's ``TwinCritic`` tower (``_build_mlp``
+    over ``cat(state, action)`` with a scalar output; algorithms/offline.py).  ``weights`` / ``biases`` as for ``MLPValue``, the first
+    layer ``obs_dim + action_dim`` wide; ``obs_mean`` / ``obs_std`` [obs_dim] normalise the OBSERVATION columns only, the action
+    columns enter as they are.  The device evaluates it on the float32 path: the observation normalised in float64 and rounded once,
+    the stored float64 action rounded once, float32 layers; the scalar is returned widened to float64."""
+
+    def __init__(self, weights: Sequence[Any], biases: Sequence[Any], obs_dim: int, activation: str = "relu", obs_mean: Optional[Any] = None,
+                 obs_std: Optional[Any] = None) -> None:
+        self._net = MLPPolicy(weights, biases, activation=activation, head="tanh", compute="float32")
+        if self._net.weights[-1].shape[0] != 1:
+            raise ValueError(f"a Q network's last layer has one output, got {self._net.weights[-1].shape[0]}")
+        self.obs_dim = int(obs_dim)
+        if not 0 < self.obs_dim < self._net.obs_dim:
+            raise ValueError(f"a Q network takes obs_dim + action_dim = {self._net.obs_dim} inputs with 0 < obs_dim, got obs_dim = {obs_dim}")
+        if (obs_mean is None) != (obs_std is None):
+            raise ValueError("obs_mean and obs_std go together")
+        self.obs_mean: Optional[np.ndarray] = None
+        self.obs_std: Optional[np.ndarray] = None
+        if obs_mean is not None:
+            self.obs_mean = np.array(obs_mean, dtype=np.float64).reshape(-1)
+            self.obs_std = np.array(obs_std, dtype=np.float64).reshape(-1)
+            if self.obs_mean.shape != (self.obs_dim,) or self.obs_std.shape != (self.obs_dim,):
+                raise ValueError(f"obs_mean / obs_std must have shape ({self.obs_dim},)")
+        self.activation = activation
+
+    @property
+    def action_dim(self) -> int:
+        return self._net.obs_dim - self.obs_dim
+
+    @property
+    def weights(self) -> List[np.ndarray]:
+        return self._net.weights
+
+    @property
+    def biases(self) -> List[np.ndarray]:
+        return self._net.biases
+
+    @classmethod
+    def from_sequential(cls, module: Any, obs_dim: Optional[int] = None, obs_mean: Optional[Any] = None, obs_std: Optional[Any] = None,
+                        activation: Optional[str] = None) -> "MLPQ":
+        """From a torch ``nn.Sequential`` of ``Linear`` and activation modules (a tower of the reference's CQL ``TwinCritic``), read as
+        ``MLPPolicy.from_sequential`` reads it; or, with ``activation`` named, from a ``ModuleList`` of ``Linear`` layers alone (a
+        tower of IQL's).  ``obs_dim``: by default the length of ``obs_mean``."""
+        if obs_dim is None:
+            if obs_mean is None:
+                raise ValueError("MLPQ.from_sequential: name obs_dim (or give obs_mean / obs_std)")
+            obs_dim = int(np.asarray(obs_mean).reshape(-1).shape[0])
+        children = list(module)
+        if activation is not None and all(hasattr(c, "weight") and hasattr(c, "bias") for c in children):
+            ws = [c.weight.detach().cpu().numpy().astype(np.float64) for c in children]
+            bs = [c.bias.detach().cpu().numpy().astype(np.float64) for c in children]
+            return cls(ws, bs, obs_dim, activation=activation, obs_mean=obs_mean, obs_std=obs_std)
+        net = MLPPolicy.from_sequential(module, head="tanh", compute="float32")
+        if activation is not None and activation != net.activation and len(net.weights) > 1:
+            raise ValueError(f"MLPQ.from_sequential: activation = {activation!r}, the module's is {net.activation!r}")
+        return cls(net.weights, net.biases, obs_dim, activation=net.activation, obs_mean=obs_mean, obs_std=obs_std)
+
+    @classmethod
+    def twins(cls, module: Any, obs_dim: Optional[int] = None, obs_mean: Optional[Any] = None, obs_std: Optional[Any] = None,
+              activation: Optional[str] = None) -> "tuple":
+        """(Q1, Q2) from a ``TwinCritic``-shaped module: its towers ``module.q1`` and ``module.q2``, each read by ``from_sequential``
+        (``activation``: by default the class of ``module.activation`` where the towers hold linear layers alone)."""
+        if activation is None and hasattr(module, "activation") and not callable(getattr(module.activation, "lower", None)):
+            activation = {"ReLU": "relu", "Tanh": "tanh", "ELU": "elu"}.get(type(module.activation).__name__)
+        only_linear = all(hasattr(c, "weight") and hasattr(c, "bias") for c in module.q1)
+        act = activation if only_linear else None
+        return tuple(cls.from_sequential(tower, obs_dim, obs_mean, obs_std, act) for tower in (module.q1, module.q2))
+
+    def to_struct(self):
+        """(gs_policy_mlp with head GS_HEAD_LINEAR, the arrays it points into)"""
+        return _lib.policy_struct(self.weights, self.biases, self.activation, _lib.GS_HEAD_LINEAR, False)
+
+    def to_opts(self):
+        """(gs_policy_mlp_opts with GS_COMPUTE_F32 and the observation columns' normalisation, the arrays it points into)"""
+        if self.obs_mean is None:
+            return _lib.policy_opts("float32")
+        return _lib.policy_opts("float32", self.obs_mean, 1.0 / self.obs_std)
+
+    def input_f32(self, obs: Any, actions: Any) -> np.ndarray:
+        """The network's float32 input rows [..., obs_dim + action_dim]: ``(obs - mean) * (1 / std)`` in float64 rounded once, then the
+        float64 actions rounded once."""
+        x = np.asarray(obs, dtype=np.float64)
+        if self.obs_mean is not None:
+            x = (x - self.obs_mean) * (1.0 / self.obs_std)
+        return np.concatenate([x.astype(np.float32), np.asarray(actions, dtype=np.float64).astype(np.float32)], axis=-1)
+
+    def forward_np(self, obs: Any, actions: Any, exact: bool = False) -> np.ndarray:
+        """Q values [...] on raw observations [..., obs_dim] and actions [..., action_dim], float64: the device contract (float32
+        products, sums and activations on the float32-rounded operands); with ``exact`` the same rounded operands evaluated in float64
+        throughout (what the float32 result is measured against)."""
+        return self._net.pre_head_np(self.input_f32(obs, actions), "float32", exact).astype(np.float64)[..., 0]

@@ -30,6 +30,7 @@ normalisation and the (Lagrangian) advantage normalised; ``permutation_np`` and 
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, Optional, Sequence, Tuple
@@ -140,6 +141,67 @@ def evaluate_rollout(env: BatchedGridEnvironment, gamma: float = 0.99, lam: floa
     h = env.handle
     h.rollout_evaluate(gamma, lam, _bootstrap_mask(bootstrap), reward_shift, reward_scale)
     return SimpleNamespace(**h.rollout_onpolicy_arrays(stream))
+
+
+def evaluate_rollout_q(env: BatchedGridEnvironment, gamma: float = 0.99, bootstrap: Sequence[str] = (), reward_shift: float = 0.0,
+                       reward_scale: float = 1.0, stream=None):
+    """The twin Q networks of ``env.set_q`` over the environment's LAST rollout, on the device (``gs_rollout_evaluate_q``; after
+    ``evaluate_rollout``, whose ``values`` and ``terminal_values`` it reads): per stored (observation, action) pair the value of
+    every installed twin under its online and its target image, their minimum, IQL's advantage ``q_adv = min(Q1, Q2) - V`` and the
+    one-step TD target ``r' + gamma * vnext`` (``vnext`` as ``gae_np`` takes it; ``bootstrap`` as ``evaluate_rollout``).  Returns an
+    object with ``q`` and ``q_min`` (dicts "online" / "target"; ``q[src]`` a list of the two twins, None where not installed),
+    ``q_adv`` and ``td_target``, all [T, B] zero-copy ``DeviceArray`` views valid until the next rollout, plus ``installed`` and
+    ``rows_per_tile``."""
+    h = env.handle
+    h.rollout_evaluate_q(gamma, _bootstrap_mask(bootstrap), reward_shift, reward_scale)
+    return SimpleNamespace(**h.rollout_q_arrays(stream))
+
+
+def q_rollout_np(q, observations, actions, exact: bool = False) -> np.ndarray:
+    """What ``gs_rollout_evaluate_q`` computes for one twin and one image: ``q`` (an ``MLPQ``) on the stored pairs ``observations``
+    [T, B, obs_dim] (raw) and ``actions`` [T, B, A] (float64), as float64 [T, B].  The device contract -- the observation normalised
+    in float64 and rounded once, the action rounded once, float32 layers; with ``exact`` the same rounded operands in float64
+    throughout (what the float32 result is measured against)."""
+    return q.forward_np(observations, actions, exact)
+
+
+def td_target_np(rewards, values, terminals, terminal_values, terminal_index, gamma: float = 0.99, bootstrap_mask: int = 0,
+                 reward_shift: float = 0.0, reward_scale: float = 1.0) -> np.ndarray:
+    """``td_target`` [T, B] of ``gs_rollout_evaluate_q`` restated in NumPy, every operation IEEE float64 in the device's order:
+    ``r' + gamma * vnext`` with the ``r'`` and ``vnext`` of ``gae_np`` (arguments as there)."""
+    rewards, values = np.asarray(rewards, dtype=np.float64), np.asarray(values, dtype=np.float64)
+    terminals = np.asarray(terminals).astype(np.uint8)
+    T, B = rewards.shape
+    term_v = np.zeros((T, B))
+    idx = np.asarray(terminal_index, dtype=np.int64).reshape(-1, 2)
+    term_v[idx[:, 0], idx[:, 1]] = np.asarray(terminal_values, dtype=np.float64)[:len(idx)]
+    done = terminals != 0
+    vnext = np.where(done, np.where((terminals & int(bootstrap_mask)) != 0, term_v, 0.0), values[1:T + 1])
+    r = (rewards - float(reward_shift)) * float(reward_scale)
+    return r + float(gamma) * vnext
+
+
+def q_combine_np(q_online, q_target, values):
+    """(q_min online, q_min target, q_adv) of ``gs_rollout_evaluate_q`` from the twins' values: ``q_online`` / ``q_target`` sequences
+    of one or two [T, B] arrays (the installed twins), ``values`` [T + 1, B] (or [T, B]).  ``fmin`` over the twins; ``q_adv`` is one
+    rounded float64 subtraction."""
+    mins = []
+    for qs in (q_online, q_target):
+        qs = [np.asarray(x, dtype=np.float64) for x in qs if x is not None]
+        mins.append(qs[0].copy() if len(qs) == 1 else np.fmin(qs[0], qs[1]))
+    T = mins[0].shape[0]
+    return mins[0], mins[1], mins[0] - np.asarray(values, dtype=np.float64)[:T]
+
+
+def polyak_np(params, target, tau: float) -> np.ndarray:
+    """The target update of ``gs_q_target_update`` in float32, operation by operation: ``(tau32 * p) + (omt32 * t)`` with
+    ``tau32 = float32(tau)`` and ``omt32 = float32(1 - tau)`` (the difference in float64, rounded once)."""
+    tau = float(tau)
+    if not (math.isfinite(tau) and 0.0 <= tau <= 1.0):
+        raise ValueError(f"tau = {tau} must lie in [0, 1]")
+    f = np.float32
+    p, t = np.asarray(params, dtype=f), np.asarray(target, dtype=f)
+    return (f(tau) * p) + (f(1.0 - tau) * t)
 
 
 def collect_onpolicy_data(env: BatchedGridEnvironment, policy, value, num_steps: int, seed: int = 0, reset: bool = True,

@@ -926,6 +926,86 @@ typedef struct gs_learner_loss {
 int gs_learner_set_loss(gs_handle* h, int32_t net, const gs_learner_loss* loss);
 int gs_learner_get_loss(gs_handle* h, int32_t net, gs_learner_loss* out);
 
+/* ---- state-action critics: twin Q networks, target networks, TD targets, Q-based signals ----
+ * The critic over concat(state, action) that the reference's value-based learners need (algorithms/offline.py: TwinCritic, IQL.update,
+ * lines 454-545), beside the policy and the state critics.  Additive to ABI 2: no struct above changes, and a handle that calls none
+ * of these entries computes what it computed before.
+ *
+ * The network.  gs_q_mlp_set(h, which, p, o) installs twin `which` (0 or 1): a gs_policy_mlp with head = GS_HEAD_LINEAR, dims[0] =
+ * obs_dim + action_dim, dims[n_layers] = 1, stochastic = 0 and o->compute = GS_COMPUTE_F32, under the layer and width limits of
+ * gs_value_mlp_set (GS_E_INVALID with a message otherwise, also for `which` outside 0 .. 1 and for action_dim = 0; the installed
+ * network stays).  o->obs_shift / obs_scale have obs_dim entries and apply to the observation columns, in float64 and rounded once
+ * as for the policy; the action columns enter as the stored float64 action rounded once to float32.  Installing packs the float32
+ * image and makes a second copy of it, the TARGET image; it drops that network's learner.  NULL removes the network.
+ * gs_q_mlp_check: the rules on the host alone.
+ *
+ * gs_rollout_evaluate_q (asynchronous, on the handle's stream, over the LAST rollout) writes float64 [T][B] arrays:
+ *   q[src][which][t][b]   the value of twin `which` on the row (obs_seq[t][b], actions[t][b]), widened from float32, under the
+ *                         online (src = 0) or the target (src = 1) image; for every installed twin.  A row's value depends on that
+ *                         row and the image alone.
+ *   q_min[src]            fmin over the installed twins (one twin installed: that twin)
+ *   q_adv                 q_min[online] - values[t][b], one rounded subtraction (IQL's advantage, offline.py:523-526)
+ *   td_target             r' + gamma * vnext, the r' and vnext of gs_rollout_evaluate's recurrence: the terminal value under
+ *                         bootstrap_mask and 0 otherwise where the transition ended an episode, values[t + 1][b] where it did not;
+ *                         nothing contracted (offline.py:504-505 with the bootstrap option)
+ * values and terminal_values are the reward critic's: GS_E_STATE unless gs_rollout_evaluate has run on the last rollout, without a
+ * rollout, and with no Q network installed; GS_E_INVALID as gs_rollout_evaluate.  gs_rollout_q_view: device pointers (NULL for a
+ * twin that is not installed), valid until the next gs_rollout; consumer_stream as gs_rollout_onpolicy_view.
+ * gs_rollout_q_download: host copies, any pointer may be NULL (a twin that is not installed is left unwritten).  Both are GS_E_STATE
+ * unless gs_rollout_evaluate_q has run on the last rollout.
+ *
+ * The Q learner.  GS_LEARNER_Q + which is a learner like a critic's (create, stats, info, download, view, set_loss with
+ * GS_LOSS_DEFAULT or GS_LOSS_EXPECTILE, federation); info.dims[0] = obs_dim + action_dim.  gs_learner_step reads the batch's
+ * observations (float32, under the Q network's own observation normalisation, compared on the host as for every network) and
+ * indices, and through the indices (clamped into the rollout) the rollout's float64 actions and td_target: the input row is the
+ * batch row followed by (float)action, the regression target (float)td_target.  It needs gs_rollout_evaluate_q on the last rollout
+ * (GS_E_STATE before any launch).  The forward pass, the head, the backward pass, the reduction and Adam are "the learner"'s; Adam
+ * writes the ONLINE image.
+ *
+ * Signals.  gs_learner_set_signal(h, net, GS_SIGNAL_Q) makes the next steps of the policy read (float)q_adv through the indices in
+ * place of the batch's advantages (which are then not required), and those of the reward critic (GS_LEARNER_VALUE) read
+ * (float)q_min[target] in place of the batch's returns (offline.py:484-493); the heads are the same kernels on the gathered
+ * values.  Such a step needs the batch's indices and gs_rollout_evaluate_q on the last rollout (GS_E_STATE).  GS_SIGNAL_Q on any
+ * other network and an unknown signal are GS_E_INVALID; no live learner is GS_E_STATE.  Host state like the loss: Adam's state and
+ * the generation stay; gs_learner_create and a *_set* entry reset it to GS_SIGNAL_BATCH.
+ *
+ * Target networks.  gs_q_target_update(h, tau) (asynchronous), over every installed twin and every float of the packed image:
+ *   t = (tau32 * p) + (omt32 * t)     tau32 = (float)tau, omt32 = (float)(1 - tau) (the difference in float64, rounded once)
+ * in float32, every operation rounded, none contracted; the padding stays 0; tau = 1 copies the online values, tau = 0 keeps the
+ * target.  tau outside [0, 1] or not finite: GS_E_INVALID; no Q network: GS_E_STATE.  gs_q_target_download: the target's parameters,
+ * float32, flat in torch order (P = the learner's param_count).  A federation (gs_fed_create accepts GS_LEARNER_Q + which) writes
+ * master parameters and the online images; target images are left alone. */
+enum { GS_LEARNER_Q = 5 /* + which */ };
+enum { GS_SIGNAL_BATCH = 0, GS_SIGNAL_Q = 1 };
+int gs_q_mlp_check(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int32_t obs_dim, int32_t action_dim);
+int gs_q_mlp_set(gs_handle* h, int32_t which, const gs_policy_mlp* p, const gs_policy_mlp_opts* o);
+typedef struct gs_q_eval_config {
+  int32_t struct_size;            /* = sizeof(gs_q_eval_config) */
+  int32_t bootstrap_mask;         /* as gs_gae_config */
+  double gamma;
+  double reward_shift, reward_scale;
+} gs_q_eval_config;
+int gs_rollout_evaluate_q(gs_handle* h, const gs_q_eval_config* cfg);
+typedef struct gs_rollout_q {
+  int32_t T, B, installed, rows_per_tile;   /* installed: bit `which` */
+  const double* q[2][2];          /* [src][which], [T][B] each; NULL: twin not installed */
+  const double* q_min[2];         /* [src] */
+  const double* q_adv;
+  const double* td_target;
+} gs_rollout_q;
+int gs_rollout_q_view(gs_handle* h, gs_rollout_q* out, void* consumer_stream);
+typedef struct gs_rollout_q_host {
+  double* q[2][2];
+  double* q_min[2];
+  double* q_adv;
+  double* td_target;
+} gs_rollout_q_host;
+int gs_rollout_q_download(gs_handle* h, const gs_rollout_q_host* out);
+int gs_learner_set_signal(gs_handle* h, int32_t net, int32_t signal);
+int gs_learner_get_signal(gs_handle* h, int32_t net, int32_t* signal);
+int gs_q_target_update(gs_handle* h, double tau);
+int gs_q_target_download(gs_handle* h, int32_t which, float* params);
+
 /* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
  * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
  * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
