@@ -22,7 +22,8 @@ from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy
                       evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches, evaluate_rollout_q, q_rollout_np, td_target_np,
                       q_combine_np, polyak_np)
 from .policy import MLPPolicy, MLPValue, MLPQ
-from .learner import DeviceLearner, ppo_grad_np, value_grad_np, awr_grad_np, expectile_grad_np, adam_np, split_parameters
+from .learner import (DeviceLearner, ppo_grad_np, value_grad_np, awr_grad_np, expectile_grad_np, pathwise_grad_np, pathwise_noise_np, adam_np,
+                      split_parameters)
 from .federated import FederatedLearners, fedavg_np, fed_noise_np, filter_outliers_np, gaussian_sigma
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -39,7 +40,7 @@ __all__ = [
     "episodes_np", "rollout_episodes", "EpisodeRecords", "EpisodeMonitor", "evaluate_policy",
     "permutation_np", "onpolicy_batch_np", "OnPolicyBatches",
     "MLPQ", "evaluate_rollout_q", "q_rollout_np", "td_target_np", "q_combine_np", "polyak_np",
-    "DeviceLearner", "ppo_grad_np", "value_grad_np", "awr_grad_np", "expectile_grad_np", "adam_np", "split_parameters",
+    "DeviceLearner", "ppo_grad_np", "value_grad_np", "awr_grad_np", "expectile_grad_np", "pathwise_grad_np", "pathwise_noise_np", "adam_np", "split_parameters",
     "FederatedLearners", "fedavg_np", "fed_noise_np", "filter_outliers_np", "gaussian_sigma",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",

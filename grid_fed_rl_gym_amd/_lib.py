@@ -348,6 +348,27 @@ def q_which(which) -> int:
     raise ValueError(f"Q network: which = {which!r} must be 0, 1 or one of {Q_NETS}")
 
 
+# the pathwise actor step (include/gridstep.h "the pathwise actor step"): the structs of gs_learner_step_pathwise / _pathwise_view
+PATHWISE_NOISE_TAG = 0x50574E4F      # 'PWNO'
+
+
+class gs_pathwise_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("stochastic", C.c_int32), ("alpha", C.c_double), ("bc_coef", C.c_double), ("seed", C.c_uint64),
+                ("draw", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class gs_pathwise_view_out(C.Structure):
+    _fields_ = [("n", C.c_int32), ("action_dim", C.c_int32), ("installed", C.c_int32), ("pre_head_stride", C.c_int32), ("pre_head", C.c_void_p),
+                ("actions", C.c_void_p),
+                ("noise", C.c_void_p), ("log_probs", C.c_void_p), ("q", C.c_void_p * 2), ("q_min", C.c_void_p), ("bc_terms", C.c_void_p),
+                ("loss_terms", C.c_void_p), ("which", C.c_void_p), ("dq_da", C.c_void_p * 2)]
+
+
+def pathwise_config(alpha=0.0, bc_coef=0.0, stochastic=True, seed=0, draw=0, struct_size=None) -> gs_pathwise_config:
+    return gs_pathwise_config(C.sizeof(gs_pathwise_config) if struct_size is None else int(struct_size), int(stochastic), float(alpha),
+                              float(bc_coef), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, 0)
+
+
 # the federation (include/gridstep.h "the federation"): the structs of gs_fed_*
 GS_FED_MAX_CLIENTS = 32
 _FED = C.c_void_p
@@ -509,6 +530,8 @@ SYMBOLS = [
     ("gs_learner_get_signal", C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32)]),
     ("gs_q_target_update", C.c_int, [_H, C.c_double]),
     ("gs_q_target_download", C.c_int, [_H, C.c_int32, C.c_void_p]),
+    ("gs_learner_step_pathwise", C.c_int, [_H, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.POINTER(gs_pathwise_config), C.c_void_p]),
+    ("gs_learner_pathwise_view", C.c_int, [_H, C.POINTER(gs_pathwise_view_out), C.c_void_p]),
     ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
     ("gs_fed_destroy", C.c_int, [_FED]),
     ("gs_fed_info", C.c_int, [_FED, C.POINTER(gs_fed_info_out)]),
@@ -1596,6 +1619,36 @@ class Handle:
             obs = batch.get("observations")
             n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
         self._check(self._lib.gs_learner_step(self._h, _net_number(net), C.byref(b), int(n), _stream_arg(stream)))
+
+    def learner_step_pathwise(self, batch: dict, n: Optional[int] = None, cfg: Optional[gs_pathwise_config] = None, stream=None) -> None:
+        """gs_learner_step_pathwise (asynchronous): one pathwise actor update of the policy on ``batch`` (as ``learner_step``'s) under
+        ``cfg`` (``pathwise_config``)."""
+        b = gs_onpolicy_batch_out()
+        addr = lambda x: None if x is None else int(x) if isinstance(x, (int, np.integer)) else int(x.__cuda_array_interface__["data"][0]) if hasattr(x, "__cuda_array_interface__") else int(x.data_ptr())
+        for k in ("observations", "indices"):
+            if batch.get(k) is not None:
+                setattr(b, k, addr(batch[k]))
+        if n is None:
+            obs = batch.get("observations")
+            n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
+        cfg = pathwise_config() if cfg is None else cfg
+        self._check(self._lib.gs_learner_step_pathwise(self._h, C.byref(b), int(n), C.byref(cfg), _stream_arg(stream)))
+
+    def learner_pathwise_view(self, stream=None) -> dict:
+        """gs_learner_pathwise_view: the last pathwise step's arrays as zero-copy ``DeviceArray`` views -- ``actions``, ``noise`` [n, A],
+        ``log_probs``, ``q_min``, ``bc_terms``, ``loss_terms`` [n] (float64), ``which`` [n] (int32), and per twin ``q`` [n] (float64)
+        and ``dq_da`` [n, A] (float32), None for a twin that was not installed; plus ``installed`` (the twins' numbers)."""
+        o = gs_pathwise_view_out()
+        self._check(self._lib.gs_learner_pathwise_view(self._h, C.byref(o), _stream_arg(stream)))
+        n, A = int(o.n), int(o.action_dim)
+        arr = lambda p, shape, ts: DeviceArray(p, shape, ts) if p else None
+        # (pre_head: the policy's float32 pre-head rows, in the learners' shared scratch: flat from the first row's start, row i at
+        # i * pre_head_stride, its first 2 A values mean | log_std; valid until the next step of any learner)
+        flat = (n - 1) * int(o.pre_head_stride) + 2 * A
+        return dict(pre_head=arr(o.pre_head, (flat,), "<f4"), pre_head_stride=int(o.pre_head_stride), actions=arr(o.actions, (n, A), "<f8"), noise=arr(o.noise, (n, A), "<f8"), log_probs=arr(o.log_probs, (n,), "<f8"),
+                    q=[arr(o.q[w], (n,), "<f8") for w in range(2)], q_min=arr(o.q_min, (n,), "<f8"), bc_terms=arr(o.bc_terms, (n,), "<f8"),
+                    loss_terms=arr(o.loss_terms, (n,), "<f8"), which=arr(o.which, (n,), "<i4"),
+                    dq_da=[arr(o.dq_da[w], (n, A), "<f4") for w in range(2)], installed=tuple(w for w in range(2) if o.installed >> w & 1))
 
     def learner_stats(self, net) -> dict:
         """gs_learner_stats: the last step's ``LEARNER_STATS`` as floats (waits for the step); ``step`` an int."""

@@ -2,7 +2,8 @@
 // network into master parameters, gs_learner_step queues one update on the minibatch gs_onpolicy_batch left (the kernels of
 // kernels_train.hip; with gs_learner_set_loss the head and its statistics are those of kernels_train_offline.hip, DESIGN.md section
 // 21; a Q learner's input rows and targets, and the heads' Q-based signals of gs_learner_set_signal, are gathered first by
-// gs_k_q_gather of kernels_q.hip, section 22), gs_learner_stats / _info / _download / _view read what it left.  The learners' buffers are made here and
+// gs_k_q_gather of kernels_q.hip, section 22), gs_learner_stats / _info / _download / _view read what it left.  gs_learner_step_pathwise is the
+// policy's step whose gradient flows through the twins (kernels_pathwise.hip, section 23).  The learners' buffers are made here and
 // released here: parameters with the learner (learner_drop), what is sized by n with the rollout's buffers (learner_scratch_release).
 #include <cmath>
 #include <cstring>
@@ -14,6 +15,7 @@ using namespace gsi;
 
 static_assert(sizeof(gs_learner_config) == 72, "gs_learner_config: two int32, eight doubles");
 static_assert(sizeof(gs_learner_loss) == 32, "gs_learner_loss: two int32, three doubles");
+static_assert(sizeof(gs_pathwise_config) == 40, "gs_pathwise_config: two int32, two doubles, a uint64, two uint32");
 static_assert(GS_POLICY_MAX_LAYERS == 4, "gs_learner_info_out::dims holds five widths");
 
 namespace gsi __attribute__((visibility("hidden"))) {
@@ -35,6 +37,10 @@ void learner_drop(gs_handle* h, int k) {
 void learner_scratch_release(gs_handle* h) {
   for (gs_handle::Learner& L : h->learner) learner_scratch_release_one(L);
   h->tr.acts.release(); h->tr.deltas.release(); h->tr.partial.release(); h->tr.qsa.release(); h->tr.qy.release();
+  gs_handle::Pathwise& pw = h->pw;
+  pw.acts.release(); pw.deltas.release(); pw.qsa.release(); pw.dqda.release(); pw.actions.release(); pw.noise.release(); pw.logp.release();
+  pw.q.release(); pw.qmin.release(); pw.bc.release(); pw.terms.release(); pw.which.release();
+  pw.n_last = 0;
 }
 
 void learner_release(gs_handle* h) {
@@ -344,6 +350,192 @@ int gs_learner_view(gs_handle* h, int32_t net, gs_learner_view_out* out, void* c
   *out = gs_learner_view_out{};
   out->n = Ln.n_last; out->loss_terms = Ln.term0;
   if (policy) { out->log_probs_new = Ln.lp_new; out->ratio = Ln.ratio; out->clipped = Ln.clipped; out->entropy_terms = Ln.term1; }
+  return GS_OK;
+}
+
+// ---- the pathwise actor step (include/gridstep.h "the pathwise actor step"): the policy's forward pass, the
+// kernels of kernels_pathwise.hip around one forward and one backward-data pass per installed twin (in the scratch of h->pw: the
+// policy's saved activations in h->tr survive them), then the policy's backward pass, reduction, statistics and Adam as above ----
+int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t n, const gs_pathwise_config* cfg, void* consumer_stream) {
+  if (!h || !batch || !cfg) return fail(h, GS_E_INVALID, "handle / batch / config is NULL");
+  if (cfg->struct_size != (int32_t)sizeof(gs_pathwise_config))
+    return fail(h, GS_E_INVALID, "gs_pathwise_config struct_size %d != %d", cfg->struct_size, (int)sizeof(gs_pathwise_config));
+  if (!std::isfinite(cfg->alpha) || cfg->alpha < 0.0 || !std::isfinite(cfg->bc_coef) || cfg->bc_coef < 0.0)
+    return fail(h, GS_E_INVALID, "gs_pathwise_config: alpha and bc_coef must be finite and >= 0");
+  if (cfg->stochastic != 0 && cfg->stochastic != 1) return fail(h, GS_E_INVALID, "gs_pathwise_config: stochastic = %d outside 0 .. 1", cfg->stochastic);
+  if (n <= 0 || n > (1 << 24)) return fail(h, GS_E_INVALID, "gs_learner_step_pathwise: n = %d outside 1 .. 2^24", n);
+  gs_handle::Learner& Ln = h->learner[GS_LEARNER_POLICY];
+  Installed I{};
+  if (!Ln.live || !installed(h, GS_LEARNER_POLICY, I))
+    return fail(h, GS_E_STATE, "gs_learner_step_pathwise: no learner for the policy (gs_learner_create after the network was installed)");
+  const int D = h->obs_dim, A = h->action_dim, DA = D + A;
+  if (A <= 0 || A > GS_PW_MAX_A) return fail(h, GS_E_STATE, "gs_learner_step_pathwise: action_dim = %d outside 1 .. %d", A, GS_PW_MAX_A);
+  Installed IQ[2]{};
+  bool have[2] = {false, false};
+  for (int w = 0; w < 2; ++w) {
+    if (!h->qnet[w].net.set) continue;
+    if (!h->learner[GS_LEARNER_Q + w].live || !installed(h, GS_LEARNER_Q + w, IQ[w]))
+      return fail(h, GS_E_STATE, "gs_learner_step_pathwise: no learner for %s (the backward pass reads its transposed images)", net_name(GS_LEARNER_Q + w));
+    have[w] = true;
+  }
+  if (!have[0] && !have[1]) return fail(h, GS_E_STATE, "gs_learner_step_pathwise before gs_q_mlp_set: no Q network is installed");
+  const gs_handle::OnPolicyBatches& ob = h->opb;
+  const gs_handle::Rollout& ro = h->ro;
+  if (!ob.prepared_on || ob.prepared_on != ro.calls) return fail(h, GS_E_STATE, "gs_learner_step_pathwise: gs_onpolicy_prepare has not run on the last rollout");
+  if (ob.cfg.dtype != GS_COMPUTE_F32) return fail(h, GS_E_STATE, "gs_learner_step_pathwise: the minibatches must be prepared with dtype GS_COMPUTE_F32");
+  const size_t Ds = (size_t)((D + 1) & ~1);
+  for (int k = -1; k < 2; ++k) {             // the policy, then the installed twins: gs_learner_step's comparison per network
+    if (k >= 0 && !have[k]) continue;
+    const Installed& J = k < 0 ? I : IQ[k];
+    const int D16 = 16 * J.L[0].kb;
+    for (int c = 0; c < D; ++c) {
+      const double shift = ob.have_norm ? ob.h_norm[c] : 0.0, scale = ob.have_norm ? ob.h_norm[Ds + c] : 1.0;
+      if (memcmp(&shift, &(*J.norm)[c], sizeof(double)) || memcmp(&scale, &(*J.norm)[D16 + c], sizeof(double)))
+        return fail(h, GS_E_STATE, "gs_learner_step_pathwise: the minibatches' obs_shift / obs_scale differ from the normalisation of %s (column %d)",
+                    net_name(k < 0 ? GS_LEARNER_POLICY : GS_LEARNER_Q + k), c);
+    }
+  }
+  const bool with_bc = cfg->bc_coef != 0.0;
+  if (!batch->observations || (with_bc && !batch->indices))
+    return fail(h, GS_E_INVALID, "gs_learner_step_pathwise: the batch lacks %s", !batch->observations ? "observations" : "indices (bc_coef != 0 reads the stored actions)");
+  GS_ENTER(h);
+  int rc = GS_OK;
+  const GsTrainNet& N = Ln.net;
+  const int segments = (n + GS_TR_SEG - 1) / GS_TR_SEG;
+  gs_handle::TrainScratch& tr = h->tr;
+  gs_handle::Pathwise& pw = h->pw;
+  int q_stride = 0;
+  for (int w = 0; w < 2; ++w)
+    if (have[w]) q_stride = std::max(q_stride, (int)h->learner[GS_LEARNER_Q + w].net.row_stride);
+  if ((rc = tr.acts.grow(h, (size_t)n * N.row_stride, "the learner's saved activations"))) return rc;
+  if ((rc = tr.deltas.grow(h, (size_t)n * N.row_stride, "the learner's backward pass"))) return rc;
+  if ((rc = tr.partial.grow(h, (size_t)segments * N.P, "the learner's partial gradients"))) return rc;
+  if ((rc = pw.acts.grow(h, (size_t)n * q_stride, "the actor step's saved activations of a twin"))) return rc;
+  if ((rc = pw.deltas.grow(h, (size_t)n * q_stride, "the actor step's backward pass of a twin"))) return rc;
+  if ((rc = pw.qsa.grow(h, (size_t)n * DA, "the actor step's input rows"))) return rc;
+  if ((rc = pw.dqda.grow(h, (size_t)2 * n * A, "the actor step's dQ/da"))) return rc;
+  if ((rc = pw.actions.grow(h, (size_t)n * A, "the actor step's actions"))) return rc;
+  if ((rc = pw.noise.grow(h, (size_t)n * A, "the actor step's noise"))) return rc;
+  if ((rc = pw.logp.grow(h, (size_t)n, "the actor step's log-probabilities"))) return rc;
+  if ((rc = pw.q.grow(h, (size_t)2 * n, "the actor step's Q values"))) return rc;
+  if ((rc = pw.qmin.grow(h, (size_t)n, "the actor step's minimum"))) return rc;
+  if ((rc = pw.bc.grow(h, (size_t)n, "the actor step's cloning terms"))) return rc;
+  if ((rc = pw.terms.grow(h, (size_t)n, "the actor step's loss terms"))) return rc;
+  if ((rc = pw.which.grow(h, (size_t)n, "the actor step's choices"))) return rc;
+  Ln.n_last = 0; pw.n_last = 0;              // (until every launch is queued; gs_learner_view's arrays are gs_learner_step's)
+  const int last = N.n_layers - 1, tiles = (n + GS_TR_ROWS - 1) / GS_TR_ROWS;
+  const gs_learner_config& lc = Ln.cfg;
+  const float* const obs = (const float*)batch->observations;
+
+  // the policy's forward pass: its saved activations stay in tr.acts until its backward pass
+  GsTrainFwdArgs F{};
+  F.N = N; F.obs = obs; F.acts = tr.acts; F.n = n; F.D = D;
+  F.obs_stride = gs_val_obs_stride(N.L[0].kb); F.panel_kb = gs_val_panel_kb(N.L[0].kb);
+  hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(N.L[0].kb), h->stream, F);
+  HIPCHK(h, hipGetLastError());
+
+  GsPwSampleArgs S{};
+  S.pre = tr.acts + N.col_off[last]; S.actions = pw.actions; S.noise = pw.noise; S.logp = pw.logp; S.sa = pw.qsa;
+  S.n = n; S.row_stride = N.row_stride; S.A = A; S.D = D; S.stochastic = cfg->stochastic; S.draw = cfg->draw; S.seed = cfg->seed;
+  hipLaunchKernelGGL(gs_k_pw_sample, dim3((n + 63) / 64), dim3(64), 0, h->stream, S);
+  HIPCHK(h, hipGetLastError());
+  GsPwRowsArgs RW{obs, pw.qsa, n, D, DA, 0};
+  hipLaunchKernelGGL(gs_k_pw_rows, dim3((unsigned)(((long long)n * D + 255) / 256)), dim3(256), 0, h->stream, RW);
+  HIPCHK(h, hipGetLastError());
+
+  // every installed twin: forward with saved activations, 1.0f at the head, backward to delta0, then through W0's action columns
+  for (int w = 0; w < 2; ++w) {
+    if (!have[w]) continue;
+    const gs_handle::Learner& Lq = h->learner[GS_LEARNER_Q + w];
+    const GsTrainNet& Q = Lq.net;
+    const int qlast = Q.n_layers - 1;
+    GsTrainFwdArgs FQ{};
+    FQ.N = Q; FQ.obs = pw.qsa; FQ.acts = pw.acts; FQ.n = n; FQ.D = DA;
+    FQ.obs_stride = gs_val_obs_stride(Q.L[0].kb); FQ.panel_kb = gs_val_panel_kb(Q.L[0].kb);
+    hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(Q.L[0].kb), h->stream, FQ);
+    HIPCHK(h, hipGetLastError());
+    GsPwSeedArgs SD{pw.deltas + Q.col_off[qlast], n, Q.row_stride, 16 * Q.L[qlast].nt, 0};
+    hipLaunchKernelGGL(gs_k_pw_seed, dim3((n + 63) / 64), dim3(64), 0, h->stream, SD);
+    HIPCHK(h, hipGetLastError());
+    if (qlast > 0) {
+      GsTrainBwdArgs BQ{};
+      BQ.N = Q; BQ.acts = pw.acts; BQ.deltas = pw.deltas; BQ.n = n;
+      hipLaunchKernelGGL(gs_k_train_bwd_data, dim3(tiles), dim3(64 * GS_POL_WAVES), 0, h->stream, BQ);
+      HIPCHK(h, hipGetLastError());
+    }
+    GsPwInputGradArgs IG{};
+    IG.delta0 = pw.deltas + Q.col_off[0]; IG.qpre = pw.acts + Q.col_off[qlast]; IG.W0 = Lq.params.p + Q.p_off[0];
+    IG.dqda = pw.dqda + (size_t)w * n * A; IG.q = pw.q + (size_t)w * n;
+    IG.n = n; IG.row_stride = Q.row_stride; IG.H0 = Q.dims[1]; IG.D = D; IG.A = A;
+    hipLaunchKernelGGL(gs_k_pw_input_grad, dim3((unsigned)(((long long)n * A + GS_PW_THREADS - 1) / GS_PW_THREADS)), dim3(GS_PW_THREADS), 0, h->stream, IG);
+    HIPCHK(h, hipGetLastError());
+  }
+
+  GsPwHeadArgs H{};
+  H.pre = S.pre; H.ghead = tr.deltas + N.col_off[last]; H.actions = pw.actions; H.noise = pw.noise; H.logp = pw.logp;
+  for (int w = 0; w < 2; ++w) { H.q[w] = have[w] ? pw.q.p + (size_t)w * n : nullptr; H.dqda[w] = have[w] ? pw.dqda.p + (size_t)w * n * A : nullptr; }
+  H.idx = with_bc ? batch->indices : nullptr; H.act = ro.act; H.N = ob.N;
+  H.n = n; H.row_stride = N.row_stride; H.width16 = 16 * N.L[last].nt; H.A = A; H.alpha = cfg->alpha; H.bc_coef = cfg->bc_coef;
+  H.which = pw.which; H.qmin = pw.qmin; H.bc = pw.bc; H.terms = pw.terms;
+  hipLaunchKernelGGL(gs_k_pw_head, dim3((n + 63) / 64), dim3(64), 0, h->stream, H);
+  HIPCHK(h, hipGetLastError());
+
+  if (last > 0) {
+    GsTrainBwdArgs B{};
+    B.N = N; B.acts = tr.acts; B.deltas = tr.deltas; B.n = n;
+    hipLaunchKernelGGL(gs_k_train_bwd_data, dim3(tiles), dim3(64 * GS_POL_WAVES), 0, h->stream, B);
+    HIPCHK(h, hipGetLastError());
+  }
+  GsTrainGradArgs G{};
+  G.N = N; G.obs = obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
+  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
+  int blocks = 0;
+  for (int l = 0; l <= last; ++l) {
+    G.blk0[l] = blocks;
+    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
+    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
+  }
+  G.blk0[last + 1] = blocks;
+  hipLaunchKernelGGL(gs_k_train_grad, dim3(blocks, segments), dim3(64), 0, h->stream, G);
+  HIPCHK(h, hipGetLastError());
+  const int red_blocks = (N.P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD);
+  GsTrainReduceArgs R{tr.partial, Ln.grad, Ln.blocksum, N.P, segments};
+  hipLaunchKernelGGL(gs_k_train_reduce, dim3(red_blocks), dim3(GS_TR_RED_THREADS), 0, h->stream, R);
+  HIPCHK(h, hipGetLastError());
+  GsPwStatArgs ST{pw.terms, pw.qmin, pw.logp, Ln.blocksum, Ln.stats, n, red_blocks};
+  hipLaunchKernelGGL(gs_k_pw_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, ST);
+  HIPCHK(h, hipGetLastError());
+
+  const double t = (double)(Ln.steps + 1);
+  GsTrainAdamArgs AD{};
+  AD.N = N; AD.params = Ln.params; AD.grad = Ln.grad; AD.m = Ln.m; AD.v = Ln.v; AD.stats = Ln.stats; AD.max_grad_norm = lc.max_grad_norm;
+  AD.wd = (float)lc.weight_decay; AD.b1 = (float)lc.beta1; AD.omb1 = (float)(1.0 - lc.beta1); AD.b2 = (float)lc.beta2; AD.omb2 = (float)(1.0 - lc.beta2);
+  AD.bc2s = (float)std::sqrt(1.0 - std::pow(lc.beta2, t)); AD.eps = (float)lc.eps; AD.step = (float)(lc.lr / (1.0 - std::pow(lc.beta1, t)));
+  hipLaunchKernelGGL(gs_k_train_adam, dim3((N.P + 255) / 256), dim3(256), 0, h->stream, AD);
+  HIPCHK(h, hipGetLastError());
+  Ln.steps += 1; pw.n_last = n; pw.installed = (have[0] ? 1 : 0) | (have[1] ? 2 : 0);
+  return publish(h, h->stream, Ln.ev, consumer_stream);
+}
+
+int gs_learner_pathwise_view(gs_handle* h, gs_pathwise_view_out* out, void* consumer_stream) {
+  if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
+  gs_handle::Learner& Ln = h->learner[GS_LEARNER_POLICY];
+  gs_handle::Pathwise& pw = h->pw;
+  if (!Ln.live || !pw.n_last) return fail(h, GS_E_STATE, "gs_learner_pathwise_view: the policy holds no pathwise step's arrays");
+  GS_ENTER(h);
+  int rc = publish(h, h->stream, Ln.ev, consumer_stream);
+  if (rc) return rc;
+  const size_t n = (size_t)pw.n_last, A = (size_t)h->action_dim;
+  *out = gs_pathwise_view_out{};
+  out->n = pw.n_last; out->action_dim = h->action_dim;
+  out->pre_head = h->tr.acts + Ln.net.col_off[Ln.net.n_layers - 1]; out->pre_head_stride = Ln.net.row_stride;
+  out->actions = pw.actions; out->noise = pw.noise; out->log_probs = pw.logp; out->q_min = pw.qmin; out->bc_terms = pw.bc; out->loss_terms = pw.terms;
+  out->which = pw.which;
+  out->installed = pw.installed;
+  for (int w = 0; w < 2; ++w) {
+    if (!(pw.installed >> w & 1)) continue;
+    out->q[w] = pw.q + w * n; out->dq_da[w] = pw.dqda + w * n * A;
+  }
   return GS_OK;
 }
 

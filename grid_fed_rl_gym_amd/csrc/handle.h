@@ -21,6 +21,7 @@
 #include "policy.h"
 #include "train.h"
 #include "q.h"
+#include "pathwise.h"
 
 // (also on the handle's parts that own a DevBuf and on gs_checks: their destructors are not part of the library's surface)
 #define GS_HIDDEN __attribute__((visibility("hidden")))
@@ -201,6 +202,13 @@ struct gs_handle : GsPlan {
   // what gs_rollout_evaluate_q made of the last rollout: q [src][which][T_cap][B], q_min [src][T_cap][B], q_adv, td [T_cap][B]; made
   // on first use (all or none), released with the rollout's buffers; evaluated_on = ro.calls of the rollout they belong to, 0 = none
   struct GS_HIDDEN QTrack { DevBuf<double> q, q_min, q_adv, td; uint64_t evaluated_on = 0; hipEvent_t ev = nullptr; } qt;
+  // gs_learner_step_pathwise (abi_learner.hip): the twins' passes of an actor step have scratch of their own (acts /
+  // deltas [n][the wider twin's row_stride], qsa [n][obs_dim + A]: the policy's saved activations in tr survive them), and the step's
+  // per-sample arrays (n_last samples; 0: none): actions / noise [n][A], logp / qmin / bc / terms [n], q [2][n], which [n], dqda
+  // [2][n][A]; installed: bit w = twin w took part.  Grown to the largest n seen and released with the rollout's buffers, like tr.
+  struct GS_HIDDEN Pathwise {
+    DevBuf<float> acts, deltas, qsa, dqda; DevBuf<double> actions, noise, logp, q, qmin, bc, terms; DevBuf<int32_t> which; int n_last = 0, installed = 0;
+  } pw;
   // gs_fed_* (abi_fed.hip): the federations this handle is a client of; gs_destroy detaches them (fed_detach)
   std::vector<gs_fed*> feds;
   // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count

@@ -9,6 +9,7 @@
 #include "policy.h"
 #include "train.h"
 #include "q.h"
+#include "pathwise.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -79,6 +80,12 @@ __global__ void gs_k_q_combine(GsQCombineArgs C);
 __global__ void gs_k_q_td(GsQTdArgs G);
 __global__ void gs_k_q_gather(GsQGatherArgs G);
 __global__ void gs_k_q_polyak(GsQPolyakArgs A);
+__global__ void gs_k_pw_sample(GsPwSampleArgs S);
+__global__ void gs_k_pw_rows(GsPwRowsArgs R);
+__global__ void gs_k_pw_seed(GsPwSeedArgs S);
+__global__ void gs_k_pw_input_grad(GsPwInputGradArgs P);
+__global__ void gs_k_pw_head(GsPwHeadArgs H);
+__global__ void gs_k_pw_stats(GsPwStatArgs S);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

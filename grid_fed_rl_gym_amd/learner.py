@@ -4,7 +4,7 @@ network, one clipped-surrogate (PPO) or critic update on a minibatch of ``OnPoli
 pass, a deterministic gradient reduction and Adam, which also rewrites the image the rollout and critic kernels read: the next
 ``rollout_device(policy="mlp")`` acts with the updated policy and no weight crosses the host.
 
-``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np`` and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
+``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np``, ``pathwise_grad_np`` (with ``pathwise_noise_np``) and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
 """
 from __future__ import annotations
 
@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from .policy import HALF_LOG_2PI, LOG_STD_MAX, LOG_STD_MIN, MLPPolicy, MLPQ, MLPValue
+from .rollout import _philox4x32
 
 HALF_LOG_2PIE = HALF_LOG_2PI + 0.5      # 0.5 * log(2 pi e): a unit Gaussian's entropy
 
@@ -186,6 +187,187 @@ def expectile_grad_np(value_layers, obs_n, returns, expectile: float, exact: boo
     return dict(grads=_backward(rounded, acts, ghead, activation), values=v, below=d < 0.0, loss_terms=terms, loss=math.fsum(terms) / n)
 
 
+def pathwise_noise_np(seed: int, draw: int, n: int, A: int) -> np.ndarray:
+    """eps [n, A] of a pathwise actor step: ``eps[i, k]`` = component ``k & 3`` of the four normals of Philox4x32-10 with counter
+    (i, k >> 2, draw, 'PWNO') and key ``seed`` -- ``fed_noise_np``'s recipe (every word w a uniform (w + 1/2) 2^-32, words (0, 1)
+    and (2, 3) one Box-Muller pair each, cosine then sine) under the actor step's counter."""
+    n, A = int(n), int(A)
+    if n < 0 or A <= 0:
+        raise ValueError(f"pathwise_noise_np: n = {n} must be >= 0 and A = {A} > 0")
+    quads = (A + 3) // 4
+    i = np.repeat(np.arange(n, dtype=np.uint64), quads)
+    q = np.tile(np.arange(quads, dtype=np.uint64), n)
+    full = lambda x: np.full(i.shape, int(x) & 0xFFFFFFFF, dtype=np.uint64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = np.stack(_philox4x32(i, q, full(draw), full(_lib.PATHWISE_NOISE_TAG), seed & 0xFFFFFFFF, seed >> 32), axis=1).astype(np.float64)
+    u = (w + 0.5) * (1.0 / 4294967296.0)
+    ra, rb = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
+    ta, tb = 2.0 * math.pi * u[:, 1], 2.0 * math.pi * u[:, 3]
+    z = np.stack([ra * np.cos(ta), ra * np.sin(ta), rb * np.cos(tb), rb * np.sin(tb)], axis=1)
+    return z.reshape(n, 4 * quads)[:, :A].copy()
+
+
+# exp, tanh and log of the pathwise heads, operation by operation as kernels_pathwise.hip performs them (gw_exp, gw_tanh, gw_log): rounded
+# float64 +, -, *, / alone, so that the heads are restated to the bit whatever math library NumPy was built on
+_PW_LN2_HI, _PW_LN2_LO, _PW_INV_LN2 = 6.93147180369123816490e-01, 1.90821492927058770002e-10, 1.4426950408889634
+_PW_HALF_LOG_2PI = 0.91893853320467274178      # the kernels' literal: 0.5 log(2 pi) rounded to nearest, one ulp above policy.HALF_LOG_2PI
+_PW_INV_FACT = [1.0 / math.factorial(j) for j in range(24)]
+_PW_INV_ODD = [1.0 / (2 * j + 1) for j in range(1, 16)]
+
+
+def pathwise_exp_np(x) -> np.ndarray:
+    """exp as the pathwise heads compute it: k = rint(x / ln 2), r = x - k ln 2 in two parts, the Taylor sum to r^17 by Horner's
+    rule, times 2^k."""
+    x = np.asarray(x, dtype=np.float64)
+    k = np.rint(x * _PW_INV_LN2)
+    r = (x - k * _PW_LN2_HI) - k * _PW_LN2_LO
+    p = np.full(x.shape, _PW_INV_FACT[17])
+    for j in range(16, -1, -1):
+        p = _PW_INV_FACT[j] + r * p
+    return np.ldexp(p, k.astype(np.int64))
+
+
+def pathwise_tanh_np(x) -> np.ndarray:
+    """tanh as the pathwise heads compute it, u = min(|x|, 40): below 0.5 from m = expm1(2 u) (the Taylor sum to (2 u)^23) as
+    m / (m + 2), else from e = exp(-2 u) as (1 - e) / (1 + e); the sign of x."""
+    x = np.asarray(x, dtype=np.float64)
+    u = np.fmin(np.abs(x), 40.0)
+    y = 2.0 * np.where(u < 0.5, u, 0.0)
+    p = np.full(x.shape, _PW_INV_FACT[23])
+    for j in range(22, 0, -1):
+        p = _PW_INV_FACT[j] + y * p
+    m = y * p
+    e = pathwise_exp_np(-2.0 * u)
+    return np.copysign(np.where(u < 0.5, m / (m + 2.0), (1.0 - e) / (1.0 + e)), x)
+
+
+def pathwise_log_np(v) -> np.ndarray:
+    """log of positive normal numbers as the pathwise heads compute it: v = m 2^e with sqrt(1/2) <= m < sqrt(2), s = (m - 1) / (m + 1),
+    log m = 2 s (1 + z P(z)) with z = s s and P the sum of z^(j - 1) / (2 j + 1), j = 1 .. 15; plus e ln 2 in two parts."""
+    v = np.asarray(v, dtype=np.float64)
+    m, e = np.frexp(v)
+    small = m < 0.7071067811865476
+    m = np.where(small, m * 2.0, m)
+    ed = (e - small).astype(np.float64)
+    f = m - 1.0
+    s = f / (2.0 + f)
+    z = s * s
+    p = np.full(v.shape, _PW_INV_ODD[14])
+    for j in range(13, -1, -1):
+        p = _PW_INV_ODD[j] + z * p
+    t2 = 2.0 * s
+    logm = t2 + t2 * (z * p)
+    return ed * _PW_LN2_HI + (ed * _PW_LN2_LO + logm)
+
+
+def _pathwise_sample(out: np.ndarray, eps):
+    """The sampling head of include/gridstep.h ("the pathwise actor step") in float64 on the pre-head values ``out`` [n, 2 A] (mean |
+    log_std) and the noise ``eps`` [n, A]: ``inside`` [n, A] (the clamp of log_std is inactive), ``std``, the actions ``a`` =
+    tanh(mean + std eps), and per sample the log-probability ``lp``, summed in action order from k = 0."""
+    n, A = out.shape[0], out.shape[1] // 2
+    eps = np.asarray(eps, dtype=np.float64).reshape(n, A)
+    mean, lsr = out[:, :A], out[:, A:]
+    inside = (lsr >= LOG_STD_MIN) & (lsr <= LOG_STD_MAX)
+    ls = np.clip(lsr, LOG_STD_MIN, LOG_STD_MAX)
+    std = pathwise_exp_np(ls)
+    a = pathwise_tanh_np(mean + std * eps)
+    terms = (((-0.5 * eps) * eps - ls) - _PW_HALF_LOG_2PI) - pathwise_log_np((1.0 - a * a) + 1e-6)
+    lp = terms[:, 0].copy()
+    for k in range(1, A):
+        lp += terms[:, k]
+    return inside, std, eps, a, lp
+
+
+def _pathwise_head(inside, std, eps, a, lp, q, dq_da, alpha: float, bc_coef: float, stored, exact: bool, which=None):
+    """The actor head of include/gridstep.h in float64: the smaller twin (``which``: choices to use in place of the ones found),
+    the loss terms, and dL / d(mean | log_std) [n, 2 A], rounded once to float32 unless ``exact``."""
+    n, A = a.shape
+    if len(q) == 1:
+        found = np.zeros(n, dtype=np.int32)
+    else:
+        found = np.where(q[0] <= q[1], 0, 1).astype(np.int32)
+    use = found if which is None else np.asarray(which).reshape(n).astype(np.int32)
+    if use.size and (use.min() < 0 or use.max() >= len(q)):
+        raise ValueError(f"pathwise_grad_np: which must name one of the {len(q)} twin(s)")
+    rows = np.arange(n)
+    qs, ds = np.stack(q, axis=0), np.stack(dq_da, axis=0)
+    qmin = qs[use, rows]
+    dq = ds[use, rows].astype(np.float64)
+    if bc_coef != 0.0:
+        d = a - np.asarray(stored, dtype=np.float64).reshape(n, A)
+    else:
+        d = np.zeros_like(a)
+    sq = d * d
+    bc = sq[:, 0].copy()
+    for k in range(1, A):
+        bc += sq[:, k]
+    terms = (alpha * lp - qmin) + bc_coef * bc
+    om = 1.0 - a * a
+    t1 = (alpha * (2.0 * a)) / (om + 1e-6)
+    t2 = (2.0 * bc_coef) * d
+    G = (((t1 - dq) + t2) * om) / n
+    gls = np.where(inside, (G * std) * eps - alpha / n, 0.0)
+    ghead = np.concatenate([G, gls], axis=1)
+    return found, use, qmin, bc, terms, (ghead if exact else ghead.astype(np.float32))
+
+
+def pathwise_grad_np(policy_layers, q_layers_list, obs_n, eps, alpha: float, bc_coef: float, stored_actions=None, exact: bool = False,
+                     which=None, activation: str = "relu", q_activation: str = "relu") -> Dict[str, Any]:
+    """The pathwise actor loss of include/gridstep.h ("the pathwise actor step") and its gradient with respect to the POLICY, as
+    ``gs_learner_step_pathwise`` computes them: ``L = mean(alpha lp - min_w Q_w(s, a) + bc_coef |a - a_stored|^2)`` with
+    ``a = tanh(mean + std eps)`` and the gradient flowing through the twins into the policy.  ``policy_layers`` as for
+    ``ppo_grad_np``; ``q_layers_list``: one or two Q networks' [(W, b)] over [obs | action] (the last width 1), used read-only;
+    ``obs_n`` [n, obs_dim] the NORMALISED observations; ``eps`` [n, A] the noise (zeros: the deterministic actor);
+    ``stored_actions`` [n, A] float64, needed when ``bc_coef`` != 0.  Layers in float32 -- or, with ``exact``, the same
+    float32-rounded operands in float64 throughout --, the heads in float64, head gradients rounded once to float32 unless
+    ``exact``; the action enters a twin rounded to float32 either way.  ``which`` [n]: the twin to take per sample in place of
+    the smaller one this evaluation finds (a sample whose two values lie at a rounding from each other).  Returns ``grads``
+    [(dW, db)] of the policy, ``actions`` [n, A], ``log_probs`` [n], ``q`` [twins, n] (float64), ``q_min`` [n], ``which`` [n]
+    (found here), ``dq_da`` [twins, n, A], ``bc_terms``, ``loss_terms`` [n], ``log_std_outside`` [n, A] and the scalars ``loss``,
+    ``surrogate`` (mean q_min) and ``entropy`` (-mean lp)."""
+    alpha, bc_coef = _pathwise_check(alpha, bc_coef)
+    q_layers_list = list(q_layers_list)
+    if not 1 <= len(q_layers_list) <= 2:
+        raise ValueError(f"pathwise_grad_np: one or two Q networks, got {len(q_layers_list)}")
+    rounded, acts = _forward(policy_layers, obs_n, activation, exact)
+    out = acts[-1].astype(np.float64)
+    n, A = out.shape[0], out.shape[1] // 2
+    if out.shape[1] != 2 * A or A == 0:
+        raise ValueError(f"pathwise_grad_np: the policy's last width {out.shape[1]} must be 2 A (mean | log_std)")
+    eps = np.asarray(eps, dtype=np.float64)
+    if eps.shape != (n, A):
+        raise ValueError(f"pathwise_grad_np: eps must be [{n}, {A}], got {eps.shape}")
+    if bc_coef != 0.0 and (stored_actions is None or np.shape(stored_actions) != (n, A)):
+        raise ValueError(f"pathwise_grad_np: bc_coef != 0 needs stored_actions [{n}, {A}]")
+    inside, std, eps, a, lp = _pathwise_sample(out, eps)
+    work = np.float64 if exact else np.float32
+    D = acts[0].shape[1]
+    sa = np.concatenate([acts[0], a.astype(np.float32).astype(work)], axis=1)
+    qv, dq = [], []
+    for layers in q_layers_list:
+        if np.asarray(layers[0][0]).shape[1] != D + A or np.asarray(layers[-1][0]).shape[0] != 1:
+            raise ValueError(f"pathwise_grad_np: a Q network maps {D + A} columns to 1")
+        qr, qa = _forward(layers, sa, q_activation, exact)
+        delta = np.ones((n, 1), dtype=work)
+        for l in range(len(qr) - 1, 0, -1):
+            delta = (delta @ qr[l][0]) * _act_grad(qa[l], q_activation)
+        qv.append(qa[-1].astype(np.float64)[:, 0])
+        dq.append(delta @ qr[0][0][:, D:])
+    found, use, qmin, bc, terms, ghead = _pathwise_head(inside, std, eps, a, lp, qv, dq, alpha, bc_coef, stored_actions, exact, which)
+    ghead = ghead.astype(work) if exact else ghead
+    return dict(grads=_backward(rounded, acts, ghead, activation), actions=a, log_probs=lp, q=np.stack(qv, axis=0), q_min=qmin, which=found,
+                dq_da=np.stack(dq, axis=0), bc_terms=bc, loss_terms=terms, log_std_outside=~inside, loss=math.fsum(terms) / n,
+                surrogate=math.fsum(qmin) / n, entropy=-(math.fsum(lp) / n))
+
+
+def _pathwise_check(alpha, bc_coef) -> Tuple[float, float]:
+    alpha, bc_coef = float(alpha), float(bc_coef)
+    for k, x in (("alpha", alpha), ("bc_coef", bc_coef)):
+        if not math.isfinite(x) or x < 0.0:
+            raise ValueError(f"{k} = {x} must be finite and >= 0")
+    return alpha, bc_coef
+
+
 def _awr_check(temperature, weight_max) -> Tuple[float, float]:
     temperature, weight_max = float(temperature), float(weight_max)
     for k, x in (("temperature", temperature), ("weight_max", weight_max)):
@@ -253,6 +435,13 @@ class DeviceLearner:
     regresses on the target networks' ``min(Q1, Q2)`` instead of the batch's returns -- with ``policy_loss="awr"`` and
     ``value_loss="expectile"`` that is IQL.  ``update_targets(tau)`` moves the target networks.
 
+    The pathwise actor: ``policy_loss="pathwise"`` makes the policy's step ``gs_learner_step_pathwise`` --
+    ``mean(alpha lp - min(Q1, Q2)(s, a) + bc_coef |a - a_stored|^2)`` with ``a`` sampled inside the step
+    (``pathwise_stochastic=False``: ``a = tanh(mean)``) and the gradient flowing through the installed twins, which need learners
+    ("q1" / "q2" among ``nets``, of this or of another ``DeviceLearner`` on the handle) but are not stepped by it.  The noise of a
+    step is ``pathwise_noise_np(pathwise_seed, draw, n, A)`` with ``draw`` = the policy's steps taken.  Host state: the C loss kind
+    is not involved.
+
     ``step(batch)``: one ``gs_learner_step`` per network on a dict of ``OnPolicyBatches.epoch`` (prepared with float32 and the
     networks' own observation normalisation).  After a step the ``MLPPolicy`` / ``MLPValue`` objects the networks were installed
     from no longer describe them: ``policy()`` / ``value(net)`` rebuild current ones from the device's parameters."""
@@ -260,7 +449,8 @@ class DeviceLearner:
     def __init__(self, env, nets: Sequence[str] = ("policy", "value"), lr: float = 3e-4, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0, clip: float = 0.2, ent_coef: float = 0.0, max_grad_norm: float = 0.0,
                  policy_loss: str = "ppo", temperature: float = 1.0, weight_max: float = 20.0, value_loss: str = "mse",
-                 expectile: float = 0.7, q_loss: str = "mse", advantage_source: str = "batch", value_target: str = "batch") -> None:
+                 expectile: float = 0.7, q_loss: str = "mse", advantage_source: str = "batch", value_target: str = "batch",
+                 alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True, pathwise_seed: int = 0) -> None:
         if isinstance(nets, str):
             nets = (nets,)
         self.nets = tuple(nets)
@@ -293,6 +483,13 @@ class DeviceLearner:
                     raise ValueError(f"DeviceLearner: {what} = 'q' needs {'policy' if k == _lib.GS_LEARNER_POLICY else 'value'!r} among nets {self.nets}")
                 signals[k] = source
         self.advantage_source, self.value_target = advantage_source, value_target
+        self._pathwise: Optional[dict] = None
+        if policy_loss == "pathwise":
+            if _lib.GS_LEARNER_POLICY not in self._ids:
+                raise ValueError(f"DeviceLearner: policy_loss = 'pathwise' needs 'policy' among nets {self.nets}")
+            self._pathwise = self._pathwise_state(alpha, bc_coef, pathwise_stochastic, pathwise_seed)
+        else:
+            _pathwise_check(alpha, bc_coef)
         self.env = env
         self.config = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                            clip=float(clip), ent_coef=float(ent_coef), max_grad_norm=float(max_grad_norm))
@@ -308,7 +505,7 @@ class DeviceLearner:
     def _loss_struct(k: int, loss: str, temperature, weight_max, expectile, what: Optional[str] = None) -> "_lib.gs_learner_loss":
         """The ``gs_learner_loss`` of network number ``k`` for the loss named ``loss``; ValueError for what the ABI would refuse."""
         policy = k == _lib.GS_LEARNER_POLICY
-        names = ("ppo", "awr", "bc") if policy else ("mse", "expectile")
+        names = ("ppo", "awr", "bc", "pathwise") if policy else ("mse", "expectile")
         if loss not in names:
             raise ValueError(f"DeviceLearner: {what or ('policy_loss' if policy else 'value_loss')} = {loss!r} must be one of {names}")
         if loss == "bc":
@@ -320,22 +517,39 @@ class DeviceLearner:
             return _lib.learner_loss("expectile", 0.0, 0.0, _expectile_check(expectile))
         return _lib.learner_loss("default", 0.0, 0.0, 0.0)
 
+    @staticmethod
+    def _pathwise_state(alpha, bc_coef, stochastic, seed) -> dict:
+        alpha, bc_coef = _pathwise_check(alpha, bc_coef)
+        if not isinstance(stochastic, (bool, np.bool_)):
+            raise ValueError(f"DeviceLearner: pathwise_stochastic = {stochastic!r} must be True or False")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"DeviceLearner: pathwise_seed = {seed!r} must be an integer in [0, 2^64)")
+        return dict(alpha=alpha, bc_coef=bc_coef, stochastic=bool(stochastic), seed=int(seed))
+
     def set_loss(self, net="policy", loss: Optional[str] = None, temperature: float = 1.0, weight_max: float = 20.0,
-                 expectile: float = 0.7) -> None:
+                 expectile: float = 0.7, alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True,
+                 pathwise_seed: int = 0) -> None:
         """Another loss for ``net`` from its next step (``gs_learner_set_loss``): the policy's "ppo", "awr" (``temperature``,
-        ``weight_max``) or "bc"; a critic's "mse" or "expectile" (``expectile``).  Adam's moments and step count stay, and a
+        ``weight_max``), "bc" or "pathwise" (``alpha``, ``bc_coef``, ``pathwise_stochastic``, ``pathwise_seed``; host state, the C
+        loss returns to its default); a critic's "mse" or "expectile" (``expectile``).  Adam's moments and step count stay, and a
         ``FederatedLearners`` on the learner stays valid."""
         k = self._id(net)
         if loss is None:
             raise ValueError("DeviceLearner.set_loss: name the loss")
-        self.env.handle.learner_set_loss(k, self._loss_struct(k, loss, temperature, weight_max, expectile))
+        struct = self._loss_struct(k, loss, temperature, weight_max, expectile)
+        state = self._pathwise_state(alpha, bc_coef, pathwise_stochastic, pathwise_seed) if loss == "pathwise" else None
+        self.env.handle.learner_set_loss(k, struct)
+        if k == _lib.GS_LEARNER_POLICY:
+            self._pathwise = state
 
     def loss(self, net="policy") -> dict:
         """The loss of ``net`` in force: ``name`` ("ppo", "awr", "bc", "mse" or "expectile") and ``gs_learner_get_loss``'s ``kind``,
         ``temperature``, ``weight_max`` and ``expectile``."""
         k = self._id(net)
         out = self.env.handle.learner_get_loss(k)
-        if out["kind"] == "default":
+        if k == _lib.GS_LEARNER_POLICY and self._pathwise is not None:
+            out.update(self._pathwise, name="pathwise")
+        elif out["kind"] == "default":
             out["name"] = "ppo" if k == _lib.GS_LEARNER_POLICY else "mse"
         elif out["kind"] == "awr":
             out["name"] = "bc" if math.isinf(out["temperature"]) and math.isinf(out["weight_max"]) else "awr"
@@ -353,7 +567,34 @@ class DeviceLearner:
         """One update of every network on ``batch`` (asynchronous on the handle's stream; ``stream``: a consumer's stream)."""
         n = int(batch["observations"].shape[0])
         for net in self._ids:
-            self.env.handle.learner_step(net, batch, n, stream)
+            if net == _lib.GS_LEARNER_POLICY and self._pathwise is not None:
+                self.step_pathwise(batch, stream=stream)
+            else:
+                self.env.handle.learner_step(net, batch, n, stream)
+
+    def step_pathwise(self, batch: dict, alpha: Optional[float] = None, bc_coef: Optional[float] = None, stochastic: Optional[bool] = None,
+                      seed: Optional[int] = None, draw: Optional[int] = None, stream=None) -> None:
+        """One pathwise actor update of the policy on ``batch`` (``gs_learner_step_pathwise``, asynchronous): what is not given is
+        the learner's ``policy_loss="pathwise"`` state (``alpha`` 0, ``bc_coef`` 0, stochastic, seed 0 without one); ``draw``: by
+        default the policy's steps taken."""
+        k = self._id("policy")
+        base = self._pathwise or dict(alpha=0.0, bc_coef=0.0, stochastic=True, seed=0)
+        state = self._pathwise_state(base["alpha"] if alpha is None else alpha, base["bc_coef"] if bc_coef is None else bc_coef,
+                                     base["stochastic"] if stochastic is None else stochastic, base["seed"] if seed is None else seed)
+        if draw is None:
+            draw = self.env.handle.learner_info(k)["step"]
+        if isinstance(draw, bool) or not isinstance(draw, (int, np.integer)) or not 0 <= int(draw) < 2 ** 32:
+            raise ValueError(f"DeviceLearner.step_pathwise: draw = {draw!r} must be an integer in [0, 2^32)")
+        cfg = _lib.pathwise_config(state["alpha"], state["bc_coef"], state["stochastic"], state["seed"], int(draw))
+        self.env.handle.learner_step_pathwise(batch, int(batch["observations"].shape[0]), cfg, stream)
+
+    def pathwise_views(self, stream=None) -> dict:
+        """The last pathwise step's arrays as zero-copy ``DeviceArray`` views (``gs_learner_pathwise_view``): ``actions``, ``noise``
+        [n, A], ``log_probs``, ``q_min``, ``bc_terms``, ``loss_terms`` [n], ``which`` [n] (int32), ``q`` and ``dq_da`` lists per twin
+        (None for a twin that is not installed), ``installed``, and ``pre_head`` / ``pre_head_stride`` (the policy's float32 rows
+        mean | log_std in the learners' shared scratch, valid until any learner's next step)."""
+        self._id("policy")
+        return self.env.handle.learner_pathwise_view(stream)
 
     def stats(self, net="policy") -> dict:
         """The last step's ``loss``, ``surrogate``, ``entropy``, ``approx_kl``, ``clip_fraction``, ``value_loss``, ``grad_norm`` and

@@ -1006,6 +1006,82 @@ int gs_learner_get_signal(gs_handle* h, int32_t net, int32_t* signal);
 int gs_q_target_update(gs_handle* h, double tau);
 int gs_q_target_download(gs_handle* h, int32_t which, float* params);
 
+/* ---- the pathwise actor step: the policy's gradient through the twin Q networks ----
+ * The actor update that SAC, TD3, DDPG + BC, MADDPG and CQL share (the reference's CQL._update_actor, algorithms/offline.py:230-244:
+ * (alpha * log_prob - min(Q1, Q2)(s, pi(s))).mean() with pi(s) drawn by the reparameterisation trick, offline.py:114-136): the action
+ * is sampled inside the step, the twins evaluate it, and dQ/da flows back into the policy.  Additive to ABI 2: no struct above
+ * changes, GS_LOSS_* and GS_SIGNAL_* are as they were, and a handle that calls neither entry computes what it computed before.
+ *
+ * gs_learner_step_pathwise (asynchronous, on the handle's stream) steps the POLICY's learner alone, on the minibatch of n samples
+ * gs_onpolicy_batch left in `batch`.  Every installed twin is used read-only (one twin installed: the minimum is that twin).  It
+ * needs: a live learner for the policy AND for every installed twin (the twin's transposed images are what the backward pass
+ * reads), at least one installed twin, gs_onpolicy_prepare on the last rollout with dtype GS_COMPUTE_F32, and obs_shift / obs_scale
+ * bit-equal (compared on the host, per network) to the policy's and to every installed twin's observation normalisation:
+ * GS_E_STATE otherwise.  It reads batch->observations, and batch->indices when bc_coef != 0 only; neither recorded
+ * log-probabilities nor batch->advantages nor gs_rollout_evaluate_q.  GS_E_INVALID: a wrong struct_size, alpha or bc_coef NaN,
+ * negative or infinite, stochastic outside {0, 1}, n outside 1 .. 2^24, a missing pointer.  Every check runs before any launch.
+ *
+ * Per sample i.  Layers in float32 on the matrix cores (gs_learner_step's kernels), heads in float64 on float32 values, head
+ * gradients rounded once to float32, nothing contracted:
+ *     ls_k = clamp(log_std_k, -20, 2);   std_k = exp(ls_k)
+ *     eps_k = component k & 3 of the four normals (the recipe of the load noise: words (0, 1) and (2, 3) one Box-Muller pair each,
+ *             cosine then sine) of Philox4x32-10 with counter (i, k >> 2, draw, 'PWNO' = 0x50574E4F) and key seed;
+ *             0 when stochastic == 0 (the deterministic actor a = tanh(mean))
+ *     x_k = mean_k + std_k * eps_k;   a_k = tanh(x_k)
+ *     lp = sum_k (((-0.5 eps_k) eps_k - ls_k) - 0.5 log(2 pi)) - log((1 - a_k a_k) + 1e-6)      in action order from k = 0
+ *   exp, tanh and log above are NOT a math library's: they are sums of rounded float64 +, -, *, / (frexp, ldexp and rint are exact),
+ *   so that a host restates the heads to the bit whatever library it has (a library's own functions agree across machines to an
+ *   ulp only).  With LN2_HI = 0x1.62e42feep-1, LN2_LO = 0x1.a39ef35793c76p-33, every sum by Horner's rule from the last term:
+ *     exp(x):   k = rint(x * 1.4426950408889634);  r = (x - k LN2_HI) - k LN2_LO;  p = sum_{j=0..17} r^j / j!;  ldexp(p, k)
+ *     tanh(x):  u = min(|x|, 40);  u < 0.5:  y = 2 u,  m = y * sum_{j=1..23} y^(j-1) / j!,  t = m / (m + 2);
+ *               else  e = exp(-2 u),  t = (1 - e) / (1 + e);  copysign(t, x)
+ *     log(v):   (m, e) = frexp(v);  m < 0.7071067811865476: m = 2 m, e = e - 1;  f = m - 1;  s = f / (2 + f);  z = s s;
+ *               P = sum_{j=1..15} z^(j-1) / (2 j + 1);  t2 = 2 s;  e LN2_HI + (e LN2_LO + (t2 + t2 (z P)))
+ *   (1 / j! and 1 / (2 j + 1) are the rounded float64 quotients; 0.5 log(2 pi) is 0.91893853320467274178.)  Each lies within 4 ulp
+ *   of the correctly rounded value on the heads' ranges.  lp is gs_logp_term's expression (policy_head.h) with this log.
+ *   The twins' input row is [obs_i | (float)a_k].  Twin w runs forward with saved activations and gives q_w (float32, widened); the
+ *   head gradient 1.0f goes into its last layer's delta, the backward pass runs to the first layer's delta0, and
+ *     dqda_w[i][k] = sum_j delta0[i][j] * W0[j][obs_dim + k]      W0: the twin's float32 master parameters; float32 products and sums,
+ *                                                                 j ascending from 0 in ONE chain: the order depends on H0 alone
+ *     w* = (q_0 <= q_1) ? 0 : 1 (one twin: that twin);   qmin = q_{w*}
+ *     bc_i = sum_k (a_k - s_k)(a_k - s_k)      s: the stored float64 action, read through the clamped index; 0 when bc_coef == 0
+ *     term_i = (alpha * lp - qmin) + bc_coef * bc_i;      L = (1/n) sum_i term_i
+ *     G_k = ((((alpha * (2 a_k)) / ((1 - a_k a_k) + 1e-6) - dqda_{w*}[k]) + (2 bc_coef) (a_k - s_k)) * (1 - a_k a_k)) / n
+ *     dL/dmean_k = G_k
+ *     dL/dlog_std_k = (G_k * std_k) * eps_k - alpha / n   where -20 <= log_std_k <= 2, and 0 outside
+ *   Then the policy's backward pass, gradient reduction, statistics and Adam are "the learner"'s, by the same kernels: Adam rewrites
+ *   the installed policy image, and the policy learner's step count advances.  The twins' parameters, gradients, Adam state, step
+ *   counts, online and target images are not written.  A row's action, log-probability, q and dqda depend on that row, the
+ *   parameters, seed and draw alone.
+ * gs_learner_stats on the policy afterwards: loss = L, surrogate = (1/n) sum qmin_i, entropy = -(1/n) sum lp_i, approx_kl,
+ * clip_fraction and value_loss NaN, grad_norm as ever; reduced by ONE workgroup in the order of gs_episode_stats.
+ * gs_learner_pathwise_view: device pointers of the last pathwise step's arrays (GS_E_STATE without one); q[w] and dq_da[w] are
+ * NULL for a twin that was not installed.  Lifetime and consumer_stream as gs_learner_view; gs_learner_view on the policy is
+ * GS_E_STATE after a pathwise step (its arrays belong to gs_learner_step). */
+typedef struct gs_pathwise_config {
+  int32_t struct_size;            /* = sizeof(gs_pathwise_config) */
+  int32_t stochastic;             /* 0: eps = 0, the deterministic actor a = tanh(mean) */
+  double alpha, bc_coef;          /* finite, >= 0 */
+  uint64_t seed;
+  uint32_t draw, reserved;
+} gs_pathwise_config;
+typedef struct gs_pathwise_view_out {
+  int32_t n, action_dim, installed, pre_head_stride;   /* installed: bit `which` */
+  const float* pre_head;          /* [n] rows of pre_head_stride floats, the first 2 A of a row: mean | log_std as the heads read them;
+                                     the learners' shared scratch: valid until the next step of ANY learner of the handle */
+  const double* actions;          /* [n][A] */
+  const double* noise;            /* [n][A] */
+  const double* log_probs;        /* [n] */
+  const double* q[2];             /* [n] each */
+  const double* q_min;            /* [n] */
+  const double* bc_terms;         /* [n] */
+  const double* loss_terms;       /* [n] term_i */
+  const int32_t* which;           /* [n] w* */
+  const float* dq_da[2];          /* [n][A] each */
+} gs_pathwise_view_out;
+int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t n, const gs_pathwise_config* cfg, void* consumer_stream);
+int gs_learner_pathwise_view(gs_handle* h, gs_pathwise_view_out* out, void* consumer_stream);
+
 /* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
  * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
  * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
