@@ -56,15 +56,27 @@ def _forward(layers, obs_n, activation: str, exact: bool):
     return rounded, acts
 
 
-def _backward(rounded, acts, ghead, activation: str):
-    """[(dW_l, db_l)] from the head gradient [n, last width] (the layers' dtype)"""
+def _backward(rounded, acts, ghead, activation: str, deltas: Optional[list] = None):
+    """[(dW_l, db_l)] from the head gradient [n, last width] (the layers' dtype); ``deltas``: a list that receives delta_l [n, width
+    of layer l] per layer, in layer order"""
     grads: List[Tuple[np.ndarray, np.ndarray]] = [None] * len(rounded)      # type: ignore[list-item]
     delta = ghead
     for l in range(len(rounded) - 1, -1, -1):
         grads[l] = (delta.T @ acts[l], delta.sum(axis=0))
+        if deltas is not None:
+            deltas.insert(0, delta)
         if l:
             delta = (delta @ rounded[l][0]) * _act_grad(acts[l], activation)
     return grads
+
+
+def _with_backprop(result: Dict[str, Any], exact: bool, acts, deltas) -> Dict[str, Any]:
+    """``exact`` results also carry ``backprop``: ``acts`` (a_0 = the input rows, then every layer's output) and ``deltas`` (dL / d
+    pre-activation per layer) in float64 -- dW_l = delta_l^T a_l and db_l = the column sums of delta_l, term by term, for bounds on
+    what rounding those terms can cost"""
+    if exact:
+        result["backprop"] = dict(acts=acts, deltas=deltas)
+    return result
 
 
 def _gaussian_head(out: np.ndarray, actions):
@@ -122,9 +134,11 @@ def ppo_grad_np(policy_layers, obs_n, actions, lp_old, adv, clip: float, ent_coe
     dlp = np.where(flags, 0.0, -((r * adv) / n))
     ghead = _head_grad(dlp, inside, inv, e, ent_coef, n, exact)
     surrogate, entropy = math.fsum(surr) / n, math.fsum(ent) / n
-    return dict(grads=_backward(rounded, acts, ghead, activation), log_probs_new=lp, ratio=r, clipped=found.astype(np.int32),
-                surrogate_terms=surr, entropy_terms=ent, log_std_outside=~inside, loss=-surrogate - ent_coef * entropy,
-                surrogate=surrogate, entropy=entropy, approx_kl=math.fsum(lp_old - lp) / n, clip_fraction=float(np.count_nonzero(found)) / n)
+    deltas: list = []
+    out = dict(grads=_backward(rounded, acts, ghead, activation, deltas), log_probs_new=lp, ratio=r, clipped=found.astype(np.int32),
+               surrogate_terms=surr, entropy_terms=ent, log_std_outside=~inside, loss=-surrogate - ent_coef * entropy,
+               surrogate=surrogate, entropy=entropy, approx_kl=math.fsum(lp_old - lp) / n, clip_fraction=float(np.count_nonzero(found)) / n)
+    return _with_backprop(out, exact, acts, deltas)
 
 
 def value_grad_np(value_layers, obs_n, returns, exact: bool = False, activation: str = "relu") -> Dict[str, Any]:
@@ -137,7 +151,9 @@ def value_grad_np(value_layers, obs_n, returns, exact: bool = False, activation:
     d = v - np.asarray(returns).astype(np.float64).reshape(n)
     ghead = ((2.0 * d) / n)[:, None]
     ghead = ghead if exact else ghead.astype(np.float32)
-    return dict(grads=_backward(rounded, acts, ghead, activation), values=v, loss_terms=d * d, loss=math.fsum(d * d) / n)
+    deltas: list = []
+    out = dict(grads=_backward(rounded, acts, ghead, activation, deltas), values=v, loss_terms=d * d, loss=math.fsum(d * d) / n)
+    return _with_backprop(out, exact, acts, deltas)
 
 
 def awr_grad_np(policy_layers, obs_n, actions, adv, temperature: float, weight_max: float, ent_coef: float, exact: bool = False,
@@ -355,9 +371,11 @@ def pathwise_grad_np(policy_layers, q_layers_list, obs_n, eps, alpha: float, bc_
         dq.append(delta @ qr[0][0][:, D:])
     found, use, qmin, bc, terms, ghead = _pathwise_head(inside, std, eps, a, lp, qv, dq, alpha, bc_coef, stored_actions, exact, which)
     ghead = ghead.astype(work) if exact else ghead
-    return dict(grads=_backward(rounded, acts, ghead, activation), actions=a, log_probs=lp, q=np.stack(qv, axis=0), q_min=qmin, which=found,
-                dq_da=np.stack(dq, axis=0), bc_terms=bc, loss_terms=terms, log_std_outside=~inside, loss=math.fsum(terms) / n,
-                surrogate=math.fsum(qmin) / n, entropy=-(math.fsum(lp) / n))
+    deltas: list = []
+    res = dict(grads=_backward(rounded, acts, ghead, activation, deltas), actions=a, log_probs=lp, q=np.stack(qv, axis=0), q_min=qmin, which=found,
+               dq_da=np.stack(dq, axis=0), bc_terms=bc, loss_terms=terms, log_std_outside=~inside, loss=math.fsum(terms) / n,
+               surrogate=math.fsum(qmin) / n, entropy=-(math.fsum(lp) / n))
+    return _with_backprop(res, exact, acts, deltas)
 
 
 def _pathwise_check(alpha, bc_coef) -> Tuple[float, float]:
