@@ -32,16 +32,6 @@ struct GS_HIDDEN gs_fed {
 
 namespace {
 
-const char* net_name(int net) {
-  static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2",
-                                 "Q network 0", "Q network 1"};
-  return names[net];
-}
-
-const std::vector<double>& norm_of(const gs_handle* h, int net) {
-  return net == GS_LEARNER_POLICY ? h->pol.h_norm : net >= GS_LEARNER_Q ? h->qnet[net - GS_LEARNER_Q].net.h_norm : h->critic[net - 1].net.h_norm;
-}
-
 GsFedClient client_of(gs_handle::Learner& L) {
   GsFedClient c{};
   c.params = L.params; c.m = L.m; c.v = L.v;
@@ -172,10 +162,12 @@ int gs_fed_create(gs_handle* const* clients, int32_t n_clients, int32_t net, gs_
     if (clients[k]->device != clients[0]->device)
       return fail(nullptr, GS_E_INVALID, "gs_fed_create: client %d lies on device %d, client 0 on device %d", k, clients[k]->device, clients[0]->device);
   }
+  Installed I[GS_FED_MAX_CLIENTS]{};           // (a live learner's network is installed: every *_set* entry drops the learner first)
   for (int k = 0; k < n_clients; ++k)
-    if (!clients[k]->learner[net].live) return fail(nullptr, GS_E_STATE, "gs_fed_create: client %d holds no learner for %s", k, net_name(net));
+    if (!clients[k]->learner[net].live || !installed(clients[k], net, I[k]))
+      return fail(nullptr, GS_E_STATE, "gs_fed_create: client %d holds no learner for %s", k, net_name(net));
   const GsTrainNet& N0 = clients[0]->learner[net].net;
-  const std::vector<double>& norm0 = norm_of(clients[0], net);
+  const std::vector<double>& norm0 = *I[0].norm;
   for (int k = 1; k < n_clients; ++k) {
     const GsTrainNet& N = clients[k]->learner[net].net;
     bool same = N.n_layers == N0.n_layers && N.activation == N0.activation && N.P == N0.P;
@@ -183,7 +175,7 @@ int gs_fed_create(gs_handle* const* clients, int32_t n_clients, int32_t net, gs_
     for (int l = 0; same && l < N0.n_layers; ++l)
       same = N.L[l].kb == N0.L[l].kb && N.L[l].nt == N0.L[l].nt && N.p_off[l] == N0.p_off[l] && (!l || N.T[l].kb == N0.T[l].kb);
     if (!same) return fail(nullptr, GS_E_INVALID, "gs_fed_create: client %d differs from client 0 in layers, widths or activation", k);
-    const std::vector<double>& norm = norm_of(clients[k], net);
+    const std::vector<double>& norm = *I[k].norm;
     if (norm.size() != norm0.size() || (!norm.empty() && memcmp(norm.data(), norm0.data(), norm.size() * sizeof(double))))
       return fail(nullptr, GS_E_INVALID, "gs_fed_create: the observation normalisation of client %d differs from client 0's", k);
   }

@@ -3,8 +3,10 @@
 // kernels_train.hip; with gs_learner_set_loss the head and its statistics are those of kernels_train_offline.hip, DESIGN.md section
 // 21; a Q learner's input rows and targets, and the heads' Q-based signals of gs_learner_set_signal, are gathered first by
 // gs_k_q_gather of kernels_q.hip, section 22), gs_learner_stats / _info / _download / _view read what it left.  gs_learner_step_pathwise is the
-// policy's step whose gradient flows through the twins (kernels_pathwise.hip, section 23).  The learners' buffers are made here and
-// released here: parameters with the learner (learner_drop), what is sized by n with the rollout's buffers (learner_scratch_release).
+// policy's step whose gradient flows through the twins (kernels_pathwise.hip, section 23).  Both steps run one pipeline: the checks on
+// the minibatches, the growth of h->tr and every launch of kernels_train.hip (queue_*) are file-local helpers, stated once; a step adds
+// its head and statistics.  The table of the learners' networks (net_name, installed; handle.h) is defined here.  The learners' buffers
+// are made and released here: parameters with the learner (learner_drop), what is sized by n with the rollout's (learner_scratch_release).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -48,32 +50,117 @@ void learner_release(gs_handle* h) {
   learner_scratch_release(h);
 }
 
-}  // namespace gsi
-
-namespace {
-
 const char* net_name(int net) {
   static const char* names[] = {"the policy", "the value network", "the cost critic of channel 0", "the cost critic of channel 1", "the cost critic of channel 2",
                                  "Q network 0", "Q network 1"};
   return names[net];
 }
 
-bool net_ok(int net) { return net >= 0 && net < GS_LEARNER_COUNT; }
-bool net_is_q(int net) { return net >= GS_LEARNER_Q; }
-
-// the installed network `net` trains: its layers, widths, activation and host normalisation; false: not installed
-struct Installed { const GsPolicyLayerF32* L; const int32_t* dims; int n_layers, activation; const std::vector<double>* norm; const DevBuf<char>* blob; };
-bool installed(gs_handle* h, int net, Installed& I) {
+bool installed(const gs_handle* h, int net, Installed& I) {
   if (net == GS_LEARNER_POLICY) {
     const gs_handle::Policy& p = h->pol;
     if (!p.set || p.compute != GS_COMPUTE_F32) return false;
     I = Installed{p.args32.L, p.dims, p.args32.n_layers, p.args32.activation, &p.h_norm, &p.blob};
     return true;
   }
-  const gs_handle::Value& v = net_is_q(net) ? h->qnet[net - GS_LEARNER_Q].net : h->critic[net - 1].net;
+  const gs_handle::Value& v = net >= GS_LEARNER_Q ? h->qnet[net - GS_LEARNER_Q].net : h->critic[net - 1].net;
   if (!v.set) return false;
   I = Installed{v.args.L, v.dims, v.args.n_layers, v.args.activation, &v.h_norm, &v.blob};
   return true;
+}
+
+}  // namespace gsi
+
+namespace {
+
+bool net_ok(int net) { return net >= 0 && net < GS_LEARNER_COUNT; }
+bool net_is_q(int net) { return net >= GS_LEARNER_Q; }
+
+// ---- the stages the two steps share, each stated once; `who` is the entry's name, for the message ----
+// gs_onpolicy_prepare has run on the last rollout, in float32
+int check_batches(gs_handle* h, const char* who) {
+  const gs_handle::OnPolicyBatches& ob = h->opb;
+  if (!ob.prepared_on || ob.prepared_on != h->ro.calls) return fail(h, GS_E_STATE, "%s: gs_onpolicy_prepare has not run on the last rollout", who);
+  if (ob.cfg.dtype != GS_COMPUTE_F32) return fail(h, GS_E_STATE, "%s: the minibatches must be prepared with dtype GS_COMPUTE_F32", who);
+  return GS_OK;
+}
+
+// the minibatches' shift and scale are, bit for bit, the normalisation learner `net`'s network `I` was installed with
+int check_norm(gs_handle* h, const char* who, int net, const Installed& I) {
+  const gs_handle::OnPolicyBatches& ob = h->opb;
+  const int D = h->obs_dim, D16 = 16 * I.L[0].kb;
+  const size_t Ds = (size_t)((D + 1) & ~1);
+  for (int c = 0; c < D; ++c) {
+    const double shift = ob.have_norm ? ob.h_norm[c] : 0.0, scale = ob.have_norm ? ob.h_norm[Ds + c] : 1.0;
+    if (memcmp(&shift, &(*I.norm)[c], sizeof(double)) || memcmp(&scale, &(*I.norm)[D16 + c], sizeof(double)))
+      return fail(h, GS_E_STATE, "%s: the minibatches' obs_shift / obs_scale differ from the normalisation of %s (column %d)", who, net_name(net), c);
+  }
+  return GS_OK;
+}
+
+// h->tr holds network N's saved activations, backward pass and partial gradients over n rows
+int grow_scratch(gs_handle* h, const GsTrainNet& N, int n) {
+  gs_handle::TrainScratch& tr = h->tr;
+  int rc = GS_OK;
+  if ((rc = tr.acts.grow(h, (size_t)n * N.row_stride, "the learner's saved activations"))) return rc;
+  if ((rc = tr.deltas.grow(h, (size_t)n * N.row_stride, "the learner's backward pass"))) return rc;
+  return tr.partial.grow(h, (size_t)gs_tr_segments(n) * N.P, "the learner's partial gradients");
+}
+
+int queue_forward(gs_handle* h, const GsTrainNet& N, const float* obs, float* acts, int n, int D) {
+  GsTrainFwdArgs F{};
+  F.N = N; F.obs = obs; F.acts = acts; F.n = n; F.D = D;
+  F.obs_stride = gs_val_obs_stride(N.L[0].kb); F.panel_kb = gs_val_panel_kb(N.L[0].kb);
+  hipLaunchKernelGGL(gs_k_train_forward, dim3((n + GS_TR_ROWS - 1) / GS_TR_ROWS), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(N.L[0].kb), h->stream, F);
+  HIPCHK(h, hipGetLastError());
+  return GS_OK;
+}
+
+// from the head gradient in the last layer's block of `deltas` down to layer 0; a one-layer network has nothing to pass back
+int queue_bwd_data(gs_handle* h, const GsTrainNet& N, const float* acts, float* deltas, int n) {
+  if (N.n_layers < 2) return GS_OK;
+  GsTrainBwdArgs B{};
+  B.N = N; B.acts = acts; B.deltas = deltas; B.n = n;
+  hipLaunchKernelGGL(gs_k_train_bwd_data, dim3((n + GS_TR_ROWS - 1) / GS_TR_ROWS), dim3(64 * GS_POL_WAVES), 0, h->stream, B);
+  HIPCHK(h, hipGetLastError());
+  return GS_OK;
+}
+
+// the weight gradients of h->tr's passes over the input rows `obs`, then their sum into Ln.grad.  Returns the reduction's workgroup
+// count, which the statistics kernel needs, or (negative) the code of a failure
+int queue_grad_reduce(gs_handle* h, gs_handle::Learner& Ln, const float* obs, int n, int D) {
+  const GsTrainNet& N = Ln.net;
+  gs_handle::TrainScratch& tr = h->tr;
+  const int segments = gs_tr_segments(n);
+  GsTrainGradArgs G{};
+  G.N = N; G.obs = obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
+  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
+  int blocks = 0;
+  for (int l = 0; l < N.n_layers; ++l) {
+    G.blk0[l] = blocks;
+    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
+    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
+  }
+  G.blk0[N.n_layers] = blocks;
+  hipLaunchKernelGGL(gs_k_train_grad, dim3(blocks, segments), dim3(64), 0, h->stream, G);
+  HIPCHK(h, hipGetLastError());
+  GsTrainReduceArgs R{tr.partial, Ln.grad, Ln.blocksum, N.P, segments};
+  hipLaunchKernelGGL(gs_k_train_reduce, dim3(gs_tr_red_blocks(N.P)), dim3(GS_TR_RED_THREADS), 0, h->stream, R);
+  HIPCHK(h, hipGetLastError());
+  return gs_tr_red_blocks(N.P);
+}
+
+// Adam's step Ln.steps + 1 on Ln.grad and the norm in Ln.stats; the scalars in float64, each rounded once to float32
+int queue_adam(gs_handle* h, gs_handle::Learner& Ln) {
+  const gs_learner_config& cfg = Ln.cfg;
+  const double t = (double)(Ln.steps + 1);
+  GsTrainAdamArgs A{};
+  A.N = Ln.net; A.params = Ln.params; A.grad = Ln.grad; A.m = Ln.m; A.v = Ln.v; A.stats = Ln.stats; A.max_grad_norm = cfg.max_grad_norm;
+  A.wd = (float)cfg.weight_decay; A.b1 = (float)cfg.beta1; A.omb1 = (float)(1.0 - cfg.beta1); A.b2 = (float)cfg.beta2; A.omb2 = (float)(1.0 - cfg.beta2);
+  A.bc2s = (float)std::sqrt(1.0 - std::pow(cfg.beta2, t)); A.eps = (float)cfg.eps; A.step = (float)(cfg.lr / (1.0 - std::pow(cfg.beta1, t)));
+  hipLaunchKernelGGL(gs_k_train_adam, dim3((Ln.net.P + 255) / 256), dim3(256), 0, h->stream, A);
+  HIPCHK(h, hipGetLastError());
+  return GS_OK;
 }
 
 }  // namespace
@@ -114,8 +201,7 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
   N.row_stride = stride; N.P = (int32_t)P;
   Ln.A = net == GS_LEARNER_POLICY ? h->action_dim : 0;
   int rc = alloc_all(h, "the learner's parameters", Ln.params.want((size_t)P), Ln.grad.want((size_t)P), Ln.m.want((size_t)P), Ln.v.want((size_t)P),
-                     Ln.wt.want(wt_floats), Ln.stats.want(GS_TR_STAT_COUNT),
-                     Ln.blocksum.want((size_t)((P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD))));
+                     Ln.wt.want(wt_floats), Ln.stats.want(GS_TR_STAT_COUNT), Ln.blocksum.want((size_t)gs_tr_red_blocks(N.P)));
   if (rc) return rc;
   // the installed image, unpacked into torch order (the image holds float32 values: the snapshot is exact), and its transposes
   const float* const image = (const float*)I.blob->p;
@@ -125,17 +211,9 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(img.data(), image, image_floats * sizeof(float), hipMemcpyDeviceToHost));
   for (int l = 0; l < I.n_layers; ++l) {
-    const int n_out = N.dims[l + 1], n_in = N.dims[l], kb = I.L[l].kb, nt = I.L[l].nt;
-    const float* w = img.data() + (I.L[l].w - image);
-    const float* b = img.data() + (I.L[l].b - image);
-    float* dst = flat.data() + N.p_off[l];
-    for (int o = 0; o < n_out; ++o)
-      for (int k = 0; k < n_in; ++k) {
-        const float x = w[(((size_t)(o >> 4) * kb + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (o & 15)) * 4 + (k & 3)];
-        dst[(size_t)o * n_in + k] = x;
-        if (l) wt[wt_off[l] + (((size_t)(k >> 4) * nt + (o >> 4)) * 64 + ((o & 15) >> 2) * 16 + (k & 15)) * 4 + (o & 3)] = x;
-      }
-    for (int o = 0; o < n_out; ++o) dst[(size_t)n_out * n_in + o] = b[o];
+    const int kb = I.L[l].kb, nt = I.L[l].nt;
+    const GsPolicyLayerF32 host{img.data() + (I.L[l].w - image), img.data() + (I.L[l].b - image), kb, nt};
+    gs_policy_unpack_f32(host, N.dims[l + 1], N.dims[l], flat.data() + N.p_off[l], l ? wt.data() + wt_off[l] : nullptr);
     if (l) N.T[l] = GsPolicyLayerF32{Ln.wt.p + wt_off[l], nullptr, nt, kb};
   }
   HIPCHK(h, hipMemcpy(Ln.params, flat.data(), (size_t)P * sizeof(float), hipMemcpyHostToDevice));
@@ -160,15 +238,10 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   if (!Ln.live || !installed(h, net, I)) return fail(h, GS_E_STATE, "gs_learner_step: no learner for %s (gs_learner_create after the network was installed)", net_name(net));
   const gs_handle::OnPolicyBatches& ob = h->opb;
   const gs_handle::Rollout& ro = h->ro;
-  if (!ob.prepared_on || ob.prepared_on != ro.calls) return fail(h, GS_E_STATE, "gs_learner_step: gs_onpolicy_prepare has not run on the last rollout");
-  if (ob.cfg.dtype != GS_COMPUTE_F32) return fail(h, GS_E_STATE, "gs_learner_step: the minibatches must be prepared with dtype GS_COMPUTE_F32");
-  const int D = h->obs_dim, D16 = 16 * I.L[0].kb;
-  const size_t Ds = (size_t)((D + 1) & ~1);
-  for (int c = 0; c < D; ++c) {
-    const double shift = ob.have_norm ? ob.h_norm[c] : 0.0, scale = ob.have_norm ? ob.h_norm[Ds + c] : 1.0;
-    if (memcmp(&shift, &(*I.norm)[c], sizeof(double)) || memcmp(&scale, &(*I.norm)[D16 + c], sizeof(double)))
-      return fail(h, GS_E_STATE, "gs_learner_step: the minibatches' obs_shift / obs_scale differ from the normalisation of %s (column %d)", net_name(net), c);
-  }
+  int rc = GS_OK;
+  if ((rc = check_batches(h, "gs_learner_step"))) return rc;
+  if ((rc = check_norm(h, "gs_learner_step", net, I))) return rc;
+  const int D = h->obs_dim;
   const bool policy = net == GS_LEARNER_POLICY, qnet = net_is_q(net);
   // what the head regresses on or weights with: a field of the batch, or (a Q learner, GS_SIGNAL_Q) an array of gs_rollout_evaluate_q
   // gathered through the indices into tr.qy
@@ -180,13 +253,9 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   if (!batch->observations || (!gathered && !target) || ((policy || gathered) && !batch->indices))
     return fail(h, GS_E_INVALID, "gs_learner_step: the batch lacks %s", !batch->observations ? "observations" : (!gathered && !target) ? (policy ? "advantages" : "returns") : "indices");
   GS_ENTER(h);
-  int rc = GS_OK;
   const GsTrainNet& N = Ln.net;
-  const int segments = (n + GS_TR_SEG - 1) / GS_TR_SEG;
   gs_handle::TrainScratch& tr = h->tr;
-  if ((rc = tr.acts.grow(h, (size_t)n * N.row_stride, "the learner's saved activations"))) return rc;
-  if ((rc = tr.deltas.grow(h, (size_t)n * N.row_stride, "the learner's backward pass"))) return rc;
-  if ((rc = tr.partial.grow(h, (size_t)segments * N.P, "the learner's partial gradients"))) return rc;
+  if ((rc = grow_scratch(h, N, n))) return rc;
   if ((rc = Ln.term0.grow(h, (size_t)n, "the learner's loss terms"))) return rc;
   if (policy) {
     if ((rc = Ln.term1.grow(h, (size_t)n, "the learner's entropy terms"))) return rc;
@@ -198,7 +267,7 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   if (gathered && (rc = tr.qy.grow(h, (size_t)n, "the learner's gathered targets"))) return rc;
   if (qnet && (rc = tr.qsa.grow(h, (size_t)n * Din, "the Q learner's input rows"))) return rc;
   Ln.n_last = 0;           // (until every launch is queued)
-  const int last = N.n_layers - 1, tiles = (n + GS_TR_ROWS - 1) / GS_TR_ROWS;
+  const int last = N.n_layers - 1;
   const gs_learner_config& cfg = Ln.cfg;
 
   if (gathered) {
@@ -213,85 +282,58 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
     target = tr.qy.p;
   }
 
-  GsTrainFwdArgs F{};
-  F.N = N; F.obs = qnet ? tr.qsa.p : (const float*)batch->observations; F.acts = tr.acts; F.n = n; F.D = Din;
-  F.obs_stride = gs_val_obs_stride(N.L[0].kb); F.panel_kb = gs_val_panel_kb(N.L[0].kb);
-  hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(N.L[0].kb), h->stream, F);
-  HIPCHK(h, hipGetLastError());
+  const float* const rows = qnet ? tr.qsa.p : (const float*)batch->observations;
+  if ((rc = queue_forward(h, N, rows, tr.acts, n, Din))) return rc;
 
-  GsTrainHeadArgs H{};
-  H.pre = tr.acts + N.col_off[last]; H.ghead = tr.deltas + N.col_off[last];
-  H.n = n; H.row_stride = N.row_stride; H.width16 = 16 * N.L[last].nt; H.A = Ln.A;
-  H.term0 = Ln.term0;
-  if (policy) {
-    H.idx = batch->indices; H.act = ro.act; H.logp = ro.logp; H.adv = (const float*)target; H.N = ob.N;
-    H.clip = cfg.clip; H.ent_coef = cfg.ent_coef;
-    H.lp_new = Ln.lp_new; H.ratio = Ln.ratio; H.clipped = Ln.clipped; H.term1 = Ln.term1;
-  } else {
-    H.ret = (const float*)target;
-  }
-  if (loss == GS_LOSS_AWR) {                 // (the heads of kernels_train_offline.hip: the same grid, the same arrays)
+  // the head: one thread per sample on the pre-head values, dL/d(pre-head) into the last layer's block of deltas
+  const float* const pre = tr.acts + N.col_off[last];
+  float* const ghead = tr.deltas + N.col_off[last];
+  const int width16 = 16 * N.L[last].nt;
+  if (loss == GS_LOSS_AWR) {                 // (the heads of kernels_train_offline.hip: the same grid, the same arrays; AWR is the policy's)
     GsTrainAwrHeadArgs W{};
-    W.pre = H.pre; W.ghead = H.ghead; W.n = n; W.row_stride = H.row_stride; W.width16 = H.width16; W.A = H.A;
-    W.idx = H.idx; W.act = H.act; W.adv = H.adv; W.N = H.N;
+    W.pre = pre; W.ghead = ghead; W.n = n; W.row_stride = N.row_stride; W.width16 = width16; W.A = Ln.A;
+    W.idx = batch->indices; W.act = ro.act; W.adv = (const float*)target; W.N = ob.N;
     W.temperature = Ln.loss.temperature; W.weight_max = Ln.loss.weight_max; W.ent_coef = cfg.ent_coef;
     W.lp_new = Ln.lp_new; W.weight = Ln.ratio; W.capped = Ln.clipped; W.term0 = Ln.term0; W.term1 = Ln.term1;
     hipLaunchKernelGGL(gs_k_train_head_awr, dim3((n + 63) / 64), dim3(64), 0, h->stream, W);
-  } else if (loss == GS_LOSS_EXPECTILE) {
+  } else if (loss == GS_LOSS_EXPECTILE) {    // (a critic's)
     GsTrainExpectileArgs E{};
-    E.pre = H.pre; E.ghead = H.ghead; E.ret = H.ret; E.term0 = Ln.term0; E.n = n; E.row_stride = H.row_stride; E.width16 = H.width16;
+    E.pre = pre; E.ghead = ghead; E.ret = (const float*)target; E.term0 = Ln.term0; E.n = n; E.row_stride = N.row_stride; E.width16 = width16;
     E.tau = Ln.loss.expectile;
     hipLaunchKernelGGL(gs_k_train_head_expectile, dim3((n + 63) / 64), dim3(64), 0, h->stream, E);
   } else {
+    GsTrainHeadArgs H{};
+    H.pre = pre; H.ghead = ghead; H.n = n; H.row_stride = N.row_stride; H.width16 = width16; H.A = Ln.A;
+    H.term0 = Ln.term0;
+    if (policy) {
+      H.idx = batch->indices; H.act = ro.act; H.logp = ro.logp; H.adv = (const float*)target; H.N = ob.N;
+      H.clip = cfg.clip; H.ent_coef = cfg.ent_coef;
+      H.lp_new = Ln.lp_new; H.ratio = Ln.ratio; H.clipped = Ln.clipped; H.term1 = Ln.term1;
+    } else {
+      H.ret = (const float*)target;
+    }
     hipLaunchKernelGGL(gs_k_train_head, dim3((n + 63) / 64), dim3(64), 0, h->stream, H);
   }
   HIPCHK(h, hipGetLastError());
 
-  if (last > 0) {
-    GsTrainBwdArgs B{};
-    B.N = N; B.acts = tr.acts; B.deltas = tr.deltas; B.n = n;
-    hipLaunchKernelGGL(gs_k_train_bwd_data, dim3(tiles), dim3(64 * GS_POL_WAVES), 0, h->stream, B);
-    HIPCHK(h, hipGetLastError());
-  }
+  if ((rc = queue_bwd_data(h, N, tr.acts, tr.deltas, n))) return rc;
+  const int red_blocks = queue_grad_reduce(h, Ln, rows, n, Din);
+  if (red_blocks < 0) return red_blocks;
 
-  GsTrainGradArgs G{};
-  G.N = N; G.obs = F.obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = Din;
-  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
-  int blocks = 0;
-  for (int l = 0; l <= last; ++l) {
-    G.blk0[l] = blocks;
-    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
-    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
-  }
-  G.blk0[last + 1] = blocks;
-  hipLaunchKernelGGL(gs_k_train_grad, dim3(blocks, segments), dim3(64), 0, h->stream, G);
-  HIPCHK(h, hipGetLastError());
-
-  const int red_blocks = (N.P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD);
-  GsTrainReduceArgs R{tr.partial, Ln.grad, Ln.blocksum, N.P, segments};
-  hipLaunchKernelGGL(gs_k_train_reduce, dim3(red_blocks), dim3(GS_TR_RED_THREADS), 0, h->stream, R);
-  HIPCHK(h, hipGetLastError());
-
-  GsTrainStatArgs S{};
-  S.term0 = Ln.term0; S.term1 = Ln.term1; S.lp_new = Ln.lp_new; S.logp = ro.logp; S.idx = batch->indices; S.clipped = Ln.clipped;
-  S.blocksum = Ln.blocksum; S.stats = Ln.stats; S.N = ob.N; S.n = n; S.blocks = red_blocks; S.policy = policy; S.ent_coef = cfg.ent_coef;
   if (loss == GS_LOSS_AWR) {
     GsTrainAwrStatArgs W{};
-    W.term0 = S.term0; W.term1 = S.term1; W.lp_new = S.lp_new; W.logp = ro.logp_recorded ? ro.logp.p : nullptr; W.idx = S.idx; W.capped = S.clipped;
-    W.blocksum = S.blocksum; W.stats = S.stats; W.N = S.N; W.n = n; W.blocks = red_blocks; W.ent_coef = cfg.ent_coef;
+    W.term0 = Ln.term0; W.term1 = Ln.term1; W.lp_new = Ln.lp_new; W.logp = ro.logp_recorded ? ro.logp.p : nullptr; W.idx = batch->indices; W.capped = Ln.clipped;
+    W.blocksum = Ln.blocksum; W.stats = Ln.stats; W.N = ob.N; W.n = n; W.blocks = red_blocks; W.ent_coef = cfg.ent_coef;
     hipLaunchKernelGGL(gs_k_train_stats_awr, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, W);
   } else {                                   // (an expectile critic: a critic's sum of term0)
+    GsTrainStatArgs S{};
+    S.term0 = Ln.term0; S.term1 = Ln.term1; S.lp_new = Ln.lp_new; S.logp = ro.logp; S.idx = batch->indices; S.clipped = Ln.clipped;
+    S.blocksum = Ln.blocksum; S.stats = Ln.stats; S.N = ob.N; S.n = n; S.blocks = red_blocks; S.policy = policy; S.ent_coef = cfg.ent_coef;
     hipLaunchKernelGGL(gs_k_train_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, S);
   }
   HIPCHK(h, hipGetLastError());
 
-  const double t = (double)(Ln.steps + 1);
-  GsTrainAdamArgs A{};
-  A.N = N; A.params = Ln.params; A.grad = Ln.grad; A.m = Ln.m; A.v = Ln.v; A.stats = Ln.stats; A.max_grad_norm = cfg.max_grad_norm;
-  A.wd = (float)cfg.weight_decay; A.b1 = (float)cfg.beta1; A.omb1 = (float)(1.0 - cfg.beta1); A.b2 = (float)cfg.beta2; A.omb2 = (float)(1.0 - cfg.beta2);
-  A.bc2s = (float)std::sqrt(1.0 - std::pow(cfg.beta2, t)); A.eps = (float)cfg.eps; A.step = (float)(cfg.lr / (1.0 - std::pow(cfg.beta1, t)));
-  hipLaunchKernelGGL(gs_k_train_adam, dim3((N.P + 255) / 256), dim3(256), 0, h->stream, A);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = queue_adam(h, Ln))) return rc;
   Ln.steps += 1; Ln.n_last = n;
   return publish(h, h->stream, Ln.ev, consumer_stream);
 }
@@ -381,35 +423,22 @@ int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, i
   if (!have[0] && !have[1]) return fail(h, GS_E_STATE, "gs_learner_step_pathwise before gs_q_mlp_set: no Q network is installed");
   const gs_handle::OnPolicyBatches& ob = h->opb;
   const gs_handle::Rollout& ro = h->ro;
-  if (!ob.prepared_on || ob.prepared_on != ro.calls) return fail(h, GS_E_STATE, "gs_learner_step_pathwise: gs_onpolicy_prepare has not run on the last rollout");
-  if (ob.cfg.dtype != GS_COMPUTE_F32) return fail(h, GS_E_STATE, "gs_learner_step_pathwise: the minibatches must be prepared with dtype GS_COMPUTE_F32");
-  const size_t Ds = (size_t)((D + 1) & ~1);
-  for (int k = -1; k < 2; ++k) {             // the policy, then the installed twins: gs_learner_step's comparison per network
-    if (k >= 0 && !have[k]) continue;
-    const Installed& J = k < 0 ? I : IQ[k];
-    const int D16 = 16 * J.L[0].kb;
-    for (int c = 0; c < D; ++c) {
-      const double shift = ob.have_norm ? ob.h_norm[c] : 0.0, scale = ob.have_norm ? ob.h_norm[Ds + c] : 1.0;
-      if (memcmp(&shift, &(*J.norm)[c], sizeof(double)) || memcmp(&scale, &(*J.norm)[D16 + c], sizeof(double)))
-        return fail(h, GS_E_STATE, "gs_learner_step_pathwise: the minibatches' obs_shift / obs_scale differ from the normalisation of %s (column %d)",
-                    net_name(k < 0 ? GS_LEARNER_POLICY : GS_LEARNER_Q + k), c);
-    }
-  }
+  int rc = GS_OK;
+  if ((rc = check_batches(h, "gs_learner_step_pathwise"))) return rc;
+  if ((rc = check_norm(h, "gs_learner_step_pathwise", GS_LEARNER_POLICY, I))) return rc;
+  for (int w = 0; w < 2; ++w)
+    if (have[w] && (rc = check_norm(h, "gs_learner_step_pathwise", GS_LEARNER_Q + w, IQ[w]))) return rc;
   const bool with_bc = cfg->bc_coef != 0.0;
   if (!batch->observations || (with_bc && !batch->indices))
     return fail(h, GS_E_INVALID, "gs_learner_step_pathwise: the batch lacks %s", !batch->observations ? "observations" : "indices (bc_coef != 0 reads the stored actions)");
   GS_ENTER(h);
-  int rc = GS_OK;
   const GsTrainNet& N = Ln.net;
-  const int segments = (n + GS_TR_SEG - 1) / GS_TR_SEG;
   gs_handle::TrainScratch& tr = h->tr;
   gs_handle::Pathwise& pw = h->pw;
   int q_stride = 0;
   for (int w = 0; w < 2; ++w)
     if (have[w]) q_stride = std::max(q_stride, (int)h->learner[GS_LEARNER_Q + w].net.row_stride);
-  if ((rc = tr.acts.grow(h, (size_t)n * N.row_stride, "the learner's saved activations"))) return rc;
-  if ((rc = tr.deltas.grow(h, (size_t)n * N.row_stride, "the learner's backward pass"))) return rc;
-  if ((rc = tr.partial.grow(h, (size_t)segments * N.P, "the learner's partial gradients"))) return rc;
+  if ((rc = grow_scratch(h, N, n))) return rc;
   if ((rc = pw.acts.grow(h, (size_t)n * q_stride, "the actor step's saved activations of a twin"))) return rc;
   if ((rc = pw.deltas.grow(h, (size_t)n * q_stride, "the actor step's backward pass of a twin"))) return rc;
   if ((rc = pw.qsa.grow(h, (size_t)n * DA, "the actor step's input rows"))) return rc;
@@ -423,16 +452,11 @@ int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, i
   if ((rc = pw.terms.grow(h, (size_t)n, "the actor step's loss terms"))) return rc;
   if ((rc = pw.which.grow(h, (size_t)n, "the actor step's choices"))) return rc;
   Ln.n_last = 0; pw.n_last = 0;              // (until every launch is queued; gs_learner_view's arrays are gs_learner_step's)
-  const int last = N.n_layers - 1, tiles = (n + GS_TR_ROWS - 1) / GS_TR_ROWS;
-  const gs_learner_config& lc = Ln.cfg;
+  const int last = N.n_layers - 1;
   const float* const obs = (const float*)batch->observations;
 
   // the policy's forward pass: its saved activations stay in tr.acts until its backward pass
-  GsTrainFwdArgs F{};
-  F.N = N; F.obs = obs; F.acts = tr.acts; F.n = n; F.D = D;
-  F.obs_stride = gs_val_obs_stride(N.L[0].kb); F.panel_kb = gs_val_panel_kb(N.L[0].kb);
-  hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(N.L[0].kb), h->stream, F);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = queue_forward(h, N, obs, tr.acts, n, D))) return rc;
 
   GsPwSampleArgs S{};
   S.pre = tr.acts + N.col_off[last]; S.actions = pw.actions; S.noise = pw.noise; S.logp = pw.logp; S.sa = pw.qsa;
@@ -449,20 +473,11 @@ int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, i
     const gs_handle::Learner& Lq = h->learner[GS_LEARNER_Q + w];
     const GsTrainNet& Q = Lq.net;
     const int qlast = Q.n_layers - 1;
-    GsTrainFwdArgs FQ{};
-    FQ.N = Q; FQ.obs = pw.qsa; FQ.acts = pw.acts; FQ.n = n; FQ.D = DA;
-    FQ.obs_stride = gs_val_obs_stride(Q.L[0].kb); FQ.panel_kb = gs_val_panel_kb(Q.L[0].kb);
-    hipLaunchKernelGGL(gs_k_train_forward, dim3(tiles), dim3(64 * GS_POL_WAVES), gs_tr_lds_bytes(Q.L[0].kb), h->stream, FQ);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = queue_forward(h, Q, pw.qsa, pw.acts, n, DA))) return rc;
     GsPwSeedArgs SD{pw.deltas + Q.col_off[qlast], n, Q.row_stride, 16 * Q.L[qlast].nt, 0};
     hipLaunchKernelGGL(gs_k_pw_seed, dim3((n + 63) / 64), dim3(64), 0, h->stream, SD);
     HIPCHK(h, hipGetLastError());
-    if (qlast > 0) {
-      GsTrainBwdArgs BQ{};
-      BQ.N = Q; BQ.acts = pw.acts; BQ.deltas = pw.deltas; BQ.n = n;
-      hipLaunchKernelGGL(gs_k_train_bwd_data, dim3(tiles), dim3(64 * GS_POL_WAVES), 0, h->stream, BQ);
-      HIPCHK(h, hipGetLastError());
-    }
+    if ((rc = queue_bwd_data(h, Q, pw.acts, pw.deltas, n))) return rc;
     GsPwInputGradArgs IG{};
     IG.delta0 = pw.deltas + Q.col_off[0]; IG.qpre = pw.acts + Q.col_off[qlast]; IG.W0 = Lq.params.p + Q.p_off[0];
     IG.dqda = pw.dqda + (size_t)w * n * A; IG.q = pw.q + (size_t)w * n;
@@ -480,39 +495,14 @@ int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, i
   hipLaunchKernelGGL(gs_k_pw_head, dim3((n + 63) / 64), dim3(64), 0, h->stream, H);
   HIPCHK(h, hipGetLastError());
 
-  if (last > 0) {
-    GsTrainBwdArgs B{};
-    B.N = N; B.acts = tr.acts; B.deltas = tr.deltas; B.n = n;
-    hipLaunchKernelGGL(gs_k_train_bwd_data, dim3(tiles), dim3(64 * GS_POL_WAVES), 0, h->stream, B);
-    HIPCHK(h, hipGetLastError());
-  }
-  GsTrainGradArgs G{};
-  G.N = N; G.obs = obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
-  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
-  int blocks = 0;
-  for (int l = 0; l <= last; ++l) {
-    G.blk0[l] = blocks;
-    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
-    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
-  }
-  G.blk0[last + 1] = blocks;
-  hipLaunchKernelGGL(gs_k_train_grad, dim3(blocks, segments), dim3(64), 0, h->stream, G);
-  HIPCHK(h, hipGetLastError());
-  const int red_blocks = (N.P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD);
-  GsTrainReduceArgs R{tr.partial, Ln.grad, Ln.blocksum, N.P, segments};
-  hipLaunchKernelGGL(gs_k_train_reduce, dim3(red_blocks), dim3(GS_TR_RED_THREADS), 0, h->stream, R);
-  HIPCHK(h, hipGetLastError());
+  // the policy's backward pass, reduction, statistics and Adam, as gs_learner_step's
+  if ((rc = queue_bwd_data(h, N, tr.acts, tr.deltas, n))) return rc;
+  const int red_blocks = queue_grad_reduce(h, Ln, obs, n, D);
+  if (red_blocks < 0) return red_blocks;
   GsPwStatArgs ST{pw.terms, pw.qmin, pw.logp, Ln.blocksum, Ln.stats, n, red_blocks};
   hipLaunchKernelGGL(gs_k_pw_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, ST);
   HIPCHK(h, hipGetLastError());
-
-  const double t = (double)(Ln.steps + 1);
-  GsTrainAdamArgs AD{};
-  AD.N = N; AD.params = Ln.params; AD.grad = Ln.grad; AD.m = Ln.m; AD.v = Ln.v; AD.stats = Ln.stats; AD.max_grad_norm = lc.max_grad_norm;
-  AD.wd = (float)lc.weight_decay; AD.b1 = (float)lc.beta1; AD.omb1 = (float)(1.0 - lc.beta1); AD.b2 = (float)lc.beta2; AD.omb2 = (float)(1.0 - lc.beta2);
-  AD.bc2s = (float)std::sqrt(1.0 - std::pow(lc.beta2, t)); AD.eps = (float)lc.eps; AD.step = (float)(lc.lr / (1.0 - std::pow(lc.beta1, t)));
-  hipLaunchKernelGGL(gs_k_train_adam, dim3((N.P + 255) / 256), dim3(256), 0, h->stream, AD);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = queue_adam(h, Ln))) return rc;
   Ln.steps += 1; pw.n_last = n; pw.installed = (have[0] ? 1 : 0) | (have[1] ? 2 : 0);
   return publish(h, h->stream, Ln.ev, consumer_stream);
 }

@@ -223,16 +223,13 @@ int gs_q_target_download(gs_handle* h, int32_t which, float* params) {
   std::vector<float> img(Q.image_floats);
   HIPCHK(h, hipMemcpyAsync(img.data(), Q.target, Q.image_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  // the packed image into torch order (policy.h: W[16 nt + (lane & 15)][16 kb + 4 (lane >> 4) + j])
+  // the packed image into torch order
   float* dst = params;
   for (int l = 0; l < Q.qargs.n_layers; ++l) {
-    const int n_out = Q.net.dims[l + 1], n_in = Q.net.dims[l], kb = Q.TL[l].kb;
-    const float* w = img.data() + (Q.TL[l].w - Q.target.p);
-    const float* b = img.data() + (Q.TL[l].b - Q.target.p);
-    for (int o = 0; o < n_out; ++o)
-      for (int k = 0; k < n_in; ++k)
-        *dst++ = w[(((size_t)(o >> 4) * kb + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (o & 15)) * 4 + (k & 3)];
-    for (int o = 0; o < n_out; ++o) *dst++ = b[o];
+    const int n_out = Q.net.dims[l + 1], n_in = Q.net.dims[l];
+    const GsPolicyLayerF32 host{img.data() + (Q.TL[l].w - Q.target.p), img.data() + (Q.TL[l].b - Q.target.p), Q.TL[l].kb, Q.TL[l].nt};
+    gs_policy_unpack_f32(host, n_out, n_in, dst, nullptr);
+    dst += (size_t)n_out * (n_in + 1);
   }
   return GS_OK;
 }

@@ -2,8 +2,8 @@
 // kernels of kernels_fed.hip, shared with abi_fed.hip.
 //
 // Parameters are flat float32 in torch order, as the learner's (train.h).  The images a round rewrites are the learner's: the forward
-// image of layer l ([nt][kb][64 lanes][4], policy.h) and, for l >= 1, the image of W_l^T.  The slot formulas below restate those of
-// gs_k_train_adam (kernels_train.hip), which is the other writer of these images.
+// image of layer l ([nt][kb][64 lanes][4], policy.h) and, for l >= 1, the image of W_l^T.  gs_k_fed_apply finds a parameter's slots
+// with policy.h's gs_pol32_slot; gs_k_train_adam (kernels_train.hip) is the other writer of these images.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,15 +16,6 @@ constexpr int GS_FED_RED_THREADS = 256, GS_FED_RED_PER_THREAD = 4, GS_FED_BLOCK 
 constexpr int GS_FED_SUM_THREADS = 1024;
 constexpr int GS_FED_APPLY_THREADS = 256;
 constexpr int GS_FED_MAX_PAIRS = GS_FED_MAX_CLIENTS * (GS_FED_MAX_CLIENTS + 1) / 2;
-
-// W_l[o][k] in the forward image of a layer with kb k blocks
-__host__ __device__ inline size_t gs_fed_slot_w(int o, int k, int kb) {
-  return (((size_t)(o >> 4) * kb + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (o & 15)) * 4 + (k & 3);
-}
-// W_l[o][k] in the image of W_l^T (the output index is k, the k axis runs over o), kbt = that image's k blocks = nt of the forward one
-__host__ __device__ inline size_t gs_fed_slot_t(int o, int k, int kbt) {
-  return (((size_t)(k >> 4) * kbt + (o >> 4)) * 64 + ((o & 15) >> 2) * 16 + (k & 15)) * 4 + (o & 3);
-}
 
 // what a round reads and writes of one client, rebuilt from the handle's learner on every call
 struct GsFedClient {

@@ -416,6 +416,12 @@ void batches_release(gs_handle* h);
 void learner_drop(gs_handle* h, int k);
 void learner_scratch_release(gs_handle* h);
 void learner_release(gs_handle* h);
+// the table of the learners' networks: learner `net` by name, for a message, and the installed network it trains -- its layers,
+// widths, activation, host normalisation (shift then scale, [16 kb_0] each) and image; false: not installed (the policy: not with
+// GS_COMPUTE_F32)
+const char* net_name(int net);
+struct Installed { const GsPolicyLayerF32* L; const int32_t* dims; int n_layers, activation; const std::vector<double>* norm; const DevBuf<char>* blob; };
+bool installed(const gs_handle* h, int net, Installed& I);
 
 // ---- owner of the Q networks, their targets and their arrays over the rollout (abi_q.hip) ----
 void q_release(gs_handle* h);              // everything

@@ -110,8 +110,8 @@ gs_k_fed_apply(GsFedApplyArgs A) {
   const int n_out = A.S.dims[l + 1], n_in = A.S.dims[l], local = j - A.S.p_off[l];
   const bool bias = local >= n_out * n_in;
   const int o = bias ? local - n_out * n_in : local / n_in, k = bias ? 0 : local - o * n_in;
-  const size_t slot = bias ? (size_t)o : gs_fed_slot_w(o, k, A.S.kb[l]);
-  const size_t slot_t = !bias && l ? gs_fed_slot_t(o, k, A.S.kbt[l]) : 0;
+  const size_t slot = bias ? (size_t)o : gs_pol32_slot(o, k, A.S.kb[l]);
+  const size_t slot_t = !bias && l ? gs_pol32_slot(k, o, A.S.kbt[l]) : 0;      // (W^T: the output index is k, the k axis runs over o)
   for (int c = 0; c < A.n_clients; ++c) {
     const GsFedClient& C = A.clients[c];
     C.params[j] = w;

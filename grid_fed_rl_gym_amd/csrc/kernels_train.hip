@@ -392,6 +392,7 @@ gs_k_train_adam(GsTrainAdamArgs A) {
     return;
   }
   const int o = local / n_in, k = local - o * n_in;
+  // (policy.h's gs_pol32_slot(o, k, L.kb) and gs_pol32_slot(k, o, T.kb), written out: through the function the registers are allocated differently)
   const_cast<float*>(L.w)[(((size_t)(o >> 4) * L.kb + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (o & 15)) * 4 + (k & 3)] = w;
   if (l) {                                   // W^T: the output index is k, the k axis runs over o
     const GsPolicyLayerF32 T = A.N.T[l];

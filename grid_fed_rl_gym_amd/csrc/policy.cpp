@@ -90,13 +90,8 @@ GsPolicyImageF32 gs_policy_pack_f32(const gs_policy_mlp& p, const gs_policy_mlp_
   for (int l = 0; l < p.n_layers; ++l) {
     const int K = p.dims[l], N = p.dims[l + 1];
     float* w = im.blob.data() + im.w_off[l];
-    for (int nt = 0; nt < im.nt[l]; ++nt)
-      for (int kb = 0; kb < im.kb[l]; ++kb)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 4; ++j) {
-            const int n = 16 * nt + (lane & 15), k = 16 * kb + 4 * (lane >> 4) + j;
-            if (n < N && k < K) w[(((size_t)nt * im.kb[l] + kb) * 64 + lane) * 4 + j] = (float)p.weights[l][(size_t)n * K + k];
-          }
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) w[gs_pol32_slot(n, k, im.kb[l])] = (float)p.weights[l][(size_t)n * K + k];
     for (int n = 0; n < N; ++n) im.blob[im.b_off[l] + n] = (float)p.biases[l][n];
   }
   const int D = p.dims[0], D16 = 16 * im.kb[0];
@@ -106,6 +101,16 @@ GsPolicyImageF32 gs_policy_pack_f32(const gs_policy_mlp& p, const gs_policy_mlp_
     im.norm[D16 + i] = o.obs_scale ? o.obs_scale[i] : 1.0;
   }
   return im;
+}
+
+void gs_policy_unpack_f32(const GsPolicyLayerF32& L, int n_out, int n_in, float* dst, float* wt) {
+  for (int o = 0; o < n_out; ++o)
+    for (int k = 0; k < n_in; ++k) {
+      const float x = L.w[gs_pol32_slot(o, k, L.kb)];
+      dst[(size_t)o * n_in + k] = x;
+      if (wt) wt[gs_pol32_slot(k, o, L.nt)] = x;
+    }
+  for (int o = 0; o < n_out; ++o) dst[(size_t)n_out * n_in + o] = L.b[o];
 }
 
 GsPolicyImage gs_policy_pack(const gs_policy_mlp& p) {

@@ -65,6 +65,11 @@ struct GsPolicyLayerF32 {
   const float* b;       // [16 nt]
   int32_t kb, nt;       // 16-wide k blocks, 16-wide column tiles
 };
+// That layout, stated once for the host and the device (a constexpr function is both): where W[o][k] lies in `w` of a layer with kb k
+// blocks.  The image of W^T (train.h, GsTrainNet::T) holds W[o][k] at gs_pol32_slot(k, o, that image's kb).
+constexpr size_t gs_pol32_slot(int o, int k, int kb) {
+  return (((size_t)(o >> 4) * kb + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (o & 15)) * 4 + (k & 3);
+}
 
 struct GsPolicyArgsF32 {
   const double* obs;    // [B][D]
@@ -88,6 +93,10 @@ struct GsPolicyImageF32 {
   size_t w_off[GS_POLICY_MAX_LAYERS], b_off[GS_POLICY_MAX_LAYERS]; int32_t kb[GS_POLICY_MAX_LAYERS], nt[GS_POLICY_MAX_LAYERS];
 };
 GsPolicyImageF32 gs_policy_pack_f32(const gs_policy_mlp& p, const gs_policy_mlp_opts& o);
+// The way back, for one layer of n_out x n_in whose packed image `L` lies in HOST memory: W row-major [n_out][n_in], then b [n_out],
+// into `dst` (torch order; the image holds float32 values, so this is exact).  `wt`, unless NULL, receives the packed image of W^T
+// (L.nt k blocks, L.kb column tiles); its padding is not written.
+void gs_policy_unpack_f32(const GsPolicyLayerF32& L, int n_out, int n_in, float* dst, float* wt);
 
 // ---- the value network (GS_HEAD_LINEAR): gs_k_value_mlp_f32, kernels_value.hip ---------------------------------------------------
 // The float32 path's layers with a scalar output, over any number of rows.  A workgroup of GS_POL_WAVES wavefronts owns GS_VAL_ROWS

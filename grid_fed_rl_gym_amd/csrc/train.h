@@ -1,5 +1,6 @@
 // train.h -- the learner of gs_learner_* (include/gridstep.h "the learner"): tile shapes and argument blocks of
-// the kernels of kernels_train.hip, shared with abi_learner.hip.
+// the kernels of kernels_train.hip, shared with abi_learner.hip, which fills every block and queues every launch in one place each
+// (its queue_* helpers; the reduction's workgroup count is gs_tr_red_blocks below).
 //
 // A network of L layers with widths dims[0 .. L] has P = sum_l dims[l + 1] (dims[l] + 1) parameters, flat in torch order: W_0
 // row-major [out][in], b_0, W_1, b_1, ...  Gradients, Adam's m and v, and every partial gradient share that order.
@@ -17,10 +18,13 @@
 constexpr int GS_TR_ROWS = 32;
 // rows of one partial weight gradient: a compile-time constant, so that the gradient's bits depend on n alone
 constexpr int GS_TR_SEG = 256;
+constexpr int gs_tr_segments(int n) { return (n + GS_TR_SEG - 1) / GS_TR_SEG; }
 // a wavefront of the weight-gradient kernel owns GS_TR_WT_OUT x GS_TR_WT 16 x 16 tiles of dW (32 outputs x 64 inputs), each summed
 // in GS_TR_CHAINS accumulator sets that take the k-steps in turn
 constexpr int GS_TR_WT_OUT = 2, GS_TR_WT = 4, GS_TR_CHAINS = 4;
 constexpr int GS_TR_RED_THREADS = 256, GS_TR_RED_PER_THREAD = 4;      // the segment reduction: 1024 parameters per workgroup
+// ... so P parameters take this many workgroups: the launch of gs_k_train_reduce, the length of its `blocksum`, what the statistics add up
+constexpr int gs_tr_red_blocks(int P) { return (P + GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD - 1) / (GS_TR_RED_THREADS * GS_TR_RED_PER_THREAD); }
 constexpr int GS_TR_STAT_THREADS = 1024;
 // LDS of the forward kernel: the activation tile and the observation tile, staged in the value kernel's panels (policy.h)
 inline int gs_tr_lds_bytes(int kb0) { return GS_TR_ROWS * (gs_val_obs_stride(kb0) + GS_POL32_ACT_STRIDE) * 4; }
