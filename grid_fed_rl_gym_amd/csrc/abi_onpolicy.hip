@@ -14,11 +14,12 @@ using namespace gsi;
 static int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
                         const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0) {
   if (rows <= 0) return GS_OK;
-  if (rows > 0x7fffffffLL - GS_VAL_ROWS) return fail(h, GS_E_INVALID, "%lld rows exceed the value kernel's 32-bit row index", rows);
+  unsigned blocks = 0;
+  if (int rc = scalar_net_grid(h, rows, "value", &blocks)) return rc;
   GsValueArgs a = val.args;
   a.obs = obs; a.out = out; a.rows = (int32_t)rows; a.rows_dev = rows_dev;
   a.scatter_idx = scatter_idx; a.scatter_out = scatter_out; a.scatter_T = scatter_T; a.scatter_B = h->B;
-  hipLaunchKernelGGL(gs_k_value_mlp_f32, dim3((unsigned)((rows + GS_VAL_ROWS - 1) / GS_VAL_ROWS)), dim3(64 * GS_POL_WAVES), val.lds, h->stream, a);
+  hipLaunchKernelGGL(gs_k_value_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), val.lds, h->stream, a);
   HIPCHK(h, hipGetLastError());
   return GS_OK;
 }
@@ -36,6 +37,22 @@ void onpolicy_release(gs_handle* h) {
   h->ro.logp_recorded = false;
 }
 
+int scalar_net_install(gs_handle* h, gs_handle::Value& val, const void* kernel, const gs_policy_mlp& p, const gs_policy_mlp_opts& o, ScalarNet& net) {
+  net.im = gs_policy_pack_f32(p, o);
+  val.lds = gs_val_lds_bytes(net.im.kb[0]);
+  HIPCHK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
+  if (int rc = upload_image_f32(h, val.blob, net.im, &net.image, &net.norm)) return rc;
+  for (int l = 0; l <= p.n_layers; ++l) val.dims[l] = p.dims[l];
+  val.h_norm = net.im.norm;
+  return GS_OK;
+}
+
+int scalar_net_grid(gs_handle* h, long long rows, const char* kernel, unsigned* blocks) {
+  if (rows > 0x7fffffffLL - GS_VAL_ROWS) return fail(h, GS_E_INVALID, "%lld rows exceed the %s kernel's 32-bit row index", rows, kernel);
+  *blocks = (unsigned)((rows + GS_VAL_ROWS - 1) / GS_VAL_ROWS);
+  return GS_OK;
+}
+
 // what gs_value_mlp_set and gs_cost_value_mlp_set (abi_costs.hip) share: `p` has passed gs_value_check; NULL removes the network
 int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, const gs_policy_mlp_opts* o, bool want_out) {
   GS_ENTER(h);
@@ -47,19 +64,11 @@ int value_install(gs_handle* h, gs_handle::Value& val, const gs_policy_mlp* p, c
   if (!p) return GS_OK;
   int rc = want_out ? val.out.grow(h, (size_t)h->B, "the value network's output") : GS_OK;
   if (rc) return rc;
-  const GsPolicyImageF32 im = gs_policy_pack_f32(*p, *o);
-  val.lds = gs_val_lds_bytes(im.kb[0]);
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_value_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-  const float* image = nullptr; const double* norm = nullptr;
-  if ((rc = upload_image_f32(h, val.blob, im, &image, &norm))) return rc;
-  GsValueArgs& a = val.args;
-  a = GsValueArgs{};
-  a.shift = norm; a.scale = norm + 16 * im.kb[0];
-  a.D = h->obs_dim; a.n_layers = p->n_layers; a.activation = p->activation;
-  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
-  for (int l = 0; l < p->n_layers; ++l) a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
-  for (int l = 0; l <= p->n_layers; ++l) val.dims[l] = p->dims[l];
-  val.h_norm = im.norm;
+  ScalarNet net;
+  if ((rc = scalar_net_install(h, val, (const void*)gs_k_value_mlp_f32, *p, *o, net))) return rc;
+  val.args = GsValueArgs{};
+  scalar_net_args(val.args, *p, net);
+  val.args.D = h->obs_dim;
   val.set = true;
   return GS_OK;
 }

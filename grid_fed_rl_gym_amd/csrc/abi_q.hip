@@ -41,11 +41,12 @@ std::string gs_q_check(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int3
 // one launch of twin `Q` under the layer table `L` (the online or the target image) over the last rollout's T * B rows
 static int launch_q(gs_handle* h, const gs_handle::QNet& Q, const GsPolicyLayerF32* L, double* out) {
   const long long rows = (long long)h->ro.T * h->B;
-  if (rows > 0x7fffffffLL - GS_VAL_ROWS) return fail(h, GS_E_INVALID, "%lld rows exceed the Q kernel's 32-bit row index", rows);
+  unsigned blocks = 0;
+  if (int rc = scalar_net_grid(h, rows, "Q", &blocks)) return rc;
   GsQArgs a = Q.qargs;
   a.obs = h->ro.obs_seq; a.act = h->ro.act; a.out = out; a.rows = (int32_t)rows;
   for (int l = 0; l < a.n_layers; ++l) a.L[l] = L[l];
-  hipLaunchKernelGGL(gs_k_q_mlp_f32, dim3((unsigned)((rows + GS_VAL_ROWS - 1) / GS_VAL_ROWS)), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a);
+  hipLaunchKernelGGL(gs_k_q_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a);
   HIPCHK(h, hipGetLastError());
   return GS_OK;
 }
@@ -90,13 +91,11 @@ int gs_q_mlp_set(gs_handle* h, int32_t which, const gs_policy_mlp* p, const gs_p
   h->qt.evaluated_on = 0;                    // (what the last evaluation left belongs to the networks that were installed then)
   if (!p) return GS_OK;
   const int D = h->obs_dim, A = h->action_dim;
-  const QOpts q(*o, D, A);
-  const GsPolicyImageF32 im = gs_policy_pack_f32(*p, q.o);      // (shift and scale are 0 beyond D + A: a padded column normalises to 0)
-  val.lds = gs_val_lds_bytes(im.kb[0]);
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_q_mlp_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-  const float* image = nullptr; const double* norm = nullptr;
-  int rc = upload_image_f32(h, val.blob, im, &image, &norm);
+  const QOpts q(*o, D, A);                   // (packed, shift and scale are 0 beyond D + A: a padded column normalises to 0)
+  ScalarNet net;
+  int rc = scalar_net_install(h, val, (const void*)gs_k_q_mlp_f32, *p, q.o, net);
   if (rc) return rc;
+  const GsPolicyImageF32& im = net.im;
   if ((rc = Q.target.alloc(h, im.blob.size(), "the Q network's target image"))) { val.blob.release(); return rc; }
   HIPCHK(h, hipMemcpy(Q.target, im.blob.data(), im.blob.size() * sizeof(float), hipMemcpyHostToDevice));
   Q.image_floats = im.blob.size();
@@ -104,15 +103,12 @@ int gs_q_mlp_set(gs_handle* h, int32_t which, const gs_policy_mlp* p, const gs_p
   val.args.n_layers = p->n_layers; val.args.activation = p->activation;
   GsQArgs& a = Q.qargs;
   a = GsQArgs{};
-  a.shift = norm; a.scale = norm + 16 * im.kb[0];
-  a.D = D; a.A = A; a.n_layers = p->n_layers; a.activation = p->activation;
-  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
+  scalar_net_args(a, *p, net);
+  a.D = D; a.A = A;
   for (int l = 0; l < p->n_layers; ++l) {
-    val.args.L[l] = a.L[l] = GsPolicyLayerF32{image + im.w_off[l], image + im.b_off[l], im.kb[l], im.nt[l]};
+    val.args.L[l] = a.L[l];
     Q.TL[l] = GsPolicyLayerF32{Q.target.p + im.w_off[l], Q.target.p + im.b_off[l], im.kb[l], im.nt[l]};
   }
-  for (int l = 0; l <= p->n_layers; ++l) val.dims[l] = p->dims[l];
-  val.h_norm = im.norm;
   val.set = true;
   return GS_OK;
 }

@@ -66,6 +66,19 @@ __device__ __forceinline__ void rng_normal_quad(uint64_t seed, uint64_t instance
   gs_sincos_turns(u1, &sn, &cs); z[0] = ra * cs; z[1] = ra * sn;
   gs_sincos_turns(u3, &sn, &cs); z[2] = rb * cs; z[3] = rb * sn;
 }
+// ONE of those four normals, component `comp` = 0 .. 3, from the words `r` of a Philox call the caller made with its own counter
+// and tag: the same operations on the same words, so it is z[comp] of the recipe above to the bit.  The policies' action noise,
+// the pathwise actor's and the federation's take their normals one at a time through this function.
+// (rng_normal_quad keeps its own statement of the recipe: written as four calls of this function it computes the same values, but
+// the step kernels that inline it come out with other instructions and, some, more spills -- DESIGN.md section 24.)
+__device__ __forceinline__ double rng_normal_component(const U4& r, int comp) {
+  const uint32_t wr = comp & 2 ? r.c : r.a, wt = comp & 2 ? r.d : r.b;
+  const double ur = ((double)wr + 0.5) * (1.0 / 4294967296.0), ut = ((double)wt + 0.5) * (1.0 / 4294967296.0);
+  const double ra = sqrt(-2.0 * gs_log01(ur));
+  double sn, cs;
+  gs_sincos_turns(ut, &sn, &cs);
+  return ra * (comp & 1 ? sn : cs);
+}
 
 enum { DRAW_IRRADIANCE = 0, DRAW_WEATHER = 1, DRAW_LOAD0 = 16 };
 

@@ -402,6 +402,25 @@ static inline bool critic_current(const gs_handle* h, const gs_handle::Critic& c
 // queues the copies of c's arrays over the last rollout to these host pointers (NULL: not wanted)
 int critic_download(gs_handle* h, const gs_handle::Critic& c, double* values, double* term_values, double* adv, double* ret);
 
+// ---- what the two scalar-output networks share on the host (abi_onpolicy.hip): gs_k_value_mlp_f32 (value_install) and gs_k_q_mlp_f32 (gs_q_mlp_set) ----
+// a packed network and where its parts lie on the device
+struct ScalarNet { GsPolicyImageF32 im; const float* image = nullptr; const double* norm = nullptr; };
+// packs `p` with `o` (both checked by the caller), sizes the LDS of `kernel` and uploads the image into val.blob; also val.lds,
+// val.dims and val.h_norm.  val.args and val.set are the caller's.
+int scalar_net_install(gs_handle* h, gs_handle::Value& val, const void* kernel, const gs_policy_mlp& p, const gs_policy_mlp_opts& o, ScalarNet& net);
+// the fields GsValueArgs and GsQArgs have in common
+template <typename Args>
+static inline void scalar_net_args(Args& a, const gs_policy_mlp& p, const ScalarNet& net) {
+  const GsPolicyImageF32& im = net.im;
+  a.shift = net.norm; a.scale = net.norm + 16 * im.kb[0];
+  a.n_layers = p.n_layers; a.activation = p.activation;
+  a.panel_kb = gs_val_panel_kb(im.kb[0]); a.obs_stride = gs_val_obs_stride(im.kb[0]);
+  for (int l = 0; l < p.n_layers; ++l) a.L[l] = GsPolicyLayerF32{net.image + im.w_off[l], net.image + im.b_off[l], im.kb[l], im.nt[l]};
+}
+// the workgroups of a launch of GS_VAL_ROWS rows each over `rows` > 0 rows; refuses a count the kernels' 32-bit row index cannot
+// hold (`kernel`: "value" / "Q", for the message)
+int scalar_net_grid(gs_handle* h, long long rows, const char* kernel, unsigned* blocks);
+
 // ---- owner of the rollout's constraint arrays (abi_costs.hip) ----
 void costs_release(gs_handle* h);
 

@@ -10,6 +10,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "block_reduce.h"
 #include "gs_internal.h"
 #include "env_device.h"
 
@@ -27,20 +28,9 @@ __device__ __forceinline__ uint32_t opb_pass(uint32_t x, int hb, uint32_t mask, 
   return (L << hb) | R;
 }
 
-// gs_k_ep_stats's reduction (kernels_episodes.hip): a butterfly over the wavefront's lanes (partners at 32, 16, 8, 4, 2, 1), the 16
-// wavefronts' results through LDS, a second butterfly (8, 4, 2, 1): a balanced tree of depth 10, the same value in every thread
-__device__ __forceinline__ double opb_block_sum(double v, double* lds) {
-#pragma clang fp contract(off)
-  constexpr int W = GS_OPB_STAT_THREADS / 64;
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  __syncthreads();      // (the reduction before this one has been read)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  static_assert(W == 16, "the second butterfly runs over 16 lanes");
-  v = lds[threadIdx.x & (W - 1)];
-  for (int off = W / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
+// gs_k_ep_stats's reduction (kernels_episodes.hip): block_reduce.h over the 16 wavefronts, known at compile time
+constexpr int OPB_STAT_WAVES = GS_OPB_STAT_THREADS / 64;
+static_assert(OPB_STAT_WAVES == 16, "the second butterfly runs over 16 lanes");
 
 }  // namespace
 
@@ -85,7 +75,7 @@ gs_k_opb_mbstats(const double* __restrict__ stage, int n, double* __restrict__ a
   double sum = 0.0;
 #pragma unroll 4
   for (int k = tid; k < n; k += GS_OPB_STAT_THREADS) sum = sum + stage[k];
-  sum = opb_block_sum(sum, lds);
+  sum = gs_block_sum<OPB_STAT_WAVES>(sum, lds);
   const double dn = (double)n;
   const double mean = sum / dn;
   // pass 2: the squared deviations from the mean, the same entries in the same order
@@ -95,7 +85,7 @@ gs_k_opb_mbstats(const double* __restrict__ stage, int n, double* __restrict__ a
     const double d = stage[k] - mean;
     m2 = m2 + d * d;
   }
-  m2 = opb_block_sum(m2, lds);
+  m2 = gs_block_sum<OPB_STAT_WAVES>(m2, lds);
   if (tid != 0) return;
   adv_stats[0] = mean;
   __asm__ volatile("" ::: "memory");      // (two 8-byte stores, not one of 16)

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_reduce.h"
 #include "gs_internal.h"
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -143,27 +144,12 @@ extern "C" __global__ void __launch_bounds__(256)
 gs_k_ep_accumulate_costs(GsEpisodeArgs E) { ep_accumulate<true, 4>(E); }
 
 // ---- the statistics pass -------------------------------------------------------------------------------------------------------
-// The reduction of one quantity over the workgroup, in a fixed order: a butterfly over the wavefront's lanes (partners at 32, 16,
-// 8, 4, 2, 1 lanes), the 16 wavefronts' results through LDS, a second butterfly (8, 4, 2, 1) over those: a balanced binary tree of
-// depth 10 over the 1024 threads' values (IEEE addition commutes, so both partners of a butterfly step hold the same bits).  Every
-// thread returns the same value.
-struct EpSum { template <typename X> __device__ X operator()(X a, X b) const { return a + b; } };
+// Every quantity is reduced over the workgroup by block_reduce.h (the order of the operations is stated there), the 16 wavefronts
+// known at compile time.
 struct EpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
 struct EpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
-
-template <typename X, typename Op>
-__device__ __forceinline__ X ep_block_reduce(X v, Op op, X* lds) {
-#pragma clang fp contract(off)
-  constexpr int W = GS_EP_STAT_THREADS / 64;
-  for (int off = 32; off > 0; off >>= 1) v = op(v, (X)__shfl_xor(v, off));
-  __syncthreads();      // (the reduction before this one has been read)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  static_assert(W == 16, "the second butterfly runs over 16 lanes");
-  v = lds[threadIdx.x & (W - 1)];
-  for (int off = W / 2; off > 0; off >>= 1) v = op(v, (X)__shfl_xor(v, off));
-  return v;
-}
+constexpr int EP_STAT_WAVES = GS_EP_STAT_THREADS / 64;
+static_assert(EP_STAT_WAVES == 16, "the second butterfly runs over 16 lanes");
 
 extern "C" __global__ void __launch_bounds__(GS_EP_STAT_THREADS)
 gs_k_ep_stats(GsEpisodeArgs E) {
@@ -191,17 +177,17 @@ gs_k_ep_stats(GsEpisodeArgs E) {
     }
     n_success += clean && r > E.success_return;
   }
-  cnt = ep_block_reduce(cnt, EpSum(), lds_i);
-  cnt_partial = ep_block_reduce(cnt_partial, EpSum(), lds_i);
-  len_sum = ep_block_reduce(len_sum, EpSum(), lds_i);
-  n_success = ep_block_reduce(n_success, EpSum(), lds_i);
-  ret_sum = ep_block_reduce(ret_sum, EpSum(), lds_f);
-  ret_min = ep_block_reduce(ret_min, EpMin(), lds_f);
-  ret_max = ep_block_reduce(ret_max, EpMax(), lds_f);
-  len_min = ep_block_reduce(len_min, EpMin(), lds_f);
-  len_max = ep_block_reduce(len_max, EpMax(), lds_f);
+  cnt = gs_block_sum<EP_STAT_WAVES>(cnt, lds_i);
+  cnt_partial = gs_block_sum<EP_STAT_WAVES>(cnt_partial, lds_i);
+  len_sum = gs_block_sum<EP_STAT_WAVES>(len_sum, lds_i);
+  n_success = gs_block_sum<EP_STAT_WAVES>(n_success, lds_i);
+  ret_sum = gs_block_sum<EP_STAT_WAVES>(ret_sum, lds_f);
+  ret_min = gs_block_reduce<EP_STAT_WAVES>(ret_min, lds_f, EpMin());
+  ret_max = gs_block_reduce<EP_STAT_WAVES>(ret_max, lds_f, EpMax());
+  len_min = gs_block_reduce<EP_STAT_WAVES>(len_min, lds_f, EpMin());
+  len_max = gs_block_reduce<EP_STAT_WAVES>(len_max, lds_f, EpMax());
   if (with_costs)
-    for (int c = 0; c < 3; ++c) { cost_sum[c] = ep_block_reduce(cost_sum[c], EpSum(), lds_f); viol[c] = ep_block_reduce(viol[c], EpSum(), lds_i); }
+    for (int c = 0; c < 3; ++c) { cost_sum[c] = gs_block_sum<EP_STAT_WAVES>(cost_sum[c], lds_f); viol[c] = gs_block_sum<EP_STAT_WAVES>(viol[c], lds_i); }
   const double N = (double)cnt;
   const double mean = ret_sum / N;
   // pass 2: the squared deviations from the mean, the same entries in the same order
@@ -212,7 +198,7 @@ gs_k_ep_stats(GsEpisodeArgs E) {
     const double d = E.e_ret[k] - mean;
     m2 = m2 + d * d;
   }
-  m2 = ep_block_reduce(m2, EpSum(), lds_f);
+  m2 = gs_block_sum<EP_STAT_WAVES>(m2, lds_f);
   if (tid != 0) return;
   GsEpisodeStats& S = *E.stats;
   const bool some = cnt > 0;

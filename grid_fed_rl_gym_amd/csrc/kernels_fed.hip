@@ -9,33 +9,16 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "block_reduce.h"
 #include "env_device.h"
 #include "fed.h"
 
 namespace {
 
-// the butterfly of the learner's gradient norm (gt_block_sum of kernels_train.hip): within a wavefront, then over the wavefronts
-__device__ __forceinline__ double gf_block_sum(double v, double* lds) {
-#pragma clang fp contract(off)
-  const int W = blockDim.x >> 6;             // 4 or 16 wavefronts
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = lds[threadIdx.x & (W - 1)];
-  for (int off = W / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
-
-// component `comp` of the four normals of env_device.h's rng_normal_quad recipe, tag 'FEDN'
+// component `comp` of the four normals of one Philox call (env_device.h's rng_normal_component), tag 'FEDN'
 __device__ __forceinline__ double gf_noise(uint64_t seed, uint32_t quad, uint32_t round, uint32_t net, int comp) {
   const U4 r = philox(quad, round, net, 0x4645444Eu, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const uint32_t wr = comp & 2 ? r.c : r.a, wt = comp & 2 ? r.d : r.b;
-  const double ur = ((double)wr + 0.5) * (1.0 / 4294967296.0), ut = ((double)wt + 0.5) * (1.0 / 4294967296.0);
-  const double ra = sqrt(-2.0 * gs_log01(ur));
-  double sn, cs;
-  gs_sincos_turns(ut, &sn, &cs);
-  return ra * (comp & 1 ? sn : cs);
+  return rng_normal_component(r, comp);
 }
 
 }  // namespace
@@ -58,7 +41,7 @@ gs_k_fed_gram(GsFedGramArgs A) {
     const double di = (double)pi[j] - g, dk = (double)pk[j] - g;
     ss = ss + di * dk;
   }
-  ss = gf_block_sum(ss, lds);
+  ss = gs_block_sum(ss, lds);
   if (threadIdx.x == 0) A.blocksum[(size_t)e * A.blocks + blockIdx.x] = ss;
 }
 
@@ -71,7 +54,7 @@ gs_k_fed_sum(GsFedSumArgs A) {
   const double* __restrict__ src = A.blocksum + (size_t)e * A.blocks;
   double s = 0.0;
   for (int k = threadIdx.x; k < A.blocks; k += GS_FED_SUM_THREADS) s = s + src[k];
-  s = gf_block_sum(s, lds);
+  s = gs_block_sum(s, lds);
   if (threadIdx.x) return;
   A.out[e] = s;
   if (!A.coef) return;

@@ -12,25 +12,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "block_reduce.h"
 #include "env_device.h"
 #include "pathwise.h"
 #include "train.h"
 
 namespace {
-
-// gt_block_sum of kernels_train.hip, restated: the same butterfly, so a sum here has the bits it has there
-template <typename X>
-__device__ __forceinline__ X gw_block_sum(X v, X* lds) {
-#pragma clang fp contract(off)
-  const int W = blockDim.x >> 6;             // 16 wavefronts
-  for (int off = 32; off > 0; off >>= 1) v = v + (X)__shfl_xor(v, off);
-  __syncthreads();                           // (the reduction before this one has been read)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = lds[threadIdx.x & (W - 1)];
-  for (int off = W / 2; off > 0; off >>= 1) v = v + (X)__shfl_xor(v, off);
-  return v;
-}
 
 // ---- exp, tanh and log of the heads, from rounded float64 +, -, *, / alone (include/gridstep.h "the pathwise actor step" states them;
 // learner.py's pathwise_exp_np / _tanh_np / _log_np perform the same operations one by one, so the heads are restated to the bit
@@ -92,15 +79,10 @@ __device__ __forceinline__ double gw_logp_term(double eps, double ls, double act
   return (((-0.5 * eps) * eps - ls) - 0.91893853320467274178) - gw_log((1.0 - act * act) + 1e-6);
 }
 
-// component `comp` of the four normals of env_device.h's rng_normal_quad recipe, tag 'PWNO', counter (sample, quad, draw, tag)
+// component `comp` of the four normals of one Philox call (env_device.h's rng_normal_component), tag 'PWNO', counter (sample, quad, draw, tag)
 __device__ __forceinline__ double gw_noise(uint64_t seed, uint32_t sample, uint32_t quad, uint32_t draw, int comp) {
   const U4 r = philox(sample, quad, draw, GS_PW_NOISE_TAG, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const uint32_t wr = comp & 2 ? r.c : r.a, wt = comp & 2 ? r.d : r.b;
-  const double ur = ((double)wr + 0.5) * (1.0 / 4294967296.0), ut = ((double)wt + 0.5) * (1.0 / 4294967296.0);
-  const double ra = sqrt(-2.0 * gs_log01(ur));
-  double sn, cs;
-  gs_sincos_turns(ut, &sn, &cs);
-  return ra * (comp & 1 ? sn : cs);
+  return rng_normal_component(r, comp);
 }
 
 }  // namespace
@@ -238,7 +220,7 @@ gs_k_pw_head(GsPwHeadArgs H) {
   for (int k = 2 * A; k < H.width16; ++k) g[k] = 0.0f;
 }
 
-// ---- statistics of the step: ONE workgroup, thread i over entries i, i + 1024, ..., then the tree of gw_block_sum -------------------
+// ---- statistics of the step: ONE workgroup, thread i over entries i, i + 1024, ..., then the tree of gs_block_sum -------------------
 extern "C" __global__ void __launch_bounds__(GS_TR_STAT_THREADS)
 gs_k_pw_stats(GsPwStatArgs S) {
 #pragma clang fp contract(off)
@@ -251,9 +233,9 @@ gs_k_pw_stats(GsPwStatArgs S) {
     tl = tl + S.logp[k];
   }
   for (int k = tid; k < S.blocks; k += GS_TR_STAT_THREADS) gs = gs + S.blocksum[k];
-  t0 = gw_block_sum(t0, lds);
-  gs = gw_block_sum(gs, lds);
-  tq = gw_block_sum(tq, lds); tl = gw_block_sum(tl, lds);
+  t0 = gs_block_sum(t0, lds);
+  gs = gs_block_sum(gs, lds);
+  tq = gs_block_sum(tq, lds); tl = gs_block_sum(tl, lds);
   if (tid) return;
   const double n = (double)S.n, nan = __builtin_nan("");
   double* o = S.stats;

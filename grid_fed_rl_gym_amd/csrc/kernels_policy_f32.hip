@@ -32,16 +32,11 @@ namespace {
 
 constexpr int GQ_RT = GS_POL_ROWS / 16;      // row tiles per workgroup
 
-// component `comp` of the four normals of env_device.h's rng_normal_quad recipe, tag 'PNOI' (the float64 kernel's gp_noise, word
-// for word: the stochastic contract of gs_policy_mlp is one contract)
+// component `comp` of the four normals of one Philox call (env_device.h's rng_normal_component), tag 'PNOI' (the float64 kernel's
+// gp_noise, word for word: the stochastic contract of gs_policy_mlp is one contract)
 __device__ __forceinline__ double gq_noise(uint64_t seed, uint64_t instance, uint32_t t, uint32_t quad, int comp) {
   const U4 r = philox((uint32_t)instance, t, quad, 0x504E4F49u, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const uint32_t wr = comp & 2 ? r.c : r.a, wt = comp & 2 ? r.d : r.b;
-  const double ur = ((double)wr + 0.5) * (1.0 / 4294967296.0), ut = ((double)wt + 0.5) * (1.0 / 4294967296.0);
-  const double ra = sqrt(-2.0 * gs_log01(ur));
-  double sn, cs;
-  gs_sincos_turns(ut, &sn, &cs);
-  return ra * (comp & 1 ? sn : cs);
+  return rng_normal_component(r, comp);
 }
 
 }  // namespace

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "block_reduce.h"
 #include "mlp_f32.h"
 #include "train.h"
 
@@ -39,19 +40,6 @@ __device__ __forceinline__ float gt_act_grad(float y, int kind) {
   if (kind == GS_ACT_RELU) return y > 0.0f ? 1.0f : 0.0f;
   if (kind == GS_ACT_TANH) return 1.0f - y * y;
   return y > 0.0f ? 1.0f : y + 1.0f;         // elu, alpha = 1: exp(x) = y + 1
-}
-
-template <typename X>
-__device__ __forceinline__ X gt_block_sum(X v, X* lds) {
-#pragma clang fp contract(off)
-  const int W = blockDim.x >> 6;             // 4 or 16 wavefronts
-  for (int off = 32; off > 0; off >>= 1) v = v + (X)__shfl_xor(v, off);
-  __syncthreads();                           // (the reduction before this one has been read)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = lds[threadIdx.x & (W - 1)];
-  for (int off = W / 2; off > 0; off >>= 1) v = v + (X)__shfl_xor(v, off);
-  return v;
 }
 
 }  // namespace
@@ -319,11 +307,11 @@ gs_k_train_reduce(GsTrainReduceArgs A) {
     A.grad[p] = g;
     ss = ss + (double)g * (double)g;
   }
-  ss = gt_block_sum(ss, lds);
+  ss = gs_block_sum(ss, lds);
   if (threadIdx.x == 0) A.blocksum[blockIdx.x] = ss;
 }
 
-// ---- statistics of the step: ONE workgroup, thread i over entries i, i + 1024, ..., then the tree of gt_block_sum --------------------
+// ---- statistics of the step: ONE workgroup, thread i over entries i, i + 1024, ..., then the tree of gs_block_sum --------------------
 extern "C" __global__ void __launch_bounds__(GS_TR_STAT_THREADS)
 gs_k_train_stats(GsTrainStatArgs S) {
 #pragma clang fp contract(off)
@@ -344,9 +332,9 @@ gs_k_train_stats(GsTrainStatArgs S) {
     }
   }
   for (int k = tid; k < S.blocks; k += GS_TR_STAT_THREADS) gs = gs + S.blocksum[k];
-  t0 = gt_block_sum(t0, lds);
-  gs = gt_block_sum(gs, lds);
-  if (S.policy) { t1 = gt_block_sum(t1, lds); kl = gt_block_sum(kl, lds); nc = gt_block_sum(nc, lds_i); }
+  t0 = gs_block_sum(t0, lds);
+  gs = gs_block_sum(gs, lds);
+  if (S.policy) { t1 = gs_block_sum(t1, lds); kl = gs_block_sum(kl, lds); nc = gs_block_sum(nc, lds_i); }
   if (tid) return;
   const double n = (double)S.n;
   double* o = S.stats;

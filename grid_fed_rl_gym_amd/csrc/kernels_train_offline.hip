@@ -9,25 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "block_reduce.h"
 #include "train.h"
-
-namespace {
-
-// gt_block_sum of kernels_train.hip, restated: the same butterfly, so a sum here has the bits it has there
-template <typename X>
-__device__ __forceinline__ X go_block_sum(X v, X* lds) {
-#pragma clang fp contract(off)
-  const int W = blockDim.x >> 6;             // 16 wavefronts
-  for (int off = 32; off > 0; off >>= 1) v = v + (X)__shfl_xor(v, off);
-  __syncthreads();                           // (the reduction before this one has been read)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = lds[threadIdx.x & (W - 1)];
-  for (int off = W / 2; off > 0; off >>= 1) v = v + (X)__shfl_xor(v, off);
-  return v;
-}
-
-}  // namespace
 
 // ---- the advantage-weighted head: L = -(1/n) sum w_i lp_i - ent_coef (1/n) sum h_i -------------------------------------------------
 extern "C" __global__ void __launch_bounds__(64)
@@ -92,7 +75,7 @@ gs_k_train_head_expectile(GsTrainExpectileArgs H) {
   for (int k = 1; k < H.width16; ++k) g[k] = 0.0f;
 }
 
-// ---- statistics of an advantage-weighted step: ONE workgroup, thread i over entries i, i + 1024, ..., then the tree of go_block_sum --
+// ---- statistics of an advantage-weighted step: ONE workgroup, thread i over entries i, i + 1024, ..., then the tree of gs_block_sum --
 extern "C" __global__ void __launch_bounds__(GS_TR_STAT_THREADS)
 gs_k_train_stats_awr(GsTrainAwrStatArgs S) {
 #pragma clang fp contract(off)
@@ -113,9 +96,9 @@ gs_k_train_stats_awr(GsTrainAwrStatArgs S) {
     nc += S.capped[k];
   }
   for (int k = tid; k < S.blocks; k += GS_TR_STAT_THREADS) gs = gs + S.blocksum[k];
-  t0 = go_block_sum(t0, lds);
-  gs = go_block_sum(gs, lds);
-  t1 = go_block_sum(t1, lds); kl = go_block_sum(kl, lds); nc = go_block_sum(nc, lds_i);
+  t0 = gs_block_sum(t0, lds);
+  gs = gs_block_sum(gs, lds);
+  t1 = gs_block_sum(t1, lds); kl = gs_block_sum(kl, lds); nc = gs_block_sum(nc, lds_i);
   if (tid) return;
   const double n = (double)S.n, nan = __builtin_nan("");
   const double surr = t0 / n, ent = t1 / n;
