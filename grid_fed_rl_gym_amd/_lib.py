@@ -369,6 +369,51 @@ def pathwise_config(alpha=0.0, bc_coef=0.0, stochastic=True, seed=0, draw=0, str
                               float(bc_coef), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, 0)
 
 
+# policy-action TD targets (include/gridstep.h "policy-action TD targets"): GS_Q_TARGET_*, the noise tags and the structs of
+# gs_rollout_evaluate_q_next / gs_rollout_q_next_*
+GS_Q_TARGET_VALUE, GS_Q_TARGET_POLICY = 0, 1
+Q_TARGETS = {"value": GS_Q_TARGET_VALUE, "policy": GS_Q_TARGET_POLICY}
+Q_NEXT_ROLLOUT_TAG = 0x514E5854       # 'QNXT'
+Q_NEXT_TERMINAL_TAG = 0x514E5445      # 'QNTE'
+_fp = C.POINTER(C.c_float)
+
+
+class gs_q_next_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("bootstrap_mask", C.c_int32), ("stochastic", C.c_int32), ("reserved", C.c_int32),
+                ("gamma", C.c_double), ("alpha", C.c_double), ("reward_shift", C.c_double), ("reward_scale", C.c_double),
+                ("seed", C.c_uint64), ("draw", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+class gs_rollout_q_next(C.Structure):
+    _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("installed", C.c_int32), ("rows_per_tile", C.c_int32), ("action_dim", C.c_int32),
+                ("terminal_capacity", C.c_int32), ("next_pre_head", C.c_void_p), ("next_actions", C.c_void_p), ("next_noise", C.c_void_p), ("next_log_probs", C.c_void_p),
+                ("q_next", C.c_void_p * 2), ("q_next_min", C.c_void_p), ("td_target", C.c_void_p), ("term_pre_head", C.c_void_p),
+                ("term_actions", C.c_void_p), ("term_noise", C.c_void_p), ("term_log_probs", C.c_void_p), ("term_q", C.c_void_p * 2), ("term_q_min", C.c_void_p),
+                ("term_value", C.c_void_p)]
+
+
+class gs_rollout_q_next_host(C.Structure):
+    _fields_ = [("next_pre_head", _fp), ("next_actions", _dp), ("next_noise", _dp), ("next_log_probs", _dp), ("q_next", _dp * 2), ("q_next_min", _dp),
+                ("td_target", _dp), ("term_pre_head", _fp), ("term_actions", _dp), ("term_noise", _dp), ("term_log_probs", _dp), ("term_q", _dp * 2),
+                ("term_q_min", _dp), ("term_value", _dp)]
+
+
+def q_next_config(gamma=0.99, alpha=0.0, bootstrap_mask=0, stochastic=True, seed=0, draw=0, reward_shift=0.0, reward_scale=1.0,
+                  struct_size=None) -> gs_q_next_config:
+    return gs_q_next_config(C.sizeof(gs_q_next_config) if struct_size is None else int(struct_size), int(bootstrap_mask), int(stochastic), 0,
+                            float(gamma), float(alpha), float(reward_shift), float(reward_scale), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                            int(draw) & 0xFFFFFFFF, 0)
+
+
+def q_target_number(source) -> int:
+    """GS_Q_TARGET_* from its name in ``Q_TARGETS`` or its number (an unknown number is the library's to refuse)."""
+    if isinstance(source, str):
+        if source not in Q_TARGETS:
+            raise ValueError(f"Q target: unknown source {source!r}; one of {sorted(Q_TARGETS)}")
+        return Q_TARGETS[source]
+    return int(source)
+
+
 # the federation (include/gridstep.h "the federation"): the structs of gs_fed_*
 GS_FED_MAX_CLIENTS = 32
 _FED = C.c_void_p
@@ -530,6 +575,11 @@ SYMBOLS = [
     ("gs_learner_get_signal", C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32)]),
     ("gs_q_target_update", C.c_int, [_H, C.c_double]),
     ("gs_q_target_download", C.c_int, [_H, C.c_int32, C.c_void_p]),
+    ("gs_rollout_evaluate_q_next", C.c_int, [_H, C.POINTER(gs_q_next_config)]),
+    ("gs_rollout_q_next_view", C.c_int, [_H, C.POINTER(gs_rollout_q_next), C.c_void_p]),
+    ("gs_rollout_q_next_download", C.c_int, [_H, C.POINTER(gs_rollout_q_next_host)]),
+    ("gs_q_set_target_source", C.c_int, [_H, C.c_int32]),
+    ("gs_q_get_target_source", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("gs_learner_step_pathwise", C.c_int, [_H, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.POINTER(gs_pathwise_config), C.c_void_p]),
     ("gs_learner_pathwise_view", C.c_int, [_H, C.POINTER(gs_pathwise_view_out), C.c_void_p]),
     ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
@@ -1769,6 +1819,72 @@ class Handle:
         out = np.empty(int(param_count), dtype=np.float32)
         self._check(self._lib.gs_q_target_download(self._h, q_which(which), out.ctypes.data))
         return out
+
+    # -- policy-action TD targets (gs_rollout_evaluate_q_next, gs_rollout_q_next_*, gs_q_*_target_source) ---------------------------
+    def rollout_evaluate_q_next(self, cfg: Optional[gs_q_next_config] = None) -> None:
+        """gs_rollout_evaluate_q_next (asynchronous): the installed policy's action and log-probability at every next state, the
+        target twins' values of it, their minimum and the Bellman target ``r' + gamma (min Q_target - alpha log pi)``."""
+        cfg = q_next_config() if cfg is None else cfg
+        self._check(self._lib.gs_rollout_evaluate_q_next(self._h, C.byref(cfg)))
+
+    def rollout_q_next_arrays(self, stream=None) -> dict:
+        """gs_rollout_q_next_view as zero-copy ``DeviceArray`` views: ``next_pre_head`` [T, B, 2 A] float32, ``next_actions``
+        / ``next_noise`` [T, B, A], ``next_log_probs`` / ``q_next_min`` / ``td_target`` [T, B], ``q_next`` [twin 0, twin 1] (None for a twin that is
+        not installed); under a bootstrap mask the terminal list's ``term_*`` arrays over its first ``n_terminal`` entries (None
+        otherwise); plus ``installed`` and ``rows_per_tile``.  Valid until the next rollout."""
+        v = gs_rollout_q_next()
+        self._check(self._lib.gs_rollout_q_next_view(self._h, C.byref(v), _stream_arg(stream)))
+        T, B, A = int(v.T), int(v.B), int(v.action_dim)
+        n = int(self.rollout_device_view().n_terminal) if v.term_log_probs else 0
+        arr = lambda p, shape, dt="<f8": DeviceArray(p, shape, dt) if p else None
+        return dict(next_pre_head=arr(v.next_pre_head, (T, B, 2 * A), "<f4"), next_actions=arr(v.next_actions, (T, B, A)), next_noise=arr(v.next_noise, (T, B, A)),
+                    next_log_probs=arr(v.next_log_probs, (T, B)), q_next=[arr(v.q_next[w], (T, B)) for w in range(2)],
+                    q_next_min=arr(v.q_next_min, (T, B)), td_target=arr(v.td_target, (T, B)),
+                    term_pre_head=arr(v.term_pre_head, (n, 2 * A), "<f4"), term_actions=arr(v.term_actions, (n, A)), term_noise=arr(v.term_noise, (n, A)),
+                    term_log_probs=arr(v.term_log_probs, (n,)), term_q=[arr(v.term_q[w], (n,)) for w in range(2)],
+                    term_q_min=arr(v.term_q_min, (n,)), term_value=arr(v.term_value, (n,)),
+                    installed=tuple(w for w in range(2) if v.installed >> w & 1), rows_per_tile=int(v.rows_per_tile), n_terminal=n)
+
+    Q_NEXT_KEYS = ("next_pre_head", "next_actions", "next_noise", "next_log_probs", "q_next", "q_next_min", "td_target", "term_pre_head", "term_actions",
+                   "term_noise", "term_log_probs", "term_q", "term_q_min", "term_value")
+
+    def rollout_q_next_download(self, want=Q_NEXT_KEYS, n_terminal: Optional[int] = None) -> dict:
+        """gs_rollout_q_next_download: host copies of what ``want`` names, shaped as ``rollout_q_next_arrays``'s (``q_next`` and
+        ``term_q`` hold both twins' arrays; a twin that is not installed, and every terminal array when the last evaluation ran
+        under mask 0, is left as NaN).  The terminal arrays need ``n_terminal`` (read from the device when not given)."""
+        unknown = set(want) - set(self.Q_NEXT_KEYS)
+        if unknown:
+            raise PowerFlowError(f"rollout_q_next_download: unknown array(s) {sorted(unknown)}")
+        T, B, A = getattr(self, "_rollout_T", 0), self.B, self.action_dim
+        if n_terminal is None and any(k.startswith("term_") for k in want):
+            n_terminal = int(self.rollout_device_view().n_terminal)
+        n = int(n_terminal or 0)
+        shapes = dict(next_pre_head=(T, B, 2 * A), next_actions=(T, B, A), next_noise=(T, B, A), next_log_probs=(T, B), q_next_min=(T, B), td_target=(T, B),
+                      term_pre_head=(n, 2 * A), term_actions=(n, A), term_noise=(n, A), term_log_probs=(n,), term_q_min=(n,), term_value=(n,))
+        o = gs_rollout_q_next_host()
+        out: dict = {}
+        for k in want:
+            if k in ("q_next", "term_q"):
+                out[k] = [np.full((T, B) if k == "q_next" else (n,), np.nan) for _ in range(2)]
+                for w in range(2):
+                    getattr(o, k)[w] = _ptr(out[k][w], _dp)
+            else:
+                f32 = k.endswith("pre_head")
+                out[k] = np.full(shapes[k], np.nan, dtype=np.float32 if f32 else np.float64)
+                setattr(o, k, _ptr(out[k], _fp if f32 else _dp))
+        self._check(self._lib.gs_rollout_q_next_download(self._h, C.byref(o)))
+        return out
+
+    def q_set_target_source(self, source) -> None:
+        """gs_q_set_target_source: "value" (gs_rollout_evaluate_q's td_target) or "policy" (gs_rollout_evaluate_q_next's) from the
+        next step of a Q learner (``Q_TARGETS``, or the number)."""
+        self._check(self._lib.gs_q_set_target_source(self._h, q_target_number(source)))
+
+    def q_get_target_source(self) -> str:
+        """gs_q_get_target_source: the name of the source in force."""
+        o = C.c_int32(0)
+        self._check(self._lib.gs_q_get_target_source(self._h, C.byref(o)))
+        return {v: k for k, v in Q_TARGETS.items()}[int(o.value)]
 
     def rollout_device_view(self) -> gs_rollout_device:
         """Device pointers of the last rollout (gs_rollout_device_view) for a consumer that stays on the GPU."""

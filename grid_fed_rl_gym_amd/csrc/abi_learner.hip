@@ -247,7 +247,11 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   // gathered through the indices into tr.qy
   const bool gathered = qnet || Ln.signal == GS_SIGNAL_Q;
   const void* target = gathered ? nullptr : policy ? batch->advantages : net == GS_LEARNER_VALUE ? batch->returns : batch->cost_returns[net - GS_LEARNER_COST_VALUE];
-  if (gathered && !q_current(h)) return fail(h, GS_E_STATE, "gs_learner_step: gs_rollout_evaluate_q has not run on the last rollout (%s reads its arrays)", net_name(net));
+  // (a Q learner under GS_Q_TARGET_POLICY regresses on gs_rollout_evaluate_q_next's target: DESIGN.md section 25)
+  const bool policy_target = qnet && h->qn.target_source == GS_Q_TARGET_POLICY;
+  if (policy_target && !q_next_current(h))
+    return fail(h, GS_E_STATE, "gs_learner_step: gs_rollout_evaluate_q_next has not run on the last rollout (%s reads its td_target under GS_Q_TARGET_POLICY)", net_name(net));
+  if (gathered && !policy_target && !q_current(h)) return fail(h, GS_E_STATE, "gs_learner_step: gs_rollout_evaluate_q has not run on the last rollout (%s reads its arrays)", net_name(net));
   const int loss = Ln.loss.kind;
   if (policy && loss == GS_LOSS_DEFAULT && !ro.logp_recorded) return fail(h, GS_E_STATE, "gs_learner_step: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
   if (!batch->observations || (!gathered && !target) || ((policy || gathered) && !batch->indices))
@@ -274,7 +278,7 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
     const size_t cap = (size_t)ro.T_cap * h->B;
     GsQGatherArgs Q{};
     Q.idx = batch->indices; Q.y = tr.qy; Q.N = ob.N; Q.n = n;
-    Q.src = qnet ? h->qt.td.p : policy ? h->qt.q_adv.p : h->qt.q_min.p + cap;      // td_target; q_adv; q_min[target]
+    Q.src = policy_target ? h->qn.td.p : qnet ? h->qt.td.p : policy ? h->qt.q_adv.p : h->qt.q_min.p + cap;      // td_target; q_adv; q_min[target]
     if (qnet) { Q.obs = (const float*)batch->observations; Q.act = ro.act; Q.sa = tr.qsa; Q.D = D; Q.DA = Din; }
     const long long total = (long long)n * (qnet ? Din : 1);
     hipLaunchKernelGGL(gs_k_q_gather, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, Q);

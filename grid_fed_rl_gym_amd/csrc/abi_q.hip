@@ -89,6 +89,7 @@ int gs_q_mlp_set(gs_handle* h, int32_t which, const gs_policy_mlp* p, const gs_p
   val.blob.release(); Q.target.release();
   val.set = false; Q.image_floats = 0;
   h->qt.evaluated_on = 0;                    // (what the last evaluation left belongs to the networks that were installed then)
+  h->qn.evaluated_on = 0;
   if (!p) return GS_OK;
   const int D = h->obs_dim, A = h->action_dim;
   const QOpts q(*o, D, A);                   // (packed, shift and scale are 0 beyond D + A: a padded column normalises to 0)

@@ -38,6 +38,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   onpolicy_release(h);           // (sized by T as well)
   costs_release(h);
   q_rollout_release(h);
+  q_next_rollout_release(h);
   episodes_release(h, keep_term_count);      // (the list is sized by the capacity; the carries outlive a longer rollout)
   batches_release(h);
   learner_scratch_release(h);
@@ -73,6 +74,7 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
   learner_drop(h, 0);              // (a learner trains the network it was created on)
   pol.blob.release();
   pol.set = false;
+  h->qn.evaluated_on = 0;          // (the policy-action targets belong to the policy that was installed then)
   if (!p) return GS_OK;
   int rc = pol.act.grow(h, (size_t)h->B * h->action_dim, "the policy's actions");
   if (rc) return rc;

@@ -202,6 +202,14 @@ struct gs_handle : GsPlan {
   // what gs_rollout_evaluate_q made of the last rollout: q [src][which][T_cap][B], q_min [src][T_cap][B], q_adv, td [T_cap][B]; made
   // on first use (all or none), released with the rollout's buffers; evaluated_on = ro.calls of the rollout they belong to, 0 = none
   struct GS_HIDDEN QTrack { DevBuf<double> q, q_min, q_adv, td; uint64_t evaluated_on = 0; hipEvent_t ev = nullptr; } qt;
+  // gs_rollout_evaluate_q_next (abi_q_next.hip): pre [T_cap][B][2 A], act / eps [T_cap][B][A], lp / q_min / td [T_cap][B],
+  // q [which][T_cap][B] and the same over the terminal list (term_cap entries; t_q [which][term_cap]); made on first use (all or none),
+  // released with the rollout's buffers; evaluated_on as QTrack's; with_terms: the last evaluation wrote the terminal arrays.
+  // target_source: gs_q_set_target_source, host state that outlives rollouts and networks
+  struct GS_HIDDEN QNext {
+    DevBuf<float> pre, t_pre; DevBuf<double> act, eps, lp, q, q_min, td, t_act, t_eps, t_lp, t_q, t_q_min, t_value;
+    uint64_t evaluated_on = 0; bool with_terms = false; hipEvent_t ev = nullptr; int target_source = GS_Q_TARGET_VALUE;
+  } qn;
   // gs_learner_step_pathwise (abi_learner.hip): the twins' passes of an actor step have scratch of their own (acts /
   // deltas [n][the wider twin's row_stride], qsa [n][obs_dim + A]: the policy's saved activations in tr survive them), and the step's
   // per-sample arrays (n_last samples; 0: none): actions / noise [n][A], logp / qmin / bc / terms [n], q [2][n], which [n], dqda
@@ -446,6 +454,10 @@ bool installed(const gs_handle* h, int net, Installed& I);
 void q_release(gs_handle* h);              // everything
 void q_rollout_release(gs_handle* h);      // what is sized by the rollout's capacity
 static inline bool q_current(const gs_handle* h) { return h->qt.evaluated_on && h->qt.evaluated_on == h->ro.calls; }
+
+// ---- owner of the policy-action targets over the rollout (abi_q_next.hip) ----
+void q_next_rollout_release(gs_handle* h);
+static inline bool q_next_current(const gs_handle* h) { return h->qn.evaluated_on && h->qn.evaluated_on == h->ro.calls; }
 
 // ---- the federations of a handle that is being destroyed lose it (abi_fed.hip) ----
 void fed_detach(gs_handle* h);

@@ -9,6 +9,7 @@
 #include "policy.h"
 #include "train.h"
 #include "q.h"
+#include "q_next.h"
 #include "pathwise.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
@@ -76,6 +77,9 @@ __global__ void gs_k_train_head_awr(GsTrainAwrHeadArgs H);
 __global__ void gs_k_train_head_expectile(GsTrainExpectileArgs H);
 __global__ void gs_k_train_stats_awr(GsTrainAwrStatArgs S);
 __global__ void gs_k_q_mlp_f32(GsQArgs P);
+__global__ void gs_k_q_mlp_rows_f32(GsQArgs P, const int32_t* rows_dev);
+__global__ void gs_k_policy_rows_f32(GsPolicyRowsArgs P);
+__global__ void gs_k_q_next_td(GsQNextTdArgs G);
 __global__ void gs_k_q_combine(GsQCombineArgs C);
 __global__ void gs_k_q_td(GsQTdArgs G);
 __global__ void gs_k_q_gather(GsQGatherArgs G);

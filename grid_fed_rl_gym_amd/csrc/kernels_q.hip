@@ -1,5 +1,6 @@
 // kernels_q.hip -- state-action critics over the last rollout (include/gridstep.h "state-action critics"):
 //   gs_k_q_mlp_f32   a Q network (GS_HEAD_LINEAR, float32 layers) on the rows (obs_seq[t][b], actions[t][b])
+//   gs_k_q_mlp_rows_f32   the same body over a list whose length lies on the device
 //   gs_k_q_combine   the minimum over the twins and q_adv = min(Q1, Q2) - V
 //   gs_k_q_td        the one-step TD target r' + gamma * vnext
 //   gs_k_q_gather    the Q learner's input rows and targets, and the Q-based signals of the policy's and the critic's heads
@@ -82,6 +83,10 @@ struct GqaNet {
 
 extern "C" __global__ void __launch_bounds__(64 * GS_POL_WAVES)
 gs_k_q_mlp_f32(GsQArgs P) { gq_scalar_net<GqaNet>(P, nullptr); }
+
+// the same body launched over a list's capacity, the row count read on the device (the terminal list of gs_rollout_evaluate_q_next)
+extern "C" __global__ void __launch_bounds__(64 * GS_POL_WAVES)
+gs_k_q_mlp_rows_f32(GsQArgs P, const int32_t* rows_dev) { gq_scalar_net<GqaNet>(P, rows_dev); }
 
 extern "C" __global__ void __launch_bounds__(256)
 gs_k_q_combine(GsQCombineArgs C) {

@@ -223,7 +223,7 @@ def pathwise_noise_np(seed: int, draw: int, n: int, A: int) -> np.ndarray:
     return z.reshape(n, 4 * quads)[:, :A].copy()
 
 
-# exp, tanh and log of the pathwise heads, operation by operation as kernels_pathwise.hip performs them (gw_exp, gw_tanh, gw_log): rounded
+# exp, tanh and log of the pathwise heads, operation by operation as the kernels perform them (gw_exp, gw_tanh, gw_log of csrc/gw_math.h): rounded
 # float64 +, -, *, / alone, so that the heads are restated to the bit whatever math library NumPy was built on
 _PW_LN2_HI, _PW_LN2_LO, _PW_INV_LN2 = 6.93147180369123816490e-01, 1.90821492927058770002e-10, 1.4426950408889634
 _PW_HALF_LOG_2PI = 0.91893853320467274178      # the kernels' literal: 0.5 log(2 pi) rounded to nearest, one ulp above policy.HALF_LOG_2PI
@@ -453,6 +453,10 @@ class DeviceLearner:
     regresses on the target networks' ``min(Q1, Q2)`` instead of the batch's returns -- with ``policy_loss="awr"`` and
     ``value_loss="expectile"`` that is IQL.  ``update_targets(tau)`` moves the target networks.
 
+    Policy-action targets: ``q_target="policy"`` makes the Q learners regress on ``td_target`` of the last
+    ``evaluate_rollout_q_next`` -- ``r' + gamma (min Q_target(s', pi(s')) - alpha log pi(a' | s'))``, the critic target of SAC,
+    TD3 + BC and DDPG -- instead of the last ``evaluate_rollout_q``'s (``set_q_target`` changes it later; it is the handle's state).
+
     The pathwise actor: ``policy_loss="pathwise"`` makes the policy's step ``gs_learner_step_pathwise`` --
     ``mean(alpha lp - min(Q1, Q2)(s, a) + bc_coef |a - a_stored|^2)`` with ``a`` sampled inside the step
     (``pathwise_stochastic=False``: ``a = tanh(mean)``) and the gradient flowing through the installed twins, which need learners
@@ -468,7 +472,8 @@ class DeviceLearner:
                  eps: float = 1e-8, weight_decay: float = 0.0, clip: float = 0.2, ent_coef: float = 0.0, max_grad_norm: float = 0.0,
                  policy_loss: str = "ppo", temperature: float = 1.0, weight_max: float = 20.0, value_loss: str = "mse",
                  expectile: float = 0.7, q_loss: str = "mse", advantage_source: str = "batch", value_target: str = "batch",
-                 alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True, pathwise_seed: int = 0) -> None:
+                 alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True, pathwise_seed: int = 0,
+                 q_target: str = "value") -> None:
         if isinstance(nets, str):
             nets = (nets,)
         self.nets = tuple(nets)
@@ -508,6 +513,11 @@ class DeviceLearner:
             self._pathwise = self._pathwise_state(alpha, bc_coef, pathwise_stochastic, pathwise_seed)
         else:
             _pathwise_check(alpha, bc_coef)
+        if q_target not in _lib.Q_TARGETS:
+            raise ValueError(f"DeviceLearner: q_target = {q_target!r} must be one of {sorted(_lib.Q_TARGETS)}")
+        if q_target == "policy" and not any(k >= _lib.GS_LEARNER_Q for k in self._ids):
+            raise ValueError(f"DeviceLearner: q_target = 'policy' needs 'q1' or 'q2' among nets {self.nets}")
+        self.q_target = q_target
         self.env = env
         self.config = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                            clip=float(clip), ent_coef=float(ent_coef), max_grad_norm=float(max_grad_norm))
@@ -518,6 +528,8 @@ class DeviceLearner:
                 env.handle.learner_set_loss(net, losses[net])
             if net in signals:                                # (a learner left at "batch" never calls the entry)
                 env.handle.learner_set_signal(net, signals[net])
+        if q_target != "value":                               # (a learner left at "value" never calls the entry)
+            env.handle.q_set_target_source(q_target)
 
     @staticmethod
     def _loss_struct(k: int, loss: str, temperature, weight_max, expectile, what: Optional[str] = None) -> "_lib.gs_learner_loss":
@@ -681,6 +693,17 @@ class DeviceLearner:
 
     def signal(self, net) -> str:
         return self.env.handle.learner_get_signal(self._id(net))
+
+    def set_q_target(self, source: str) -> None:
+        """Which Bellman target the Q learners regress on from their next step (``gs_q_set_target_source``; state of the HANDLE,
+        shared by every learner on it): "value", ``td_target`` of the last ``evaluate_rollout_q`` (``r' + gamma V(s')``), or
+        "policy", ``td_target`` of the last ``evaluate_rollout_q_next`` (``r' + gamma (min Q_target(s', pi(s')) - alpha log pi)``)."""
+        if source not in _lib.Q_TARGETS:
+            raise ValueError(f"DeviceLearner.set_q_target: source = {source!r} must be one of {sorted(_lib.Q_TARGETS)}")
+        if not any(k >= _lib.GS_LEARNER_Q for k in self._ids):
+            raise ValueError(f"DeviceLearner.set_q_target: no Q network among this learner's nets {self.nets}")
+        self.env.handle.q_set_target_source(source)
+        self.q_target = source
 
     def update_targets(self, tau: float = 0.005) -> None:
         """The target networks of every installed twin move towards the online ones, ``t = tau p + (1 - tau) t`` in float32 on the

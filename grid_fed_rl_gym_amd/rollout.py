@@ -204,6 +204,134 @@ def polyak_np(params, target, tau: float) -> np.ndarray:
     return (f(tau) * p) + (f(1.0 - tau) * t)
 
 
+def evaluate_rollout_q_next(env: BatchedGridEnvironment, gamma: float = 0.99, alpha: float = 0.0, bootstrap: Sequence[str] = (),
+                            stochastic: bool = True, seed: int = 0, draw: int = 0, reward_shift: float = 0.0, reward_scale: float = 1.0,
+                            stream=None):
+    """The policy-action Bellman target over the environment's LAST rollout, on the device (``gs_rollout_evaluate_q_next``; the
+    reference's ``CQL._update_critic``, algorithms/offline.py:173-178): the installed float32 tanh-Gaussian policy's action and
+    log-probability at every next state (``stochastic=False``: ``a' = tanh(mean)``), every installed twin's TARGET image on it,
+    their minimum, and ``td_target = r' + gamma (q_next_min - alpha next_log_probs)`` where the episode went on (``bootstrap`` as
+    ``evaluate_rollout``: such an end takes the same expression on its terminal observation; any other end 0).  The noise is
+    ``q_next_noise_np(seed, draw, t * B + b, A)``.  It does not need ``evaluate_rollout``.  Returns an object with
+    ``next_pre_head`` [T, B, 2 A] float32, ``next_actions`` / ``next_noise`` [T, B, A], ``next_log_probs``, ``q_next_min``,
+    ``td_target`` [T, B], ``q_next`` (a list of the two twins, None where not installed), the terminal list's ``term_*`` arrays
+    ([n_terminal, ...]; None without a bootstrap mask), all zero-copy ``DeviceArray`` views valid until the next rollout, plus
+    ``installed``, ``rows_per_tile`` and ``n_terminal``."""
+    gamma, alpha = float(gamma), float(alpha)
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"evaluate_rollout_q_next: alpha = {alpha} must be a finite value >= 0")
+    if not isinstance(stochastic, (bool, np.bool_)):
+        raise ValueError(f"evaluate_rollout_q_next: stochastic = {stochastic!r} must be True or False")
+    _q_next_seed(seed, draw, "evaluate_rollout_q_next")
+    h = env.handle
+    h.rollout_evaluate_q_next(_lib.q_next_config(gamma, alpha, _bootstrap_mask(bootstrap), bool(stochastic), int(seed), int(draw), reward_shift,
+                                                 reward_scale))
+    return SimpleNamespace(**h.rollout_q_next_arrays(stream))
+
+
+def _q_next_seed(seed, draw, who: str) -> None:
+    integer = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+    if not integer(seed) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"{who}: seed = {seed!r} must be an integer in [0, 2^64)")
+    if not integer(draw) or not 0 <= int(draw) < 1 << 32:
+        raise ValueError(f"{who}: draw = {draw!r} must be an integer in [0, 2^32)")
+
+
+def q_next_noise_np(seed: int, draw: int, index, A: int, terminal: bool = False) -> np.ndarray:
+    """eps [n, A] of ``gs_rollout_evaluate_q_next`` for the transitions ``index`` [n] (``t * B + b`` each; NOT a row's place in a
+    list): ``eps[j, k]`` = component ``k & 3`` of the four normals of Philox4x32-10 with counter (index[j], k >> 2, draw, tag) and
+    key ``seed`` -- ``pathwise_noise_np``'s recipe (every word w a uniform (w + 1/2) 2^-32, words (0, 1) and (2, 3) one Box-Muller
+    pair each, cosine then sine).  tag: 'QNXT' for the rollout's rows, 'QNTE' (``terminal``) for the terminal observations."""
+    _q_next_seed(seed, draw, "q_next_noise_np")
+    A = int(A)
+    idx = np.asarray(index)
+    if A <= 0:
+        raise ValueError(f"q_next_noise_np: A = {A} must be > 0")
+    if idx.ndim != 1 or (idx.size and (not np.issubdtype(idx.dtype, np.integer) or idx.min() < 0 or idx.max() >= 1 << 32)):
+        raise ValueError("q_next_noise_np: index must be a one-dimensional array of integers in [0, 2^32)")
+    n, quads = idx.size, (A + 3) // 4
+    i = np.repeat(idx.astype(np.uint64), quads)
+    q = np.tile(np.arange(quads, dtype=np.uint64), n)
+    full = lambda x: np.full(i.shape, int(x) & 0xFFFFFFFF, dtype=np.uint64)
+    tag = _lib.Q_NEXT_TERMINAL_TAG if terminal else _lib.Q_NEXT_ROLLOUT_TAG
+    seed = int(seed)
+    w = np.stack(_philox4x32(i, q, full(draw), full(tag), seed & 0xFFFFFFFF, seed >> 32), axis=1).astype(np.float64)
+    u = (w + 0.5) * (1.0 / 4294967296.0)
+    ra, rb = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
+    ta, tb = 2.0 * math.pi * u[:, 1], 2.0 * math.pi * u[:, 3]
+    z = np.stack([ra * np.cos(ta), ra * np.sin(ta), rb * np.cos(tb), rb * np.sin(tb)], axis=1)
+    return z.reshape(n, 4 * quads)[:, :A].copy()
+
+
+def policy_rows_np(policy, observations, eps, exact: bool = False, pre_head=None):
+    """(pre_head [n, 2 A], actions [n, A], log_probs [n]) of ``gs_k_policy_rows_f32`` restated in NumPy: ``policy`` (an ``MLPPolicy``
+    with the Gaussian head) on raw ``observations`` [n, obs_dim] under the float32 device contract (``exact``: the same rounded
+    operands in float64 throughout, what the float32 result is measured against), then the sampling head of the pathwise actor
+    step (``learner._pathwise_sample``: ITS exp, tanh and log, float64 on the pre-head values) with the noise ``eps`` [n, A]; None is
+    the deterministic actor, eps = 0.  ``pre_head``: values to run the head on in place of the layers' (the device's own, for a
+    bit-for-bit statement of the head)."""
+    from .learner import _pathwise_sample      # (learner.py imports this module)
+
+    if getattr(policy, "head", None) != "gaussian_tanh":
+        raise ValueError("policy_rows_np: the policy needs the Gaussian head (mean | log_std)")
+    obs = np.asarray(observations, dtype=np.float64)
+    if obs.ndim != 2 or obs.shape[1] != policy.obs_dim:
+        raise ValueError(f"policy_rows_np: observations must be [n, {policy.obs_dim}], got {obs.shape}")
+    n, A = obs.shape[0], policy.action_dim
+    if pre_head is None:
+        pre = policy.pre_head_np(obs, "float32", exact)
+    else:
+        pre = np.asarray(pre_head)
+        if pre.shape != (n, 2 * A):
+            raise ValueError(f"policy_rows_np: pre_head must be [{n}, {2 * A}], got {pre.shape}")
+    if eps is None:
+        eps = np.zeros((n, A))
+    eps = np.asarray(eps, dtype=np.float64)
+    if eps.shape != (n, A):
+        raise ValueError(f"policy_rows_np: eps must be [{n}, {A}], got {eps.shape}")
+    _, _, _, a, lp = _pathwise_sample(pre.astype(np.float64), eps)
+    return pre, a, lp
+
+
+def td_policy_np(rewards, next_log_probs, q_next_min, terminals, terminal_q, terminal_index, gamma: float = 0.99, alpha: float = 0.0,
+                 bootstrap_mask: int = 0, reward_shift: float = 0.0, reward_scale: float = 1.0, terminal_log_probs=None) -> np.ndarray:
+    """``td_target`` [T, B] of ``gs_rollout_evaluate_q_next`` restated in NumPy, every operation IEEE float64 in the device's order:
+    ``r' + gamma * v`` with ``r' = (rewards - reward_shift) * reward_scale`` and ``v = q_next_min - alpha * next_log_probs`` where
+    the transition did not end an episode, the terminal entry's value where it did and its flag meets ``bootstrap_mask``, 0
+    otherwise (mask 0: the reference's ``1 - terminals``, algorithms/offline.py:175-178).  The terminal entry's value for the
+    transition ``terminal_index[e]`` (t, b): ``terminal_q[e] - alpha * terminal_log_probs[e]`` (the device's ``term_q_min`` and
+    ``term_log_probs``), or ``terminal_q[e]`` itself without ``terminal_log_probs`` (the device's ``term_value``)."""
+    rewards = np.asarray(rewards, dtype=np.float64)
+    lp, qm = np.asarray(next_log_probs, dtype=np.float64), np.asarray(q_next_min, dtype=np.float64)
+    terminals = np.asarray(terminals).astype(np.uint8)
+    if rewards.ndim != 2 or lp.shape != rewards.shape or qm.shape != rewards.shape or terminals.shape != rewards.shape:
+        raise ValueError(f"td_policy_np: rewards, next_log_probs, q_next_min and terminals must share one [T, B] shape, got {rewards.shape}, "
+                         f"{lp.shape}, {qm.shape}, {terminals.shape}")
+    gamma, alpha, mask = float(gamma), float(alpha), int(bootstrap_mask)
+    if not math.isfinite(gamma):
+        raise ValueError(f"td_policy_np: gamma = {gamma} must be finite")
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"td_policy_np: alpha = {alpha} must be a finite value >= 0")
+    if not 0 <= mask <= 3:
+        raise ValueError(f"td_policy_np: bootstrap_mask = {mask} outside 0 .. 3")
+    T, B = rewards.shape
+    idx = np.asarray(terminal_index, dtype=np.int64).reshape(-1, 2)
+    tq = np.asarray(terminal_q, dtype=np.float64).reshape(-1)
+    if mask and len(tq) < len(idx):
+        raise ValueError(f"td_policy_np: {len(idx)} terminal entries but {len(tq)} terminal values")
+    term_v = np.zeros((T, B))
+    if mask and len(idx):
+        tv = tq[:len(idx)]
+        if terminal_log_probs is not None:
+            tv = tv - alpha * np.asarray(terminal_log_probs, dtype=np.float64).reshape(-1)[:len(idx)]
+        term_v[idx[:, 0], idx[:, 1]] = tv
+    done = terminals != 0
+    v = qm - alpha * lp
+    vnext = np.where(done, np.where((terminals & mask) != 0, term_v, 0.0), v)
+    r = (rewards - float(reward_shift)) * float(reward_scale)
+    return r + gamma * vnext
+
+
 def collect_onpolicy_data(env: BatchedGridEnvironment, policy, value, num_steps: int, seed: int = 0, reset: bool = True,
                           gamma: float = 0.99, lam: float = 0.95, bootstrap: Sequence[str] = (), reward_shift: float = 0.0,
                           reward_scale: float = 1.0) -> Dict[str, np.ndarray]:

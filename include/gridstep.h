@@ -1082,6 +1082,96 @@ typedef struct gs_pathwise_view_out {
 int gs_learner_step_pathwise(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t n, const gs_pathwise_config* cfg, void* consumer_stream);
 int gs_learner_pathwise_view(gs_handle* h, gs_pathwise_view_out* out, void* consumer_stream);
 
+/* ---- policy-action TD targets: Q_target(s', pi(s')) - alpha log pi(a' | s') ----
+ * The Bellman target of SAC, TD3 + BC, DDPG and the Bellman half of CQL (the reference's CQL._update_critic, algorithms/offline.py:
+ * 173-178): the POLICY's action at the next state, valued by the target twins.  Additive to ABI 2: no struct above changes, and a
+ * handle that calls none of these entries computes what it computed before.
+ *
+ * gs_rollout_evaluate_q_next (asynchronous, on the handle's stream, over the LAST rollout) needs a rollout, at least one installed
+ * twin and an installed policy with GS_COMPUTE_F32 and GS_HEAD_GAUSSIAN_TANH (GS_E_STATE otherwise); it does not need
+ * gs_rollout_evaluate.  GS_E_INVALID: a wrong struct_size, a bootstrap_mask, gamma, reward_shift or reward_scale gs_rollout_evaluate
+ * refuses, alpha NaN, negative or infinite, stochastic outside {0, 1}.  Every check runs before any launch.  With i = t B + b the
+ * index of transition (t, b), whose next state is the row obs_seq[t + 1][b]:
+ *   next_pre_head[i][0 .. 2A)   float32, mean | log_std of the installed policy on that row: the float32 layers of the policy's
+ *                               compute path (float64 normalisation rounded once, products and sums on the matrix cores), 64 rows a tile
+ *   next_actions[i][A], next_log_probs[i]     the sampling head of "the pathwise actor step", operation for operation in float64
+ *                               on those float32 values with ITS exp, tanh and log, nothing contracted; eps_k is component k & 3 of
+ *                               Philox4x32-10 with counter (i, k >> 2, draw, 'QNXT' = 0x514E5854) and key seed, 0 when stochastic
+ *                               == 0 (a = tanh(mean)); lp in ONE chain from k = 0
+ *   next_noise[i][A]            eps as the head used it
+ *   q_next[which][i]            the value of twin `which` under its TARGET image on (obs_seq[t + 1][b], next_actions[i]), as q[1]
+ *                               of gs_rollout_evaluate_q is on the stored action
+ *   q_next_min[i]               fmin over the installed twins (one twin: that twin)
+ *   td_target[i]                r' + gamma * v;  r' = (rew - reward_shift) * reward_scale;  v = q_next_min[i] - alpha *
+ *                               next_log_probs[i] where the transition did not end an episode, term_value[e] where it did and its
+ *                               flag meets bootstrap_mask, 0 otherwise.  Every product and every sum rounded, in that order: alpha *
+ *                               lp, the difference, gamma * v, the sum.  bootstrap_mask 0 is the reference's (1 - terminals).
+ * Under a non-zero mask (and a terminal list) entry e of the terminal list, for the transition (t, b) of term_idx[e], gets
+ * term_pre_head / term_actions / term_noise / term_log_probs / term_q[which] / term_q_min / term_value the same way on its terminal observation,
+ * with the noise counter (t B + b, k >> 2, draw, 'QNTE' = 0x514E5445): the list's order does not enter.  Entries in list order, the
+ * first terminal_count of them; under mask 0 they are not written.
+ * A row's outputs depend on that row, the images, seed, draw and its transition's index alone.  The arrays are made on first use,
+ * sized by the rollout's capacity, and go with the rollout's buffers; gs_policy_mlp_set* and gs_q_mlp_set make the evaluation stale,
+ * a learner's step does not: the targets are those of the last evaluation (re-evaluate between epochs).
+ * gs_rollout_q_next_view: device pointers (NULL for a twin that is not installed), valid until the next gs_rollout; consumer_stream
+ * as gs_rollout_onpolicy_view.  gs_rollout_q_next_download: host copies, any pointer may be NULL; the terminal arrays take the
+ * terminal count of the last rollout.  Both are GS_E_STATE unless gs_rollout_evaluate_q_next has run on the last rollout.
+ *
+ * gs_q_set_target_source(h, source): which array a step of GS_LEARNER_Q + which regresses on through the batch's indices:
+ * GS_Q_TARGET_VALUE (the default) td_target of gs_rollout_evaluate_q, GS_Q_TARGET_POLICY td_target of gs_rollout_evaluate_q_next,
+ * which must then be current on the last rollout (GS_E_STATE before any launch) while gs_rollout_evaluate_q need not be.  Host state
+ * of the handle; an unknown value is GS_E_INVALID.  Signals (GS_SIGNAL_Q) read gs_rollout_evaluate_q's arrays whatever the source. */
+enum { GS_Q_TARGET_VALUE = 0, GS_Q_TARGET_POLICY = 1 };
+typedef struct gs_q_next_config {
+  int32_t struct_size;            /* = sizeof(gs_q_next_config) */
+  int32_t bootstrap_mask;         /* as gs_gae_config */
+  int32_t stochastic;             /* 0: eps = 0, the deterministic actor a' = tanh(mean) */
+  int32_t reserved;
+  double gamma, alpha;            /* alpha: finite, >= 0 */
+  double reward_shift, reward_scale;
+  uint64_t seed;
+  uint32_t draw, reserved2;
+} gs_q_next_config;
+int gs_rollout_evaluate_q_next(gs_handle* h, const gs_q_next_config* cfg);
+typedef struct gs_rollout_q_next {
+  int32_t T, B, installed, rows_per_tile;   /* installed: bit `which` */
+  int32_t action_dim, terminal_capacity;    /* terminal arrays: terminal_capacity entries allocated, NULL under bootstrap_mask 0 */
+  const float* next_pre_head;     /* [T][B][2 A] */
+  const double* next_actions;     /* [T][B][A] */
+  const double* next_noise;       /* [T][B][A] eps as the head used it */
+  const double* next_log_probs;   /* [T][B] */
+  const double* q_next[2];        /* [which], [T][B] each; NULL: twin not installed */
+  const double* q_next_min;
+  const double* td_target;
+  const float* term_pre_head;     /* [terminal_capacity][2 A] */
+  const double* term_actions;     /* [terminal_capacity][A] */
+  const double* term_noise;
+  const double* term_log_probs;   /* [terminal_capacity] */
+  const double* term_q[2];
+  const double* term_q_min;
+  const double* term_value;
+} gs_rollout_q_next;
+int gs_rollout_q_next_view(gs_handle* h, gs_rollout_q_next* out, void* consumer_stream);
+typedef struct gs_rollout_q_next_host {
+  float* next_pre_head;
+  double* next_actions;
+  double* next_noise;
+  double* next_log_probs;
+  double* q_next[2];
+  double* q_next_min;
+  double* td_target;
+  float* term_pre_head;           /* the first terminal_count entries are written */
+  double* term_actions;
+  double* term_noise;
+  double* term_log_probs;
+  double* term_q[2];
+  double* term_q_min;
+  double* term_value;
+} gs_rollout_q_next_host;
+int gs_rollout_q_next_download(gs_handle* h, const gs_rollout_q_next_host* out);
+int gs_q_set_target_source(gs_handle* h, int32_t source);
+int gs_q_get_target_source(gs_handle* h, int32_t* source);
+
 /* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
  * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
  * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
