@@ -369,6 +369,29 @@ def pathwise_config(alpha=0.0, bc_coef=0.0, stochastic=True, seed=0, draw=0, str
                               float(bc_coef), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, 0)
 
 
+# the conservative critic step (include/gridstep.h "the conservative critic step"): the tags and the structs of
+# gs_learner_step_conservative / _conservative_view
+CQL_UNIFORM_TAG = 0x43514C55         # 'CQLU'
+CQL_NOISE_TAG = 0x43514C4E           # 'CQLN'
+CQL_MAX_N = (1 << 24) // 3
+
+
+class gs_conservative_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("stochastic", C.c_int32), ("conservative_weight", C.c_double), ("seed", C.c_uint64),
+                ("draw", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class gs_conservative_view_out(C.Structure):
+    _fields_ = [("net", C.c_int32), ("n", C.c_int32), ("action_dim", C.c_int32), ("pre_head_stride", C.c_int32), ("pre_head", C.c_void_p),
+                ("random_actions", C.c_void_p), ("policy_actions", C.c_void_p), ("policy_noise", C.c_void_p), ("policy_log_probs", C.c_void_p),
+                ("targets", C.c_void_p), ("q", C.c_void_p), ("weights", C.c_void_p), ("loss_terms", C.c_void_p), ("scalars", C.c_void_p)]
+
+
+def conservative_config(conservative_weight=5.0, stochastic=True, seed=0, draw=0, struct_size=None) -> gs_conservative_config:
+    return gs_conservative_config(C.sizeof(gs_conservative_config) if struct_size is None else int(struct_size), int(stochastic),
+                                  float(conservative_weight), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFF, 0)
+
+
 # policy-action TD targets (include/gridstep.h "policy-action TD targets"): GS_Q_TARGET_*, the noise tags and the structs of
 # gs_rollout_evaluate_q_next / gs_rollout_q_next_*
 GS_Q_TARGET_VALUE, GS_Q_TARGET_POLICY = 0, 1
@@ -582,6 +605,8 @@ SYMBOLS = [
     ("gs_q_get_target_source", C.c_int, [_H, C.POINTER(C.c_int32)]),
     ("gs_learner_step_pathwise", C.c_int, [_H, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.POINTER(gs_pathwise_config), C.c_void_p]),
     ("gs_learner_pathwise_view", C.c_int, [_H, C.POINTER(gs_pathwise_view_out), C.c_void_p]),
+    ("gs_learner_step_conservative", C.c_int, [_H, C.c_int32, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.POINTER(gs_conservative_config), C.c_void_p]),
+    ("gs_learner_conservative_view", C.c_int, [_H, C.POINTER(gs_conservative_view_out), C.c_void_p]),
     ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
     ("gs_fed_destroy", C.c_int, [_FED]),
     ("gs_fed_info", C.c_int, [_FED, C.POINTER(gs_fed_info_out)]),
@@ -1699,6 +1724,35 @@ class Handle:
                     q=[arr(o.q[w], (n,), "<f8") for w in range(2)], q_min=arr(o.q_min, (n,), "<f8"), bc_terms=arr(o.bc_terms, (n,), "<f8"),
                     loss_terms=arr(o.loss_terms, (n,), "<f8"), which=arr(o.which, (n,), "<i4"),
                     dq_da=[arr(o.dq_da[w], (n, A), "<f4") for w in range(2)], installed=tuple(w for w in range(2) if o.installed >> w & 1))
+
+    def learner_step_conservative(self, net, batch: dict, n: Optional[int] = None, cfg: Optional[gs_conservative_config] = None, stream=None) -> None:
+        """gs_learner_step_conservative (asynchronous): one conservative critic update of twin ``net`` ("q1" / "q2") on ``batch`` (as
+        ``learner_step``'s) under ``cfg`` (``conservative_config``)."""
+        b = gs_onpolicy_batch_out()
+        addr = lambda x: None if x is None else int(x) if isinstance(x, (int, np.integer)) else int(x.__cuda_array_interface__["data"][0]) if hasattr(x, "__cuda_array_interface__") else int(x.data_ptr())
+        for k in ("observations", "indices"):
+            if batch.get(k) is not None:
+                setattr(b, k, addr(batch[k]))
+        if n is None:
+            obs = batch.get("observations")
+            n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
+        cfg = conservative_config() if cfg is None else cfg
+        self._check(self._lib.gs_learner_step_conservative(self._h, _net_number(net), C.byref(b), int(n), C.byref(cfg), _stream_arg(stream)))
+
+    def learner_conservative_view(self, stream=None) -> dict:
+        """gs_learner_conservative_view: the last conservative step's arrays as zero-copy ``DeviceArray`` views -- ``random_actions``,
+        ``policy_actions``, ``policy_noise`` [n, A], ``policy_log_probs``, ``loss_terms`` [n], ``q``, ``weights`` [3 n], ``scalars``
+        [4] (m, S, lse, qbar) (float64), ``targets`` [n] (float32), ``pre_head`` / ``pre_head_stride`` as ``learner_pathwise_view``'s;
+        plus ``net`` (the twin's learner number), ``n`` and ``action_dim``."""
+        o = gs_conservative_view_out()
+        self._check(self._lib.gs_learner_conservative_view(self._h, C.byref(o), _stream_arg(stream)))
+        n, A = int(o.n), int(o.action_dim)
+        flat = (n - 1) * int(o.pre_head_stride) + 2 * A
+        return dict(net=int(o.net), n=n, action_dim=A, pre_head=DeviceArray(o.pre_head, (flat,), "<f4"), pre_head_stride=int(o.pre_head_stride),
+                    random_actions=DeviceArray(o.random_actions, (n, A), "<f8"), policy_actions=DeviceArray(o.policy_actions, (n, A), "<f8"),
+                    policy_noise=DeviceArray(o.policy_noise, (n, A), "<f8"), policy_log_probs=DeviceArray(o.policy_log_probs, (n,), "<f8"),
+                    targets=DeviceArray(o.targets, (n,), "<f4"), q=DeviceArray(o.q, (3 * n,), "<f8"), weights=DeviceArray(o.weights, (3 * n,), "<f8"),
+                    loss_terms=DeviceArray(o.loss_terms, (n,), "<f8"), scalars=DeviceArray(o.scalars, (4,), "<f8"))
 
     def learner_stats(self, net) -> dict:
         """gs_learner_stats: the last step's ``LEARNER_STATS`` as floats (waits for the step); ``step`` an int."""

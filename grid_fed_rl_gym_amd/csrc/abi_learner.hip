@@ -3,7 +3,8 @@
 // kernels_train.hip; with gs_learner_set_loss the head and its statistics are those of kernels_train_offline.hip, DESIGN.md section
 // 21; a Q learner's input rows and targets, and the heads' Q-based signals of gs_learner_set_signal, are gathered first by
 // gs_k_q_gather of kernels_q.hip, section 22), gs_learner_stats / _info / _download / _view read what it left.  gs_learner_step_pathwise is the
-// policy's step whose gradient flows through the twins (kernels_pathwise.hip, section 23).  Both steps run one pipeline: the checks on
+// policy's step whose gradient flows through the twins (kernels_pathwise.hip, section 23), gs_learner_step_conservative a twin's step
+// with the logsumexp penalty over 3 n rows (kernels_conservative.hip, section 26).  All steps run one pipeline: the checks on
 // the minibatches, the growth of h->tr and every launch of kernels_train.hip (queue_*) are file-local helpers, stated once; a step adds
 // its head and statistics.  The table of the learners' networks (net_name, installed; handle.h) is defined here.  The learners' buffers
 // are made and released here: parameters with the learner (learner_drop), what is sized by n with the rollout's (learner_scratch_release).
@@ -18,6 +19,7 @@ using namespace gsi;
 static_assert(sizeof(gs_learner_config) == 72, "gs_learner_config: two int32, eight doubles");
 static_assert(sizeof(gs_learner_loss) == 32, "gs_learner_loss: two int32, three doubles");
 static_assert(sizeof(gs_pathwise_config) == 40, "gs_pathwise_config: two int32, two doubles, a uint64, two uint32");
+static_assert(sizeof(gs_conservative_config) == 32, "gs_conservative_config: two int32, a double, a uint64, two uint32");
 static_assert(GS_POLICY_MAX_LAYERS == 4, "gs_learner_info_out::dims holds five widths");
 
 namespace gsi __attribute__((visibility("hidden"))) {
@@ -34,6 +36,7 @@ void learner_drop(gs_handle* h, int k) {
   learner_scratch_release_one(L);
   if (L.ev) { (void)hipEventDestroy(L.ev); L.ev = nullptr; }
   L.live = false; L.steps = 0; L.loss = gs_learner_loss{}; L.signal = GS_SIGNAL_BATCH;
+  if (k == GS_LEARNER_POLICY || k == h->cq.net) h->cq.n_last = 0;      // (the conservative step's view names both learners)
 }
 
 void learner_scratch_release(gs_handle* h) {
@@ -43,6 +46,10 @@ void learner_scratch_release(gs_handle* h) {
   pw.acts.release(); pw.deltas.release(); pw.qsa.release(); pw.dqda.release(); pw.actions.release(); pw.noise.release(); pw.logp.release();
   pw.q.release(); pw.qmin.release(); pw.bc.release(); pw.terms.release(); pw.which.release();
   pw.n_last = 0;
+  gs_handle::Conservative& cq = h->cq;
+  cq.random.release(); cq.actions.release(); cq.noise.release(); cq.logp.release(); cq.q.release(); cq.weights.release(); cq.terms.release();
+  cq.scalars.release(); cq.y.release();
+  cq.n_last = 0;
 }
 
 void learner_release(gs_handle* h) {
@@ -530,6 +537,125 @@ int gs_learner_pathwise_view(gs_handle* h, gs_pathwise_view_out* out, void* cons
     if (!(pw.installed >> w & 1)) continue;
     out->q[w] = pw.q + w * n; out->dq_da[w] = pw.dqda + w * n * A;
   }
+  return GS_OK;
+}
+
+// ---- the conservative critic step (include/gridstep.h "the conservative critic step"): the policy's forward
+// pass gives the policy block's actions, gs_k_q_gather the data block and the targets, gs_k_cql_rows the rest of the 3 n input rows;
+// then the twin's forward pass, the logsumexp and the head of kernels_conservative.hip, and the twin's backward pass, reduction,
+// statistics and Adam as above.  The policy's saved activations lie BEHIND the twin's 3 n rows in tr.acts (cq.pre_off): the view's
+// pre-head values outlive the twin's passes ----
+int gs_learner_step_conservative(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, const gs_conservative_config* cfg,
+                                 void* consumer_stream) {
+  const char* const who = "gs_learner_step_conservative";
+  if (!h || !batch || !cfg) return fail(h, GS_E_INVALID, "handle / batch / config is NULL");
+  if (cfg->struct_size != (int32_t)sizeof(gs_conservative_config))
+    return fail(h, GS_E_INVALID, "gs_conservative_config struct_size %d != %d", cfg->struct_size, (int)sizeof(gs_conservative_config));
+  if (net != GS_LEARNER_Q && net != GS_LEARNER_Q + 1) return fail(h, GS_E_INVALID, "%s: net %d is not GS_LEARNER_Q + {0, 1}", who, net);
+  if (!std::isfinite(cfg->conservative_weight) || cfg->conservative_weight < 0.0)
+    return fail(h, GS_E_INVALID, "gs_conservative_config: conservative_weight must be finite and >= 0");
+  if (cfg->stochastic != 0 && cfg->stochastic != 1) return fail(h, GS_E_INVALID, "gs_conservative_config: stochastic = %d outside 0 .. 1", cfg->stochastic);
+  if (n <= 0 || n > GS_CQL_MAX_N) return fail(h, GS_E_INVALID, "%s: n = %d outside 1 .. 2^24 / 3", who, n);
+  gs_handle::Learner& Ln = h->learner[net];
+  gs_handle::Learner& Lp = h->learner[GS_LEARNER_POLICY];
+  Installed I{}, IP{};
+  if (!Ln.live || !installed(h, net, I)) return fail(h, GS_E_STATE, "%s: no learner for %s (gs_learner_create after the network was installed)", who, net_name(net));
+  if (Ln.loss.kind != GS_LOSS_DEFAULT) return fail(h, GS_E_STATE, "%s: the loss of %s must be GS_LOSS_DEFAULT (the penalty joins the squared error)", who, net_name(net));
+  if (!Lp.live || !installed(h, GS_LEARNER_POLICY, IP) || h->pol.args32.head != GS_HEAD_GAUSSIAN_TANH)
+    return fail(h, GS_E_STATE, "%s: no learner for the policy (GS_COMPUTE_F32, GS_HEAD_GAUSSIAN_TANH: its forward pass gives the policy block's actions)", who);
+  const int D = h->obs_dim, A = h->action_dim, DA = D + A;
+  if (A <= 0 || A > GS_PW_MAX_A) return fail(h, GS_E_STATE, "%s: action_dim = %d outside 1 .. %d", who, A, GS_PW_MAX_A);
+  const gs_handle::OnPolicyBatches& ob = h->opb;
+  const gs_handle::Rollout& ro = h->ro;
+  int rc = GS_OK;
+  if ((rc = check_batches(h, who))) return rc;
+  if ((rc = check_norm(h, who, GS_LEARNER_POLICY, IP))) return rc;
+  if ((rc = check_norm(h, who, net, I))) return rc;
+  const bool policy_target = h->qn.target_source == GS_Q_TARGET_POLICY;
+  if (policy_target && !q_next_current(h))
+    return fail(h, GS_E_STATE, "%s: gs_rollout_evaluate_q_next has not run on the last rollout (%s reads its td_target under GS_Q_TARGET_POLICY)", who, net_name(net));
+  if (!policy_target && !q_current(h)) return fail(h, GS_E_STATE, "%s: gs_rollout_evaluate_q has not run on the last rollout (%s reads its td_target)", who, net_name(net));
+  if (!batch->observations || !batch->indices) return fail(h, GS_E_INVALID, "%s: the batch lacks %s", who, !batch->observations ? "observations" : "indices");
+  GS_ENTER(h);
+  const GsTrainNet& N = Ln.net;
+  const GsTrainNet& NP = Lp.net;
+  gs_handle::TrainScratch& tr = h->tr;
+  gs_handle::Conservative& cq = h->cq;
+  const int rows = 3 * n;
+  const size_t pre_off = (size_t)rows * N.row_stride;      // (a multiple of 16 floats: the policy's rows keep their alignment)
+  if ((rc = tr.acts.grow(h, pre_off + (size_t)n * NP.row_stride, "the learner's saved activations"))) return rc;
+  if ((rc = grow_scratch(h, N, rows))) return rc;
+  if ((rc = tr.qsa.grow(h, (size_t)rows * DA, "the Q learner's input rows"))) return rc;
+  if ((rc = cq.random.grow(h, (size_t)n * A, "the conservative step's uniform actions"))) return rc;
+  if ((rc = cq.actions.grow(h, (size_t)n * A, "the conservative step's policy actions"))) return rc;
+  if ((rc = cq.noise.grow(h, (size_t)n * A, "the conservative step's noise"))) return rc;
+  if ((rc = cq.logp.grow(h, (size_t)n, "the conservative step's log-probabilities"))) return rc;
+  if ((rc = cq.y.grow(h, (size_t)n, "the conservative step's targets"))) return rc;
+  if ((rc = cq.q.grow(h, (size_t)rows, "the conservative step's values"))) return rc;
+  if ((rc = cq.weights.grow(h, (size_t)rows, "the conservative step's softmax weights"))) return rc;
+  if ((rc = cq.terms.grow(h, (size_t)n, "the conservative step's loss terms"))) return rc;
+  if ((rc = cq.scalars.grow(h, 4, "the conservative step's scalars"))) return rc;
+  Ln.n_last = 0; cq.n_last = 0;              // (until every launch is queued; gs_learner_view's arrays are gs_learner_step's)
+  const float* const obs = (const float*)batch->observations;
+  const int plast = NP.n_layers - 1, last = N.n_layers - 1;
+
+  // the policy block's actions: the policy's forward pass, then section 23's sampling head under this step's tag
+  float* const pacts = tr.acts + pre_off;
+  if ((rc = queue_forward(h, NP, obs, pacts, n, D))) return rc;
+  GsPwSampleArgs S{};
+  S.pre = pacts + NP.col_off[plast]; S.actions = cq.actions; S.noise = cq.noise; S.logp = cq.logp; S.sa = tr.qsa + (size_t)2 * n * DA;
+  S.n = n; S.row_stride = NP.row_stride; S.A = A; S.D = D; S.stochastic = cfg->stochastic; S.draw = cfg->draw; S.tag = GS_CQL_NOISE_TAG; S.seed = cfg->seed;
+  hipLaunchKernelGGL(gs_k_pw_sample, dim3((n + 63) / 64), dim3(64), 0, h->stream, S);
+  HIPCHK(h, hipGetLastError());
+
+  // the data block and the targets (gs_learner_step's gather), then the other blocks' observations and the uniform actions
+  GsQGatherArgs Q{};
+  Q.idx = batch->indices; Q.y = cq.y; Q.N = ob.N; Q.n = n; Q.src = policy_target ? h->qn.td.p : h->qt.td.p;
+  Q.obs = obs; Q.act = ro.act; Q.sa = tr.qsa; Q.D = D; Q.DA = DA;
+  const unsigned elem_blocks = (unsigned)(((long long)n * DA + 255) / 256);
+  hipLaunchKernelGGL(gs_k_q_gather, dim3(elem_blocks), dim3(256), 0, h->stream, Q);
+  HIPCHK(h, hipGetLastError());
+  GsCqlRowsArgs RW{obs, tr.qsa, cq.random, n, D, A, cfg->draw, cfg->seed};
+  hipLaunchKernelGGL(gs_k_cql_rows, dim3(elem_blocks), dim3(256), 0, h->stream, RW);
+  HIPCHK(h, hipGetLastError());
+
+  if ((rc = queue_forward(h, N, tr.qsa, tr.acts, rows, DA))) return rc;
+  const float* const qpre = tr.acts + N.col_off[last];
+  GsCqlLseArgs LS{qpre, cq.scalars, n, N.row_stride};
+  hipLaunchKernelGGL(gs_k_cql_lse, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, LS);
+  HIPCHK(h, hipGetLastError());
+  GsCqlHeadArgs H{};
+  H.qpre = qpre; H.ghead = tr.deltas + N.col_off[last]; H.y = cq.y; H.scalars = cq.scalars; H.q = cq.q; H.weights = cq.weights; H.terms = cq.terms;
+  H.n = n; H.row_stride = N.row_stride; H.width16 = 16 * N.L[last].nt; H.cw = cfg->conservative_weight;
+  hipLaunchKernelGGL(gs_k_cql_head, dim3((rows + 63) / 64), dim3(64), 0, h->stream, H);
+  HIPCHK(h, hipGetLastError());
+
+  if ((rc = queue_bwd_data(h, N, tr.acts, tr.deltas, rows))) return rc;
+  const int red_blocks = queue_grad_reduce(h, Ln, tr.qsa, rows, DA);
+  if (red_blocks < 0) return red_blocks;
+  GsCqlStatArgs ST{cq.terms, cq.scalars, Ln.blocksum, Ln.stats, n, red_blocks, cfg->conservative_weight};
+  hipLaunchKernelGGL(gs_k_cql_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, ST);
+  HIPCHK(h, hipGetLastError());
+  if ((rc = queue_adam(h, Ln))) return rc;
+  Ln.steps += 1; cq.n_last = n; cq.net = net; cq.pre_off = pre_off;
+  return publish(h, h->stream, Ln.ev, consumer_stream);
+}
+
+int gs_learner_conservative_view(gs_handle* h, gs_conservative_view_out* out, void* consumer_stream) {
+  if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");
+  gs_handle::Conservative& cq = h->cq;
+  if (!cq.n_last || !h->learner[cq.net].live || !h->learner[GS_LEARNER_POLICY].live)
+    return fail(h, GS_E_STATE, "gs_learner_conservative_view: no Q learner holds a conservative step's arrays");
+  gs_handle::Learner& Ln = h->learner[cq.net];
+  const GsTrainNet& NP = h->learner[GS_LEARNER_POLICY].net;
+  GS_ENTER(h);
+  int rc = publish(h, h->stream, Ln.ev, consumer_stream);
+  if (rc) return rc;
+  *out = gs_conservative_view_out{};
+  out->net = cq.net; out->n = cq.n_last; out->action_dim = h->action_dim;
+  out->pre_head = h->tr.acts + cq.pre_off + NP.col_off[NP.n_layers - 1]; out->pre_head_stride = NP.row_stride;
+  out->random_actions = cq.random; out->policy_actions = cq.actions; out->policy_noise = cq.noise; out->policy_log_probs = cq.logp;
+  out->targets = cq.y; out->q = cq.q; out->weights = cq.weights; out->loss_terms = cq.terms; out->scalars = cq.scalars;
   return GS_OK;
 }
 

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 struct GsSum { template <typename X> __device__ X operator()(X a, X b) const { return a + b; } };
+struct GsMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
+struct GsMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
 
 // The reduction of one value per thread over the workgroup, in a fixed order: a butterfly over the wavefront's 64 lanes (partners
 // at 32, 16, 8, 4, 2, 1 lanes), the W wavefronts' results through lds[W], a second butterfly over those (partners at W / 2, ..., 1):

@@ -217,6 +217,14 @@ struct gs_handle : GsPlan {
   struct GS_HIDDEN Pathwise {
     DevBuf<float> acts, deltas, qsa, dqda; DevBuf<double> actions, noise, logp, q, qmin, bc, terms; DevBuf<int32_t> which; int n_last = 0, installed = 0;
   } pw;
+  // gs_learner_step_conservative (abi_learner.hip): the last conservative critic step's arrays (n_last minibatch
+  // rows; 0: none), of twin `net`: random [n][A], the policy block's actions / noise [n][A] and logp [n], y [n] (the targets: tr.qy is
+  // the next plain step's), q / weights [3 n], terms [n], scalars [4] m, S, lse, qbar.  pre_off: where the policy's saved
+  // activations begin in tr.acts, behind the twin's 3 n rows, so that the view's pre-head values outlive the twin's passes.  Made on
+  // first use, grown to the largest n seen and released with the rollout's buffers, like tr.
+  struct GS_HIDDEN Conservative {
+    DevBuf<double> random, actions, noise, logp, q, weights, terms, scalars; DevBuf<float> y; int n_last = 0, net = 0; size_t pre_off = 0;
+  } cq;
   // gs_fed_* (abi_fed.hip): the federations this handle is a client of; gs_destroy detaches them (fed_detach)
   std::vector<gs_fed*> feds;
   // entries that move the environment outside gs_rollout (gs_reset, gs_set_state, gs_step*, gs_upload_injections, gs_solve*) count

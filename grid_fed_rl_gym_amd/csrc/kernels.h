@@ -11,6 +11,7 @@
 #include "q.h"
 #include "q_next.h"
 #include "pathwise.h"
+#include "conservative.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -90,6 +91,10 @@ __global__ void gs_k_pw_seed(GsPwSeedArgs S);
 __global__ void gs_k_pw_input_grad(GsPwInputGradArgs P);
 __global__ void gs_k_pw_head(GsPwHeadArgs H);
 __global__ void gs_k_pw_stats(GsPwStatArgs S);
+__global__ void gs_k_cql_rows(GsCqlRowsArgs R);
+__global__ void gs_k_cql_lse(GsCqlLseArgs L);
+__global__ void gs_k_cql_head(GsCqlHeadArgs H);
+__global__ void gs_k_cql_stats(GsCqlStatArgs S);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

@@ -145,9 +145,7 @@ gs_k_ep_accumulate_costs(GsEpisodeArgs E) { ep_accumulate<true, 4>(E); }
 
 // ---- the statistics pass -------------------------------------------------------------------------------------------------------
 // Every quantity is reduced over the workgroup by block_reduce.h (the order of the operations is stated there), the 16 wavefronts
-// known at compile time.
-struct EpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
-struct EpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
+// known at compile time (fmin and fmax: its GsMin and GsMax).
 constexpr int EP_STAT_WAVES = GS_EP_STAT_THREADS / 64;
 static_assert(EP_STAT_WAVES == 16, "the second butterfly runs over 16 lanes");
 
@@ -182,10 +180,10 @@ gs_k_ep_stats(GsEpisodeArgs E) {
   len_sum = gs_block_sum<EP_STAT_WAVES>(len_sum, lds_i);
   n_success = gs_block_sum<EP_STAT_WAVES>(n_success, lds_i);
   ret_sum = gs_block_sum<EP_STAT_WAVES>(ret_sum, lds_f);
-  ret_min = gs_block_reduce<EP_STAT_WAVES>(ret_min, lds_f, EpMin());
-  ret_max = gs_block_reduce<EP_STAT_WAVES>(ret_max, lds_f, EpMax());
-  len_min = gs_block_reduce<EP_STAT_WAVES>(len_min, lds_f, EpMin());
-  len_max = gs_block_reduce<EP_STAT_WAVES>(len_max, lds_f, EpMax());
+  ret_min = gs_block_reduce<EP_STAT_WAVES>(ret_min, lds_f, GsMin());
+  ret_max = gs_block_reduce<EP_STAT_WAVES>(ret_max, lds_f, GsMax());
+  len_min = gs_block_reduce<EP_STAT_WAVES>(len_min, lds_f, GsMin());
+  len_max = gs_block_reduce<EP_STAT_WAVES>(len_max, lds_f, GsMax());
   if (with_costs)
     for (int c = 0; c < 3; ++c) { cost_sum[c] = gs_block_sum<EP_STAT_WAVES>(cost_sum[c], lds_f); viol[c] = gs_block_sum<EP_STAT_WAVES>(viol[c], lds_i); }
   const double N = (double)cnt;

@@ -22,9 +22,10 @@ namespace {
 
 // exp, tanh and log of the heads (gw_exp, gw_tanh, gw_log, gw_logp_term): gw_math.h, shared with kernels_q_next.hip
 
-// component `comp` of the four normals of one Philox call (env_device.h's rng_normal_component), tag 'PWNO', counter (sample, quad, draw, tag)
-__device__ __forceinline__ double gw_noise(uint64_t seed, uint32_t sample, uint32_t quad, uint32_t draw, int comp) {
-  const U4 r = philox(sample, quad, draw, GS_PW_NOISE_TAG, (uint32_t)seed, (uint32_t)(seed >> 32));
+// component `comp` of the four normals of one Philox call (env_device.h's rng_normal_component), counter (sample, quad, draw, tag);
+// tag 0: 'PWNO'
+__device__ __forceinline__ double gw_noise(uint64_t seed, uint32_t sample, uint32_t quad, uint32_t draw, uint32_t tag, int comp) {
+  const U4 r = philox(sample, quad, draw, tag ? tag : GS_PW_NOISE_TAG, (uint32_t)seed, (uint32_t)(seed >> 32));
   return rng_normal_component(r, comp);
 }
 
@@ -45,7 +46,7 @@ gs_k_pw_sample(GsPwSampleArgs S) {
   for (int k = 0; k < A; ++k) {
     const double mean = (double)pre[k];
     const double ls = fmin(fmax((double)pre[A + k], -20.0), 2.0);
-    const double eps = S.stochastic ? gw_noise(S.seed, (uint32_t)i, (uint32_t)(k >> 2), S.draw, k & 3) : 0.0;
+    const double eps = S.stochastic ? gw_noise(S.seed, (uint32_t)i, (uint32_t)(k >> 2), S.draw, S.tag, k & 3) : 0.0;
     const double x = mean + gw_exp(ls) * eps;
     const double a = gw_tanh(x);
     const double term = gw_logp_term(eps, ls, a);

@@ -16,7 +16,7 @@ struct GsPwSampleArgs {
   double* logp;               // [n]
   float* sa;                  // [n][D + A] the twins' input rows: the action columns (float)a_k are written here
   int32_t n, row_stride, A, D, stochastic, reserved;
-  uint32_t draw, reserved2;
+  uint32_t draw, tag;         // tag: the noise counter's fourth word; 0 means GS_PW_NOISE_TAG (the conservative critic step passes its own)
   uint64_t seed;
 };
 

@@ -4,7 +4,7 @@ network, one clipped-surrogate (PPO) or critic update on a minibatch of ``OnPoli
 pass, a deterministic gradient reduction and Adam, which also rewrites the image the rollout and critic kernels read: the next
 ``rollout_device(policy="mlp")`` acts with the updated policy and no weight crosses the host.
 
-``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np``, ``pathwise_grad_np`` (with ``pathwise_noise_np``) and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
+``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np``, ``pathwise_grad_np`` (with ``pathwise_noise_np``), ``cql_grad_np`` (with ``cql_uniform_np`` and ``cql_noise_np``) and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
 """
 from __future__ import annotations
 
@@ -203,10 +203,11 @@ def expectile_grad_np(value_layers, obs_n, returns, expectile: float, exact: boo
     return dict(grads=_backward(rounded, acts, ghead, activation), values=v, below=d < 0.0, loss_terms=terms, loss=math.fsum(terms) / n)
 
 
-def pathwise_noise_np(seed: int, draw: int, n: int, A: int) -> np.ndarray:
+def pathwise_noise_np(seed: int, draw: int, n: int, A: int, tag: int = _lib.PATHWISE_NOISE_TAG) -> np.ndarray:
     """eps [n, A] of a pathwise actor step: ``eps[i, k]`` = component ``k & 3`` of the four normals of Philox4x32-10 with counter
     (i, k >> 2, draw, 'PWNO') and key ``seed`` -- ``fed_noise_np``'s recipe (every word w a uniform (w + 1/2) 2^-32, words (0, 1)
-    and (2, 3) one Box-Muller pair each, cosine then sine) under the actor step's counter."""
+    and (2, 3) one Box-Muller pair each, cosine then sine) under the actor step's counter.  ``tag``: the counter's fourth word, for
+    the steps that share the sampling head under a tag of their own (``cql_noise_np``)."""
     n, A = int(n), int(A)
     if n < 0 or A <= 0:
         raise ValueError(f"pathwise_noise_np: n = {n} must be >= 0 and A = {A} > 0")
@@ -215,7 +216,7 @@ def pathwise_noise_np(seed: int, draw: int, n: int, A: int) -> np.ndarray:
     q = np.tile(np.arange(quads, dtype=np.uint64), n)
     full = lambda x: np.full(i.shape, int(x) & 0xFFFFFFFF, dtype=np.uint64)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    w = np.stack(_philox4x32(i, q, full(draw), full(_lib.PATHWISE_NOISE_TAG), seed & 0xFFFFFFFF, seed >> 32), axis=1).astype(np.float64)
+    w = np.stack(_philox4x32(i, q, full(draw), full(tag), seed & 0xFFFFFFFF, seed >> 32), axis=1).astype(np.float64)
     u = (w + 0.5) * (1.0 / 4294967296.0)
     ra, rb = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
     ta, tb = 2.0 * math.pi * u[:, 1], 2.0 * math.pi * u[:, 3]
@@ -378,6 +379,118 @@ def pathwise_grad_np(policy_layers, q_layers_list, obs_n, eps, alpha: float, bc_
     return _with_backprop(res, exact, acts, deltas)
 
 
+def cql_noise_np(seed: int, draw: int, n: int, A: int) -> np.ndarray:
+    """eps [n, A] of a conservative critic step's policy candidates: ``pathwise_noise_np`` under the tag 'CQLN', so that a pathwise
+    step with the same seed and draw does not reuse the numbers."""
+    return pathwise_noise_np(seed, draw, n, A, tag=_lib.CQL_NOISE_TAG)
+
+
+def cql_uniform_np(seed: int, draw: int, n: int, A: int) -> np.ndarray:
+    """The uniform candidate actions [n, A] (float64) of a conservative critic step: ``u[i, k] = (word + 0.5) 2^-31 - 1`` with
+    ``word`` = word ``k & 3`` of Philox4x32-10 with counter (i, k >> 2, draw, 'CQLU') and key ``seed``; every operation is exact in
+    float64, and the values lie strictly inside (-1, 1).  The twin reads them rounded to float32."""
+    n, A = int(n), int(A)
+    if n < 0 or A <= 0:
+        raise ValueError(f"cql_uniform_np: n = {n} must be >= 0 and A = {A} > 0")
+    quads = (A + 3) // 4
+    i = np.repeat(np.arange(n, dtype=np.uint64), quads)
+    q = np.tile(np.arange(quads, dtype=np.uint64), n)
+    full = lambda x: np.full(i.shape, int(x) & 0xFFFFFFFF, dtype=np.uint64)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = np.stack(_philox4x32(i, q, full(draw), full(_lib.CQL_UNIFORM_TAG), seed & 0xFFFFFFFF, seed >> 32), axis=1).astype(np.float64)
+    u = (w + 0.5) * (1.0 / 2147483648.0) - 1.0
+    return u.reshape(n, 4 * quads)[:, :A].copy()
+
+
+_STAT_THREADS = 1024      # GS_TR_STAT_THREADS
+
+
+def _block_sum_np(x) -> float:
+    """The sum of ``x`` in the order of the one-workgroup statistics kernels (gs_k_train_stats, gs_k_cql_lse): thread t adds entries
+    t, t + 1024, ... ascending from 0.0, then the balanced tree of csrc/block_reduce.h over the 1024 threads (partners at 32, 16,
+    ..., 1 lanes within a wavefront of 64, then at 8, 4, 2, 1 over the 16 wavefronts)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    pad = (-x.size) % _STAT_THREADS
+    rows = np.concatenate([x, np.zeros(pad)]).reshape(-1, _STAT_THREADS)
+    v = np.zeros(_STAT_THREADS)
+    for r in rows:
+        v = v + r      # (a thread whose entry lies beyond the end adds nothing; + 0.0 leaves a sum that began at 0.0 as it is)
+    v = v.reshape(_STAT_THREADS // 64, 64)
+    lane = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, lane ^ off]
+    w = v[:, 0]
+    wave = np.arange(w.size)
+    for off in (8, 4, 2, 1):
+        w = w + w[wave ^ off]
+    return float(w[0])
+
+
+def _cql_weight_check(conservative_weight) -> float:
+    cw = float(conservative_weight)
+    if not math.isfinite(cw) or cw < 0.0:
+        raise ValueError(f"conservative_weight = {cw} must be finite and >= 0")
+    return cw
+
+
+CQL_EXP_FLOOR = -700.0      # GS_CQL_EXP_FLOOR: what lies this far below the maximum adds nothing to the logsumexp
+
+
+def cql_grad_np(q_layers, obs_n, data_actions, random_actions, policy_actions, targets, conservative_weight: float, exact: bool = False,
+                activation: str = "relu", q=None, scalars=None) -> Dict[str, Any]:
+    """The conservative critic loss of include/gridstep.h ("the conservative critic step") of ONE twin and its gradient, as
+    ``gs_learner_step_conservative`` computes them: ``mse(Q(s, a_data), y) + conservative_weight (logsumexp_j q_j - mean Q(s,
+    a_data))`` with j over all 3 n values ``Q(s, a_data) | Q(s, a_random) | Q(s, a_policy)`` -- the logsumexp runs over the batch,
+    as the reference's.  ``q_layers``: [(W, b)] over [obs | action], the last width 1; ``obs_n`` [n, obs_dim] the NORMALISED
+    observations; the three action arrays [n, A] (constants of the step; they enter the twin rounded to float32); ``targets`` [n].
+    Layers in float32 -- or, with ``exact``, the same float32-rounded operands in float64 throughout, with the library's exp and
+    log and exactly rounded sums --, the head in float64, its gradient rounded once to float32 unless ``exact``.  ``q`` [3 n]: values
+    to run the head on in place of this evaluation's (the device's float32 values, widened); ``scalars``: (m, S, ...) to take the
+    maximum and the sum of exponentials from (the device's), as ``pre_head=`` in ``policy_rows_np``.  Returns what ``value_grad_np``
+    returns -- ``grads`` [(dW, db)], ``values`` [n], ``loss_terms`` [n] ((q_i - y_i)^2), ``loss`` (value_loss + conservative_weight
+    penalty) -- plus ``value_loss``, ``q`` [3 n], ``weights`` [3 n] (the softmax over the batch), ``penalty`` and ``scalars`` [4]
+    (m, S, lse, qbar)."""
+    cw = _cql_weight_check(conservative_weight)
+    work = np.float64 if exact else np.float32
+    obs = np.asarray(obs_n).astype(np.float32)
+    n = obs.shape[0]
+    blocks = []
+    for name, a in (("data_actions", data_actions), ("random_actions", random_actions), ("policy_actions", policy_actions)):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[0] != n:
+            raise ValueError(f"cql_grad_np: {name} must be [{n}, A], got {a.shape}")
+        blocks.append(np.concatenate([obs, a.astype(np.float32)], axis=1))
+    if n == 0 or np.asarray(q_layers[-1][0]).shape[0] != 1:
+        raise ValueError("cql_grad_np: at least one row, and a Q network whose last width is 1")
+    rounded, acts = _forward(q_layers, np.concatenate(blocks, axis=0), activation, exact)
+    qv = acts[-1].astype(np.float64)[:, 0]
+    if q is not None:
+        qv = np.asarray(q, dtype=np.float64).reshape(3 * n)
+    y = np.asarray(targets).astype(np.float64).reshape(n)
+    m = float(np.max(qv)) if scalars is None else float(scalars[0])
+    d = qv - m
+    inside = d >= CQL_EXP_FLOOR
+    e = np.where(inside, np.exp(np.where(inside, d, 0.0)) if exact else pathwise_exp_np(np.where(inside, d, 0.0)), 0.0)
+    if scalars is not None:
+        S = float(scalars[1])
+    else:
+        S = math.fsum(e) if exact else _block_sum_np(e)
+    lse = m + (math.log(S) if exact else float(pathwise_log_np(np.float64(S))))
+    qbar = (math.fsum(qv[:n]) if exact else _block_sum_np(qv[:n])) / n
+    penalty = lse - qbar
+    p = e / S
+    inv_n = 1.0 / n
+    dq = qv[:n] - y
+    terms = dq * dq
+    g = np.concatenate([(2.0 * dq) * inv_n + cw * (p[:n] - inv_n), cw * p[n:]])[:, None]
+    ghead = g if exact else g.astype(np.float32)
+    deltas: list = []
+    value_loss = (math.fsum(terms) if exact else _block_sum_np(terms)) / n
+    out = dict(grads=_backward(rounded, acts, ghead, activation, deltas), values=qv[:n], loss_terms=terms, loss=value_loss + cw * penalty,
+               value_loss=value_loss, q=qv, weights=p, penalty=penalty, scalars=np.array([m, S, lse, qbar]))
+    return _with_backprop(out, exact, acts, deltas)
+
+
 def _pathwise_check(alpha, bc_coef) -> Tuple[float, float]:
     alpha, bc_coef = float(alpha), float(bc_coef)
     for k, x in (("alpha", alpha), ("bc_coef", bc_coef)):
@@ -464,6 +577,13 @@ class DeviceLearner:
     step is ``pathwise_noise_np(pathwise_seed, draw, n, A)`` with ``draw`` = the policy's steps taken.  Host state: the C loss kind
     is not involved.
 
+    The conservative critic: ``conservative_weight`` > 0 makes the Q networks' step
+    ``gs_learner_step_conservative`` -- CQL's ``mse(Q(s, a), y) + conservative_weight (logsumexp over the batch of Q(s, a_data) |
+    Q(s, a_uniform) | Q(s, a_policy) - mean Q(s, a_data))`` per twin, the policy's candidates sampled inside the step
+    (``conservative_stochastic=False``: ``tanh(mean)``).  It needs ``q_loss="mse"`` and a learner for the policy on the handle (of
+    this or of another ``DeviceLearner``), which it reads and does not step.  The uniform candidates of a step are
+    ``cql_uniform_np(conservative_seed, draw, n, A)`` and its noise ``cql_noise_np(...)`` with ``draw`` = that twin's steps taken.
+
     ``step(batch)``: one ``gs_learner_step`` per network on a dict of ``OnPolicyBatches.epoch`` (prepared with float32 and the
     networks' own observation normalisation).  After a step the ``MLPPolicy`` / ``MLPValue`` objects the networks were installed
     from no longer describe them: ``policy()`` / ``value(net)`` rebuild current ones from the device's parameters."""
@@ -473,7 +593,8 @@ class DeviceLearner:
                  policy_loss: str = "ppo", temperature: float = 1.0, weight_max: float = 20.0, value_loss: str = "mse",
                  expectile: float = 0.7, q_loss: str = "mse", advantage_source: str = "batch", value_target: str = "batch",
                  alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True, pathwise_seed: int = 0,
-                 q_target: str = "value") -> None:
+                 q_target: str = "value", conservative_weight: float = 0.0, conservative_stochastic: bool = True,
+                 conservative_seed: int = 0) -> None:
         if isinstance(nets, str):
             nets = (nets,)
         self.nets = tuple(nets)
@@ -518,6 +639,14 @@ class DeviceLearner:
         if q_target == "policy" and not any(k >= _lib.GS_LEARNER_Q for k in self._ids):
             raise ValueError(f"DeviceLearner: q_target = 'policy' needs 'q1' or 'q2' among nets {self.nets}")
         self.q_target = q_target
+        self._conservative: Optional[dict] = None
+        state = self._conservative_state(conservative_weight, conservative_stochastic, conservative_seed)
+        if state["conservative_weight"] > 0.0:
+            if not any(k >= _lib.GS_LEARNER_Q for k in self._ids):
+                raise ValueError(f"DeviceLearner: conservative_weight > 0 needs 'q1' or 'q2' among nets {self.nets}")
+            if q_loss != "mse":
+                raise ValueError(f"DeviceLearner: conservative_weight > 0 needs q_loss = 'mse' (the penalty joins the squared error), got {q_loss!r}")
+            self._conservative = state
         self.env = env
         self.config = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                            clip=float(clip), ent_coef=float(ent_coef), max_grad_norm=float(max_grad_norm))
@@ -555,6 +684,15 @@ class DeviceLearner:
         if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
             raise ValueError(f"DeviceLearner: pathwise_seed = {seed!r} must be an integer in [0, 2^64)")
         return dict(alpha=alpha, bc_coef=bc_coef, stochastic=bool(stochastic), seed=int(seed))
+
+    @staticmethod
+    def _conservative_state(conservative_weight, stochastic, seed) -> dict:
+        cw = _cql_weight_check(conservative_weight)
+        if not isinstance(stochastic, (bool, np.bool_)):
+            raise ValueError(f"DeviceLearner: conservative_stochastic = {stochastic!r} must be True or False")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"DeviceLearner: conservative_seed = {seed!r} must be an integer in [0, 2^64)")
+        return dict(conservative_weight=cw, stochastic=bool(stochastic), seed=int(seed))
 
     def set_loss(self, net="policy", loss: Optional[str] = None, temperature: float = 1.0, weight_max: float = 20.0,
                  expectile: float = 0.7, alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True,
@@ -599,6 +737,8 @@ class DeviceLearner:
         for net in self._ids:
             if net == _lib.GS_LEARNER_POLICY and self._pathwise is not None:
                 self.step_pathwise(batch, stream=stream)
+            elif net >= _lib.GS_LEARNER_Q and self._conservative is not None:
+                self.step_conservative(batch, net, stream=stream)
             else:
                 self.env.handle.learner_step(net, batch, n, stream)
 
@@ -625,6 +765,33 @@ class DeviceLearner:
         mean | log_std in the learners' shared scratch, valid until any learner's next step)."""
         self._id("policy")
         return self.env.handle.learner_pathwise_view(stream)
+
+    def step_conservative(self, batch: dict, net, conservative_weight: Optional[float] = None, stochastic: Optional[bool] = None,
+                          seed: Optional[int] = None, draw: Optional[int] = None, stream=None) -> None:
+        """One conservative critic update of twin ``net`` ("q1" / "q2") on ``batch`` (``gs_learner_step_conservative``,
+        asynchronous): what is not given is the learner's ``conservative_weight`` state (weight 0, stochastic, seed 0 without one);
+        ``draw``: by default that twin's steps taken, so twins stepped in turn see the same candidate actions."""
+        k = self._id(net)
+        if k < _lib.GS_LEARNER_Q:
+            raise ValueError(f"DeviceLearner.step_conservative: {net!r} is not a Q network ('q1' / 'q2')")
+        base = self._conservative or dict(conservative_weight=0.0, stochastic=True, seed=0)
+        state = self._conservative_state(base["conservative_weight"] if conservative_weight is None else conservative_weight,
+                                         base["stochastic"] if stochastic is None else stochastic, base["seed"] if seed is None else seed)
+        if draw is None:
+            draw = self.env.handle.learner_info(k)["step"]
+        if isinstance(draw, bool) or not isinstance(draw, (int, np.integer)) or not 0 <= int(draw) < 2 ** 32:
+            raise ValueError(f"DeviceLearner.step_conservative: draw = {draw!r} must be an integer in [0, 2^32)")
+        cfg = _lib.conservative_config(state["conservative_weight"], state["stochastic"], state["seed"], int(draw))
+        self.env.handle.learner_step_conservative(k, batch, int(batch["observations"].shape[0]), cfg, stream)
+
+    def conservative_views(self, stream=None) -> dict:
+        """The last conservative step's arrays as zero-copy ``DeviceArray`` views (``gs_learner_conservative_view``):
+        ``random_actions``, ``policy_actions``, ``policy_noise`` [n, A], ``policy_log_probs``, ``loss_terms`` [n], ``q``, ``weights``
+        [3 n] (rows: data | uniform | policy), ``scalars`` [4] (m, S, lse, qbar), ``targets`` [n] (float32), ``net``, ``n``,
+        ``action_dim``, and ``pre_head`` / ``pre_head_stride`` as ``pathwise_views``'."""
+        if not any(k >= _lib.GS_LEARNER_Q for k in self._ids):
+            raise ValueError(f"DeviceLearner.conservative_views: no Q network among this learner's nets {self.nets}")
+        return self.env.handle.learner_conservative_view(stream)
 
     def stats(self, net="policy") -> dict:
         """The last step's ``loss``, ``surrogate``, ``entropy``, ``approx_kl``, ``clip_fraction``, ``value_loss``, ``grad_norm`` and

@@ -1172,6 +1172,73 @@ int gs_rollout_q_next_download(gs_handle* h, const gs_rollout_q_next_host* out);
 int gs_q_set_target_source(gs_handle* h, int32_t source);
 int gs_q_get_target_source(gs_handle* h, int32_t* source);
 
+/* ---- the conservative critic step: a twin's regression plus the logsumexp penalty ----
+ * The critic update of CQL (the reference's CQL._update_critic with CQL._compute_cql_loss, algorithms/offline.py:166-228), per twin w
+ * on n minibatch rows:
+ *     L_w = mse(Q_w(s, a_data), y) + conservative_weight * (logsumexp_j q_j - mean_i Q_w(s_i, a_data_i))
+ * where j runs over ALL 3 n values Q_w(s, a_data) | Q_w(s, a_uniform) | Q_w(s, a_policy): the logsumexp runs over the BATCH, as the
+ * reference's logsumexp(dim=0) does (not per state, as the CQL paper's).  The twins share no parameter, so the reference's summed
+ * loss separates into one step per twin.  Additive to ABI 2: no struct above changes, and a handle that never calls these entries
+ * computes what it computed before.
+ *
+ * gs_learner_step_conservative (asynchronous, on the handle's stream) steps the learner of twin net = GS_LEARNER_Q + which alone, on
+ * the minibatch of n samples gs_onpolicy_batch left in `batch`.  It needs (GS_E_STATE otherwise): everything gs_learner_step needs
+ * for that Q learner under the current gs_q_set_target_source (gs_rollout_evaluate_q, or gs_rollout_evaluate_q_next under
+ * GS_Q_TARGET_POLICY, on the last rollout); the Q learner's loss at GS_LOSS_DEFAULT; a live learner for the POLICY (GS_COMPUTE_F32,
+ * GS_HEAD_GAUSSIAN_TANH), whose network is read and not written; obs_shift / obs_scale bit-equal to the policy's and to this twin's
+ * normalisation; 1 <= action_dim <= 128.  GS_E_INVALID: a wrong struct_size, a net that is not GS_LEARNER_Q + {0, 1},
+ * conservative_weight NaN, negative or infinite, stochastic outside {0, 1}, n outside 1 .. 2^24 / 3, a batch without observations
+ * or indices.  Every check runs before any launch.
+ *
+ * Per step, nothing contracted.  The twin's input rows j in [0, 3 n): [0, n) the data block, [n, 2 n) the uniform block, [2 n, 3 n)
+ * the policy block; all three carry the observation columns of batch row j mod n.  With i = j mod n:
+ *   data action      the stored float64 action through the clamped index, rounded once (gs_learner_step's rule); y_i = (float)td[idx_i]
+ *   uniform action   u_k = ((double)word + 0.5) * 2^-31 - 1.0, word = word k & 3 of Philox4x32-10 with counter (i, k >> 2, draw,
+ *                    'CQLU' = 0x43514C55) and key seed: exact in float64, strictly inside (-1, 1); the column is (float)u_k
+ *   policy action    the sampling head of "the pathwise actor step", operation for operation, on the policy learner's pre-head values
+ *                    of row i, its noise under the tag 'CQLN' = 0x43514C4E in place of 'PWNO'; 0 noise when stochastic == 0
+ * Q1 and Q2 stepped with the same seed and draw see the same candidate actions: neither step writes the policy.
+ * One forward pass of the twin over the 3 n rows with saved activations gives q_j (float32, widened).  ONE workgroup of 1024 threads:
+ *     m = max_j q_j;   d_j = q_j - m;   e_j = d_j < -700 ? 0 : exp(d_j)      exp and log: those of "the pathwise actor step"
+ *     S = sum_j e_j      thread t adds j = t, t + 1024, ... ascending from 0.0, then the balanced tree over the 1024 threads
+ *     lse = m + log(S);   qbar = (sum_{i < n} q_i) / n  in the same order;   penalty = lse - qbar
+ * The head, per row, with inv_n = 1.0 / n, p_j = e_j / S and cw = conservative_weight:
+ *     data rows:        dq = q_i - (double)y_i;  term_i = dq * dq;  g = (2.0 * dq) * inv_n + cw * (p_i - inv_n)
+ *     candidate rows:   g = cw * p_j
+ *     dL/dq_j = (float)g
+ * Then the twin's backward pass, gradient reduction (ceil(3 n / 256) segments), statistics and Adam are "the learner"'s over the
+ * 3 n rows, by the same kernels: Adam rewrites the ONLINE image of twin `which`, and its step count advances.  The other twin, the
+ * policy and both target images are not written.  A row's q depends on that row and the parameters alone.
+ * gs_learner_stats on that net afterwards: value_loss = (sum_i term_i) / n, surrogate = penalty, loss = value_loss + cw * penalty,
+ * entropy, approx_kl and clip_fraction NaN, grad_norm as ever.
+ * gs_learner_conservative_view: device pointers of the LAST conservative step's arrays, whichever twin took it (GS_E_STATE without
+ * one).  Lifetime and consumer_stream as gs_learner_pathwise_view; pre_head lies in the learners' shared scratch.  gs_learner_view
+ * on that Q net is GS_E_STATE after a conservative step (its arrays belong to gs_learner_step). */
+typedef struct gs_conservative_config {
+  int32_t struct_size;            /* = sizeof(gs_conservative_config) */
+  int32_t stochastic;             /* policy candidates: 1 sampled, 0 tanh(mean) */
+  double conservative_weight;     /* finite, >= 0 (the reference's default is 5.0) */
+  uint64_t seed;
+  uint32_t draw, reserved;
+} gs_conservative_config;
+typedef struct gs_conservative_view_out {
+  int32_t net, n, action_dim, pre_head_stride;
+  const float* pre_head;          /* [n] rows of pre_head_stride floats, the first 2 A of a row: the policy's mean | log_std; the
+                                     learners' shared scratch: valid until the next step of ANY learner of the handle */
+  const double* random_actions;   /* [n][A] u_k */
+  const double* policy_actions;   /* [n][A] */
+  const double* policy_noise;     /* [n][A] */
+  const double* policy_log_probs; /* [n] */
+  const float* targets;           /* [n] y_i */
+  const double* q;                /* [3 n] */
+  const double* weights;          /* [3 n] p_j */
+  const double* loss_terms;       /* [n] term_i */
+  const double* scalars;          /* [4] m, S, lse, qbar */
+} gs_conservative_view_out;
+int gs_learner_step_conservative(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, const gs_conservative_config* cfg,
+                                 void* consumer_stream);
+int gs_learner_conservative_view(gs_handle* h, gs_conservative_view_out* out, void* consumer_stream);
+
 /* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
  * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
  * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
