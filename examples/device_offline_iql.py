@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=3.0); ap.add_argument("--weight-max", type=float, default=100.0)
     ap.add_argument("--expectile", type=float, default=0.7); ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--tau", type=float, default=0.005); ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--fresh-targets", action="store_true", help="recompute Q, V and the targets per minibatch, as the reference's update(batch) does")
     ap.add_argument("--clip-norm", type=float, default=0.5)
     a = ap.parse_args()
     spec = G.ieee13_like("epsilon")
@@ -72,7 +73,7 @@ def main():
             env.set_q(w, twins[w])
         learners.append(G.DeviceLearner(env, nets=nets, lr=a.lr, max_grad_norm=0.5, policy_loss="awr", temperature=a.temperature,
                                         weight_max=a.weight_max, value_loss="expectile", expectile=a.expectile, advantage_source="q",
-                                        value_target="q"))
+                                        value_target="q", fresh_targets=a.fresh_targets, gamma=a.gamma, bootstrap=("terminated", "truncated")))
         batches.append(G.OnPolicyBatches(env, a.minibatch, policy=policy, adv_norm="none", dtype=np.float32, seed=0, fields=["observations", "indices"]))
         G.evaluate_rollout(env, gamma=a.gamma, lam=0.95, bootstrap=("terminated", "truncated"))
         batches[-1].prepare()                                          # (once: observations and indices do not change with the evaluations)
@@ -84,8 +85,10 @@ def main():
         for k, env in enumerate(envs):
             for epoch in range(a.epochs):
                 # V, the twins under both images, q_adv and the TD target as the networks stand now, on the SAME rollout
-                G.evaluate_rollout(env, gamma=a.gamma, lam=0.95, bootstrap=bootstrap)
-                G.evaluate_rollout_q(env, gamma=a.gamma, bootstrap=bootstrap)
+                # (--fresh-targets: once, before the first epoch; every step then refreshes its own minibatch's rows: section 27)
+                if not a.fresh_targets or (r == 0 and epoch == 0):
+                    G.evaluate_rollout(env, gamma=a.gamma, lam=0.95, bootstrap=bootstrap)
+                    G.evaluate_rollout_q(env, gamma=a.gamma, bootstrap=bootstrap)
                 for batch in batches[k].epoch(a.epochs * r + epoch):
                     learners[k].step(batch)
                     learners[k].update_targets(a.tau)

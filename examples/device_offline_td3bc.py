@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--lr", type=float, default=1e-3); ap.add_argument("--tau", type=float, default=0.005)
     ap.add_argument("--gamma", type=float, default=0.99); ap.add_argument("--clip-norm", type=float, default=0.5)
+    ap.add_argument("--fresh-targets", action="store_true", help="recompute the Bellman target per minibatch, as the reference's update(batch) does")
     a = ap.parse_args()
     spec = G.ieee13_like("epsilon")
     D, A = spec.obs_dim, spec.action_dim
@@ -70,7 +71,8 @@ def main():
         for w in range(2):
             env.set_q(w, twins[w])
         learners.append(G.DeviceLearner(env, nets=nets, lr=a.lr, max_grad_norm=0.5, policy_loss="pathwise", alpha=a.alpha, bc_coef=a.bc_coef,
-                                        pathwise_stochastic=not a.deterministic, pathwise_seed=7, q_target="policy"))
+                                        pathwise_stochastic=not a.deterministic, pathwise_seed=7, q_target="policy",
+                                        fresh_targets=a.fresh_targets, gamma=a.gamma, bootstrap=bootstrap, target_seed=11))
         batches.append(G.OnPolicyBatches(env, a.minibatch, policy=policy, adv_norm="none", dtype=np.float32, seed=0, fields=["observations", "indices"]))
         # (the minibatches are prepared over an evaluated rollout; neither field asked for here depends on that evaluation, and no
         # learner reads V)
@@ -85,7 +87,9 @@ def main():
             for epoch in range(a.epochs):
                 e = a.epochs * r + epoch
                 # pi(s'), the target twins on it and the Bellman target as the networks stand now, on the SAME rollout
-                G.evaluate_rollout_q_next(env, gamma=a.gamma, alpha=a.alpha, bootstrap=bootstrap, stochastic=not a.deterministic, seed=11, draw=e)
+                # (--fresh-targets: once, before the first epoch; every step then refreshes its own minibatch's rows: section 27)
+                if not a.fresh_targets or e == 0:
+                    G.evaluate_rollout_q_next(env, gamma=a.gamma, alpha=a.alpha, bootstrap=bootstrap, stochastic=not a.deterministic, seed=11, draw=e)
                 for batch in batches[k].epoch(e):
                     learners[k].step(batch)                            # Q1, Q2 on the target; the pathwise actor through the twins
                     learners[k].update_targets(a.tau)

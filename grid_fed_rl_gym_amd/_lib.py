@@ -428,6 +428,41 @@ def q_next_config(gamma=0.99, alpha=0.0, bootstrap_mask=0, stochastic=True, seed
                             int(draw) & 0xFFFFFFFF, 0)
 
 
+# per-minibatch targets (include/gridstep.h "per-minibatch targets"): the groups and the config of gs_learner_refresh
+GS_REFRESH_TD_POLICY, GS_REFRESH_Q_TARGET, GS_REFRESH_TD_VALUE, GS_REFRESH_Q_ADV = 1, 2, 4, 8
+REFRESH_GROUPS = {"td_policy": GS_REFRESH_TD_POLICY, "q_target": GS_REFRESH_Q_TARGET, "td_value": GS_REFRESH_TD_VALUE, "q_adv": GS_REFRESH_Q_ADV}
+
+
+class gs_refresh_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("groups", C.c_int32), ("bootstrap_mask", C.c_int32), ("stochastic", C.c_int32),
+                ("gamma", C.c_double), ("alpha", C.c_double), ("reward_shift", C.c_double), ("reward_scale", C.c_double),
+                ("seed", C.c_uint64), ("draw", C.c_uint32), ("reserved", C.c_uint32), ("reserved2", C.c_uint64)]
+
+
+def refresh_groups(groups) -> int:
+    """GS_REFRESH_* bits from a name of ``REFRESH_GROUPS``, a sequence of names, or the number (an unknown bit is the library's to
+    refuse)."""
+    if isinstance(groups, str):
+        groups = (groups,)
+    if isinstance(groups, (bool, np.bool_)):
+        raise ValueError(f"refresh: groups = {groups!r} is neither a name, a sequence of names nor the bits")
+    if isinstance(groups, (int, np.integer)):
+        return int(groups)
+    bits = 0
+    for g in groups:
+        if g not in REFRESH_GROUPS:
+            raise ValueError(f"refresh: unknown group {g!r}; one of {sorted(REFRESH_GROUPS)}")
+        bits |= REFRESH_GROUPS[g]
+    return bits
+
+
+def refresh_config(groups, gamma=0.99, alpha=0.0, bootstrap_mask=0, stochastic=True, seed=0, draw=0, reward_shift=0.0, reward_scale=1.0,
+                   struct_size=None) -> gs_refresh_config:
+    return gs_refresh_config(C.sizeof(gs_refresh_config) if struct_size is None else int(struct_size), refresh_groups(groups), int(bootstrap_mask),
+                             int(stochastic), float(gamma), float(alpha), float(reward_shift), float(reward_scale), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                             int(draw) & 0xFFFFFFFF, 0, 0)
+
+
 def q_target_number(source) -> int:
     """GS_Q_TARGET_* from its name in ``Q_TARGETS`` or its number (an unknown number is the library's to refuse)."""
     if isinstance(source, str):
@@ -607,6 +642,7 @@ SYMBOLS = [
     ("gs_learner_pathwise_view", C.c_int, [_H, C.POINTER(gs_pathwise_view_out), C.c_void_p]),
     ("gs_learner_step_conservative", C.c_int, [_H, C.c_int32, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.POINTER(gs_conservative_config), C.c_void_p]),
     ("gs_learner_conservative_view", C.c_int, [_H, C.POINTER(gs_conservative_view_out), C.c_void_p]),
+    ("gs_learner_refresh", C.c_int, [_H, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.POINTER(gs_refresh_config), C.c_void_p]),
     ("gs_fed_create", C.c_int, [C.POINTER(_H), C.c_int32, C.c_int32, C.POINTER(_FED)]),
     ("gs_fed_destroy", C.c_int, [_FED]),
     ("gs_fed_info", C.c_int, [_FED, C.POINTER(gs_fed_info_out)]),
@@ -1738,6 +1774,19 @@ class Handle:
             n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
         cfg = conservative_config() if cfg is None else cfg
         self._check(self._lib.gs_learner_step_conservative(self._h, _net_number(net), C.byref(b), int(n), C.byref(cfg), _stream_arg(stream)))
+
+    def learner_refresh(self, batch: dict, cfg: gs_refresh_config, n: Optional[int] = None, stream=None) -> None:
+        """gs_learner_refresh (asynchronous): the groups of ``cfg`` (``refresh_config``) re-evaluated for the transitions
+        ``batch["indices"]`` names (a device int32 array, as ``learner_step``'s) under the images as they are now, written into the
+        arrays of ``rollout_evaluate_q_next`` / ``rollout_evaluate_q`` at those transitions."""
+        b = gs_onpolicy_batch_out()
+        addr = lambda x: None if x is None else int(x) if isinstance(x, (int, np.integer)) else int(x.__cuda_array_interface__["data"][0]) if hasattr(x, "__cuda_array_interface__") else int(x.data_ptr())
+        idx = batch.get("indices")
+        if idx is not None:
+            b.indices = addr(idx)
+        if n is None:
+            n = int(idx.shape[0]) if hasattr(idx, "shape") else 0
+        self._check(self._lib.gs_learner_refresh(self._h, C.byref(b), int(n), C.byref(cfg), _stream_arg(stream)))
 
     def learner_conservative_view(self, stream=None) -> dict:
         """gs_learner_conservative_view: the last conservative step's arrays as zero-copy ``DeviceArray`` views -- ``random_actions``,

@@ -24,6 +24,20 @@ void dataset_release(gs_handle* h, bool keep_stats) {
   ds.idx_pending = false;
 }
 
+// map[0 .. N) of the last rollout's N = T * B transitions: -1, then the rollout's terminal list scattered (the list's length is read on
+// the device: no host round trip).  Queued on the handle's stream; the dataset's map and the refresh's (abi_refresh.hip) are made by it.
+int terminal_map_fill(gs_handle* h, int32_t* map, long long N) {
+  const gs_handle::Rollout& ro = h->ro;
+  hipLaunchKernelGGL(gs_k_ds_map_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, map, N);
+  HIPCHK(h, hipGetLastError());
+  if (ro.term_cap > 0) {
+    hipLaunchKernelGGL(gs_k_ds_map_scatter, dim3((unsigned)((ro.term_cap + 255) / 256)), dim3(256), 0, h->stream, map, ro.term_count.p, ro.term_idx.p,
+                       ro.term_cap, ro.T, h->B);
+    HIPCHK(h, hipGetLastError());
+  }
+  return GS_OK;
+}
+
 }  // namespace gsi
 
 static inline int ds_ct(const gs_handle* h) { return h->obs_dim + h->action_dim + 1; }
@@ -53,17 +67,11 @@ int gs_dataset_build(gs_handle* h, uint32_t flags) {
   if (keep && !ds.have_stats) return fail(h, GS_E_STATE, "gs_dataset_build(GS_DATASET_KEEP_STATS): the handle holds no statistics");
   GS_ENTER(h);
   const int D = h->obs_dim, A = h->action_dim, Ct = ds_ct(h);
-  // the map: -1, then the rollout's terminal list scattered (the list's length is read on the device: no host round trip)
+  // the map (terminal_map_fill)
   ds.built_on = 0;
   int rc = ds.map.grow(h, (size_t)N, "the dataset's terminal map");
   if (rc) return rc;
-  hipLaunchKernelGGL(gs_k_ds_map_fill, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, ds.map.p, N);
-  HIPCHK(h, hipGetLastError());
-  if (ro.term_cap > 0) {
-    hipLaunchKernelGGL(gs_k_ds_map_scatter, dim3((unsigned)((ro.term_cap + 255) / 256)), dim3(256), 0, h->stream, ds.map.p, ro.term_count.p, ro.term_idx.p,
-                       ro.term_cap, ro.T, h->B);
-    HIPCHK(h, hipGetLastError());
-  }
+  if ((rc = terminal_map_fill(h, ds.map.p, N))) return rc;
   if (!keep) {
     if ((rc = ds_stats_ensure(h))) return rc;
     const long long chunks = (N + GS_DS_ROWS_PER_CHUNK - 1) / GS_DS_ROWS_PER_CHUNK;

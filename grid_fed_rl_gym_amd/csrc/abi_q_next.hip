@@ -107,6 +107,7 @@ int gs_rollout_evaluate_q_next(gs_handle* h, const gs_q_next_config* cfg) {
     HIPCHK(h, hipGetLastError());
   }
   t.with_terms = terms;
+  t.mask = cfg->bootstrap_mask;
   t.evaluated_on = ro.calls;
   return GS_OK;
 }

@@ -39,6 +39,7 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   costs_release(h);
   q_rollout_release(h);
   q_next_rollout_release(h);
+  refresh_release(h);
   episodes_release(h, keep_term_count);      // (the list is sized by the capacity; the carries outlive a longer rollout)
   batches_release(h);
   learner_scratch_release(h);

@@ -209,7 +209,18 @@ struct gs_handle : GsPlan {
   struct GS_HIDDEN QNext {
     DevBuf<float> pre, t_pre; DevBuf<double> act, eps, lp, q, q_min, td, t_act, t_eps, t_lp, t_q, t_q_min, t_value;
     uint64_t evaluated_on = 0; bool with_terms = false; hipEvent_t ev = nullptr; int target_source = GS_Q_TARGET_VALUE;
+    int mask = 0;      // the bootstrap_mask of the last evaluation (gs_learner_refresh's GS_REFRESH_TD_POLICY asks for the same)
   } qn;
+  // gs_learner_refresh (abi_refresh.hip).  map [T_cap][B]: transition -> terminal entry of the rollout map_on (=
+  // ro.calls, 0 = none), made on the first refresh of a rollout.  The rest is scratch for n batch rows, grown to the largest n seen:
+  // tb [n][2] the rows' (t, b), ie / t_tb [n][2] the compacted terminal rows' (i, e) and their entries' (t, b), pos [n], count [1]; own / next / tobs
+  // [n][D] and act [n][A] the gathered rows; pre / t_pre [n][2 A], nact / neps / t_nact / t_neps [n][A], nlp / t_nlp [n] what the policy
+  // leaves; q / t_q [2][n] the twins'; v / t_v [n] the value network's.  All of it is released with the rollout's buffers.
+  struct GS_HIDDEN Refresh {
+    uint64_t map_on = 0; size_t n_cap = 0; hipEvent_t ev = nullptr;
+    DevBuf<int32_t> map, tb, ie, t_tb, pos, count;
+    DevBuf<double> own, next, tobs, act, nact, neps, nlp, t_nact, t_neps, t_nlp, q, t_q, v, t_v; DevBuf<float> pre, t_pre;
+  } rfr;
   // gs_learner_step_pathwise (abi_learner.hip): the twins' passes of an actor step have scratch of their own (acts /
   // deltas [n][the wider twin's row_stride], qsa [n][obs_dim + A]: the policy's saved activations in tr survive them), and the step's
   // per-sample arrays (n_last samples; 0: none): actions / noise [n][A], logp / qmin / bc / terms [n], q [2][n], which [n], dqda
@@ -467,10 +478,15 @@ static inline bool q_current(const gs_handle* h) { return h->qt.evaluated_on && 
 void q_next_rollout_release(gs_handle* h);
 static inline bool q_next_current(const gs_handle* h) { return h->qn.evaluated_on && h->qn.evaluated_on == h->ro.calls; }
 
+// ---- owner of the per-minibatch refresh's map and scratch (abi_refresh.hip) ----
+void refresh_release(gs_handle* h);
+
 // ---- the federations of a handle that is being destroyed lose it (abi_fed.hip) ----
 void fed_detach(gs_handle* h);
 
 // ---- owner of the dataset's buffers (abi_dataset.hip); keep_stats: only what depends on the rollout's length goes ----
 void dataset_release(gs_handle* h, bool keep_stats = false);
+// map[0 .. N) = -1, then entry k of the last rollout's terminal list (t, b) -> map[t B + b] = k; queued on the handle's stream
+int terminal_map_fill(gs_handle* h, int32_t* map, long long N);
 
 }  // namespace gsi

@@ -12,6 +12,7 @@
 #include "q_next.h"
 #include "pathwise.h"
 #include "conservative.h"
+#include "refresh.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -95,6 +96,11 @@ __global__ void gs_k_cql_rows(GsCqlRowsArgs R);
 __global__ void gs_k_cql_lse(GsCqlLseArgs L);
 __global__ void gs_k_cql_head(GsCqlHeadArgs H);
 __global__ void gs_k_cql_stats(GsCqlStatArgs S);
+__global__ void gs_k_refresh_terms(GsRefreshTermsArgs G);
+__global__ void gs_k_refresh_rows(GsRefreshRowsArgs G);
+__global__ void gs_k_refresh_td_policy(GsRefreshTdPolicyArgs G);
+__global__ void gs_k_refresh_td_value(GsRefreshTdValueArgs G);
+__global__ void gs_k_refresh_combine(GsRefreshCombineArgs C);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .policy import HALF_LOG_2PI, LOG_STD_MAX, LOG_STD_MIN, MLPPolicy, MLPQ, MLPValue
-from .rollout import _philox4x32
+from .rollout import _bootstrap_mask, _philox4x32
 
 HALF_LOG_2PIE = HALF_LOG_2PI + 0.5      # 0.5 * log(2 pi e): a unit Gaussian's entropy
 
@@ -577,6 +577,14 @@ class DeviceLearner:
     step is ``pathwise_noise_np(pathwise_seed, draw, n, A)`` with ``draw`` = the policy's steps taken.  Host state: the C loss kind
     is not involved.
 
+    Per-minibatch targets: ``fresh_targets=True`` makes ``step(batch)`` re-evaluate, for the batch's
+    transitions and with the networks as they are at that moment, the signals its steps are about to read (``refresh_targets``),
+    in the reference's order.  Under ``q_target="policy"``: "td_policy" (``gamma``, this learner's ``alpha``, ``bootstrap``, noise
+    seed ``target_seed``, ``draw`` = the first Q net's steps taken, sampled unless ``pathwise_stochastic=False``), the Q steps,
+    then the other networks.  Under the IQL wiring (``advantage_source="q"`` and ``value_target="q"``): "q_target", the value
+    step, "td_value", the Q steps, "q_adv", the policy step.  The full evaluations (``evaluate_rollout_q_next`` /
+    ``evaluate_rollout_q``) then run once, before the first epoch.  The default calls no new entry.
+
     The conservative critic: ``conservative_weight`` > 0 makes the Q networks' step
     ``gs_learner_step_conservative`` -- CQL's ``mse(Q(s, a), y) + conservative_weight (logsumexp over the batch of Q(s, a_data) |
     Q(s, a_uniform) | Q(s, a_policy) - mean Q(s, a_data))`` per twin, the policy's candidates sampled inside the step
@@ -594,7 +602,8 @@ class DeviceLearner:
                  expectile: float = 0.7, q_loss: str = "mse", advantage_source: str = "batch", value_target: str = "batch",
                  alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True, pathwise_seed: int = 0,
                  q_target: str = "value", conservative_weight: float = 0.0, conservative_stochastic: bool = True,
-                 conservative_seed: int = 0) -> None:
+                 conservative_seed: int = 0, fresh_targets: bool = False, gamma: float = 0.99, bootstrap: Sequence[str] = (),
+                 target_seed: int = 0) -> None:
         if isinstance(nets, str):
             nets = (nets,)
         self.nets = tuple(nets)
@@ -647,6 +656,13 @@ class DeviceLearner:
             if q_loss != "mse":
                 raise ValueError(f"DeviceLearner: conservative_weight > 0 needs q_loss = 'mse' (the penalty joins the squared error), got {q_loss!r}")
             self._conservative = state
+        self._fresh: Optional[dict] = None
+        if not isinstance(fresh_targets, (bool, np.bool_)):
+            raise ValueError(f"DeviceLearner: fresh_targets = {fresh_targets!r} must be True or False")
+        if fresh_targets:
+            self._fresh = self._fresh_state(q_target, advantage_source, value_target, gamma, bootstrap, target_seed, float(alpha),
+                                            bool(pathwise_stochastic))
+        self.fresh_targets = bool(fresh_targets)
         self.env = env
         self.config = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                            clip=float(clip), ent_coef=float(ent_coef), max_grad_norm=float(max_grad_norm))
@@ -694,6 +710,34 @@ class DeviceLearner:
             raise ValueError(f"DeviceLearner: conservative_seed = {seed!r} must be an integer in [0, 2^64)")
         return dict(conservative_weight=cw, stochastic=bool(stochastic), seed=int(seed))
 
+    def _fresh_state(self, q_target, advantage_source, value_target, gamma, bootstrap, seed, alpha, stochastic) -> dict:
+        """What ``fresh_targets=True`` refreshes per minibatch, and under which configuration; ValueError for what cannot be."""
+        if not any(k >= _lib.GS_LEARNER_Q for k in self._ids):
+            raise ValueError(f"DeviceLearner: fresh_targets = True needs 'q1' or 'q2' among nets {self.nets}")
+        if q_target == "policy":
+            wiring = "policy"
+        elif advantage_source == "q" and value_target == "q":
+            wiring = "iql"
+        else:
+            raise ValueError("DeviceLearner: fresh_targets = True needs q_target = 'policy' (the policy-action target) or the IQL wiring "
+                             "(advantage_source = 'q' and value_target = 'q')")
+        gamma = float(gamma)
+        if not math.isfinite(gamma):
+            raise ValueError(f"DeviceLearner: gamma = {gamma} must be finite")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"DeviceLearner: target_seed = {seed!r} must be an integer in [0, 2^64)")
+        return dict(wiring=wiring, gamma=gamma, mask=_bootstrap_mask(bootstrap), seed=int(seed), alpha=alpha, stochastic=stochastic)
+
+    def _refresh(self, batch: dict, groups: str, stream=None) -> None:
+        """One ``gs_learner_refresh`` of ``groups`` on ``batch`` under the ``fresh_targets`` configuration; the noise of
+        "td_policy" is drawn with ``draw`` = the first Q net's steps taken."""
+        f = self._fresh
+        draw = 0
+        if groups == "td_policy":
+            draw = int(self.env.handle.learner_info(next(k for k in self._ids if k >= _lib.GS_LEARNER_Q))["step"]) & 0xFFFFFFFF
+        cfg = _lib.refresh_config(groups, f["gamma"], f["alpha"] if groups == "td_policy" else 0.0, f["mask"], f["stochastic"], f["seed"], draw)
+        self.env.handle.learner_refresh(batch, cfg, stream=stream)
+
     def set_loss(self, net="policy", loss: Optional[str] = None, temperature: float = 1.0, weight_max: float = 20.0,
                  expectile: float = 0.7, alpha: float = 0.0, bc_coef: float = 0.0, pathwise_stochastic: bool = True,
                  pathwise_seed: int = 0) -> None:
@@ -734,13 +778,41 @@ class DeviceLearner:
     def step(self, batch: dict, stream=None) -> None:
         """One update of every network on ``batch`` (asynchronous on the handle's stream; ``stream``: a consumer's stream)."""
         n = int(batch["observations"].shape[0])
+        if self._fresh is not None:
+            return self._step_fresh(batch, n, stream)
         for net in self._ids:
-            if net == _lib.GS_LEARNER_POLICY and self._pathwise is not None:
-                self.step_pathwise(batch, stream=stream)
-            elif net >= _lib.GS_LEARNER_Q and self._conservative is not None:
-                self.step_conservative(batch, net, stream=stream)
-            else:
-                self.env.handle.learner_step(net, batch, n, stream)
+            self._step_net(net, batch, n, stream)
+
+    def _step_net(self, net: int, batch: dict, n: int, stream=None) -> None:
+        if net == _lib.GS_LEARNER_POLICY and self._pathwise is not None:
+            self.step_pathwise(batch, stream=stream)
+        elif net >= _lib.GS_LEARNER_Q and self._conservative is not None:
+            self.step_conservative(batch, net, stream=stream)
+        else:
+            self.env.handle.learner_step(net, batch, n, stream)
+
+    def _step_fresh(self, batch: dict, n: int, stream=None) -> None:
+        """``step`` under ``fresh_targets=True``: the reference's order of recomputation and optimiser steps inside one
+        ``update(batch)``.  The policy-action wiring (algorithms/offline.py:166-255): "td_policy", the Q steps, then every other
+        network.  The IQL wiring (:482-540): "q_target", the value step, "td_value", the Q steps, "q_adv", the policy step, then
+        every other network."""
+        qs = [k for k in self._ids if k >= _lib.GS_LEARNER_Q]
+        if self._fresh["wiring"] == "policy":
+            self._refresh(batch, "td_policy", stream)
+            order = qs + [k for k in self._ids if k < _lib.GS_LEARNER_Q]
+            for net in order:
+                self._step_net(net, batch, n, stream)
+            return
+        self._refresh(batch, "q_target", stream)
+        self._step_net(_lib.GS_LEARNER_VALUE, batch, n, stream)
+        self._refresh(batch, "td_value", stream)
+        for net in qs:
+            self._step_net(net, batch, n, stream)
+        self._refresh(batch, "q_adv", stream)
+        self._step_net(_lib.GS_LEARNER_POLICY, batch, n, stream)
+        for net in self._ids:
+            if net not in qs and net not in (_lib.GS_LEARNER_VALUE, _lib.GS_LEARNER_POLICY):
+                self._step_net(net, batch, n, stream)
 
     def step_pathwise(self, batch: dict, alpha: Optional[float] = None, bc_coef: Optional[float] = None, stochastic: Optional[bool] = None,
                       seed: Optional[int] = None, draw: Optional[int] = None, stream=None) -> None:

@@ -229,6 +229,61 @@ def evaluate_rollout_q_next(env: BatchedGridEnvironment, gamma: float = 0.99, al
     return SimpleNamespace(**h.rollout_q_next_arrays(stream))
 
 
+def refresh_targets(env: BatchedGridEnvironment, batch, groups, gamma: float = 0.99, alpha: float = 0.0, bootstrap: Sequence[str] = (),
+                    stochastic: bool = True, seed: int = 0, draw: int = 0, reward_shift: float = 0.0, reward_scale: float = 1.0,
+                    stream=None) -> None:
+    """Per-minibatch targets (``gs_learner_refresh``, asynchronous): the signal ``groups`` -- names of
+    ``_lib.REFRESH_GROUPS`` ("td_policy", "q_target", "td_value", "q_adv"), one or several, or the bits -- re-evaluated for the
+    transitions ``batch["indices"]`` names (a minibatch of ``OnPolicyBatches.epoch``, or any dict with a device int32 array of
+    ``t * B + b``) under the networks as they are NOW, and written into the arrays of ``evaluate_rollout_q_next`` ("td_policy") /
+    ``evaluate_rollout_q`` (the others) at those transitions; every other position keeps its bits.  What the reference's
+    ``update(batch)`` recomputes per minibatch (algorithms/offline.py:173-178, :482-540).  The evaluation a group replaces rows of
+    must have run on the last rollout ("td_policy": under the same ``bootstrap``).  The other arguments are
+    ``evaluate_rollout_q_next``'s; the noise of row j is ``q_next_noise_np(seed, draw, [j], A)``.  ``refresh_rows_np`` restates
+    which rows are read."""
+    gamma, alpha = float(gamma), float(alpha)
+    bits = _lib.refresh_groups(groups)
+    if bits <= 0 or bits & ~sum(_lib.REFRESH_GROUPS.values()):
+        raise ValueError(f"refresh_targets: groups = {groups!r} names no group or an unknown one (any of {sorted(_lib.REFRESH_GROUPS)})")
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError(f"refresh_targets: alpha = {alpha} must be a finite value >= 0")
+    if not isinstance(stochastic, (bool, np.bool_)):
+        raise ValueError(f"refresh_targets: stochastic = {stochastic!r} must be True or False")
+    _q_next_seed(seed, draw, "refresh_targets")
+    if not hasattr(batch, "get") or batch.get("indices") is None:
+        raise ValueError("refresh_targets: the batch holds no 'indices'")
+    env.handle.learner_refresh(batch, _lib.refresh_config(bits, gamma, alpha, _bootstrap_mask(bootstrap), bool(stochastic), int(seed), int(draw),
+                                                          reward_shift, reward_scale), stream=stream)
+
+
+def refresh_rows_np(indices, T: int, B: int, terminals, terminal_index, bootstrap_mask: int = 0):
+    """Which rows ``gs_learner_refresh`` reads for the batch ``indices`` [n] over a rollout of ``T`` steps and ``B`` instances,
+    restated in NumPy: (own [n], next [n], pairs [m, 2]).  ``own[i]`` = j_i, the index clamped into [0, T B): row j_i of the
+    flattened ``obs_seq`` [(T + 1) B, obs_dim] is the transition's state; ``next[i]`` = j_i + B its next state; ``pairs``: the
+    (i, e) of every batch row whose transition ended an episode under the mask (``terminals`` [T, B] & ``bootstrap_mask``) and has
+    an entry e in ``terminal_index`` [(t, b)] -- in ascending i, a duplicate index once per occurrence; where an (t, b) occurs
+    more than once in the list the LAST entry counts (the device's map is scattered in list order)."""
+    idx = np.asarray(indices)
+    if idx.ndim != 1 or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+        raise ValueError("refresh_rows_np: indices must be a one-dimensional array of integers")
+    T, B, mask = int(T), int(B), int(bootstrap_mask)
+    if T <= 0 or B <= 0:
+        raise ValueError(f"refresh_rows_np: T = {T} and B = {B} must be > 0")
+    if not 0 <= mask <= 3:
+        raise ValueError(f"refresh_rows_np: bootstrap_mask = {mask} outside 0 .. 3")
+    flags = np.asarray(terminals).astype(np.uint8)
+    if flags.shape != (T, B):
+        raise ValueError(f"refresh_rows_np: terminals must be [{T}, {B}], got {flags.shape}")
+    own = np.clip(idx.astype(np.int64), 0, T * B - 1)
+    entry = np.full(T * B, -1, dtype=np.int64)
+    tb = np.asarray(terminal_index, dtype=np.int64).reshape(-1, 2)
+    inside = (tb[:, 0] >= 0) & (tb[:, 0] < T) & (tb[:, 1] >= 0) & (tb[:, 1] < B)
+    entry[(tb[:, 0] * B + tb[:, 1])[inside]] = np.nonzero(inside)[0]
+    hit = ((flags.reshape(-1)[own] & mask) != 0) & (entry[own] >= 0)
+    rows = np.nonzero(hit)[0]
+    return own, own + B, np.stack([rows, entry[own[rows]]], axis=1).astype(np.int64).reshape(-1, 2)
+
+
 def _q_next_seed(seed, draw, who: str) -> None:
     integer = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
     if not integer(seed) or not 0 <= int(seed) < 1 << 64:

@@ -1239,6 +1239,53 @@ int gs_learner_step_conservative(gs_handle* h, int32_t net, const gs_onpolicy_ba
                                  void* consumer_stream);
 int gs_learner_conservative_view(gs_handle* h, gs_conservative_view_out* out, void* consumer_stream);
 
+/* ---- per-minibatch targets: refresh the rollout's bootstrap signals over a row list ----
+ * The reference recomputes every bootstrap quantity inside each update(batch), with the networks as they are at that moment
+ * (algorithms/offline.py:173-178 for CQL, :482-540 for IQL); gs_rollout_evaluate_q and gs_rollout_evaluate_q_next write them once over
+ * the whole rollout.  gs_learner_refresh re-evaluates the selected groups for the n transitions of a minibatch with the images as
+ * they are NOW and writes the results into the same per-rollout arrays at those transitions' positions; every other position keeps
+ * its bits.  The learner's steps read those arrays through the batch's indices, so no step changes.  Additive to ABI 2: no struct
+ * above changes, and a handle that never calls this entry computes what it computed before.
+ *
+ * gs_learner_refresh (asynchronous, on the handle's stream) reads batch->indices alone: j_i = t B + b, clamped into the rollout as
+ * gs_learner_step clamps it.  Groups (bits of `groups`; several may be set, they run in this order):
+ *   GS_REFRESH_TD_POLICY   "policy-action TD targets" at j: the installed policy on the next state (noise counter (j, k >> 2, draw,
+ *                          'QNXT'), key seed), the TARGET twins on its action; writes next_pre_head, next_actions, next_noise,
+ *                          next_log_probs, q_next[which], q_next_min and td_target at j.  Where done[j] & bootstrap_mask and the
+ *                          transition has a terminal entry e, also that entry's term_* arrays (tag 'QNTE', the entry's (t, b)),
+ *                          term_value[e], and td_target[j] from it.  Rounding order: that section's.  Needs gs_rollout_evaluate_q_next
+ *                          on the last rollout under the SAME bootstrap_mask, so that every row holds the result of some evaluation.
+ *   GS_REFRESH_Q_TARGET    the TARGET twins on (s_j, a_j): q[target][which][j], q_min[target][j] of gs_rollout_evaluate_q.
+ *   GS_REFRESH_TD_VALUE    the installed value network on the next state of j (on the terminal observation where done[j] &
+ *                          bootstrap_mask and an entry exists; 0 for any other finished transition): td_target[j] of
+ *                          gs_rollout_evaluate_q = r' + gamma * vnext.  The values stay in the refresh's scratch: values, advantages
+ *                          and returns of gs_rollout_evaluate are NOT written.
+ *   GS_REFRESH_Q_ADV       the value network on s_j and the ONLINE twins on (s_j, a_j): q[online][which][j], q_min[online][j], q_adv[j]
+ *                          = q_min - V, one rounded subtraction.
+ * The last three need gs_rollout_evaluate_q on the last rollout; the last two an installed value network; TD_POLICY a policy with
+ * GS_COMPUTE_F32 and GS_HEAD_GAUSSIAN_TANH; every group an installed twin: GS_E_STATE otherwise.  GS_E_INVALID: a wrong struct_size,
+ * groups 0 or an unknown bit, what gs_rollout_evaluate refuses of bootstrap_mask / gamma / reward_shift / reward_scale, alpha NaN,
+ * negative or infinite, stochastic outside {0, 1}, n outside 1 .. 2^24, a batch without indices.  Every check runs before any launch:
+ * a refused call leaves every array's bits as they were.
+ * A refreshed row holds exactly the bits a full gs_rollout_evaluate_q_next / gs_rollout_evaluate_q under the same config and images
+ * leaves there (a row's outputs depend on that row, the images, seed, draw and its transition's index alone).  An index may occur
+ * more than once in a batch: the duplicates compute the same bits from the same inputs, so their colliding stores are benign.
+ * The views and downloads of those two evaluations stay as they are and show the refreshed rows.  consumer_stream: as
+ * gs_learner_step. */
+enum { GS_REFRESH_TD_POLICY = 1, GS_REFRESH_Q_TARGET = 2, GS_REFRESH_TD_VALUE = 4, GS_REFRESH_Q_ADV = 8 };
+typedef struct gs_refresh_config {
+  int32_t struct_size;            /* = sizeof(gs_refresh_config) */
+  int32_t groups;                 /* GS_REFRESH_* bits */
+  int32_t bootstrap_mask;         /* as gs_gae_config */
+  int32_t stochastic;             /* TD_POLICY: 0: eps = 0, a' = tanh(mean) */
+  double gamma, alpha;            /* alpha: finite, >= 0 (TD_POLICY) */
+  double reward_shift, reward_scale;
+  uint64_t seed;
+  uint32_t draw, reserved;
+  uint64_t reserved2;
+} gs_refresh_config;
+int gs_learner_refresh(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t n, const gs_refresh_config* cfg, void* consumer_stream);
+
 /* ---- the federation: clipped, noised federated averaging over the learners of K handles, in place ----
  * K handles of ONE process and ONE device, each with a live learner for the same network `net` (GS_LEARNER_*), form a federation.
  * A round measures the clients' updates against the global parameters, clips them, averages them, adds Gaussian noise and writes
