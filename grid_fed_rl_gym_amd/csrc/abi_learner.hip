@@ -188,7 +188,7 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
   Installed I{};
   if (!installed(h, net, I))
     return fail(h, GS_E_STATE, "gs_learner_create: %s is not installed%s", net_name(net), net == GS_LEARNER_POLICY ? " with GS_COMPUTE_F32" : "");
-  if (net == GS_LEARNER_POLICY && h->pol.args32.head != GS_HEAD_GAUSSIAN_TANH)
+  if (net == GS_LEARNER_POLICY && !policy_rows_ready(h))
     return fail(h, GS_E_STATE, "gs_learner_create: the policy needs the Gaussian head (GS_HEAD_GAUSSIAN_TANH)");
   GS_ENTER(h);
   learner_drop(h, net);
@@ -561,7 +561,7 @@ int gs_learner_step_conservative(gs_handle* h, int32_t net, const gs_onpolicy_ba
   Installed I{}, IP{};
   if (!Ln.live || !installed(h, net, I)) return fail(h, GS_E_STATE, "%s: no learner for %s (gs_learner_create after the network was installed)", who, net_name(net));
   if (Ln.loss.kind != GS_LOSS_DEFAULT) return fail(h, GS_E_STATE, "%s: the loss of %s must be GS_LOSS_DEFAULT (the penalty joins the squared error)", who, net_name(net));
-  if (!Lp.live || !installed(h, GS_LEARNER_POLICY, IP) || h->pol.args32.head != GS_HEAD_GAUSSIAN_TANH)
+  if (!Lp.live || !installed(h, GS_LEARNER_POLICY, IP) || !policy_rows_ready(h))
     return fail(h, GS_E_STATE, "%s: no learner for the policy (GS_COMPUTE_F32, GS_HEAD_GAUSSIAN_TANH: its forward pass gives the policy block's actions)", who);
   const int D = h->obs_dim, A = h->action_dim, DA = D + A;
   if (A <= 0 || A > GS_PW_MAX_A) return fail(h, GS_E_STATE, "%s: action_dim = %d outside 1 .. %d", who, A, GS_PW_MAX_A);

@@ -10,20 +10,6 @@
 
 using namespace gsi;
 
-// one launch over `rows` rows of obs (device pointers) on the handle's main stream; rows_dev / scatter_*: GsValueArgs
-static int launch_value(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
-                        const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0) {
-  if (rows <= 0) return GS_OK;
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "value", &blocks)) return rc;
-  GsValueArgs a = val.args;
-  a.obs = obs; a.out = out; a.rows = (int32_t)rows; a.rows_dev = rows_dev;
-  a.scatter_idx = scatter_idx; a.scatter_out = scatter_out; a.scatter_T = scatter_T; a.scatter_B = h->B;
-  hipLaunchKernelGGL(gs_k_value_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), val.lds, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
 namespace gsi __attribute__((visibility("hidden"))) {
 
 void value_release(gs_handle* h) {
@@ -35,22 +21,6 @@ void onpolicy_release(gs_handle* h) {
   for (gs_handle::Critic& c : h->critic) { c.values.release(); c.term_values.release(); c.adv.release(); c.ret.release(); c.evaluated_on = 0; }
   if (h->ro.ev_eval) { (void)hipEventDestroy(h->ro.ev_eval); h->ro.ev_eval = nullptr; }
   h->ro.logp_recorded = false;
-}
-
-int scalar_net_install(gs_handle* h, gs_handle::Value& val, const void* kernel, const gs_policy_mlp& p, const gs_policy_mlp_opts& o, ScalarNet& net) {
-  net.im = gs_policy_pack_f32(p, o);
-  val.lds = gs_val_lds_bytes(net.im.kb[0]);
-  HIPCHK(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-  if (int rc = upload_image_f32(h, val.blob, net.im, &net.image, &net.norm)) return rc;
-  for (int l = 0; l <= p.n_layers; ++l) val.dims[l] = p.dims[l];
-  val.h_norm = net.im.norm;
-  return GS_OK;
-}
-
-int scalar_net_grid(gs_handle* h, long long rows, const char* kernel, unsigned* blocks) {
-  if (rows > 0x7fffffffLL - GS_VAL_ROWS) return fail(h, GS_E_INVALID, "%lld rows exceed the %s kernel's 32-bit row index", rows, kernel);
-  *blocks = (unsigned)((rows + GS_VAL_ROWS - 1) / GS_VAL_ROWS);
-  return GS_OK;
 }
 
 // what gs_value_mlp_set and gs_cost_value_mlp_set (abi_costs.hip) share: `p` has passed gs_value_check; NULL removes the network
@@ -87,10 +57,10 @@ int critic_evaluate(gs_handle* h, gs_handle::Critic& c, const double* signal, in
   // all four or none: a later call must not find `values` and launch on the others
   if (!c.values && (rc = alloc_all(h, "a critic's arrays over the rollout", c.values.want((cap + 1) * B), c.term_values.want((size_t)ro.term_cap),
                                    c.adv.want(cap * B), c.ret.want(cap * B)))) return rc;
-  if ((rc = launch_value(h, c.net, ro.obs_seq, c.values, (long long)((T + 1) * B)))) return rc;
+  if ((rc = launch_value_rows(h, c.net, ro.obs_seq, c.values, (long long)((T + 1) * B)))) return rc;
   // the terminal rows: launched over the list's capacity, the count read on the device; every value also goes to its (t, b) in
   // `ret`, where gs_k_gae looks for it before it writes the return there
-  if ((rc = launch_value(h, c.net, ro.term_obs, c.term_values, ro.term_cap, ro.term_count, ro.term_idx, c.ret, (int)T))) return rc;
+  if ((rc = launch_value_rows(h, c.net, ro.term_obs, c.term_values, ro.term_cap, ro.term_count, ro.term_idx, c.ret, (int)T))) return rc;
   GsGaeArgs g{c.values, signal, ro.done, c.adv, c.ret, (int32_t)T, h->B, bootstrap_mask, 0, gamma, lambda, shift, scale};
   hipLaunchKernelGGL(gs_k_gae, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, g);
   HIPCHK(h, hipGetLastError());
@@ -137,7 +107,7 @@ int gs_value_mlp_eval(gs_handle* h, double* values_host) {
   if (!val.set) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_value_mlp_set");
   if (!h->was_reset) return fail(h, GS_E_STATE, "gs_value_mlp_eval before gs_reset");
   GS_ENTER(h);
-  int rc = launch_value(h, val, h->d_obs2[h->obs_cur], val.out, h->B);
+  int rc = launch_value_rows(h, val, h->d_obs2[h->obs_cur], val.out, h->B);
   if (rc) return rc;
   HIPCHK(h, hipMemcpyAsync(values_host, val.out, (size_t)h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -38,19 +38,6 @@ std::string gs_q_check(const gs_policy_mlp* p, const gs_policy_mlp_opts* o, int3
   return gs_value_check(p, &q.o, obs_dim + action_dim);
 }
 
-// one launch of twin `Q` under the layer table `L` (the online or the target image) over the last rollout's T * B rows
-static int launch_q(gs_handle* h, const gs_handle::QNet& Q, const GsPolicyLayerF32* L, double* out) {
-  const long long rows = (long long)h->ro.T * h->B;
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "Q", &blocks)) return rc;
-  GsQArgs a = Q.qargs;
-  a.obs = h->ro.obs_seq; a.act = h->ro.act; a.out = out; a.rows = (int32_t)rows;
-  for (int l = 0; l < a.n_layers; ++l) a.L[l] = L[l];
-  hipLaunchKernelGGL(gs_k_q_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
 namespace gsi __attribute__((visibility("hidden"))) {
 
 void q_rollout_release(gs_handle* h) {
@@ -137,7 +124,7 @@ int gs_rollout_evaluate_q(gs_handle* h, const gs_q_eval_config* cfg) {
     if (!Q.net.set) continue;
     for (int s = 0; s < 2; ++s) {
       double* out = t.q + (size_t)(2 * s + w) * cap;
-      if ((rc = launch_q(h, Q, s ? Q.TL : Q.qargs.L, out))) return rc;
+      if ((rc = launch_q_rows(h, Q, s ? Q.TL : Q.qargs.L, ro.obs_seq, ro.act, (long long)TB, nullptr, out))) return rc;
       C.q[s][w] = out;
     }
   }

@@ -10,41 +10,6 @@ using namespace gsi;
 
 static_assert(sizeof(gs_q_next_config) == 64, "gs_q_next_config: four int32, four doubles, a uint64, two uint32");
 
-namespace {
-
-// gs_k_policy_rows_f32 under the installed policy over `rows` rows of `obs`; rows_dev / idx: GsPolicyRowsArgs
-int launch_policy_rows(gs_handle* h, const gs_q_next_config& cfg, const double* obs, long long rows, const int32_t* rows_dev, const int32_t* idx,
-                       uint32_t tag, float* pre, double* act, double* eps, double* lp) {
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "policy-rows", &blocks)) return rc;
-  const GsPolicyArgsF32& p = h->pol.args32;
-  GsPolicyRowsArgs a{};
-  a.obs = obs; a.rows_dev = rows_dev; a.idx = idx; a.shift = p.shift; a.scale = p.scale;
-  a.pre_head = pre; a.act = act; a.noise = eps; a.logp = lp;
-  a.rows = (int32_t)rows; a.B = h->B; a.D = p.D; a.A = p.A; a.n_layers = p.n_layers; a.activation = p.activation;
-  a.obs_stride = gs_val_obs_stride(p.L[0].kb); a.panel_kb = gs_val_panel_kb(p.L[0].kb);
-  a.stochastic = cfg.stochastic; a.draw = cfg.draw; a.tag = tag; a.seed = cfg.seed;
-  for (int l = 0; l < p.n_layers; ++l) a.L[l] = p.L[l];
-  hipLaunchKernelGGL(gs_k_policy_rows_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), gs_qn_lds_bytes(p.L[0].kb, p.A), h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
-// twin `Q` under its TARGET image over `rows` rows of (obs, act); rows_dev: NULL, or the list's length on the device
-int launch_q_target(gs_handle* h, const gs_handle::QNet& Q, const double* obs, const double* act, long long rows, const int32_t* rows_dev, double* out) {
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "Q", &blocks)) return rc;
-  GsQArgs a = Q.qargs;
-  a.obs = obs; a.act = act; a.out = out; a.rows = (int32_t)rows;
-  for (int l = 0; l < a.n_layers; ++l) a.L[l] = Q.TL[l];
-  if (rows_dev) hipLaunchKernelGGL(gs_k_q_mlp_rows_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a, rows_dev);
-  else hipLaunchKernelGGL(gs_k_q_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
-}  // namespace
-
 namespace gsi __attribute__((visibility("hidden"))) {
 
 void q_next_rollout_release(gs_handle* h) {
@@ -71,7 +36,7 @@ int gs_rollout_evaluate_q_next(gs_handle* h, const gs_q_next_config* cfg) {
   gs_handle::QNext& t = h->qn;
   if (ro.T <= 0) return fail(h, GS_E_STATE, "gs_rollout_evaluate_q_next: no rollout has been collected on this handle");
   if (!h->qnet[0].net.set && !h->qnet[1].net.set) return fail(h, GS_E_STATE, "gs_rollout_evaluate_q_next before gs_q_mlp_set");
-  if (!h->pol.set || h->pol.compute != GS_COMPUTE_F32 || h->pol.args32.head != GS_HEAD_GAUSSIAN_TANH)
+  if (!policy_rows_ready(h))
     return fail(h, GS_E_STATE, "gs_rollout_evaluate_q_next: it needs an installed policy with GS_COMPUTE_F32 and GS_HEAD_GAUSSIAN_TANH");
   GS_ENTER(h);
   const size_t B = h->B, D = h->obs_dim, A = h->action_dim, cap = (size_t)ro.T_cap * B, TB = (size_t)ro.T * B, tc = (size_t)ro.term_cap;
@@ -80,20 +45,19 @@ int gs_rollout_evaluate_q_next(gs_handle* h, const gs_q_next_config* cfg) {
                                 t.q.want(2 * cap), t.q_min.want(cap), t.td.want(cap), t.t_pre.want(tc * 2 * A), t.t_act.want(tc * A), t.t_eps.want(tc * A), t.t_lp.want(tc),
                                 t.t_q.want(2 * tc), t.t_q_min.want(tc), t.t_value.want(tc))))
     return rc;
-  // (the cap on a kernel's dynamic LDS is a setting of the FUNCTION: always the most, policy.h GS_POL_LDS_MAX)
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_rows_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-  HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_q_mlp_rows_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
+  if ((rc = rows_kernels_lds_cap(h))) return rc;
   const bool terms = cfg->bootstrap_mask && ro.term_cap > 0;
   const double* const next_obs = ro.obs_seq + B * D;      // row (t + 1, b) for transition (t, b)
   GsQNextTdArgs G{};
-  if ((rc = launch_policy_rows(h, *cfg, next_obs, (long long)TB, nullptr, nullptr, GS_QN_ROLLOUT_TAG, t.pre, t.act, t.eps, t.lp))) return rc;
-  if (terms && (rc = launch_policy_rows(h, *cfg, ro.term_obs, ro.term_cap, ro.term_count, ro.term_idx, GS_QN_TERMINAL_TAG, t.t_pre, t.t_act, t.t_eps, t.t_lp))) return rc;
+  const PolicyNoise noise{cfg->stochastic, cfg->draw, cfg->seed};
+  if ((rc = launch_policy_rows(h, noise, next_obs, (long long)TB, nullptr, nullptr, GS_QN_ROLLOUT_TAG, t.pre, t.act, t.eps, t.lp))) return rc;
+  if (terms && (rc = launch_policy_rows(h, noise, ro.term_obs, ro.term_cap, ro.term_count, ro.term_idx, GS_QN_TERMINAL_TAG, t.t_pre, t.t_act, t.t_eps, t.t_lp))) return rc;
   for (int w = 0; w < 2; ++w) {
     const gs_handle::QNet& Q = h->qnet[w];
     if (!Q.net.set) continue;
     G.q[w] = t.q + (size_t)w * cap; G.term_q[w] = t.t_q + (size_t)w * tc;
-    if ((rc = launch_q_target(h, Q, next_obs, t.act, (long long)TB, nullptr, t.q + (size_t)w * cap))) return rc;
-    if (terms && (rc = launch_q_target(h, Q, ro.term_obs, t.t_act, ro.term_cap, ro.term_count, t.t_q + (size_t)w * tc))) return rc;
+    if ((rc = launch_q_rows(h, Q, Q.TL, next_obs, t.act, (long long)TB, nullptr, t.q + (size_t)w * cap))) return rc;
+    if (terms && (rc = launch_q_rows(h, Q, Q.TL, ro.term_obs, t.t_act, ro.term_cap, ro.term_count, t.t_q + (size_t)w * tc))) return rc;
   }
   G.lp = t.lp; G.rew = ro.rew; G.done = ro.done; G.term_lp = t.t_lp; G.term_count = ro.term_count; G.term_idx = ro.term_idx;
   G.q_min = t.q_min; G.term_q_min = t.t_q_min; G.term_value = t.t_value; G.td = t.td;

@@ -11,55 +11,6 @@ using namespace gsi;
 static_assert(sizeof(gs_refresh_config) == 72, "gs_refresh_config: four int32, four doubles, a uint64, two uint32, a reserved uint64");
 static_assert(sizeof(gs_refresh_config) % 8 == 0, "gs_refresh_config is padded to whole doubles");
 
-namespace {
-
-// gs_k_policy_rows_f32 under the installed policy over the rows of `obs` with noise indices idx[row] = (t, b)
-int launch_policy(gs_handle* h, const gs_refresh_config& cfg, const double* obs, long long rows, const int32_t* rows_dev, const int32_t* idx, uint32_t tag,
-                  float* pre, double* act, double* eps, double* lp) {
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "policy-rows", &blocks)) return rc;
-  const GsPolicyArgsF32& p = h->pol.args32;
-  GsPolicyRowsArgs a{};
-  a.obs = obs; a.rows_dev = rows_dev; a.idx = idx; a.shift = p.shift; a.scale = p.scale;
-  a.pre_head = pre; a.act = act; a.noise = eps; a.logp = lp;
-  a.rows = (int32_t)rows; a.B = h->B; a.D = p.D; a.A = p.A; a.n_layers = p.n_layers; a.activation = p.activation;
-  a.obs_stride = gs_val_obs_stride(p.L[0].kb); a.panel_kb = gs_val_panel_kb(p.L[0].kb);
-  a.stochastic = cfg.stochastic; a.draw = cfg.draw; a.tag = tag; a.seed = cfg.seed;
-  for (int l = 0; l < p.n_layers; ++l) a.L[l] = p.L[l];
-  hipLaunchKernelGGL(gs_k_policy_rows_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), gs_qn_lds_bytes(p.L[0].kb, p.A), h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
-// twin `Q` under the layer table `L` (its online or its target image) over `rows` rows of (obs, act)
-int launch_q(gs_handle* h, const gs_handle::QNet& Q, const GsPolicyLayerF32* L, const double* obs, const double* act, long long rows, const int32_t* rows_dev,
-             double* out) {
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "Q", &blocks)) return rc;
-  GsQArgs a = Q.qargs;
-  a.obs = obs; a.act = act; a.out = out; a.rows = (int32_t)rows;
-  for (int l = 0; l < a.n_layers; ++l) a.L[l] = L[l];
-  if (rows_dev) hipLaunchKernelGGL(gs_k_q_mlp_rows_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a, rows_dev);
-  else hipLaunchKernelGGL(gs_k_q_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), Q.net.lds, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
-// the installed value network over `rows` rows of obs
-int launch_v(gs_handle* h, const double* obs, long long rows, const int32_t* rows_dev, double* out) {
-  const gs_handle::Value& val = h->critic[0].net;
-  unsigned blocks = 0;
-  if (int rc = scalar_net_grid(h, rows, "value", &blocks)) return rc;
-  GsValueArgs a = val.args;
-  a.obs = obs; a.out = out; a.rows = (int32_t)rows; a.rows_dev = rows_dev;
-  a.scatter_idx = nullptr; a.scatter_out = nullptr; a.scatter_T = 0; a.scatter_B = h->B;
-  hipLaunchKernelGGL(gs_k_value_mlp_f32, dim3(blocks), dim3(64 * GS_POL_WAVES), val.lds, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return GS_OK;
-}
-
-}  // namespace
-
 namespace gsi __attribute__((visibility("hidden"))) {
 
 void refresh_release(gs_handle* h) {
@@ -88,12 +39,13 @@ int gs_learner_refresh(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t
   gs_handle::Refresh& r = h->rfr;
   gs_handle::QNext& qn = h->qn;
   gs_handle::QTrack& qt = h->qt;
+  const gs_handle::Value& val = h->critic[0].net;
   const int groups = cfg->groups;
   const bool g_pol = groups & GS_REFRESH_TD_POLICY, g_tgt = groups & GS_REFRESH_Q_TARGET, g_tdv = groups & GS_REFRESH_TD_VALUE, g_adv = groups & GS_REFRESH_Q_ADV;
   if (ro.T <= 0) return fail(h, GS_E_STATE, "%s: no rollout has been collected on this handle", who);
   if (!h->qnet[0].net.set && !h->qnet[1].net.set) return fail(h, GS_E_STATE, "%s before gs_q_mlp_set", who);
   if (g_pol) {
-    if (!h->pol.set || h->pol.compute != GS_COMPUTE_F32 || h->pol.args32.head != GS_HEAD_GAUSSIAN_TANH)
+    if (!policy_rows_ready(h))
       return fail(h, GS_E_STATE, "%s: GS_REFRESH_TD_POLICY needs an installed policy with GS_COMPUTE_F32 and GS_HEAD_GAUSSIAN_TANH", who);
     if (!q_next_current(h)) return fail(h, GS_E_STATE, "%s: GS_REFRESH_TD_POLICY replaces rows of gs_rollout_evaluate_q_next, which has not run on the last rollout", who);
     if (qn.mask != cfg->bootstrap_mask)
@@ -144,19 +96,18 @@ int gs_learner_refresh(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t
   }
   const unsigned row_blocks = (unsigned)((n + 255) / 256);
   if (g_pol) {
-    // (the cap on a kernel's dynamic LDS is a setting of the FUNCTION: always the most, policy.h GS_POL_LDS_MAX)
-    HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_policy_rows_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-    HIPCHK(h, hipFuncSetAttribute((const void*)gs_k_q_mlp_rows_f32, hipFuncAttributeMaxDynamicSharedMemorySize, GS_VAL_LDS_MAX));
-    if ((rc = launch_policy(h, *cfg, r.next, n, nullptr, r.tb, GS_QN_ROLLOUT_TAG, r.pre, r.nact, r.neps, r.nlp))) return rc;
-    if (terms && (rc = launch_policy(h, *cfg, r.tobs, n, r.count, r.t_tb, GS_QN_TERMINAL_TAG, r.t_pre, r.t_nact, r.t_neps, r.t_nlp))) return rc;
+    if ((rc = rows_kernels_lds_cap(h))) return rc;
+    const PolicyNoise noise{cfg->stochastic, cfg->draw, cfg->seed};
+    if ((rc = launch_policy_rows(h, noise, r.next, n, nullptr, r.tb, GS_QN_ROLLOUT_TAG, r.pre, r.nact, r.neps, r.nlp))) return rc;
+    if (terms && (rc = launch_policy_rows(h, noise, r.tobs, n, r.count, r.t_tb, GS_QN_TERMINAL_TAG, r.t_pre, r.t_nact, r.t_neps, r.t_nlp))) return rc;
     GsRefreshTdPolicyArgs G{};
     for (int w = 0; w < 2; ++w) {
       const gs_handle::QNet& Q = h->qnet[w];
       if (!Q.net.set) continue;
-      if ((rc = launch_q(h, Q, Q.TL, r.next, r.nact, n, nullptr, r.q + (size_t)w * n))) return rc;
+      if ((rc = launch_q_rows(h, Q, Q.TL, r.next, r.nact, n, nullptr, r.q + (size_t)w * n))) return rc;
       G.s_q[w] = r.q + (size_t)w * n; G.q[w] = qn.q + (size_t)w * cap;
       if (terms) {
-        if ((rc = launch_q(h, Q, Q.TL, r.tobs, r.t_nact, n, r.count, r.t_q + (size_t)w * n))) return rc;
+        if ((rc = launch_q_rows(h, Q, Q.TL, r.tobs, r.t_nact, n, r.count, r.t_q + (size_t)w * n))) return rc;
         G.st_q[w] = r.t_q + (size_t)w * n; G.t_q[w] = qn.t_q + (size_t)w * tc;
       }
     }
@@ -177,7 +128,7 @@ int gs_learner_refresh(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t
     for (int w = 0; w < 2; ++w) {
       const gs_handle::QNet& Q = h->qnet[w];
       if (!Q.net.set) continue;
-      if (int rc2 = launch_q(h, Q, src ? Q.TL : Q.qargs.L, r.own, r.act, n, nullptr, r.q + (size_t)w * n)) return rc2;
+      if (int rc2 = launch_q_rows(h, Q, src ? Q.TL : Q.qargs.L, r.own, r.act, n, nullptr, r.q + (size_t)w * n)) return rc2;
       C.s_q[w] = r.q + (size_t)w * n; C.q[w] = qt.q + (size_t)(2 * src + w) * cap;
     }
     C.idx = idx; C.values = values; C.q_min = qt.q_min + (size_t)src * cap; C.q_adv = qt.q_adv; C.N = N; C.n = n;
@@ -187,14 +138,14 @@ int gs_learner_refresh(gs_handle* h, const gs_onpolicy_batch_out* batch, int32_t
   };
   if (g_tgt && (rc = twins_on_own(1, nullptr))) return rc;
   if (g_tdv) {
-    if ((rc = launch_v(h, r.next, n, nullptr, r.v))) return rc;
-    if (terms && (rc = launch_v(h, r.tobs, n, r.count, r.t_v))) return rc;
+    if ((rc = launch_value_rows(h, val, r.next, r.v, n))) return rc;
+    if (terms && (rc = launch_value_rows(h, val, r.tobs, r.t_v, n, r.count))) return rc;
     GsRefreshTdValueArgs G{idx, terms ? r.pos.p : nullptr, r.v, r.t_v, ro.rew, ro.done, qt.td, N, n, 0, cfg->gamma, cfg->reward_shift, cfg->reward_scale};
     hipLaunchKernelGGL(gs_k_refresh_td_value, dim3(row_blocks), dim3(256), 0, h->stream, G);
     HIPCHK(h, hipGetLastError());
   }
   if (g_adv) {
-    if ((rc = launch_v(h, r.own, n, nullptr, r.v))) return rc;
+    if ((rc = launch_value_rows(h, val, r.own, r.v, n))) return rc;
     if ((rc = twins_on_own(0, r.v))) return rc;
   }
   return publish(h, h->stream, r.ev, consumer_stream);

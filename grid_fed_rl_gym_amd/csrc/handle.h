@@ -429,7 +429,8 @@ static inline bool critic_current(const gs_handle* h, const gs_handle::Critic& c
 // queues the copies of c's arrays over the last rollout to these host pointers (NULL: not wanted)
 int critic_download(gs_handle* h, const gs_handle::Critic& c, double* values, double* term_values, double* adv, double* ret);
 
-// ---- what the two scalar-output networks share on the host (abi_onpolicy.hip): gs_k_value_mlp_f32 (value_install) and gs_k_q_mlp_f32 (gs_q_mlp_set) ----
+// ---- what the scalar-output networks share on the host (scalar_net.hip): gs_k_value_mlp_f32 (value_install) and gs_k_q_mlp_f32 (gs_q_mlp_set),
+// and the one launch of every kernel that runs a network over rows ----
 // a packed network and where its parts lie on the device
 struct ScalarNet { GsPolicyImageF32 im; const float* image = nullptr; const double* norm = nullptr; };
 // packs `p` with `o` (both checked by the caller), sizes the LDS of `kernel` and uploads the image into val.blob; also val.lds,
@@ -447,6 +448,22 @@ static inline void scalar_net_args(Args& a, const gs_policy_mlp& p, const Scalar
 // the workgroups of a launch of GS_VAL_ROWS rows each over `rows` > 0 rows; refuses a count the kernels' 32-bit row index cannot
 // hold (`kernel`: "value" / "Q", for the message)
 int scalar_net_grid(gs_handle* h, long long rows, const char* kernel, unsigned* blocks);
+// The launches below are queued on the handle's main stream over `rows` rows (device pointers); rows_dev: NULL, or the device word
+// holding how many of them are there.
+// the value network `val` on obs; rows <= 0: nothing; scatter_*: GsValueArgs
+int launch_value_rows(gs_handle* h, const gs_handle::Value& val, const double* obs, double* out, long long rows, const int32_t* rows_dev = nullptr,
+                      const int32_t* scatter_idx = nullptr, double* scatter_out = nullptr, int scatter_T = 0);
+// twin `Q` under the layer table `L` (its online image Q.qargs.L or its target image Q.TL) on (obs, act)
+int launch_q_rows(gs_handle* h, const gs_handle::QNet& Q, const GsPolicyLayerF32* L, const double* obs, const double* act, long long rows, const int32_t* rows_dev,
+                  double* out);
+// the installed policy (policy_rows_ready) on obs with noise indices idx[row] = (t, b), NULL: the row; `noise`: the caller's config
+struct PolicyNoise { int32_t stochastic; uint32_t draw; uint64_t seed; };
+int launch_policy_rows(gs_handle* h, const PolicyNoise& noise, const double* obs, long long rows, const int32_t* rows_dev, const int32_t* idx, uint32_t tag,
+                       float* pre, double* act, double* eps, double* lp);
+// the most dynamic LDS for gs_k_policy_rows_f32 and gs_k_q_mlp_rows_f32, which no install sizes: before an entry's first launch of them
+int rows_kernels_lds_cap(gs_handle* h);
+// gs_k_policy_rows_f32 can run: a float32 tanh-Gaussian policy is installed
+static inline bool policy_rows_ready(const gs_handle* h) { return h->pol.set && h->pol.compute == GS_COMPUTE_F32 && h->pol.args32.head == GS_HEAD_GAUSSIAN_TANH; }
 
 // ---- owner of the rollout's constraint arrays (abi_costs.hip) ----
 void costs_release(gs_handle* h);

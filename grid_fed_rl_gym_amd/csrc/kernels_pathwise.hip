@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "block_reduce.h"
+#include "bootstrap.h"
 #include "env_device.h"
 #include "gw_math.h"
 #include "pathwise.h"
@@ -137,7 +138,7 @@ gs_k_pw_head(GsPwHeadArgs H) {
   const double* stored = nullptr;
   if (with_bc) {
     long long j = H.idx[i];
-    j = j < 0 ? 0 : (j >= H.N ? H.N - 1 : j);  // (an index the minibatch did not write cannot leave the rollout)
+    j = GS_RF_CLAMP(j, H.N);                 // (gb_row's rule, as text: called, H.N is read ahead of the test and this kernel's code changes)
     stored = H.act + (size_t)j * A;
   }
   double bc = 0.0;

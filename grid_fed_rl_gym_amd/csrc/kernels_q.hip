@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "bootstrap.h"
 #include "mlp_f32.h"
 #include "q.h"
 
@@ -96,9 +97,7 @@ gs_k_q_combine(GsQCombineArgs C) {
   double m[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const double* a = C.q[s][0];
-    const double* b = C.q[s][1];
-    m[s] = a && b ? fmin(a[i], b[i]) : a ? a[i] : b[i];
+    m[s] = gb_twin_min(C.q[s][0], C.q[s][1], (size_t)i);
     C.q_min[s][i] = m[s];
   }
   C.q_adv[i] = m[0] - C.values[i];
@@ -122,8 +121,7 @@ gs_k_q_td(GsQTdArgs G) {
     if (!(G.done[i] & G.mask)) return;       // (phase 0 wrote this transition's target)
     vnext = G.term_values[e];
   }
-  const double r = (G.rew[i] - G.reward_shift) * G.reward_scale;
-  G.td[i] = r + G.gamma * vnext;
+  G.td[i] = gb_td(G.rew[i], G.reward_shift, G.reward_scale, G.gamma, vnext);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -132,8 +130,7 @@ gs_k_q_gather(GsQGatherArgs G) {
   const int W = G.DA > 0 ? G.DA : 1;
   if (e >= (long long)G.n * W) return;
   const int i = (int)(e / W), k = (int)(e - (long long)i * W);
-  long long j = G.idx[i];
-  j = j < 0 ? 0 : (j >= G.N ? G.N - 1 : j);  // (an index the minibatch did not write cannot leave the rollout)
+  const long long j = gb_row(G.idx[i], G.N);
   if (k == 0) G.y[i] = (float)G.src[j];
   if (G.DA > 0) G.sa[e] = k < G.D ? G.obs[(size_t)i * G.D + k] : (float)G.act[(size_t)j * (G.DA - G.D) + (k - G.D)];
 }

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "bootstrap.h"
 #include "env_device.h"
 #include "gw_math.h"
 #include "mlp_f32.h"
@@ -124,21 +125,20 @@ gs_k_q_next_td(GsQNextTdArgs G) {
   if (G.phase == 0) {
     if (e >= (long long)G.T * G.B) return;
     i = (size_t)e;
-    const double m = G.q[0] && G.q[1] ? fmin(G.q[0][i], G.q[1][i]) : G.q[0] ? G.q[0][i] : G.q[1][i];
+    const double m = gb_twin_min(G.q[0], G.q[1], i);
     G.q_min[i] = m;
-    const double v = m - G.alpha * G.lp[i];
+    const double v = gb_soft_value(m, G.alpha, G.lp[i]);
     vnext = G.done[i] ? 0.0 : v;
   } else {
     if (e >= min(*G.term_count, G.term_cap)) return;
-    const double m = G.term_q[0] && G.term_q[1] ? fmin(G.term_q[0][e], G.term_q[1][e]) : G.term_q[0] ? G.term_q[0][e] : G.term_q[1][e];
+    const double m = gb_twin_min(G.term_q[0], G.term_q[1], (size_t)e);
     G.term_q_min[e] = m;
-    vnext = m - G.alpha * G.term_lp[e];
+    vnext = gb_soft_value(m, G.alpha, G.term_lp[e]);
     G.term_value[e] = vnext;
     const int t = G.term_idx[2 * e], b = G.term_idx[2 * e + 1];
     if ((unsigned)t >= (unsigned)G.T || (unsigned)b >= (unsigned)G.B) return;
     i = (size_t)t * G.B + b;
     if (!(G.done[i] & G.mask)) return;       // (phase 0 wrote this transition's target)
   }
-  const double r = (G.rew[i] - G.reward_shift) * G.reward_scale;
-  G.td[i] = r + G.gamma * vnext;
+  G.td[i] = gb_td(G.rew[i], G.reward_shift, G.reward_scale, G.gamma, vnext);
 }

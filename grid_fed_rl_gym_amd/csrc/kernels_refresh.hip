@@ -5,12 +5,14 @@
 //   gs_k_refresh_td_policy   gs_k_q_next_td's arithmetic on the refreshed rows, scattered to their transitions and terminal entries
 //   gs_k_refresh_td_value    gs_k_q_td's
 //   gs_k_refresh_combine     gs_k_q_combine's, one source at a time
+// "The arithmetic of" is a fact of the code: those kernels and these call the same functions of bootstrap.h.
 // The networks between the gather and the scatter are the existing kernels (gs_k_policy_rows_f32, gs_k_q_mlp_f32 / _rows_f32,
 // gs_k_value_mlp_f32) over the gathered blocks.  One thread per element or batch row; where include/gridstep.h states a formula
 // nothing is contracted.  Duplicate indices in a batch compute the same bits from the same inputs, so their colliding stores are benign.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "bootstrap.h"
 #include "refresh.h"
 
 extern "C" __global__ void __launch_bounds__(GS_RF_TERM_THREADS)
@@ -23,7 +25,7 @@ gs_k_refresh_terms(GsRefreshTermsArgs G) {
     const int i = base + tid;
     int e = -1;
     if (i < G.n) {
-      const long long j = GS_RF_CLAMP((long long)G.idx[i], G.N);
+      const long long j = gb_row(G.idx[i], G.N);
       if (G.done[j] & G.mask) e = G.map[j];
     }
     const unsigned long long ballot = __ballot(e >= 0);
@@ -56,7 +58,7 @@ gs_k_refresh_rows(GsRefreshRowsArgs G) {
   const long long x = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= (long long)G.n * G.W) return;
   const int i = (int)(x / G.W), c = (int)(x - (long long)i * G.W);
-  const long long j = GS_RF_CLAMP((long long)G.idx[i], G.N);
+  const long long j = gb_row(G.idx[i], G.N);
   if (c < G.D) {
     if (G.own) G.own[(size_t)i * G.D + c] = G.obs_seq[(size_t)j * G.D + c];
     if (G.next) G.next[(size_t)i * G.D + c] = G.obs_seq[(size_t)(j + G.B) * G.D + c];
@@ -71,7 +73,7 @@ gs_k_refresh_td_policy(GsRefreshTdPolicyArgs G) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= G.n) return;
-  const size_t j = (size_t)GS_RF_CLAMP((long long)G.idx[i], G.N);
+  const size_t j = (size_t)gb_row(G.idx[i], G.N);
   const int A = G.A;
   for (int c = 0; c < 2 * A; ++c) G.pre[j * (2 * A) + c] = G.s_pre[(size_t)i * (2 * A) + c];
   for (int c = 0; c < A; ++c) {
@@ -82,9 +84,9 @@ gs_k_refresh_td_policy(GsRefreshTdPolicyArgs G) {
   G.lp[j] = lp;
   if (G.s_q[0]) G.q[0][j] = G.s_q[0][i];
   if (G.s_q[1]) G.q[1][j] = G.s_q[1][i];
-  const double m = G.s_q[0] && G.s_q[1] ? fmin(G.s_q[0][i], G.s_q[1][i]) : G.s_q[0] ? G.s_q[0][i] : G.s_q[1][i];
+  const double m = gb_twin_min(G.s_q[0], G.s_q[1], (size_t)i);
   G.q_min[j] = m;
-  const double v = m - G.alpha * lp;
+  const double v = gb_soft_value(m, G.alpha, lp);
   double vnext = G.done[j] ? 0.0 : v;
   const int k = G.pos ? G.pos[i] : -1;
   if (k >= 0) {
@@ -98,13 +100,12 @@ gs_k_refresh_td_policy(GsRefreshTdPolicyArgs G) {
     G.t_lp[e] = tlp;
     if (G.st_q[0]) G.t_q[0][e] = G.st_q[0][k];
     if (G.st_q[1]) G.t_q[1][e] = G.st_q[1][k];
-    const double tm = G.st_q[0] && G.st_q[1] ? fmin(G.st_q[0][k], G.st_q[1][k]) : G.st_q[0] ? G.st_q[0][k] : G.st_q[1][k];
+    const double tm = gb_twin_min(G.st_q[0], G.st_q[1], (size_t)k);
     G.t_q_min[e] = tm;
-    vnext = tm - G.alpha * tlp;
+    vnext = gb_soft_value(tm, G.alpha, tlp);
     G.t_value[e] = vnext;
   }
-  const double r = (G.rew[j] - G.reward_shift) * G.reward_scale;
-  G.td[j] = r + G.gamma * vnext;
+  G.td[j] = gb_td(G.rew[j], G.reward_shift, G.reward_scale, G.gamma, vnext);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -112,14 +113,13 @@ gs_k_refresh_td_value(GsRefreshTdValueArgs G) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= G.n) return;
-  const size_t j = (size_t)GS_RF_CLAMP((long long)G.idx[i], G.N);
+  const size_t j = (size_t)gb_row(G.idx[i], G.N);
   double vnext = G.vn[i];
   if (G.done[j]) {
     const int k = G.pos ? G.pos[i] : -1;
     vnext = k >= 0 ? G.tv[k] : 0.0;
   }
-  const double r = (G.rew[j] - G.reward_shift) * G.reward_scale;
-  G.td[j] = r + G.gamma * vnext;
+  G.td[j] = gb_td(G.rew[j], G.reward_shift, G.reward_scale, G.gamma, vnext);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -127,12 +127,10 @@ gs_k_refresh_combine(GsRefreshCombineArgs C) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= C.n) return;
-  const size_t j = (size_t)GS_RF_CLAMP((long long)C.idx[i], C.N);
-  const double* a = C.s_q[0];
-  const double* b = C.s_q[1];
-  if (a) C.q[0][j] = a[i];
-  if (b) C.q[1][j] = b[i];
-  const double m = a && b ? fmin(a[i], b[i]) : a ? a[i] : b[i];
+  const size_t j = (size_t)gb_row(C.idx[i], C.N);
+  if (C.s_q[0]) C.q[0][j] = C.s_q[0][i];
+  if (C.s_q[1]) C.q[1][j] = C.s_q[1][i];
+  const double m = gb_twin_min(C.s_q[0], C.s_q[1], (size_t)i);
   C.q_min[j] = m;
   if (C.values) C.q_adv[j] = m - C.values[i];
 }

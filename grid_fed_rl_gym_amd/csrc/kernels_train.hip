@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "block_reduce.h"
+#include "bootstrap.h"
 #include "mlp_f32.h"
 #include "train.h"
 
@@ -130,8 +131,7 @@ gs_k_train_head(GsTrainHeadArgs H) {
     return;
   }
   const int A = H.A;
-  long long j = H.idx[i];
-  j = j < 0 ? 0 : (j >= H.N ? H.N - 1 : j);  // (an index the minibatch did not write cannot leave the rollout)
+  const long long j = gb_row(H.idx[i], H.N);
   const double* act = H.act + (size_t)j * A;
   const double lp_old = H.logp[j], adv = (double)H.adv[i];
   const double lim = 1.0 - 1e-7;
@@ -325,8 +325,7 @@ gs_k_train_stats(GsTrainStatArgs S) {
     t0 = t0 + S.term0[k];
     if (S.policy) {
       t1 = t1 + S.term1[k];
-      long long j = S.idx[k];
-      j = j < 0 ? 0 : (j >= S.N ? S.N - 1 : j);
+      const long long j = gb_row(S.idx[k], S.N);
       kl = kl + (S.logp[j] - S.lp_new[k]);
       nc += S.clipped[k];
     }

@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "block_reduce.h"
+#include "bootstrap.h"
 #include "train.h"
 
 // ---- the advantage-weighted head: L = -(1/n) sum w_i lp_i - ent_coef (1/n) sum h_i -------------------------------------------------
@@ -22,8 +23,7 @@ gs_k_train_head_awr(GsTrainAwrHeadArgs H) {
   float* g = H.ghead + (size_t)i * H.row_stride;
   const double inv_n = 1.0 / (double)H.n;
   const int A = H.A;
-  long long j = H.idx[i];
-  j = j < 0 ? 0 : (j >= H.N ? H.N - 1 : j);  // (an index the minibatch did not write cannot leave the rollout)
+  const long long j = gb_row(H.idx[i], H.N);
   const double* act = H.act + (size_t)j * A;
   const double adv = (double)H.adv[i];
   const double lim = 1.0 - 1e-7;
@@ -89,8 +89,7 @@ gs_k_train_stats_awr(GsTrainAwrStatArgs S) {
     t0 = t0 + S.term0[k];
     t1 = t1 + S.term1[k];
     if (have_old) {
-      long long j = S.idx[k];
-      j = j < 0 ? 0 : (j >= S.N ? S.N - 1 : j);
+      const long long j = gb_row(S.idx[k], S.N);
       kl = kl + (S.logp[j] - S.lp_new[k]);
     }
     nc += S.capped[k];

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "bootstrap.h"
 #include "mlp_f32.h"
 #include "policy.h"
 
@@ -62,8 +63,7 @@ gs_k_gae(GsGaeArgs G) {
     const bool done = flag != 0;
     const double v = G.values[i];
     const double vnext = done ? ((flag & G.mask) ? G.ret[i] : 0.0) : G.values[i + G.B];
-    const double r = (G.rew[i] - G.reward_shift) * G.reward_scale;
-    const double delta = (r + G.gamma * vnext) - v;
+    const double delta = gb_td(G.rew[i], G.reward_shift, G.reward_scale, G.gamma, vnext) - v;
     const double adv = done ? delta : delta + gl * adv_next;
     G.adv[i] = adv;
     G.ret[i] = adv + v;

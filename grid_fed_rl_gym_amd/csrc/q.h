@@ -19,7 +19,7 @@ struct GsQArgs {
   GsPolicyLayerF32 L[GS_POLICY_MAX_LAYERS];
 };
 
-// gs_k_q_combine: q_min[src] = fmin over the installed twins (a missing twin: NULL), q_adv = q_min[online] - values
+// gs_k_q_combine: q_min[src] = gb_twin_min (bootstrap.h) over the installed twins (a missing twin: NULL), q_adv = q_min[online] - values
 struct GsQCombineArgs {
   const double* q[2][2];      // [src][which], [n] each
   const double* values;       // [n] (the first T rows of values[T + 1][B])
@@ -28,7 +28,7 @@ struct GsQCombineArgs {
   long long n;
 };
 
-// gs_k_q_td: td[t][b] = r' + gamma * vnext, the r' and vnext of gs_k_gae.  phase 0: one thread per transition, every finished one
+// gs_k_q_td: td[t][b] = gb_td (bootstrap.h) of the r' and vnext of gs_k_gae.  phase 0: one thread per transition, every finished one
 // takes vnext = 0; phase 1: one thread per entry of the terminal list (launched over its capacity, the count read on the device),
 // which gives a transition whose flag meets the mask the value of its terminal observation
 struct GsQTdArgs {
@@ -42,7 +42,7 @@ struct GsQTdArgs {
   double gamma, reward_shift, reward_scale;
 };
 
-// gs_k_q_gather: per sample i with transition j = idx[i] clamped into the rollout: y[i] = (float)src[j]; with DA > 0 also the
+// gs_k_q_gather: per sample i with transition j = gb_row(idx[i], N) (bootstrap.h): y[i] = (float)src[j]; with DA > 0 also the
 // learner's input row sa[i] = obs[i][0 .. D) | (float)act[j][0 .. DA - D)
 struct GsQGatherArgs {
   const int32_t* idx;         // [n]

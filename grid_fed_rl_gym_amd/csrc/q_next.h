@@ -36,12 +36,12 @@ struct GsPolicyRowsArgs {
   GsPolicyLayerF32 L[GS_POLICY_MAX_LAYERS];
 };
 
-// gs_k_q_next_td, `fp contract(off)`, one thread per element.  phase 0, per transition i = t B + b:
-//   q_next_min[i] = fmin(q0[i], q1[i])  (one twin: that twin);  v = q_next_min[i] - alpha * lp[i]  (a rounded product, a rounded
-//   difference);  td[i] = r' + gamma * (done[i] ? 0 : v),  r' = (rew[i] - shift) * scale: a rounded product, then a rounded sum.
+// gs_k_q_next_td, one thread per element, by the functions of bootstrap.h.  phase 0, per transition i = t B + b:
+//   q_next_min[i] = gb_twin_min at i;  v = gb_soft_value(q_next_min[i], alpha, lp[i]);  td[i] = gb_td(rew[i], shift, scale, gamma,
+//   done[i] ? 0 : v).
 // phase 1, per entry e of the terminal list (launched over its capacity, the count read on the device): term_q_min[e] and
-// term_value[e] = term_q_min[e] - alpha * term_lp[e] the same way; where done[i] & mask for the entry's (t, b): td[i] = r' + gamma *
-// term_value[e].
+// term_value[e] = gb_soft_value(term_q_min[e], alpha, term_lp[e]) the same way; where done[i] & mask for the entry's (t, b): td[i] =
+// gb_td(.., term_value[e]).
 struct GsQNextTdArgs {
   const double* q[2];         // [T][B] each; NULL: that twin is not installed
   const double* lp;           // [T][B]

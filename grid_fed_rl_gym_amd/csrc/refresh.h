@@ -9,7 +9,8 @@
 
 #include "../../include/gridstep.h"
 
-// batch row i -> transition j = idx[i] clamped into [0, N) (gs_k_q_gather's rule): every kernel below forms j this way
+// batch row i -> transition j = idx[i] clamped into [0, N): the ONE statement of the rule, as text a host program can run
+// (tests/native/refresh_check_host.cpp does).  The kernels form j through gb_row of bootstrap.h, which is this macro as a function.
 #define GS_RF_CLAMP(j, N) ((j) < 0 ? 0 : ((j) >= (N) ? (N) - 1 : (j)))
 
 // gs_k_refresh_terms, ONE workgroup of GS_RF_TERM_THREADS threads, no atomics: the batch rows whose transition ended an episode under
@@ -48,11 +49,11 @@ struct GsRefreshRowsArgs {
   int32_t n, B, D, A, W, reserved;
 };
 
-// gs_k_refresh_td_policy, `fp contract(off)`, one thread per batch row i: the arithmetic of gs_k_q_next_td on the scratch results,
-// scattered to transition j and, where pos[i] = k >= 0, to terminal entry e = ie[k][1].
-//   m = fmin(q0[i], q1[i]) (one twin: that twin);  q_min[j] = m;  v = m - alpha * lp[i];  vnext = done[j] ? 0 : v
-//   k >= 0:  tm = fmin over term_q[.][k];  term_q_min[e] = tm;  vnext = tm - alpha * term_lp[k];  term_value[e] = vnext
-//   td[j] = (rew[j] - shift) * scale + gamma * vnext
+// gs_k_refresh_td_policy, one thread per batch row i: gs_k_q_next_td's functions of bootstrap.h on the scratch results, scattered to
+// transition j and, where pos[i] = k >= 0, to terminal entry e = ie[k][1].
+//   q_min[j] = m = gb_twin_min at i;  vnext = done[j] ? 0 : gb_soft_value(m, alpha, lp[i])
+//   k >= 0:  term_q_min[e] = tm = gb_twin_min at k;  term_value[e] = vnext = gb_soft_value(tm, alpha, term_lp[k])
+//   td[j] = gb_td(rew[j], shift, scale, gamma, vnext)
 // and the rows' pre_head / act / noise / lp / q (the terminal block's to e) are copied to their places.
 struct GsRefreshTdPolicyArgs {
   const int32_t* idx; const int32_t* pos; const int32_t* ie;      // [n], [n] or NULL, [n][2]
@@ -66,8 +67,8 @@ struct GsRefreshTdPolicyArgs {
   double gamma, alpha, reward_shift, reward_scale;
 };
 
-// gs_k_refresh_td_value, `fp contract(off)`, one thread per batch row: gs_k_q_td's rule on the refreshed values.
-//   vnext = done[j] ? (pos[i] = k >= 0 ? tv[k] : 0) : vn[i];   td[j] = (rew[j] - shift) * scale + gamma * vnext
+// gs_k_refresh_td_value, one thread per batch row: gs_k_q_td's gb_td on the refreshed values.
+//   vnext = done[j] ? (pos[i] = k >= 0 ? tv[k] : 0) : vn[i];   td[j] = gb_td(rew[j], shift, scale, gamma, vnext)
 struct GsRefreshTdValueArgs {
   const int32_t* idx; const int32_t* pos;      // pos: NULL under mask 0
   const double* vn;           // [n] V(next state of j)
@@ -79,8 +80,8 @@ struct GsRefreshTdValueArgs {
   double gamma, reward_shift, reward_scale;
 };
 
-// gs_k_refresh_combine, `fp contract(off)`, one thread per batch row: gs_k_q_combine's rule for ONE source.  q[w][j] = s_q[w][i];
-// q_min[j] = fmin over the installed twins; with `values` (the online source): q_adv[j] = q_min[j] - values[i].
+// gs_k_refresh_combine, one thread per batch row: gs_k_q_combine's gb_twin_min for ONE source.  q[w][j] = s_q[w][i];
+// q_min[j] = gb_twin_min at i; with `values` (the online source): q_adv[j] = q_min[j] - values[i].
 struct GsRefreshCombineArgs {
   const int32_t* idx;
   const double* s_q[2];       // [n] each; NULL: that twin is not installed
