@@ -78,6 +78,16 @@ class gs_rollout_device(C.Structure):
                 ("n_terminal", C.c_int32), ("reserved", C.c_int32), ("terminal_index", C.c_void_p), ("terminal_obs", C.c_void_p)]
 
 
+class gs_rollout_source(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("dtype", C.c_int32), ("T", C.c_int32), ("chunk_rows", C.c_int32), ("flags", C.c_uint32),
+                ("observations", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("next_observations", C.c_void_p),
+                ("terminals", _up), ("final_observation", C.c_void_p), ("log_probs", C.c_void_p)]
+
+
+class gs_rollout_load_info(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_terminal", C.c_int32), ("term_cap_needed", C.c_int32)]
+
+
 POLICY = {"uploaded": 0, "random": 1, "mlp": 2}
 ACTIVATION = {"relu": 0, "tanh": 1, "elu": 2}
 HEAD = {"tanh": 0, "gaussian_tanh": 1}
@@ -552,6 +562,8 @@ SYMBOLS = [
     ("gs_rollout", C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, _dp]),
     ("gs_rollout_download", C.c_int, [_H, C.POINTER(gs_rollout_view)]),
     ("gs_rollout_device_view", C.c_int, [_H, C.POINTER(gs_rollout_device)]),
+    ("gs_rollout_load_check", C.c_int, [C.POINTER(gs_rollout_source), C.c_int32, C.c_int32, C.c_int32, C.POINTER(gs_rollout_load_info)]),
+    ("gs_rollout_load", C.c_int, [_H, C.POINTER(gs_rollout_source)]),
     ("gs_dataset_build", C.c_int, [_H, C.c_uint32]),
     ("gs_dataset_stats", C.c_int, [_H, C.POINTER(gs_dataset_stats_view)]),
     ("gs_dataset_set_stats", C.c_int, [_H, C.POINTER(gs_dataset_stats_view)]),
@@ -693,6 +705,56 @@ def _i32(a) -> np.ndarray:
 
 def _ptr(a: Optional[np.ndarray], typ):
     return None if a is None else a.ctypes.data_as(typ)
+
+
+def rollout_source(B: int, obs_dim: int, action_dim: int, observations, actions, rewards, next_observations, terminals,
+                   final_observation=None, log_probs=None, chunk_rows: int = 0):
+    """(gs_rollout_source, the arrays it points into) for ``Handle.rollout_load`` and ``rollout_load_check``: shapes checked against
+    ``[T, B, ...]``, one floating dtype (float64 or float32) for all, nothing copied that is C-contiguous already."""
+    obs = np.asarray(observations)
+    if obs.dtype not in (np.float64, np.float32):
+        raise PowerFlowError(f"rollout_load: observations are {obs.dtype}; float64 or float32 (convert other types yourself: the loader does not guess)")
+    if obs.ndim != 3 or obs.shape[1:] != (B, obs_dim) or obs.shape[0] < 1:
+        raise PowerFlowError(f"rollout_load: observations shape {obs.shape} != (T, {B}, {obs_dim})")
+    T = int(obs.shape[0])
+    want = dict(observations=(obs, (T, B, obs_dim)), next_observations=(next_observations, (T, B, obs_dim)), rewards=(rewards, (T, B)),
+                actions=(actions, (T, B, action_dim)), final_observation=(final_observation, (B, obs_dim)), log_probs=(log_probs, (T, B)))
+    keep = {}
+    for k, (a, shape) in want.items():
+        if a is None:
+            if k in ("final_observation", "log_probs") or (k == "actions" and action_dim == 0):
+                continue
+            raise PowerFlowError(f"rollout_load: {k} is None")
+        a = np.asarray(a)
+        if a.dtype != obs.dtype:
+            raise PowerFlowError(f"rollout_load: {k} is {a.dtype}, observations are {obs.dtype}: the floating arrays share one dtype, float64 or float32")
+        if a.shape != shape:
+            raise PowerFlowError(f"rollout_load: {k} shape {a.shape} != {shape}")
+        keep[k] = np.ascontiguousarray(a)
+    term = np.asarray(terminals)
+    if term.dtype == np.bool_:
+        term = term.astype(np.uint8)          # (True: bit 0, terminated)
+    if term.dtype != np.uint8:
+        raise PowerFlowError(f"rollout_load: terminals are {term.dtype}; uint8 flags (bit 0 terminated, bit 1 truncated) or bool")
+    if term.shape != (T, B):
+        raise PowerFlowError(f"rollout_load: terminals shape {term.shape} != ({T}, {B})")
+    keep["terminals"] = np.ascontiguousarray(term)
+    vp = lambda k: None if k not in keep else keep[k].ctypes.data_as(C.c_void_p)
+    src = gs_rollout_source(C.sizeof(gs_rollout_source), COMPUTE["float64" if obs.dtype == np.float64 else "float32"], T, int(chunk_rows), 0,
+                            vp("observations"), vp("actions"), vp("rewards"), vp("next_observations"), _ptr(keep["terminals"], _up),
+                            vp("final_observation"), vp("log_probs"))
+    return src, keep
+
+
+def rollout_load_check(src: gs_rollout_source, B: int, obs_dim: int, action_dim: int) -> dict:
+    """gs_rollout_load_check: the host checks of ``gs_rollout_load`` without a handle or a device; ``n``, ``n_terminal`` and
+    ``term_cap_needed`` of a source that passes, PowerFlowError with the library's message otherwise."""
+    lib = load()
+    info = gs_rollout_load_info()
+    rc = lib.gs_rollout_load_check(None if src is None else C.byref(src), int(B), int(obs_dim), int(action_dim), C.byref(info))
+    if rc != GS_OK:
+        raise PowerFlowError(f"libgridstep error {rc}: {lib.gs_last_error(None).decode()}")
+    return dict(n=int(info.n), n_terminal=int(info.n_terminal), term_cap_needed=int(info.term_cap_needed))
 
 
 def make_config(**kw) -> gs_config:
@@ -1446,6 +1508,22 @@ class Handle:
         self._check(self._lib.gs_rollout_download(self._h, C.byref(v)))
         out["n_terminal"] = int(n.value)
         return out
+
+    def rollout_load(self, observations, actions, rewards, next_observations, terminals, final_observation=None, log_probs=None,
+                     chunk_rows: int = 0) -> None:
+        """gs_rollout_load: these host arrays become the handle's rollout, as if ``rollout`` had produced them (the inverse of
+        ``rollout_download``).  ``observations`` / ``next_observations`` [T, B, obs_dim], ``actions`` [T, B, action_dim], ``rewards``
+        [T, B], ``terminals`` [T, B] uint8 (bit 0 terminated, bit 1 truncated), optionally ``final_observation`` [B, obs_dim] (None:
+        ``next_observations[T - 1]``) and ``log_probs`` [T, B] (None: the rollout recorded none).  The floating arrays are all float64
+        or all float32 (widened once, exactly, on the device); C-contiguous arrays are not copied.  A live transition's next
+        observation must equal, by bits, the observation that follows it: GS_E_INVALID names the first that does not, and the handle
+        then holds no rollout.  The environment is not touched.  ``chunk_rows``: rows of ``next_observations`` per staging chunk (0: the
+        library's choice).  Returns when the arrays are on the device."""
+        src, keep = rollout_source(self.B, self.obs_dim, self.action_dim, observations, actions, rewards, next_observations, terminals,
+                                   final_observation, log_probs, chunk_rows)
+        self._check(self._lib.gs_rollout_load(self._h, C.byref(src)))
+        del keep
+        self._rollout_T = int(src.T)
 
     # -- on-policy rollouts: log-probabilities, the value network, advantages and returns (include/gridstep.h) -------------------
     def rollout_log_probs(self, on: bool = True) -> None:

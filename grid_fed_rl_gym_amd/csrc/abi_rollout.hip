@@ -148,25 +148,10 @@ int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* ac
 // Device layout (gs_rollout_device_view): obs_seq[T + 1][B][obs_dim] -- slot t is what step t started from, slot
 // t + 1 is written by step t's kernel itself (its observation output IS the next slot: no copy) --, act[T][B][A],
 // rew[T][B], done[T][B], and the side list of terminal observations (t, b, row) the in-place resets replaced.
-static int rollout_ensure(gs_handle* h, int T) {
+// the constant columns of every slot: the step kernels write only the columns that change
+static int fill_const_columns(gs_handle* h) {
   gs_handle::Rollout& ro = h->ro;
-  if (T <= ro.T_cap) return GS_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  rollout_release(h, true);
-  dataset_release(h, true);      // (its map and partial results are sized by T; installed statistics stay)
-  const size_t B = h->B, D = h->obs_dim, A = std::max(h->action_dim, 1);
-  // an instance finishes at most once per min(episode_length, 11) steps (truncation needs more than 10 violating steps
-  // since its last reset, grid_env.py:604) plus once for an episode that was already under way
-  const int min_ep = std::max(1, std::min(h->cfg.episode_length, 11));
-  const size_t cap = B * ((size_t)T / min_ep + 1);
-  int rc = ro.term_count.grow(h, 1, "the rollout's terminal counter");
-  if (rc) return rc;
-  // all or none; until gs_rollout sets ro.T again the handle holds no rollout (rollout_release)
-  if ((rc = alloc_all(h, "the rollout's buffers", ro.obs_seq.want((size_t)(T + 1) * B * D), ro.act.want((size_t)T * B * A), ro.rew.want((size_t)T * B),
-                      ro.done.want((size_t)T * B), ro.term_idx.want(cap * 2), ro.term_obs.want(cap * D)))) return rc;
-  ro.T_cap = T; ro.term_cap = (int)std::min<size_t>(cap, 0x7fffffff);
-  // the constant columns of every slot, once: the step kernels write only the columns that change
-  const long long rows = (long long)(T + 1) * B;
+  const long long rows = (long long)(ro.T_cap + 1) * h->B;
   const int w = h->obs_skip1 - h->obs_skip0;
   if (w > 0) {
     const long long total = rows * w;
@@ -174,8 +159,35 @@ static int rollout_ensure(gs_handle* h, int T) {
                        h->obs_dim, h->obs_skip0, h->obs_skip1, h->map_obs, h->d_cst);
     HIPCHK(h, hipGetLastError());
   }
+  ro.const_dirty = false;
   return GS_OK;
 }
+
+}  // extern "C"
+
+int gsi::rollout_ensure(gs_handle* h, int T, int min_term_cap) {
+  gs_handle::Rollout& ro = h->ro;
+  if (T <= ro.T_cap && min_term_cap <= ro.term_cap) return GS_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  T = std::max(T, ro.T_cap);       // (a load that only needs a longer list keeps the length the handle had)
+  rollout_release(h, true);
+  dataset_release(h, true);      // (its map and partial results are sized by T; installed statistics stay)
+  const size_t B = h->B, D = h->obs_dim, A = std::max(h->action_dim, 1);
+  // an instance finishes at most once per min(episode_length, 11) steps (truncation needs more than 10 violating steps
+  // since its last reset, grid_env.py:604) plus once for an episode that was already under way; a loaded dataset (gs_rollout_load)
+  // may end an episode at every transition and says how many it holds
+  const int min_ep = std::max(1, std::min(h->cfg.episode_length, 11));
+  const size_t cap = std::max(B * ((size_t)T / min_ep + 1), (size_t)std::max(min_term_cap, 0));
+  int rc = ro.term_count.grow(h, 1, "the rollout's terminal counter");
+  if (rc) return rc;
+  // all or none; until gs_rollout sets ro.T again the handle holds no rollout (rollout_release)
+  if ((rc = alloc_all(h, "the rollout's buffers", ro.obs_seq.want((size_t)(T + 1) * B * D), ro.act.want((size_t)T * B * A), ro.rew.want((size_t)T * B),
+                      ro.done.want((size_t)T * B), ro.term_idx.want(cap * 2), ro.term_obs.want(cap * D)))) return rc;
+  ro.T_cap = T; ro.term_cap = (int)std::min<size_t>(cap, 0x7fffffff);
+  return fill_const_columns(h);      // once: a rollout leaves them alone
+}
+
+extern "C" {
 
 int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, const double* actions) {
   if (!h || T <= 0) return fail(h, GS_E_INVALID, "handle is NULL or T <= 0");
@@ -187,6 +199,7 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   int rc = rollout_ensure(h, T);
   if (rc) return rc;
   gs_handle::Rollout& ro = h->ro;
+  if (ro.const_dirty && (rc = fill_const_columns(h))) return rc;      // (a loaded dataset's rows lay over them: gs_rollout_load)
   const size_t B = h->B, D = h->obs_dim, A = h->action_dim;
   // a stochastic policy's log-probabilities are recorded with its actions (on-policy rollouts, abi_onpolicy.hip)
   const bool stochastic = policy == GS_POLICY_MLP && (h->pol.compute == GS_COMPUTE_F32 ? h->pol.args32.stochastic : h->pol.args.stochastic);

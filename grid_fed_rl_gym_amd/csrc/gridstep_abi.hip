@@ -593,6 +593,7 @@ void gs_destroy(gs_handle* h) {
   q_release(h);
   rollout_release(h);
   dataset_release(h);
+  load_release(h);
   if (h->h_pin) (void)hipHostFree(h->h_pin);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

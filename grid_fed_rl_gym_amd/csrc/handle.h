@@ -124,7 +124,17 @@ struct gs_handle : GsPlan {
     // logp [T][B]: the log-probabilities of the last rollout's actions (recorded: by the last rollout); abi_onpolicy.hip
     bool record_logp = true, logp_recorded = false;
     DevBuf<double> logp; hipEvent_t ev_eval = nullptr;
+    // a load (abi_load.hip) overwrote whole rows of obs_seq: the next gs_rollout puts the constant columns back before it steps
+    bool const_dirty = false;
   } ro;
+  // gs_rollout_load (abi_load.hip): two page-locked staging buffers and their device chunks (`bytes` each, grown
+  // to the largest asked for), the stream the chunks are copied on, per buffer the events "copied" and "consumed", and the verdict
+  // (offending transitions, the first one's index).  Kept between loads, released with the handle.
+  struct GS_HIDDEN Loader {
+    char* pin[2] = {nullptr, nullptr}; DevBuf<char> dev[2]; size_t bytes = 0;
+    hipStream_t copy = nullptr; hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr}; bool busy[2] = {false, false};
+    DevBuf<int32_t> verdict;
+  } ld;
   // gs_dataset_*: the dataset over the last rollout (abi_dataset.hip).  built_on = ro.calls of the rollout the map (and, unless
   // the statistics were installed or kept, the statistics) was built on, 0 = none; stats = mean[Ct] then std[Ct] at stride Cs
   // (Ct = obs_dim + action_dim + 1, Cs = Ct rounded up to even) on the device; part = the chunks' partial results; idx / h_idx =
@@ -413,6 +423,11 @@ void policy_release(gs_handle* h);
 // the float32 image of an MLP as one allocation (image, then shift and scale) in `blob`; *image / *norm: where the two parts lie
 int upload_image_f32(gs_handle* h, DevBuf<char>& blob, const GsPolicyImageF32& im, const float** image, const double** norm);
 void rollout_release(gs_handle* h, bool keep_term_count = false);
+// buffers for a rollout of T steps whose terminal list holds at least min_term_cap entries (gs_rollout's own bound if that is more);
+// a handle that has them keeps them, otherwise everything sized by T_cap or term_cap goes (rollout_release) and is made again
+int rollout_ensure(gs_handle* h, int T, int min_term_cap = 0);
+// ---- owner of the loader's staging (abi_load.hip) ----
+void load_release(gs_handle* h);
 int rollout_finish(gs_handle* h);      // waits for the last rollout's number of finished episodes (ro.n_term); GS_E_STATE without one
 
 // ---- owner of the value networks and of the critics' arrays over the rollout (abi_onpolicy.hip) ----

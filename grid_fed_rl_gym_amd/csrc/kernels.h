@@ -13,6 +13,7 @@
 #include "pathwise.h"
 #include "conservative.h"
 #include "refresh.h"
+#include "rollout_load.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -101,6 +102,9 @@ __global__ void gs_k_refresh_rows(GsRefreshRowsArgs G);
 __global__ void gs_k_refresh_td_policy(GsRefreshTdPolicyArgs G);
 __global__ void gs_k_refresh_td_value(GsRefreshTdValueArgs G);
 __global__ void gs_k_refresh_combine(GsRefreshCombineArgs C);
+__global__ void gs_k_load_widen(const float* __restrict__ src, double* __restrict__ dst, long long n);
+__global__ void gs_k_load_next_f64(GsLoadNextArgs G);
+__global__ void gs_k_load_next_f32(GsLoadNextArgs G);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

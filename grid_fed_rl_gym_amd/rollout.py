@@ -27,6 +27,17 @@ episode that straddles rollouts is one episode; ``episodes_np`` restates the con
 ``OnPolicyBatches`` turns the evaluated rollout into EPOCHS of minibatches for a clipped-surrogate learner (``gs_onpolicy_*``; DESIGN.md
 section 18): a keyed permutation evaluated on the device, one gather per minibatch with the observations in the policy's
 normalisation and the (Lagrangian) advantage normalised; ``permutation_np`` and ``onpolicy_batch_np`` restate the contract.
+
+``load_rollout_data`` / ``load_rollout`` install a RECORDED dataset as the environment's rollout (``gs_rollout_load``; DESIGN.md
+section 29), the inverse of ``Handle.rollout_download``: everything above then runs on it unchanged.  The rules: the arrays are
+[T, B, ...] (or flat time-major), float64 or float32, one dtype for all; a finished transition's next observation goes to the
+terminal list, which is in ascending ``t * B + b`` order; a LIVE transition's next observation must equal, by bits (a NaN equals the
+same NaN), the observation one step later, or ``final_observation`` at the last step when one is given -- ``GS_E_INVALID`` names the
+number of offenders and the first one's (t, b), and the environment then holds no rollout; log-probabilities count as recorded only
+when given; everything computed over the previous rollout is stale; the environment itself is not touched and need not have been
+reset; the simulator's next rollout puts the constant observation columns back.  ``transitions_to_rollout`` /
+``rollout_to_transitions`` lay a flat recorded trajectory out in columns and back, marking its breaks as truncations;
+``concat_rollouts`` joins consecutive rollouts; ``save_rollout`` writes the arrays with ``np.savez``.
 """
 from __future__ import annotations
 
@@ -1077,3 +1088,161 @@ class OnPolicyBatches:
             raise PowerFlowError("OnPolicyBatches: prepare() first")
         for first, n in self.bounds():
             yield self.env.handle.onpolicy_batch(self.seed, e, first, n, out=out if n == self.minibatch else None, stream=stream)
+
+
+# ---- recorded datasets as the handle's rollout (include/gridstep.h "a recorded dataset as the handle's rollout") ----
+
+ROLLOUT_KEYS = ("observations", "actions", "rewards", "next_observations", "terminals")
+_BREAK_CHUNK = 1 << 14      # rows the by-bits comparisons look at at a time
+
+
+def _bits(x: np.ndarray) -> np.ndarray:
+    """the array's elements as unsigned integers of their width: equality by bits (a NaN equals the same NaN, 0.0 is not -0.0)"""
+    if x.dtype.itemsize not in (4, 8):
+        raise PowerFlowError(f"observations are {x.dtype}; float64 or float32")
+    return x.view(np.uint64 if x.dtype.itemsize == 8 else np.uint32)
+
+
+def _rows_differ(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """[rows] bool: row i of ``a`` differs from row i of ``b`` by bits ([rows, D] each, C-contiguous views), looked at ``_BREAK_CHUNK``
+    rows at a time so that no second copy of the observations is made"""
+    out = np.empty(len(a), dtype=bool)
+    for i in range(0, len(a), _BREAK_CHUNK):
+        x, y = np.ascontiguousarray(a[i:i + _BREAK_CHUNK]), np.ascontiguousarray(b[i:i + _BREAK_CHUNK])
+        out[i:i + _BREAK_CHUNK] = (_bits(x) != _bits(y)).any(axis=1)
+    return out
+
+
+def _flags(terminals) -> np.ndarray:
+    t = np.asarray(terminals)
+    return t.astype(np.uint8) if t.dtype == np.bool_ else t
+
+
+def _as_tb(data: dict, B: int) -> dict:
+    """``data`` as [T, B, ...] arrays: what ``Handle.rollout_download`` returns is passed through, the flat time-major dictionary of
+    ``collect_random_data`` (transition index = t * B + b) is reshaped, not copied"""
+    missing = [k for k in ROLLOUT_KEYS if k not in data]
+    if missing:
+        raise PowerFlowError(f"a rollout dictionary needs {missing}")
+    out = {k: np.asarray(data[k]) for k in ROLLOUT_KEYS + ("final_observation", "log_probs") if data.get(k) is not None}
+    if out["observations"].ndim == 2:
+        N = len(out["observations"])
+        if N % B:
+            raise PowerFlowError(f"{N} time-major transitions are no whole number of steps of {B} instances")
+        for k in ROLLOUT_KEYS + ("log_probs",):
+            if k in out:
+                out[k] = out[k].reshape((N // B, B) + out[k].shape[1:])
+    out["terminals"] = _flags(out["terminals"])
+    return out
+
+
+def load_rollout_data(env: BatchedGridEnvironment, data: dict, chunk_rows: int = 0):
+    """Installs a recorded dataset as the environment's rollout (``gs_rollout_load``, the inverse of ``Handle.rollout_download``):
+    every entry that reads "the last rollout" -- ``DeviceGridDataset``, ``evaluate_rollout*``, ``rollout_costs``, ``rollout_episodes``,
+    ``OnPolicyBatches``, ``DeviceLearner``, ``refresh_targets``, ``FederatedLearners`` -- then runs on it unchanged.  ``data``: the
+    [T, B, ...] dictionary of ``Handle.rollout_download`` or the flat time-major one of ``collect_random_data`` (reshaped, not copied),
+    float64 or float32; a bool ``terminals`` means "terminated" (bit 0); ``final_observation`` and ``log_probs`` are taken if present.
+    A live transition's ``next_observations`` must equal, by bits, the ``observations`` one step later (``transitions_to_rollout``
+    marks the breaks of a recorded trajectory).  The environment itself -- state, random chains, current observation -- is not
+    touched, and need not have been reset.  Returns the ``gs_rollout_device`` view."""
+    d = _as_tb(data, env.num_envs)
+    env.handle.rollout_load(d["observations"], d.get("actions"), d["rewards"], d["next_observations"], d["terminals"],
+                            final_observation=d.get("final_observation"), log_probs=d.get("log_probs"), chunk_rows=chunk_rows)
+    return env.handle.rollout_device_view()
+
+
+def transitions_to_rollout(data: dict, num_envs: int, timeouts=None) -> dict:
+    """A recorded trajectory in the reference's flat form (``GridDataset``'s five arrays, transition i + 1 following transition i)
+    as a [T, B, ...] rollout dictionary for ``load_rollout_data``: column b is transitions ``b * T .. (b + 1) * T - 1`` with
+    ``T = N // num_envs``; the ``N - T * num_envs`` transitions at the end are dropped and reported as ``remainder``.  ``terminals``
+    (bool or uint8) keeps its bits, ``timeouts`` [N] sets bit 1 (truncated).  A live transition whose ``next_observations`` differs
+    by bits from the ``observations`` that follow it in its column -- the last one of a column included -- is a BREAK: the recording
+    stopped there, which is a truncation, so it gets bit 1 and bootstraps under ``bootstrap=("truncated",)`` and under nothing else.
+    ``breaks`` is their number."""
+    B = int(num_envs)
+    obs, nxt = np.asarray(data["observations"]), np.asarray(data["next_observations"])
+    N = len(obs)
+    T = N // B
+    if B < 1 or T < 1:
+        raise PowerFlowError(f"{N} transitions do not fill {B} columns")
+    flags = _flags(data["terminals"]).astype(np.uint8).reshape(-1).copy()
+    if timeouts is not None:
+        flags[np.asarray(timeouts).reshape(-1) != 0] |= 2
+    flags = flags[:T * B]
+    # by bits, row i against row i + 1; a column's last row follows nothing
+    differs = np.ones(T * B, dtype=bool)
+    if T * B > 1:
+        differs[:-1] = _rows_differ(nxt[:T * B - 1], obs[1:T * B])
+    differs[T - 1::T] = True
+    breaks = differs & (flags == 0)
+    flags[breaks] |= 2
+    tb = lambda x: np.swapaxes(np.asarray(x)[:T * B].reshape((B, T) + np.asarray(x).shape[1:]), 0, 1)
+    out = {k: np.ascontiguousarray(tb(data[k])) for k in ("observations", "actions", "rewards", "next_observations")}
+    out["terminals"] = np.ascontiguousarray(tb(flags))
+    out["final_observation"] = np.ascontiguousarray(out["next_observations"][T - 1])
+    out["remainder"], out["breaks"] = N - T * B, int(breaks.sum())
+    return out
+
+
+def rollout_to_transitions(data: dict) -> dict:
+    """The inverse of ``transitions_to_rollout``'s layout: a [T, B, ...] rollout dictionary as flat arrays in which column b's
+    transitions follow one another (index = b * T + t); ``terminals`` keeps its uint8 flags."""
+    out = {}
+    for k in ROLLOUT_KEYS:
+        x = np.asarray(data[k])
+        out[k] = np.ascontiguousarray(np.swapaxes(x, 0, 1)).reshape((x.shape[0] * x.shape[1],) + x.shape[2:])
+    return out
+
+
+def concat_rollouts(a: dict, b: dict) -> dict:
+    """Two [T, B, ...] rollout dictionaries joined along T.  Legal exactly when ``a``'s ``final_observation`` equals ``b``'s
+    ``observations[0]`` by bits -- two consecutive ``reset=False`` rollouts of one environment --, since ``b``'s first step then
+    starts where ``a``'s last one ended; raises otherwise, naming the first instance that differs.  ``log_probs`` are kept when both
+    have them."""
+    fa, ob = a.get("final_observation"), np.asarray(b["observations"])
+    if fa is None:
+        raise PowerFlowError("concat_rollouts: the first rollout has no final_observation (rollout_download(want=(..., 'final_observation')))")
+    fa = np.asarray(fa)
+    if fa.shape != ob.shape[1:] or fa.dtype != ob.dtype:
+        raise PowerFlowError(f"concat_rollouts: final_observation {fa.shape} {fa.dtype} against observations[0] {ob.shape[1:]} {ob.dtype}")
+    differ = _rows_differ(fa, ob[0])
+    if differ.any():
+        raise PowerFlowError(f"concat_rollouts: the second rollout does not start where the first ended: instance {int(np.argmax(differ))} is the first of "
+                             f"{int(differ.sum())} whose observations[0] differs from the first rollout's final_observation")
+    out = {k: np.concatenate([np.asarray(a[k]), np.asarray(b[k])], axis=0) for k in ROLLOUT_KEYS}
+    out["terminals"] = np.concatenate([_flags(a["terminals"]), _flags(b["terminals"])], axis=0)
+    fb = b.get("final_observation")
+    out["final_observation"] = np.asarray(b["next_observations"])[-1].copy() if fb is None else np.asarray(fb)
+    if a.get("log_probs") is not None and b.get("log_probs") is not None:
+        out["log_probs"] = np.concatenate([np.asarray(a["log_probs"]), np.asarray(b["log_probs"])], axis=0)
+    return out
+
+
+def download_rollout(env: BatchedGridEnvironment) -> dict:
+    """The environment's last rollout as the [T, B, ...] dictionary ``load_rollout_data`` takes: the five arrays,
+    ``final_observation``, and ``log_probs`` when the rollout recorded them."""
+    h = env.handle
+    d = h.rollout_download(want=ROLLOUT_KEYS + ("final_observation",))
+    d.pop("n_terminal")
+    try:
+        d["log_probs"] = h.rollout_onpolicy_download(("log_probs",))["log_probs"]
+    except PowerFlowError as e:          # (GS_E_STATE: the rollout recorded none)
+        if f"libgridstep error {_lib.GS_E_STATE}:" not in str(e):
+            raise
+    return d
+
+
+def save_rollout(env_or_data, path) -> None:
+    """``np.savez`` of a rollout: the [T, B, ...] arrays plus ``final_observation``, and ``log_probs`` when recorded.  An environment:
+    its last rollout (``download_rollout``); a dictionary: as it is."""
+    d = env_or_data if isinstance(env_or_data, dict) else download_rollout(env_or_data)
+    keep = {k: np.asarray(d[k]) for k in ROLLOUT_KEYS + ("final_observation", "log_probs") if d.get(k) is not None}
+    keep["terminals"] = _flags(keep["terminals"])
+    with open(path, "wb") as f:
+        np.savez(f, **keep)
+
+
+def load_rollout(env: BatchedGridEnvironment, path, chunk_rows: int = 0):
+    """``load_rollout_data`` on what ``save_rollout`` wrote; returns the ``gs_rollout_device`` view."""
+    with np.load(path) as z:
+        return load_rollout_data(env, {k: z[k] for k in z.files}, chunk_rows=chunk_rows)

@@ -334,6 +334,53 @@ typedef struct gs_rollout_device {
 } gs_rollout_device;
 int gs_rollout_device_view(gs_handle* h, gs_rollout_device* out);
 
+/* ---- a recorded dataset as the handle's rollout: the inverse of gs_rollout_download -------------
+ * GridDataset(observations, actions, rewards, next_observations, terminals) (algorithms/base.py:180-205) takes five arrays from
+ * anywhere.  gs_rollout_load installs such arrays -- host memory, transition index = t * B + b, B / obs_dim / action_dim the
+ * handle's -- as the handle's rollout: the state is what a gs_rollout would have left had it produced these transitions, and every
+ * entry that reads "the last rollout" (gs_dataset_*, gs_rollout_evaluate*, gs_rollout_costs, gs_rollout_episodes, gs_onpolicy_*,
+ * gs_learner_*, gs_learner_refresh, gs_fed_*) runs on them unchanged.
+ *   obs_seq[t] = observations[t], obs_seq[T] = final_observation (NULL: next_observations[T - 1]); actions, rewards and flags as
+ *   given; every transition with terminals != 0 has an entry in the terminal list with its next_observations row, the list in
+ *   ASCENDING t * B + b order (deterministic, where gs_rollout promises no particular order); log-probabilities count as recorded
+ *   exactly when log_probs is given.  The rollout counts as a new one: whatever was computed over the previous one (critic values, Q
+ *   arrays, policy-action targets, costs, the episode list, the dataset's map, the refresh map, prepared minibatches) is stale by the
+ *   gates those entries have; installed dataset statistics stay, as after gs_rollout.
+ *   The ENVIRONMENT is not touched -- state, current observation, random chains, whether it was reset -- and a handle that was never
+ *   reset may load.  The next gs_rollout puts the constant observation columns back before it steps.
+ * Continuity: a transition with terminals == 0 has no room for a next observation of its own, so next_observations[t][b] must equal
+ * observations[t + 1][b] (t < T - 1) or, with final_observation given, final_observation[b] (t = T - 1) -- by the BITS of the source
+ * element (a NaN equals the same NaN; float32 sources are compared after their exact widening, which tells all values apart and
+ * every NaN but a signalling from the quiet one of its payload).  Checked on the device while next_observations streams through:
+ * GS_E_INVALID with the number of offending transitions and the first one's (t, b) in ascending order, and the handle then holds NO
+ * rollout (as before its first gs_rollout), never half of one.  Observations are not tested for finiteness: the simulator itself
+ * records NaN rows for unsolved instances.
+ * GS_E_INVALID before anything is allocated or launched (gs_rollout_load_check: the same checks on the host alone, no handle, no
+ * device): a wrong struct_size, an unknown dtype, T <= 0, chunk_rows < 0, non-zero flags, a NULL required pointer, T * B beyond what
+ * int32 row indices hold, a terminals value above 3.  out (may be NULL): n = T * B, n_terminal, and the capacity of the terminal
+ * list the load needs (a recorded dataset may end an episode at every transition; gs_rollout's own bound is B (T / min(episode_length,
+ * 11) + 1)).
+ * The source is staged through two page-locked buffers of chunk_rows rows of next_observations (0: the library's choice, 16 MiB),
+ * the copy of one chunk under the kernel of the one before; next_observations is never resident as a whole.  float32 sources are
+ * widened once, exactly.  The call synchronises before it returns: the source arrays are the caller's again. */
+typedef struct gs_rollout_source {
+  int32_t struct_size;            /* = sizeof(gs_rollout_source) */
+  int32_t dtype;                  /* GS_COMPUTE_F64 / GS_COMPUTE_F32: element type of every floating array below */
+  int32_t T;                      /* > 0; B, obs_dim, action_dim are the handle's */
+  int32_t chunk_rows;             /* 0: the library's choice; > 0: rows per staging chunk */
+  uint32_t flags;                 /* 0; reserved */
+  const void* observations;       /* host [T][B][obs_dim] */
+  const void* actions;            /* host [T][B][action_dim]; may be NULL only when action_dim == 0 */
+  const void* rewards;            /* host [T][B] */
+  const void* next_observations;  /* host [T][B][obs_dim] */
+  const uint8_t* terminals;       /* host [T][B]: 0, or bit 0 terminated | bit 1 truncated, as gs_rollout_view */
+  const void* final_observation;  /* host [B][obs_dim], or NULL: next_observations[T - 1] */
+  const void* log_probs;          /* host [T][B], or NULL: the rollout then "recorded none" */
+} gs_rollout_source;
+typedef struct gs_rollout_load_info { int64_t n; int32_t n_terminal, term_cap_needed; } gs_rollout_load_info;
+int gs_rollout_load_check(const gs_rollout_source* s, int32_t B, int32_t obs_dim, int32_t action_dim, gs_rollout_load_info* out);  /* host only */
+int gs_rollout_load(gs_handle* h, const gs_rollout_source* s);
+
 /* ---- closed-loop rollouts: an MLP policy evaluated on the device between two steps of gs_rollout ---------------
  * The reference's actors are plain MLPs (algorithms/base.py:157-177 `_build_mlp`: Linear + relu / tanh / elu) whose head is
  * tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) * eps) (algorithms/offline.py:69-76, 114-136).
