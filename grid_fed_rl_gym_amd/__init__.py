@@ -22,7 +22,7 @@ from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy
                       evaluate_policy, permutation_np, onpolicy_batch_np, OnPolicyBatches, evaluate_rollout_q, q_rollout_np, td_target_np,
                       q_combine_np, polyak_np, evaluate_rollout_q_next, policy_rows_np, q_next_noise_np, td_policy_np,
                       refresh_targets, refresh_rows_np, load_rollout_data, transitions_to_rollout, rollout_to_transitions, concat_rollouts,
-                      download_rollout, save_rollout, load_rollout)
+                      download_rollout, save_rollout, load_rollout, continue_rollout, rollout_window_np, ReplayWindow)
 from .policy import MLPPolicy, MLPValue, MLPQ
 from .learner import (DeviceLearner, ppo_grad_np, value_grad_np, awr_grad_np, expectile_grad_np, pathwise_grad_np, pathwise_noise_np, adam_np,
                       split_parameters)
@@ -45,6 +45,7 @@ __all__ = [
     "evaluate_rollout_q_next", "policy_rows_np", "q_next_noise_np", "td_policy_np",
     "refresh_targets", "refresh_rows_np",
     "load_rollout_data", "transitions_to_rollout", "rollout_to_transitions", "concat_rollouts", "download_rollout", "save_rollout", "load_rollout",
+    "continue_rollout", "rollout_window_np", "ReplayWindow",
     "DeviceLearner", "ppo_grad_np", "value_grad_np", "awr_grad_np", "expectile_grad_np", "pathwise_grad_np", "pathwise_noise_np", "adam_np", "split_parameters",
     "FederatedLearners", "fedavg_np", "fed_noise_np", "filter_outliers_np", "gaussian_sigma",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",

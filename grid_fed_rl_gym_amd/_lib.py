@@ -88,6 +88,15 @@ class gs_rollout_load_info(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_terminal", C.c_int32), ("term_cap_needed", C.c_int32)]
 
 
+class gs_rollout_continue_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("T", C.c_int32), ("keep", C.c_int32), ("policy", C.c_int32), ("policy_seed", C.c_uint64),
+                ("t0", C.c_uint32), ("reserved", C.c_uint32), ("actions", _dp)]
+
+
+class gs_rollout_window_info_out(C.Structure):
+    _fields_ = [("T", C.c_int32), ("kept", C.c_int32), ("t0_next", C.c_uint32), ("T_cap", C.c_int32)]
+
+
 POLICY = {"uploaded": 0, "random": 1, "mlp": 2}
 ACTIVATION = {"relu": 0, "tanh": 1, "elu": 2}
 HEAD = {"tanh": 0, "gaussian_tanh": 1}
@@ -564,6 +573,8 @@ SYMBOLS = [
     ("gs_rollout_device_view", C.c_int, [_H, C.POINTER(gs_rollout_device)]),
     ("gs_rollout_load_check", C.c_int, [C.POINTER(gs_rollout_source), C.c_int32, C.c_int32, C.c_int32, C.POINTER(gs_rollout_load_info)]),
     ("gs_rollout_load", C.c_int, [_H, C.POINTER(gs_rollout_source)]),
+    ("gs_rollout_continue", C.c_int, [_H, C.POINTER(gs_rollout_continue_config)]),
+    ("gs_rollout_window_info", C.c_int, [_H, C.POINTER(gs_rollout_window_info_out)]),
     ("gs_dataset_build", C.c_int, [_H, C.c_uint32]),
     ("gs_dataset_stats", C.c_int, [_H, C.POINTER(gs_dataset_stats_view)]),
     ("gs_dataset_set_stats", C.c_int, [_H, C.POINTER(gs_dataset_stats_view)]),
@@ -1524,6 +1535,30 @@ class Handle:
         self._check(self._lib.gs_rollout_load(self._h, C.byref(src)))
         del keep
         self._rollout_T = int(src.T)
+
+    def rollout_continue(self, T: int, keep: int, policy: str = "random", seed: int = 0, actions=None, t0: Optional[int] = None) -> None:
+        """gs_rollout_continue (asynchronous): the last ``keep`` steps of the handle's rollout move to the front on the device and ``T``
+        new steps are collected behind them; the rollout then has ``keep + T`` steps.  ``policy`` / ``seed`` / ``actions`` ([T, B, A], the
+        new steps only) as ``rollout``; ``t0``: the step index the first new step draws with (None: where the last collection's draws
+        ended, ``rollout_window_info()["t0_next"]``)."""
+        a = None
+        if policy == "uploaded":
+            a = _f64(actions)
+            if a.shape != (int(T), self.B, self.action_dim):
+                raise PowerFlowError(f"actions shape {a.shape} != ({T}, {self.B}, {self.action_dim})")
+        if t0 is None:
+            t0 = self.rollout_window_info()["t0_next"]
+        cfg = gs_rollout_continue_config(C.sizeof(gs_rollout_continue_config), int(T), int(keep), POLICY[policy], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                         int(t0) & 0xFFFFFFFF, 0, _ptr(a, _dp))
+        self._check(self._lib.gs_rollout_continue(self._h, C.byref(cfg)))
+        self._rollout_T = int(keep) + int(T)
+
+    def rollout_window_info(self) -> dict:
+        """gs_rollout_window_info (host state, no wait): ``T`` steps of the handle's rollout, ``kept`` of them from before the last
+        ``rollout_continue``, ``t0_next`` the draw index the next continue goes on with, ``T_cap`` the steps the buffers hold."""
+        o = gs_rollout_window_info_out()
+        self._check(self._lib.gs_rollout_window_info(self._h, C.byref(o)))
+        return dict(T=int(o.T), kept=int(o.kept), t0_next=int(o.t0_next), T_cap=int(o.T_cap))
 
     # -- on-policy rollouts: log-probabilities, the value network, advantages and returns (include/gridstep.h) -------------------
     def rollout_log_probs(self, on: bool = True) -> None:

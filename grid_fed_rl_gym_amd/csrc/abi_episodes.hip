@@ -49,6 +49,9 @@ int gs_rollout_episodes(gs_handle* h, const gs_episode_config* cfg) {
   if (ro.T <= 0 || ro.calls == 0) return fail(h, GS_E_STATE, "gs_rollout_episodes: no rollout has been collected on this handle");
   if (ep.live && ep.accounted_on == ro.calls) return fail(h, GS_E_STATE, "gs_rollout_episodes: the last rollout has already been accounted");
   if (cfg->start == GS_EPISODES_CONTINUE) {
+    if (ro.ended_on == ro.calls && ro.kept > 0)
+      return fail(h, GS_E_STATE, "gs_rollout_episodes: GS_EPISODES_CONTINUE on a window whose first %d steps were kept from the rollout before "
+                                 "(gs_rollout_continue): they would be counted twice.  GS_EPISODES_FRESH accounts the window as it stands", ro.kept);
     if (!ep.live) return fail(h, GS_E_STATE, "gs_rollout_episodes: GS_EPISODES_CONTINUE without an episode track (start one with FRESH or UNKNOWN)");
     if (ro.calls != ep.accounted_on + 1)
       return fail(h, GS_E_STATE, "gs_rollout_episodes: GS_EPISODES_CONTINUE, but the rollout before the last one was not accounted (%llu rollouts since)",

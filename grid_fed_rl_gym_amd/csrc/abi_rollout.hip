@@ -35,15 +35,20 @@ void rollout_release(gs_handle* h, bool keep_term_count) {
   gs_handle::Rollout& ro = h->ro;
   ro.obs_seq.release(); ro.act.release(); ro.rew.release(); ro.done.release(); ro.term_idx.release(); ro.term_obs.release();
   if (!keep_term_count) ro.term_count.release();
+  rollout_tracks_release(h, keep_term_count);
+  ro.T_cap = 0; ro.T = 0; ro.n_term = -1;
+}
+
+void rollout_tracks_release(gs_handle* h, bool keep_carries) {
   onpolicy_release(h);           // (sized by T as well)
   costs_release(h);
   q_rollout_release(h);
   q_next_rollout_release(h);
   refresh_release(h);
-  episodes_release(h, keep_term_count);      // (the list is sized by the capacity; the carries outlive a longer rollout)
+  episodes_release(h, keep_carries);         // (the list is sized by the capacity; the carries outlive a longer rollout)
   batches_release(h);
   learner_scratch_release(h);
-  ro.T_cap = 0; ro.T = 0; ro.n_term = -1;
+  window_release(h);
 }
 
 }  // namespace gsi
@@ -113,9 +118,11 @@ int gs_policy_mlp_set_opts(gs_handle* h, const gs_policy_mlp* p, const gs_policy
   return GS_OK;
 }
 
+}  // extern "C"
+
 // one launch: actions[B][A] of the installed policy on obs[B][obs_dim] (device pointers), on the handle's main stream; logp: NULL or
 // [B], the log-probabilities of the actions a stochastic policy samples
-static int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t, double* logp = nullptr) {
+int gsi::launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t, double* logp) {
   const dim3 grid((unsigned)((h->B + GS_POL_ROWS - 1) / GS_POL_ROWS)), block(64 * GS_POL_WAVES);
   if (h->pol.compute == GS_COMPUTE_F32) {
     GsPolicyArgsF32 a = h->pol.args32;
@@ -130,6 +137,8 @@ static int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t 
   return GS_OK;
 }
 
+extern "C" {
+
 int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* actions_host) {
   if (!h || !actions_host) return fail(h, GS_E_INVALID, "handle / actions_host is NULL");
   if (!h->pol.set) return fail(h, GS_E_STATE, "gs_policy_mlp_eval before gs_policy_mlp_set");
@@ -142,6 +151,7 @@ int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* ac
   return GS_OK;
 }
 
+}  // extern "C"
 
 // ---- device-resident rollout collection ---------------------------------------------------------------
 // T fused env steps back to back, nothing on the host in between (algorithms/base.py:268-298, batched).
@@ -149,7 +159,7 @@ int gs_policy_mlp_eval(gs_handle* h, uint64_t policy_seed, int32_t t, double* ac
 // t + 1 is written by step t's kernel itself (its observation output IS the next slot: no copy) --, act[T][B][A],
 // rew[T][B], done[T][B], and the side list of terminal observations (t, b, row) the in-place resets replaced.
 // the constant columns of every slot: the step kernels write only the columns that change
-static int fill_const_columns(gs_handle* h) {
+int gsi::fill_const_columns(gs_handle* h) {
   gs_handle::Rollout& ro = h->ro;
   const long long rows = (long long)(ro.T_cap + 1) * h->B;
   const int w = h->obs_skip1 - h->obs_skip0;
@@ -162,8 +172,6 @@ static int fill_const_columns(gs_handle* h) {
   ro.const_dirty = false;
   return GS_OK;
 }
-
-}  // extern "C"
 
 int gsi::rollout_ensure(gs_handle* h, int T, int min_term_cap) {
   gs_handle::Rollout& ro = h->ro;
@@ -251,6 +259,7 @@ int gs_rollout(gs_handle* h, int32_t T, int32_t policy, uint64_t policy_seed, co
   HIPCHK(h, hipMemcpyAsync(h->d_obs2[h->obs_cur], ro.obs_seq + (size_t)T * B * D, B * D * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   if (h->rows_stale) h->last_obs = h->d_obs2[h->obs_cur];      // (the slot may be reallocated by a longer rollout; this copy stays)
   ro.calls += 1;
+  rollout_ended(h, 0, (uint32_t)T);      // (gs_rollout_continue may follow while the environment is not moved)
   return GS_OK;      // asynchronous: gs_synchronize / gs_rollout_download / gs_rollout_device_view wait for it
 }
 

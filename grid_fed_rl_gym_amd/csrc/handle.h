@@ -126,7 +126,16 @@ struct gs_handle : GsPlan {
     DevBuf<double> logp; hipEvent_t ev_eval = nullptr;
     // a load (abi_load.hip) overwrote whole rows of obs_seq: the next gs_rollout puts the constant columns back before it steps
     bool const_dirty = false;
+    // gs_rollout_continue (abi_window.hip).  ended_on = `calls` of the last rollout that was COLLECTED here
+    // (gs_rollout / gs_rollout_continue; a load advances `calls` alone), moves_at_end = env_moves when it ended: the environment
+    // stands at its last slot exactly while both still match.  kept: its steps that came from the rollout before; t0_next: the draw
+    // index its last step used, plus one
+    uint64_t ended_on = 0, moves_at_end = 0; int kept = 0; uint32_t t0_next = 0;
   } ro;
+  // gs_rollout_continue's second terminal list (term_idx [term_cap][2], term_obs [term_cap][obs_dim]: the compaction writes it and the
+  // two lists change places), pos [term_cap] where each old entry went, n_old [1] the old count; made on the first shift in place,
+  // released with the rollout's buffers
+  struct GS_HIDDEN Window { DevBuf<int32_t> term_idx, pos, n_old; DevBuf<double> term_obs; } win;
   // gs_rollout_load (abi_load.hip): two page-locked staging buffers and their device chunks (`bytes` each, grown
   // to the largest asked for), the stream the chunks are copied on, per buffer the events "copied" and "consumed", and the verdict
   // (offending transitions, the first one's index).  Kept between loads, released with the handle.
@@ -423,6 +432,17 @@ void policy_release(gs_handle* h);
 // the float32 image of an MLP as one allocation (image, then shift and scale) in `blob`; *image / *norm: where the two parts lie
 int upload_image_f32(gs_handle* h, DevBuf<char>& blob, const GsPolicyImageF32& im, const float** image, const double** norm);
 void rollout_release(gs_handle* h, bool keep_term_count = false);
+// what is sized by the rollout's capacity but is not the rollout: every track over it, and the scratch that goes with it
+void rollout_tracks_release(gs_handle* h, bool keep_carries = false);
+// the constant columns of every slot of ro.obs_seq (queued); the installed policy on obs[B][obs_dim] -> act[B][A] with draw index t
+int fill_const_columns(gs_handle* h);
+int launch_policy(gs_handle* h, const double* obs, double* act, uint64_t seed, int t, double* logp = nullptr);
+// a collected rollout has ended (its `calls` counted): the environment stands at its last slot until it is moved
+static inline void rollout_ended(gs_handle* h, int kept, uint32_t t0_next) {
+  h->ro.ended_on = h->ro.calls; h->ro.moves_at_end = h->env_moves; h->ro.kept = kept; h->ro.t0_next = t0_next;
+}
+// ---- owner of the window's second terminal list (abi_window.hip) ----
+void window_release(gs_handle* h);
 // buffers for a rollout of T steps whose terminal list holds at least min_term_cap entries (gs_rollout's own bound if that is more);
 // a handle that has them keeps them, otherwise everything sized by T_cap or term_cap goes (rollout_release) and is made again
 int rollout_ensure(gs_handle* h, int T, int min_term_cap = 0);

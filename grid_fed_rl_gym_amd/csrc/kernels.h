@@ -14,6 +14,7 @@
 #include "conservative.h"
 #include "refresh.h"
 #include "rollout_load.h"
+#include "rollout_window.h"
 
 // The launch tables: host function pointers of the kernel members, indexed by their enum (members.h); nullptr where a member has no
 // such kernel.  The first generation (kernels_solve.hip): solve, step, stepc per SolveMember (nr_dense_mfma / nr_sparse_lds: none,
@@ -105,6 +106,9 @@ __global__ void gs_k_refresh_combine(GsRefreshCombineArgs C);
 __global__ void gs_k_load_widen(const float* __restrict__ src, double* __restrict__ dst, long long n);
 __global__ void gs_k_load_next_f64(GsLoadNextArgs G);
 __global__ void gs_k_load_next_f32(GsLoadNextArgs G);
+__global__ void gs_k_window_shift(GsWindowShiftArgs G);
+__global__ void gs_k_window_terms(GsWindowTermsArgs G);
+__global__ void gs_k_window_term_rows(GsWindowTermRowsArgs G);
 __global__ void gs_k_ds_chunk_stats(GsDsStatArgs A);
 __global__ void gs_k_ds_merge(double* __restrict__ part, long long chunks, int Ct, long long stride, long long N,
                               const GsDsMatrix m0, const GsDsMatrix m1, const GsDsMatrix m2, double* __restrict__ fin_mean, double* __restrict__ fin_std);

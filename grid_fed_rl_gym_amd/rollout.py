@@ -38,6 +38,11 @@ when given; everything computed over the previous rollout is stale; the environm
 reset; the simulator's next rollout puts the constant observation columns back.  ``transitions_to_rollout`` /
 ``rollout_to_transitions`` lay a flat recorded trajectory out in columns and back, marking its breaks as truncations;
 ``concat_rollouts`` joins consecutive rollouts; ``save_rollout`` writes the arrays with ``np.savez``.
+
+``continue_rollout`` / ``ReplayWindow`` slide a WINDOW over consecutive rollouts (``gs_rollout_continue``): the
+last ``keep`` steps of the environment's rollout move to the front on the device and ``num_steps`` fresh ones are collected behind
+them, so the off-policy learners train on recent experience with no transition crossing the host; ``rollout_window_np`` restates
+the result.
 """
 from __future__ import annotations
 
@@ -1246,3 +1251,74 @@ def load_rollout(env: BatchedGridEnvironment, path, chunk_rows: int = 0):
     """``load_rollout_data`` on what ``save_rollout`` wrote; returns the ``gs_rollout_device`` view."""
     with np.load(path) as z:
         return load_rollout_data(env, {k: z[k] for k in z.files}, chunk_rows=chunk_rows)
+
+
+def continue_rollout(env: BatchedGridEnvironment, num_steps: int, keep: int, seed: int = 0, policy=None, stochastic: bool = False,
+                     actions: Optional[np.ndarray] = None, t0: Optional[int] = None):
+    """A sliding window on the device (``gs_rollout_continue``): the last ``keep`` steps of the environment's rollout stay, moved to
+    the front, and ``num_steps`` new steps follow from where the environment stands; the rollout then has ``keep + num_steps`` steps and
+    everything that reads "the last rollout" runs on that window.  ``policy`` / ``stochastic`` / ``actions`` ([num_steps, B, A], the new
+    steps only) as ``rollout_device``; ``t0``: the step index the first new step draws with (None: where the last collection's draws
+    ended, so that ``rollout_device(T1)`` then ``continue_rollout(T2, keep)`` with one seed holds the tail of ``rollout_device(T1 + T2)``
+    by bits).  ``keep > 0`` needs a rollout that was collected here (not loaded) and an environment that was not moved since; the
+    window is a new rollout to every track.  Returns the ``gs_rollout_device`` view."""
+    if policy is not None and actions is not None:
+        raise ValueError("continue_rollout: either actions or a policy")
+    if env._needs_reset:
+        env.reset(seed=seed)
+    h = env.handle
+    if policy is not None:
+        if policy is not True:
+            env.set_policy(policy, stochastic=stochastic)
+        h.rollout_continue(int(num_steps), int(keep), "mlp", seed=seed, t0=t0)
+    elif actions is None:
+        h.rollout_continue(int(num_steps), int(keep), "random", seed=seed, t0=t0)
+    else:
+        h.rollout_continue(int(num_steps), int(keep), "uploaded", actions=np.asarray(actions, dtype=np.float64), t0=t0)
+    return h.rollout_device_view()
+
+
+def rollout_window_np(old: dict, new: dict, keep: int) -> dict:
+    """What ``continue_rollout`` leaves, restated: the last ``keep`` steps of the [T, B, ...] rollout dictionary ``old`` joined with
+    ``new`` (``concat_rollouts``: ``new`` must start where ``old`` ended).  Where both carry the device's terminal list
+    (``terminal_index`` [n, 2] of (t, b), in any order, and ``terminal_obs`` [n, D]), the result has it too: ``old``'s entries with
+    ``t >= T_old - keep`` in the order they lie in, renumbered ``t -= T_old - keep``, then ``new``'s with ``t += keep``."""
+    T_old, keep = len(np.asarray(old["observations"])), int(keep)
+    if not 0 <= keep <= T_old:
+        raise PowerFlowError(f"rollout_window_np: keep = {keep} outside 0 .. {T_old}")
+    drop = T_old - keep
+    tail = {k: np.asarray(old[k])[drop:] for k in ROLLOUT_KEYS + ("log_probs",) if old.get(k) is not None}
+    tail["final_observation"] = old.get("final_observation")
+    out = concat_rollouts(tail, new)
+    if all(d.get(k) is not None for d in (old, new) for k in ("terminal_index", "terminal_obs")):
+        oi, ni = np.asarray(old["terminal_index"]).reshape(-1, 2), np.asarray(new["terminal_index"]).reshape(-1, 2)
+        stay = oi[:, 0] >= drop
+        out["terminal_index"] = np.concatenate([oi[stay] - np.array([drop, 0], dtype=oi.dtype), ni + np.array([keep, 0], dtype=ni.dtype)], axis=0)
+        out["terminal_obs"] = np.concatenate([np.asarray(old["terminal_obs"])[stay], np.asarray(new["terminal_obs"])], axis=0)
+    return out
+
+
+class ReplayWindow:
+    """The last ``capacity_steps`` steps of an environment's experience as its rollout, on the device: ``collect(num_steps)`` keeps
+    ``min(capacity_steps - num_steps, current T)`` steps and appends ``num_steps`` fresh ones (``continue_rollout``), so the window
+    fills up and then slides.  ``DeviceGridDataset``, ``OnPolicyBatches``, the learners and ``refresh_targets`` read it as the last
+    rollout.  After the environment was moved between two collections (``reset``, ``step``, ``evaluate_policy``) the window cannot go
+    on: ``collect(..., fresh=True)`` starts it again."""
+
+    def __init__(self, env: BatchedGridEnvironment, capacity_steps: int) -> None:
+        if int(capacity_steps) < 1:
+            raise ValueError("ReplayWindow: capacity_steps < 1")
+        self.env, self.capacity = env, int(capacity_steps)
+
+    @property
+    def steps(self) -> int:
+        return 0 if self.env._needs_reset else self.env.handle.rollout_window_info()["T"]
+
+    def collect(self, num_steps: int, seed: int = 0, policy=None, stochastic: bool = False, actions=None, fresh: bool = False):
+        """``num_steps`` new steps behind what the window keeps; ``fresh``: keep nothing (after the environment was moved, or over
+        a loaded rollout, which ``continue_rollout`` refuses to go on from).  Returns the ``gs_rollout_device`` view."""
+        num_steps = int(num_steps)
+        if not 0 < num_steps <= self.capacity:
+            raise ValueError(f"ReplayWindow.collect: num_steps = {num_steps} outside 1 .. {self.capacity}")
+        keep = 0 if fresh else min(self.capacity - num_steps, self.steps)
+        return continue_rollout(self.env, num_steps, keep, seed=seed, policy=policy, stochastic=stochastic, actions=actions)

@@ -381,6 +381,45 @@ typedef struct gs_rollout_load_info { int64_t n; int32_t n_terminal, term_cap_ne
 int gs_rollout_load_check(const gs_rollout_source* s, int32_t B, int32_t obs_dim, int32_t action_dim, gs_rollout_load_info* out);  /* host only */
 int gs_rollout_load(gs_handle* h, const gs_rollout_source* s);
 
+/* ---- a sliding window over consecutive rollouts: the last `keep` steps stay, T fresh ones follow ---------
+ * gs_rollout_continue keeps steps T_old - keep .. T_old - 1 of the rollout the handle holds, moves them to the front ON THE DEVICE
+ * and collects T new steps behind them; the handle's rollout then has keep + T steps and every entry that reads "the last rollout"
+ * runs on that window unchanged -- a replay window for the off-policy learners with no transition crossing the host.
+ *   steps 0 .. keep - 1 are, by bits, steps T_old - keep .. T_old - 1 of the previous rollout (obs_seq slots 0 .. keep, actions,
+ *   rewards, flags, log-probabilities where recorded); slot keep is the previous slot T_old, where the environment stands; steps
+ *   keep .. keep + T - 1 are what gs_rollout(h, T, policy, policy_seed, actions) would have produced, except that new step i draws
+ *   with the index t0 + i wherever gs_rollout draws with its step index t (the random actions' counter, the policy's noise): after
+ *   gs_rollout(T1), continue(T2, keep, t0 = T1) holds the last keep + T2 steps of one gs_rollout(T1 + T2), by bits.
+ *   The terminal list holds the previous entries with t >= T_old - keep, renumbered t -= T_old - keep, each with its row, in the
+ *   order the previous list had them (a stable compaction); the new steps' entries follow.
+ *   Log-probabilities count as recorded when the kept steps had them (or keep == 0) and the new steps record them.
+ *   The window counts as a new rollout: whatever was computed over the previous one is stale, as after gs_rollout.
+ * GS_E_INVALID: a NULL handle or config, a wrong struct_size, T <= 0, keep < 0 or keep beyond the current rollout's T, an unknown
+ * policy, GS_POLICY_UPLOADED without actions.  GS_E_STATE: keep > 0 without a rollout; GS_POLICY_MLP without a policy; before
+ * gs_reset; keep > 0 on a rollout that gs_rollout_load installed (the environment does not stand at its last slot) or after the
+ * environment was moved since the rollout ended (gs_reset, gs_set_state, gs_step*, an upload of state, gs_solve*).  Every check
+ * runs before anything is queued: a refused call leaves the rollout and everything computed over it as they were.  keep == 0 is
+ * gs_rollout with the draw origin t0.
+ * Asynchronous, like gs_rollout; the host waits only where the window outgrows the buffers' capacity and they are made again (the
+ * kept part is carried over).  gs_rollout_episodes(GS_EPISODES_CONTINUE) on a window with kept steps is GS_E_STATE: it would
+ * count them twice.
+ * gs_rollout_window_info: host state, no wait.  T: steps of the handle's rollout (0: none); kept: the steps at its front that
+ * came from before the last gs_rollout_continue (0 after gs_rollout or a load); t0_next: t0 + T of the last continue, T after a
+ * plain gs_rollout -- the t0 that makes the next continue draw on; T_cap: the steps the buffers hold. */
+typedef struct gs_rollout_continue_config {
+  int32_t struct_size;            /* = sizeof(gs_rollout_continue_config) */
+  int32_t T;                      /* new steps, > 0 */
+  int32_t keep;                   /* steps kept from the end of the current rollout, 0 <= keep <= its T */
+  int32_t policy;                 /* GS_POLICY_* as gs_rollout */
+  uint64_t policy_seed;
+  uint32_t t0;                    /* the step index the first NEW step draws with */
+  uint32_t reserved;
+  const double* actions;          /* GS_POLICY_UPLOADED: host [T][B][action_dim], the new steps only */
+} gs_rollout_continue_config;
+typedef struct gs_rollout_window_info_out { int32_t T, kept; uint32_t t0_next; int32_t T_cap; } gs_rollout_window_info_out;
+int gs_rollout_continue(gs_handle* h, const gs_rollout_continue_config* cfg);
+int gs_rollout_window_info(gs_handle* h, gs_rollout_window_info_out* out);
+
 /* ---- closed-loop rollouts: an MLP policy evaluated on the device between two steps of gs_rollout ---------------
  * The reference's actors are plain MLPs (algorithms/base.py:157-177 `_build_mlp`: Linear + relu / tanh / elu) whose head is
  * tanh(mean) or tanh(mean + exp(clamp(log_std, -20, 2)) * eps) (algorithms/offline.py:69-76, 114-136).
