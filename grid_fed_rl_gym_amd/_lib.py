@@ -607,6 +607,7 @@ SYMBOLS = [
     ("gs_debug_block_times", C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int32]),
     ("gs_debug_write_rows", C.c_int, [_H, C.c_int32, _dp]),
     ("gs_debug_read_rows", C.c_int, [_H, C.c_int32, _dp]),
+    ("gs_debug_fastmath", C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp]),
     ("gs_fallback_linear", C.c_int, [_H, _dp, _dp, _dp, _dp, _up, _up, C.POINTER(C.c_int32)]),
     ("gs_set_line_impedances", C.c_int, [_H, _dp, _dp, _up]),
     ("gs_get_line_impedances", C.c_int, [_H, _dp, _dp]),

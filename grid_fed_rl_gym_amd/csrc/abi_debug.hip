@@ -7,6 +7,7 @@
 
 #include "handle.h"
 #include "mesh_schedule.h"
+#include "fastmath.h"
 
 using namespace gsi;
 
@@ -202,3 +203,36 @@ int gs_debug_read_rows(gs_handle* h, int32_t which, double* values) {
 }
 
 }  // extern "C"
+
+// ---- fastmath.h on the device, element by element (tests/test_gpu_exact_math.py) ------------------------------------------
+// thread i takes element i, so the caller decides which elements share a wavefront: gs_sqrt_fast's choice between its short path
+// and the general square root is per wavefront
+__global__ void __launch_bounds__(256) gs_k_debug_fastmath(int op, long long n, const double* __restrict__ a, const double* __restrict__ b,
+                                                           double* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double x = a[i];
+  double r;
+  switch (op) {
+    case GS_FASTMATH_SQRT: r = gs_sqrt_fast(x); break;
+    case GS_FASTMATH_DIV: r = gs_div_fast(x, b[i]); break;
+    case GS_FASTMATH_LOG01: r = gs_log01(x); break;
+    default: r = gs_sqrt_core(x); break;
+  }
+  out[i] = r;
+}
+
+extern "C" int gs_debug_fastmath(int32_t op, int64_t n, const double* in_a, const double* in_b, double* out) {
+  if (op < 0 || op >= GS_FASTMATH_COUNT || n < 1 || n > (1 << 24) || !in_a || !out || (op == GS_FASTMATH_DIV && !in_b))
+    return fail(nullptr, GS_E_INVALID, "bad arguments");
+  const size_t bytes = (size_t)n * sizeof(double);
+  double *da = nullptr, *db = nullptr, *dout = nullptr;
+  bool ok = hipMalloc(&da, bytes) == hipSuccess && hipMalloc(&dout, bytes) == hipSuccess && (!in_b || hipMalloc(&db, bytes) == hipSuccess);
+  ok = ok && hipMemcpy(da, in_a, bytes, hipMemcpyHostToDevice) == hipSuccess && (!in_b || hipMemcpy(db, in_b, bytes, hipMemcpyHostToDevice) == hipSuccess);
+  if (ok) {
+    hipLaunchKernelGGL(gs_k_debug_fastmath, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)op, (long long)n, da, db, dout);
+    ok = hipGetLastError() == hipSuccess && hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
+  return ok ? GS_OK : fail(nullptr, GS_E_HIP, "gs_debug_fastmath: allocation, copy or launch failed");
+}

@@ -53,15 +53,30 @@ __device__ __forceinline__ void rng_uniform_pair(uint64_t seed, uint64_t instanc
   *u1 = (double)(x1 >> 11) * (1.0 / 9007199254740992.0) + (0.5 / 9007199254740992.0);
 }
 
+// The uniform of a 32-bit word, (r + 1/2) 2^-32 in (0, 1): r 2^-32 + 2^-33 has at most 33 significant bits, so the one fused multiply-add
+// is exact, like the add and the multiply it replaces.  The Box-Muller radius is the square root of -2 ln u, which therefore lies in
+// [2^-32, 45.8] (u = 1 - 2^-33 and u = 2^-33): never zero, infinite, NaN or tiny, so the square root's refinement core alone gives
+// the bits of sqrt (fastmath.h gs_sqrt_core; tests/test_fastmath_exact.py evaluates both ends).
+__device__ __forceinline__ double rng_unit32(uint32_t r) { return __builtin_fma((double)r, 1.0 / 4294967296.0, 0.5 / 4294967296.0); }
+
 // Four standard normals from ONE Philox call: every 32-bit output word is a uniform (r + 1/2) 2^-32, words (0, 1) and
 // (2, 3) are one Box-Muller pair each (cosine, sine).  The load noise takes them four at a time (load l: draw
 // DRAW_LOAD0 + l / 4, component l & 3), the weather takes wind / temperature / cloud from one call: the integer
 // multiplies of Philox were half the vector work of the load-noise phase with one call per pair.
+// SHORT = false: the recipe with the compiler's own square root and division and the uniforms as an add and a multiply -- the same
+// bits, more instructions; a step kernel form whose registers come out worse through the short operations takes it (kernels_flow2.hip).
+template <bool SHORT = true>
 __device__ __forceinline__ void rng_normal_quad(uint64_t seed, uint64_t instance, uint32_t step, uint32_t draw, double (&z)[4]) {
   const U4 r = philox((uint32_t)instance, step, draw, 0x47535450u, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const double u0 = ((double)r.a + 0.5) * (1.0 / 4294967296.0), u1 = ((double)r.b + 0.5) * (1.0 / 4294967296.0);
-  const double u2 = ((double)r.c + 0.5) * (1.0 / 4294967296.0), u3 = ((double)r.d + 0.5) * (1.0 / 4294967296.0);
-  const double ra = sqrt(-2.0 * gs_log01(u0)), rb = sqrt(-2.0 * gs_log01(u2));
+  double u0, u1, u2, u3, ra, rb;
+  if constexpr (SHORT) {
+    u0 = rng_unit32(r.a); u1 = rng_unit32(r.b); u2 = rng_unit32(r.c); u3 = rng_unit32(r.d);
+    ra = gs_sqrt_core(-2.0 * gs_log01(u0)); rb = gs_sqrt_core(-2.0 * gs_log01(u2));      // (rng_unit32: why the core is enough)
+  } else {
+    u0 = ((double)r.a + 0.5) * (1.0 / 4294967296.0); u1 = ((double)r.b + 0.5) * (1.0 / 4294967296.0);
+    u2 = ((double)r.c + 0.5) * (1.0 / 4294967296.0); u3 = ((double)r.d + 0.5) * (1.0 / 4294967296.0);
+    ra = sqrt(-2.0 * gs_log01<false>(u0)); rb = sqrt(-2.0 * gs_log01<false>(u2));
+  }
   double sn, cs;
   gs_sincos_turns(u1, &sn, &cs); z[0] = ra * cs; z[1] = ra * sn;
   gs_sincos_turns(u3, &sn, &cs); z[2] = rb * cs; z[3] = rb * sn;
@@ -73,8 +88,8 @@ __device__ __forceinline__ void rng_normal_quad(uint64_t seed, uint64_t instance
 // the step kernels that inline it come out with other instructions and, some, more spills -- DESIGN.md section 24.)
 __device__ __forceinline__ double rng_normal_component(const U4& r, int comp) {
   const uint32_t wr = comp & 2 ? r.c : r.a, wt = comp & 2 ? r.d : r.b;
-  const double ur = ((double)wr + 0.5) * (1.0 / 4294967296.0), ut = ((double)wt + 0.5) * (1.0 / 4294967296.0);
-  const double ra = sqrt(-2.0 * gs_log01(ur));
+  const double ur = rng_unit32(wr), ut = rng_unit32(wt);
+  const double ra = gs_sqrt_core(-2.0 * gs_log01(ur));
   double sn, cs;
   gs_sincos_turns(ut, &sn, &cs);
   return ra * (comp & 1 ? sn : cs);
@@ -122,6 +137,7 @@ __device__ __forceinline__ void weather_update_at(const GsRows& R, const GsEnvCf
 // The same update with the weather state handed on in registers: the three rows are requested together, updated where
 // `update` holds (a padded lane keeps its rows), and what the renewables need comes back without reading them again.
 struct GsWeather { double wind, temp, cloud; };
+template <bool SHORT = true>
 __device__ __forceinline__ GsWeather weather_step(const GsRows& R, const GsEnvCfg& E, GsLaneRows S, uint64_t inst, double time_s, uint32_t step, bool update) {
   GsWeather w;
   w.wind = ROW(R.WIND); w.temp = ROW(R.TEMP); w.cloud = ROW(R.CLOUD);
@@ -135,7 +151,7 @@ __device__ __forceinline__ GsWeather weather_step(const GsRows& R, const GsEnvCf
   rng_uniform_pair(seed, inst, step, DRAW_IRRADIANCE, &u, &u_unused);
   const double irr = base * (0.8 + 0.4 * u);
   double z[4];
-  rng_normal_quad(seed, inst, step, DRAW_WEATHER, z);
+  rng_normal_quad<SHORT>(seed, inst, step, DRAW_WEATHER, z);
   const double wind = fmax(0.0, fmin(30.0, w.wind + 0.5 * z[0]));
   gs_sincos_turns((hour - 12.0) * (1.0 / 24.0), &sn, &cs);      // sin(2 pi (hour - 12) / 24)
   const double temp = 25.0 + 10.0 * sn + 2.0 * z[1];

@@ -9,6 +9,8 @@
 //   gs_fmod_pos(x, d, rd)  fmod(x, d) for x >= 0, exactly (the remainder of an fma, then one correction step)
 //   gs_div_by(x, d, rd)    x / d with rd = RN(1 / d) supplied by the host: correctly rounded (Markstein's
 //                          theorem: q = RN(x rd) is faithful, r = x - d q is exact in an fma, RN(q + r rd) = RN(x / d))
+//   gs_sqrt_fast(x)        sqrt(x), same bits, 13 vector instructions instead of 21 (gs_sqrt_core: 10, for a known range)
+//   gs_div_fast(a, b)      a / b, same bits, for operands that need none of the division's scaling: 8 instead of 11
 // Kernels follow fdlibm's k_sin / k_cos / e_log polynomials; max error ~1 ulp (tests/test_fastmath.py compiles this
 // header for the host with g++ and compares with libm / true division on 10^6 points: the arithmetic is the same on
 // both sides because every multiply-add is an explicit fma).
@@ -30,6 +32,91 @@
 #define GS_NO_CONTRACT
 #endif
 
+// ---- short exact square root and division ----------------------------------------------------------------------------------
+// The compiler's correctly rounded sqrt(double) is 21 vector instructions on gfx950 and its a / b is 11: a refinement core (the
+// hardware estimate, then fused multiply-adds) inside a frame that scales tiny or huge operands into range and back and patches the
+// special values.  Where the operands are known to need no scaling the core alone gives the same bits, because it IS the same
+// arithmetic: gs_sqrt_refine and gs_div_fast below are those cores, operation for operation, read off the compiler's assembly.
+// tests/test_fastmath_exact.py compares them bit for bit with sqrt and / on the host, with a seed of the hardware's accuracy moved
+// about at random: the refinement does not depend on which estimate it starts from.
+//
+// The seed: v_rsq_f64 / v_rcp_f64 on the device; on the host a stand-in, which a test replaces by defining the macros first.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GS_RSQ_SEED(x) __builtin_amdgcn_rsq(x)
+#define GS_RCP_SEED(x) __builtin_amdgcn_rcp(x)
+#else
+#ifndef GS_RSQ_SEED
+#define GS_RSQ_SEED(x) (1.0 / sqrt(x))
+#endif
+#ifndef GS_RCP_SEED
+#define GS_RCP_SEED(x) (1.0 / (x))
+#endif
+#endif
+
+// sqrt(x) from y ~ 1 / sqrt(x): two multiplies and seven fused multiply-adds (Goldschmidt's coupled pair g -> sqrt x, h -> 1 / (2 sqrt x),
+// then two residual steps).  Same bits as sqrt for x in [2^-767, +inf): the compiler scales by 2^256 below 2^-767 only.
+GS_HD double gs_sqrt_refine(double x, double y) {
+  GS_NO_CONTRACT
+  double g = x * y, h = y * 0.5;
+  const double r = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r, g);
+  h = __builtin_fma(h, r, h);
+  double d = __builtin_fma(-g, g, x);
+  g = __builtin_fma(d, h, g);
+  d = __builtin_fma(-g, g, x);
+  return __builtin_fma(d, h, g);
+}
+// The bare core, for an argument known to lie in [2^-767, +inf) -- no zero, no infinity, no NaN: ten vector instructions.
+GS_HD double gs_sqrt_core(double x) { return gs_sqrt_refine(x, GS_RSQ_SEED(x)); }
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// one copy per kernel of the general square root, out of line: the waves that need it are the exception
+static __device__ __attribute__((noinline)) double gs_sqrt_slow(double x) { return sqrt(x); }
+#endif
+// sqrt(x) for ANY x, bit for bit.  +0 and [2^-767, +inf) take the core (13 vector instructions with the test); a wave (on the host:
+// an element) with anything else -- a subnormal or tiny value, +inf, NaN, a negative number, -0 -- takes the general sqrt.
+//   The test is two compares: (x >= 2^-767) holds for the core's range and for +inf, the class test for +0 and +inf; exactly one of
+// the two holds on +0 and on the core's range, both on +inf, neither on the rest.
+//   +0 stays on the short path because it is ordinary here (a line that carries nothing has S = 0 exactly): the estimate of +0 is
+// +inf, and with its high word held at 2^512's the core yields g = 0 * y = +0, residuals +0, result +0.  Inside the core's range
+// the estimate is below 2^384 and the minimum changes nothing (an integer minimum on the high word: y is not negative here).
+GS_HD double gs_sqrt_fast(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const bool core = (x >= 0x1p-767) != __builtin_amdgcn_class(x, 0x240);        // class bits: 0x040 +0, 0x200 +inf
+  if (__builtin_amdgcn_ballot_w64(!core) != 0) return gs_sqrt_slow(x);           // wave-uniform: no lane diverges
+#else
+  uint64_t xb;
+  __builtin_memcpy(&xb, &x, 8);
+  const bool core = (x >= 0x1p-767) != (xb == 0 || xb == 0x7ff0000000000000ull);
+  if (!core) return sqrt(x);
+#endif
+  double y = GS_RSQ_SEED(x);
+  uint64_t yb;
+  __builtin_memcpy(&yb, &y, 8);
+  const uint32_t hi = (uint32_t)(yb >> 32);
+  yb = ((uint64_t)(hi < 0x5ff00000u ? hi : 0x5ff00000u) << 32) | (uint32_t)yb;
+  __builtin_memcpy(&y, &yb, 8);
+  return gs_sqrt_refine(x, y);
+}
+
+// a / b, correctly rounded, for a normal b and a quotient that is normal (or a = +0): the reciprocal estimate, two Newton steps,
+// the quotient, its exact remainder and one correction -- eight vector instructions, the arithmetic of the compiler's a / b without
+// its scaling of operands near the ends of the exponent range and without its patching of special values.  Not for: b = 0, inf or
+// NaN; a quotient that overflows or is subnormal; a = -0, which comes out as +0 (the remainder -b q + a of a zero quotient is +0).
+GS_HD double gs_div_fast(double a, double b) {
+  GS_NO_CONTRACT
+  double y = GS_RCP_SEED(b);
+  double e = __builtin_fma(-b, y, 1.0);
+  y = __builtin_fma(y, e, y);
+  e = __builtin_fma(-b, y, 1.0);
+  y = __builtin_fma(y, e, y);
+  const double q = a * y;
+  const double r = __builtin_fma(-b, q, a);
+  return __builtin_fma(r, y, q);
+}
+
+// (SHORT = false: the division as the compiler expands it -- the same bits; for a kernel that comes out worse through the short one)
+template <bool SHORT = true>
 GS_HD double gs_log01(double x) {
   GS_NO_CONTRACT
   const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
@@ -40,7 +127,9 @@ GS_HD double gs_log01(double x) {
   double m = __builtin_frexp(x, &k);                 // x = m 2^k, m in [0.5, 1)
   if (m < 0.70710678118654752440) { m *= 2.0; k -= 1; }       // m in [sqrt(1/2), sqrt(2))
   const double f = m - 1.0;
-  const double s = f / (2.0 + f);
+  // f is in [-0.30, 0.42] and is +0 exactly (m = 1) or at least 2^-53 in magnitude, the divisor is in [1.70, 2.42]: the quotient is
+  // +0 or normal, never -0 and never subnormal, and the short division gives the bits of f / (2 + f)
+  const double s = SHORT ? gs_div_fast(f, 2.0 + f) : f / (2.0 + f);
   const double z = s * s;
   double R = Lg7;
   R = __builtin_fma(R, z, Lg6); R = __builtin_fma(R, z, Lg5); R = __builtin_fma(R, z, Lg4);

@@ -25,7 +25,9 @@
 // The budget of the default member (gs_k_step_fbs_flow2h on the 123-bus feeder; DESIGN.md section 9 item 5 has the table).
 // Counted in the gfx950 assembly: a sweep is ~400 vector instructions per wave, 189 of them FP64 (47 per bus); the epilogue's
 // line phase 4 passes x ~60 (37 FP64), its bus phase 4 x ~140 (82 FP64), wave 0's scalar tail ~300 dependent ones on 16 useful
-// lanes; 127 registers of 128; 47 KB of code.  A wave-wide FP64 instruction holds its SIMD for 4 cycles, rsq / rcp for 16.
+// lanes; 127 registers of 128; 46.9 KB of code.  A wave-wide FP64 instruction holds its SIMD for 4 cycles, rsq / rcp for 16.
+// (The line and bus counts are from before the epilogue's square roots became gs_sqrt_fast: 8 fewer per pass since, and 32 fewer in
+// a wave's load or weather draw; 4 113 vector instructions in the kernel, 4 222 before; 2 vector and 17 scalar registers spilled.)
 // Measured (phase stamps): the launch is ONE workgroup's chain of 68-70 k cycles (every workgroup is resident, two per CU); lines
 // ~5 k, buses ~4 k, tail 5.1 k against the other waves' 2.4 k.  The line and bus phases are bound by ISSUE: four waves share a
 // SIMD and fill each other's waits (4 waves x 4 passes x ~240 cycles = 3.8 k of the line phase's 5 k) -- asking for every pass's
@@ -158,8 +160,9 @@ __device__ __forceinline__ GsPairRef f2_pair(const GsLaneRows& S, int even_row) 
 }
 
 // 1 / x and 1 / sqrt(x) for normal, finite x of ordinary magnitude (voltages, determinants): the hardware estimate and two
-// Newton steps, accurate to about an ulp.  The compiler's IEEE division is ~40 instructions, its square root ~30, and the
-// Newton-Raphson item (three reciprocals, two square roots) was bound by exactly that instruction count.
+// Newton steps, accurate to about an ulp: 5 and 9 vector instructions.  The compiler's IEEE division is 11 (counted in this
+// compiler's gfx950 assembly), its square root 21, and the Newton-Raphson item (three reciprocals, two square roots) was bound
+// by exactly that instruction count.  (Where the exact result is wanted: gs_div_fast 8, gs_sqrt_fast 13, fastmath.h.)
 __device__ __forceinline__ double f2_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
@@ -169,6 +172,10 @@ __device__ __forceinline__ double f2_rsq(double x) {
   double y = __builtin_amdgcn_rsq(x);
   y = __builtin_fma(0.5 * y, __builtin_fma(-(x * y), y, 1.0), y);
   return __builtin_fma(0.5 * y, __builtin_fma(-(x * y), y, 1.0), y);
+}
+
+template <bool SHORT> __device__ __forceinline__ double f2_sqrt(double x) {      // (f2_step SHORT_MATH says which forms take which)
+  if constexpr (SHORT) return gs_sqrt_fast(x); else return sqrt(x);
 }
 
 // The kernels take their tables by value: 1.6 KB of kernel arguments, which the compiler reads in a dozen batches at the top
@@ -269,6 +276,14 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
                                         const GsPackArgs& PA, const GsFusedChecks& FC, const GsRolloutStep& RS,
                                         const double* __restrict__ pz = nullptr, const double* __restrict__ pl = nullptr) {
   f2_touch_arguments();
+  // The square roots of the epilogue, and the load and weather draws' logarithm division, radii and uniforms, are the short exact
+  // operations of fastmath.h: the same bits as the compiler's in fewer instructions.  SHORT_MATH = false keeps the compiler's, all of
+  // them: the forms that come out with more spilled registers through the short ones (tools/kernel_resources.py --diff against the
+  // build before; DESIGN.md section 9 item 5 has the table) stay the code they were.
+  constexpr bool FLOW2H = SOLVER == F2_FBS && NW == 8 && NI == 4 && IW == 16, NR_FLOW2 = SOLVER == F2_NR && IW == 32, NR_FLOW2S = SOLVER == F2_NR && IW == 8,
+                 MESH2 = SOLVER == F2_NRM;
+  constexpr bool SHORT_MATH = !((FLOW2H && CHK && PL) || (FLOW2H && !CHK && PZ && !PL) || (NR_FLOW2 && CHK && PZ && !PL) ||
+                                (NR_FLOW2S && CHK && PZ && PL) || (MESH2 && CHK && PL));
   // IW instances per workgroup (32; 16 or 8 for small feeders, where more of a wavefront's lanes go to different buses):
   // lane = hv * IW + l, sub-group hv of the wave works on its own bus for instance l
   constexpr int HV = 64 / IW;                          // sub-groups (buses) per wavefront
@@ -458,7 +473,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
   }
   if (wave == (NW >= 2 ? 1 : 0)) {
     // _update_weather + renewable models (grid_env.py:653-681, dynamics.py:120-142, 158-170); the halves take alternate generators
-    const GsWeather wx = weather_step(R, E, S, inst, tnew, snew, valid);
+    const GsWeather wx = weather_step<SHORT_MATH>(R, E, S, inst, tnew, snew, valid);
     const double elev = solar_elevation(valid ? tnew : told);
     for (int g0 = 0; g0 < ng; g0 += HV) {
       const int gi = g0 + hv; const bool on = gi < ng; const int gg = on ? gi : 0;
@@ -488,7 +503,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
         base4[0] = b01.x; base4[1] = b01.y; base4[2] = b23.x; base4[3] = b23.y;
       }
       double z[4] = {0.0, 0.0, 0.0, 0.0};
-      if (E.stochastic_loads) rng_normal_quad(seed, inst, snew, DRAW_LOAD0 + p, z);
+      if (E.stochastic_loads) rng_normal_quad<SHORT_MATH>(seed, inst, snew, DRAW_LOAD0 + p, z);
       double lp[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -1579,7 +1594,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     const double dr = vi.x - vj.x, di = vi.y - vj.y;
     const double ir = __builtin_fma(yr, dr, -(yi * di)), ii = __builtin_fma(yr, di, yi * dr);        // I = y (Vi - Vj)
     const double sr = __builtin_fma(vi.x, ir, vi.y * ii), si = __builtin_fma(vi.y, ir, -(vi.x * ii));  // S = Vi conj(I)
-    const double ql = (rating > 0.0) ? gs_div_by(sqrt(__builtin_fma(sr, sr, si * si)), rating, rinv) : 0.0;
+    const double ql = (rating > 0.0) ? gs_div_by(f2_sqrt<SHORT_MATH>(__builtin_fma(sr, sr, si * si)), rating, rinv) : 0.0;
     const double ld = (rating > 0.0) ? gs_div_by(fabs(sr), rating, rinv) : 0.0;
     if (on) {
       f2_row(S, R.LOAD + k) = ql;
@@ -1605,7 +1620,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
     const bool on = i0 < n; const int i = on ? i0 : n - 1;
     double2 ef = final_ef(i);
     if (!on) ef = make_double2(1.0, 0.0);                     // keep the wave on the series branch of the angle
-    const double v = sqrt(__builtin_fma(ef.x, ef.x, ef.y * ef.y));
+    const double v = f2_sqrt<SHORT_MATH>(__builtin_fma(ef.x, ef.x, ef.y * ef.y));
     const double ang = f2_angle(ef.y, ef.x);
     if (on) {
       f2_st2(f2_slot(i, l), make_double2(v, ang));
@@ -1642,7 +1657,7 @@ __device__ __forceinline__ void f2_step(const GsTables& T, const GsF2Tables& F, 
       const bool on = i0 < n; const int i = on ? i0 : n - 1;
       double2 ef = final_ef(i);
       if (!on) ef = make_double2(1.0, 0.0);                     // keep the wave on the series branch of the angle
-      const double v = sqrt(__builtin_fma(ef.x, ef.x, ef.y * ef.y));
+      const double v = f2_sqrt<SHORT_MATH>(__builtin_fma(ef.x, ef.x, ef.y * ef.y));
       const double ang = f2_angle(ef.y, ef.x);
       if (on) {
         f2_st2(f2_slot(i, l), make_double2(v, ang));

@@ -1558,6 +1558,12 @@ int gs_debug_write_rows(gs_handle* h, int32_t which, const double* values);
 /* test aid: the same families read back as values[B][width] (what the statistical tests of the stochastic load
  * model look at: the realised load powers are not part of the observation, grid_env.py:769-770) */
 int gs_debug_read_rows(gs_handle* h, int32_t which, double* values);
+/* test aid: the kernels' own square root, division and logarithm (csrc/fastmath.h) applied on the current device to host arrays of
+ * n elements, out[i] = op(in_a[i] [, in_b[i]]); in_b may be NULL except for the division.  Element i is thread i of a launch of
+ * 256-thread workgroups: elements 64 k .. 64 k + 63 share a wavefront. */
+enum { GS_FASTMATH_SQRT = 0 /* gs_sqrt_fast(a) */, GS_FASTMATH_DIV = 1 /* gs_div_fast(a, b) */, GS_FASTMATH_LOG01 = 2 /* gs_log01(a) */,
+       GS_FASTMATH_SQRT_CORE = 3 /* gs_sqrt_core(a): a in [2^-767, +inf) only */, GS_FASTMATH_COUNT = 4 };
+int gs_debug_fastmath(int32_t op, int64_t n, const double* in_a, const double* in_b, double* out);
 
 /* ======================================================================================
  * Post-step checks on the state a step / solve left on the device.

@@ -13,6 +13,9 @@ sys.path.insert(0, %r)
 import grid_fed_rl_gym_amd as P
 from grid_fed_rl_gym_amd import _lib
 _lib.LIB_PATH = sys.argv[1]
+import ctypes
+_have = ctypes.CDLL(sys.argv[1])      # a build of an earlier commit lacks the newest exports: none of them is on the step path
+_lib.SYMBOLS = [s for s in _lib.SYMBOLS if hasattr(_have, s[0])]
 out = {}
 for name, fs, B, solver in (("headline", P.ieee123_like(), 8192, "fbs"), ("nr", P.ieee123_like(), 8192, "nr"), ("c2", P.ieee13_like("epsilon"), 4096, "nr")):
     env = P.BatchedGridEnvironment(fs, num_envs=B, solver=solver, stochastic_loads=True, weather_variation=True)
@@ -36,3 +39,5 @@ for rnd in range(2):
     for lib in libs:
         r = subprocess.run([sys.executable, "-c", CHILD, os.path.join(ROOT, "grid_fed_rl_gym_amd", lib)], capture_output=True, text=True)
         print(lib, r.stdout.strip(), r.stderr.strip()[-300:], flush=True)
+        if r.returncode:              # a build that failed or faulted: nothing more is started on that GPU
+            sys.exit(r.returncode)
