@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Federated PPO over four utilities on one GPU: every client trains on its own feeders, a round averages them where they lie.
 
-    python examples/device_federated_ppo.py [--clients 4] [--batch 256] [--steps 32] [--rounds 3] [--clip-norm 0.25] [--noise-std 1e-4]
+    python examples/device_federated_ppo.py [--clients 4] [--batch 256] [--steps 32] [--rounds 3] [--clip-norm 0.25] [--noise-std 1e-4] [--prox-mu 0.01]
 
 A utility of the reference (federated/core.py) is a client with its own data.  Here it is an environment handle with its own
 `load_powers=` -- `randomized_load_powers` under the client's seed -- and its own `DeviceLearner`.  A round is
 {rollout, evaluate, two epochs of `DeviceLearner.step`, `FederatedLearners.round`}: the round measures every client's update against
 the global model, clips it to `--clip-norm`, averages by the number of samples, adds Gaussian noise of `--noise-std` and writes the new
 global model into every client's master parameters and packed images (`gs_fed_aggregate`).  Adam's moments survive the round, the next
-rollout acts with the averaged policy, and there is no torch in the loop and no weight on the host.
+rollout acts with the averaged policy, and there is no torch in the loop and no weight on the host.  `--prox-mu` > 0 is FedProx: after
+every round each client is anchored at the global model and its local steps are pulled back by `prox_mu (w - g)`.
 """
 import argparse
 import os
@@ -31,7 +32,7 @@ def main():
     ap.add_argument("--steps", type=int, default=32); ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=2); ap.add_argument("--minibatch", type=int, default=2048)
     ap.add_argument("--clip-norm", type=float, default=0.25); ap.add_argument("--noise-std", type=float, default=1e-4)
-    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--lr", type=float, default=3e-4); ap.add_argument("--prox-mu", type=float, default=0.0)
     a = ap.parse_args()
     spec = G.ieee13_like("epsilon")
     D, A = spec.obs_dim, spec.action_dim
@@ -70,12 +71,15 @@ def main():
             for epoch in range(a.epochs):
                 for batch in batches[k].epoch(a.epochs * r + epoch):
                     learners[k].step(batch)
-        out = fed.round(weights=[a.batch * a.steps] * a.clients, clip_norm=a.clip_norm, noise_std=a.noise_std, seed=7)
+        out = fed.round(weights=[a.batch * a.steps] * a.clients, clip_norm=a.clip_norm, noise_std=a.noise_std, seed=7,
+                        prox_mu=a.prox_mu if a.prox_mu > 0.0 else None)
         print(f"round {r}: mean episodic return per client " + " ".join(f"{x:+.3f}" for x in returns))
         for net in fed.nets:
             s = out[net]
             print(f"    {net:6s} update norms " + " ".join(f"{x:.4f}" for x in s["norms"]) + "  clip scales " + " ".join(f"{x:.3f}" for x in s["clip_scales"])
                   + f"  Adam step {learners[0].info(net)['step']}")
+            if a.prox_mu > 0.0 and r:                                  # (the local steps of this round ran under the last round's anchor)
+                print("           proximal penalty per client " + " ".join(f"{l.anchor_stats(net)['penalty_prox']:.3e}" for l in learners))
     final = learners[0].policy()                                       # every client holds the global model now
     print("first-layer weights moved by", float(np.abs(final.weight0 - policy.weight0).max()),
           "| sigma for (epsilon 1, delta 1e-5) at this clip:", G.gaussian_sigma(1.0, 1e-5, a.clip_norm / a.clients))

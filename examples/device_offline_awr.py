@@ -2,7 +2,7 @@
 """Offline RL on the device: advantage-weighted regression with an expectile critic on ONE fixed random-action dataset.
 
     python examples/device_offline_awr.py [--batch 256] [--steps 48] [--epochs 8] [--temperature 1.0] [--expectile 0.7]
-    python examples/device_offline_awr.py --clients 4 [--rounds 4] [--clip-norm 0.5]
+    python examples/device_offline_awr.py --clients 4 [--rounds 4] [--clip-norm 0.5] [--prox-mu 0.01]
 
 An offline client of the reference (algorithms/offline.py under federated/core.py's FederatedOfflineRL) holds a dataset some
 behaviour policy collected -- `collect_random_data` is the reference's own way to make one -- and never acts while it learns.  Here
@@ -14,8 +14,8 @@ are evaluated again on the same rollout; no new data is collected.  `evaluate_po
 environment with the same feeders, so that the dataset is left alone.
 
 With `--clients K` every client has its own `load_powers=` (its own feeders, hence its own dataset) and one
-`FederatedLearners.round` follows each client's local epochs: the reference's FederatedOfflineRL with AWR.  No torch in the loop, no
-weight and no sample on the host.
+`FederatedLearners.round` follows each client's local epochs: the reference's FederatedOfflineRL with AWR (`--prox-mu` > 0: with
+FedProx's proximal term on the clients' local steps).  No torch in the loop, no weight and no sample on the host.
 """
 import argparse
 import os
@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4); ap.add_argument("--minibatch", type=int, default=2048)
     ap.add_argument("--temperature", type=float, default=1.0); ap.add_argument("--weight-max", type=float, default=20.0)
     ap.add_argument("--expectile", type=float, default=0.7); ap.add_argument("--lr", type=float, default=1e-3)
-    ap.add_argument("--clip-norm", type=float, default=0.5)
+    ap.add_argument("--clip-norm", type=float, default=0.5); ap.add_argument("--prox-mu", type=float, default=0.0)
     a = ap.parse_args()
     spec = G.ieee13_like("epsilon")
     D, A = spec.obs_dim, spec.action_dim
@@ -83,7 +83,7 @@ def main():
         line = " | ".join(f"client {k}: value loss {l.stats('value')['value_loss']:.4f}, weighted log-likelihood {l.stats('policy')['surrogate']:+.3f}, "
                           f"capped {l.stats('policy')['clip_fraction']:.3f}" for k, l in enumerate(learners))
         if fed is not None:
-            out = fed.round(weights=[a.batch * a.steps] * K, clip_norm=a.clip_norm)
+            out = fed.round(weights=[a.batch * a.steps] * K, clip_norm=a.clip_norm, prox_mu=a.prox_mu if a.prox_mu > 0.0 else None)
             line += " | update norms " + " ".join(f"{x:.3f}" for x in out["policy"]["norms"])
         print(f"round {r}: {line}")
 

@@ -25,7 +25,7 @@ from .rollout import (collect_random_data, collect_policy_data, collect_onpolicy
                       download_rollout, save_rollout, load_rollout, continue_rollout, rollout_window_np, ReplayWindow)
 from .policy import MLPPolicy, MLPValue, MLPQ
 from .learner import (DeviceLearner, ppo_grad_np, value_grad_np, awr_grad_np, expectile_grad_np, pathwise_grad_np, pathwise_noise_np, adam_np,
-                      split_parameters)
+                      split_parameters, anchor_term_np, anchor_penalty_terms_np, fisher_np, fisher_importance_np, ewc_merge_np)
 from .federated import FederatedLearners, fedavg_np, fed_noise_np, filter_outliers_np, gaussian_sigma
 from .sharding import LoopbackShards, ShardedGridEnvironment, shard_range
 from .multi_agent import AgentConfig, BatchedMultiAgentWrapper
@@ -47,6 +47,7 @@ __all__ = [
     "load_rollout_data", "transitions_to_rollout", "rollout_to_transitions", "concat_rollouts", "download_rollout", "save_rollout", "load_rollout",
     "continue_rollout", "rollout_window_np", "ReplayWindow",
     "DeviceLearner", "ppo_grad_np", "value_grad_np", "awr_grad_np", "expectile_grad_np", "pathwise_grad_np", "pathwise_noise_np", "adam_np", "split_parameters",
+    "anchor_term_np", "anchor_penalty_terms_np", "fisher_np", "fisher_importance_np", "ewc_merge_np",
     "FederatedLearners", "fedavg_np", "fed_noise_np", "filter_outliers_np", "gaussian_sigma",
     "ShardedGridEnvironment", "LoopbackShards", "shard_range",
     "AgentConfig", "BatchedMultiAgentWrapper", "feeder_from_dict", "feeder_to_dict", "network_dict_normalized",

@@ -513,6 +513,39 @@ class gs_fed_stats_out(C.Structure):
                 ("n", C.c_int32)]
 
 
+# parameter anchors (include/gridstep.h "parameter anchors"): GS_ANCHOR_* and the structs of gs_learner_anchor_* / gs_learner_fisher_*
+GS_ANCHOR_PROX, GS_ANCHOR_EWC = 1, 2
+ANCHOR_SLOTS = {"prox": GS_ANCHOR_PROX, "ewc": GS_ANCHOR_EWC, "both": GS_ANCHOR_PROX | GS_ANCHOR_EWC}
+ANCHOR_ARRAYS = ("prox", "ewc_importance", "ewc_centre", "fisher_pending")      # gs_learner_anchor_download's, in argument order
+
+
+class gs_learner_anchor_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("prox_mu", C.c_double), ("ewc_lambda", C.c_double)]
+
+
+class gs_fisher_config(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("min_importance", C.c_double), ("decay", C.c_double)]
+
+
+class gs_learner_anchor_stats_out(C.Structure):
+    _fields_ = [("penalty_prox", C.c_double), ("penalty_ewc", C.c_double), ("grad_norm_loss", C.c_double), ("prox_mu", C.c_double),
+                ("ewc_lambda", C.c_double), ("tasks", C.c_int64), ("fisher_samples", C.c_int64)]
+
+
+def anchor_config(prox_mu=0.0, ewc_lambda=0.0, struct_size=None) -> gs_learner_anchor_config:
+    return gs_learner_anchor_config(C.sizeof(gs_learner_anchor_config) if struct_size is None else int(struct_size), 0, float(prox_mu),
+                                    float(ewc_lambda))
+
+
+def fisher_config(min_importance=1e-3, decay=1.0, struct_size=None) -> gs_fisher_config:
+    return gs_fisher_config(C.sizeof(gs_fisher_config) if struct_size is None else int(struct_size), 0, float(min_importance), float(decay))
+
+
+def anchor_check(c: Optional[gs_learner_anchor_config]) -> Tuple[int, str]:
+    """gs_learner_anchor_check: (return code, message) -- the value rules of the anchors' coefficients on the host alone (no GPU)."""
+    return _host_check("gs_learner_anchor_check", None if c is None else C.byref(c))
+
+
 def learner_net(net) -> int:
     """The GS_LEARNER_* number of ``net``: "policy", "value", a cost channel's name (``COST_CHANNELS``), a twin Q network's name
     (``Q_NETS``), or the number itself for the policy and the state critics (the Q networks go by name)."""
@@ -675,6 +708,16 @@ SYMBOLS = [
     ("gs_fed_aggregate", C.c_int, [_FED, C.POINTER(gs_fed_round)]),
     ("gs_fed_stats", C.c_int, [_FED, C.POINTER(gs_fed_stats_out)]),
     ("gs_fed_download", C.c_int, [_FED, C.c_void_p]),
+    ("gs_learner_anchor_check", C.c_int, [C.POINTER(gs_learner_anchor_config)]),
+    ("gs_learner_anchor_here", C.c_int, [_H, C.c_int32, C.c_void_p]),
+    ("gs_learner_anchor_set", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_anchor_config)]),
+    ("gs_learner_anchor_get", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_anchor_config)]),
+    ("gs_learner_fisher_begin", C.c_int, [_H, C.c_int32]),
+    ("gs_learner_fisher_accumulate", C.c_int, [_H, C.c_int32, C.POINTER(gs_onpolicy_batch_out), C.c_int32, C.c_void_p]),
+    ("gs_learner_fisher_commit", C.c_int, [_H, C.c_int32, C.POINTER(gs_fisher_config)]),
+    ("gs_learner_anchor_clear", C.c_int, [_H, C.c_int32, C.c_int32]),
+    ("gs_learner_anchor_stats", C.c_int, [_H, C.c_int32, C.POINTER(gs_learner_anchor_stats_out)]),
+    ("gs_learner_anchor_download", C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 # the gs3_* entry points (three-phase solver) are bound in unbalanced.py
 
@@ -1942,6 +1985,82 @@ class Handle:
             raise PowerFlowError(f"learner_download: unknown array(s) {sorted(unknown)}")
         ptr = lambda k: out[k].ctypes.data if k in out else None
         self._check(self._lib.gs_learner_download(self._h, _net_number(net), ptr("params"), ptr("grads"), ptr("m"), ptr("v")))
+        return out
+
+    # -- parameter anchors (gs_learner_anchor_*, gs_learner_fisher_*) -----------------------------------------------------------------
+    def learner_anchor_here(self, net, params=None) -> None:
+        """gs_learner_anchor_here: the PROX centre of ``net`` becomes ``params`` (flat float32 [param_count] in torch order), or a
+        device copy of the learner's current master parameters."""
+        ptr = None
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=np.float32).reshape(-1)
+            P = self.learner_info(net)["param_count"]
+            if params.size != P:
+                raise PowerFlowError(f"learner_anchor_here: {params.size} values for {P} parameters")
+            ptr = params.ctypes.data
+        self._check(self._lib.gs_learner_anchor_here(self._h, _net_number(net), ptr))
+
+    def learner_anchor_set(self, net, cfg: gs_learner_anchor_config) -> None:
+        """gs_learner_anchor_set: the coefficients of ``cfg`` (``anchor_config``) apply from the next step of ``net``."""
+        self._check(self._lib.gs_learner_anchor_set(self._h, _net_number(net), C.byref(cfg)))
+
+    def learner_anchor_get(self, net) -> dict:
+        """gs_learner_anchor_get: ``prox_mu`` and ``ewc_lambda`` in force."""
+        o = gs_learner_anchor_config()
+        self._check(self._lib.gs_learner_anchor_get(self._h, _net_number(net), C.byref(o)))
+        return dict(prox_mu=float(o.prox_mu), ewc_lambda=float(o.ewc_lambda))
+
+    def learner_fisher_begin(self, net) -> None:
+        """gs_learner_fisher_begin: a task opens for ``net``: the pending Fisher sum and its sample count are zeroed."""
+        self._check(self._lib.gs_learner_fisher_begin(self._h, _net_number(net)))
+
+    def learner_fisher_accumulate(self, net, batch: dict, n: Optional[int] = None, stream=None) -> None:
+        """gs_learner_fisher_accumulate (asynchronous): the per-sample squared gradients of ``net``'s loss on ``batch`` (as
+        ``learner_step``'s) join the open task's pending sum; no parameter, moment or statistic changes."""
+        b = gs_onpolicy_batch_out()
+        addr = lambda x: None if x is None else int(x) if isinstance(x, (int, np.integer)) else int(x.__cuda_array_interface__["data"][0]) if hasattr(x, "__cuda_array_interface__") else int(x.data_ptr())
+        for k, x in batch.items():
+            if k in ("cost_advantages", "cost_returns"):
+                for c in range(3):
+                    getattr(b, k)[c] = addr(x[c])
+            elif k in dict(ONPOLICY_BATCH_FIELDS) or k == "adv_stats":
+                setattr(b, k, addr(x))
+        if n is None:
+            obs = batch.get("observations")
+            n = int(obs.shape[0]) if hasattr(obs, "shape") else 0
+        self._check(self._lib.gs_learner_fisher_accumulate(self._h, _net_number(net), C.byref(b), int(n), _stream_arg(stream)))
+
+    def learner_fisher_commit(self, net, cfg: gs_fisher_config) -> None:
+        """gs_learner_fisher_commit (asynchronous): the open task ends at the current master parameters and is merged into the EWC
+        slot under ``cfg`` (``fisher_config``)."""
+        self._check(self._lib.gs_learner_fisher_commit(self._h, _net_number(net), C.byref(cfg)))
+
+    def learner_anchor_clear(self, net, which="both") -> None:
+        """gs_learner_anchor_clear: ``which`` a name of ``ANCHOR_SLOTS`` or the GS_ANCHOR_* bits."""
+        if isinstance(which, str):
+            if which not in ANCHOR_SLOTS:
+                raise ValueError(f"learner anchor: unknown slot {which!r}; one of {sorted(ANCHOR_SLOTS)}")
+            which = ANCHOR_SLOTS[which]
+        self._check(self._lib.gs_learner_anchor_clear(self._h, _net_number(net), int(which)))
+
+    def learner_anchor_stats(self, net) -> dict:
+        """gs_learner_anchor_stats: ``penalty_prox``, ``penalty_ewc``, ``grad_norm_loss``, ``prox_mu``, ``ewc_lambda`` (floats) and
+        ``tasks``, ``fisher_samples`` (ints) of the last step taken with a non-zero coefficient (waits for it)."""
+        o = gs_learner_anchor_stats_out()
+        self._check(self._lib.gs_learner_anchor_stats(self._h, _net_number(net), C.byref(o)))
+        return dict(penalty_prox=float(o.penalty_prox), penalty_ewc=float(o.penalty_ewc), grad_norm_loss=float(o.grad_norm_loss),
+                    prox_mu=float(o.prox_mu), ewc_lambda=float(o.ewc_lambda), tasks=int(o.tasks), fisher_samples=int(o.fisher_samples))
+
+    def learner_anchor_download(self, net, want=ANCHOR_ARRAYS) -> dict:
+        """gs_learner_anchor_download: flat host copies [param_count], in torch order, of the arrays named in ``want``
+        (``ANCHOR_ARRAYS``: float32 but ``fisher_pending``, which is float64)."""
+        P = self.learner_info(net)["param_count"]
+        unknown = set(want) - set(ANCHOR_ARRAYS)
+        if unknown:
+            raise PowerFlowError(f"learner_anchor_download: unknown array(s) {sorted(unknown)}")
+        out = {k: np.empty(P, dtype=np.float64 if k == "fisher_pending" else np.float32) for k in want}
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        self._check(self._lib.gs_learner_anchor_download(self._h, _net_number(net), *[ptr(k) for k in ANCHOR_ARRAYS]))
         return out
 
     def learner_view(self, net, stream=None) -> dict:

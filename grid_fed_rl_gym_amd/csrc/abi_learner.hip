@@ -6,7 +6,9 @@
 // policy's step whose gradient flows through the twins (kernels_pathwise.hip, section 23), gs_learner_step_conservative a twin's step
 // with the logsumexp penalty over 3 n rows (kernels_conservative.hip, section 26).  All steps run one pipeline: the checks on
 // the minibatches, the growth of h->tr and every launch of kernels_train.hip (queue_*) are file-local helpers, stated once; a step adds
-// its head and statistics.  The table of the learners' networks (net_name, installed; handle.h) is defined here.  The learners' buffers
+// its head and statistics.  gs_learner_step's own part from its checks through the backward-data pass is learner_backprop (handle.h),
+// which gs_learner_fisher_accumulate of abi_anchor.hip calls too; queue_grad_reduce queues abi_anchor.hip's term on the parameters behind
+// the reduction while a coefficient is non-zero (section 31).  The table of the learners' networks (net_name, installed; handle.h) is defined here.  The learners' buffers
 // are made and released here: parameters with the learner (learner_drop), what is sized by n with the rollout's (learner_scratch_release).
 #include <cmath>
 #include <cstring>
@@ -34,6 +36,7 @@ void learner_drop(gs_handle* h, int k) {
   if (L.live) (void)hipStreamSynchronize(h->stream);      // (a queued step still reads and writes the parameters)
   L.params.release(); L.grad.release(); L.m.release(); L.v.release(); L.wt.release(); L.stats.release(); L.blocksum.release();
   learner_scratch_release_one(L);
+  L.an.release();      // (the anchors are the learner's: DESIGN.md section 31)
   if (L.ev) { (void)hipEventDestroy(L.ev); L.ev = nullptr; }
   L.live = false; L.steps = 0; L.loss = gs_learner_loss{}; L.signal = GS_SIGNAL_BATCH;
   if (k == GS_LEARNER_POLICY || k == h->cq.net) h->cq.n_last = 0;      // (the conservative step's view names both learners)
@@ -55,6 +58,20 @@ void learner_scratch_release(gs_handle* h) {
 void learner_release(gs_handle* h) {
   for (int k = 0; k < GS_LEARNER_COUNT; ++k) learner_drop(h, k);
   learner_scratch_release(h);
+}
+
+int train_grad_args(gs_handle* h, const GsTrainNet& N, const float* obs, int n, int D, GsTrainGradArgs& G) {
+  const gs_handle::TrainScratch& tr = h->tr;
+  G.N = N; G.obs = obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
+  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
+  int blocks = 0;
+  for (int l = 0; l < N.n_layers; ++l) {
+    G.blk0[l] = blocks;
+    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
+    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
+  }
+  G.blk0[N.n_layers] = blocks;
+  return blocks;
 }
 
 const char* net_name(int net) {
@@ -140,20 +157,17 @@ int queue_grad_reduce(gs_handle* h, gs_handle::Learner& Ln, const float* obs, in
   gs_handle::TrainScratch& tr = h->tr;
   const int segments = gs_tr_segments(n);
   GsTrainGradArgs G{};
-  G.N = N; G.obs = obs; G.acts = tr.acts; G.deltas = tr.deltas; G.partial = tr.partial; G.n = n; G.D = D;
-  const int wide_in = 16 * GS_TR_WT, wide_out = 16 * GS_TR_WT_OUT;
-  int blocks = 0;
-  for (int l = 0; l < N.n_layers; ++l) {
-    G.blk0[l] = blocks;
-    G.in_blocks[l] = (N.dims[l] + wide_in - 1) / wide_in;
-    blocks += ((N.dims[l + 1] + wide_out - 1) / wide_out) * G.in_blocks[l];
-  }
-  G.blk0[N.n_layers] = blocks;
+  const int blocks = train_grad_args(h, N, obs, n, D, G);
   hipLaunchKernelGGL(gs_k_train_grad, dim3(blocks, segments), dim3(64), 0, h->stream, G);
   HIPCHK(h, hipGetLastError());
   GsTrainReduceArgs R{tr.partial, Ln.grad, Ln.blocksum, N.P, segments};
   hipLaunchKernelGGL(gs_k_train_reduce, dim3(gs_tr_red_blocks(N.P)), dim3(GS_TR_RED_THREADS), 0, h->stream, R);
   HIPCHK(h, hipGetLastError());
+  // the terms on the parameters (abi_anchor.hip): one more launch, only while a coefficient is non-zero
+  if (Ln.an.mu != 0.0 || Ln.an.lambda != 0.0) {
+    const int rc = anchor_queue(h, Ln);
+    if (rc) return rc;
+  }
   return gs_tr_red_blocks(N.P);
 }
 
@@ -238,16 +252,52 @@ int gs_learner_create(gs_handle* h, int32_t net, const gs_learner_config* cfg) {
 
 int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, void* consumer_stream) {
   if (!h || !batch) return fail(h, GS_E_INVALID, "handle / batch is NULL");
-  if (!net_ok(net)) return fail(h, GS_E_INVALID, "gs_learner_step: unknown net %d", net);
-  if (n <= 0 || n > (1 << 24)) return fail(h, GS_E_INVALID, "gs_learner_step: n = %d outside 1 .. 2^24", n);
+  LearnerPass ps{};
+  int rc = learner_backprop(h, "gs_learner_step", net, batch, n, nullptr, ps);
+  if (rc) return rc;
+  gs_handle::Learner& Ln = h->learner[net];
+  const gs_handle::OnPolicyBatches& ob = h->opb;
+  const gs_handle::Rollout& ro = h->ro;
+  const gs_learner_config& cfg = Ln.cfg;
+  const bool policy = net == GS_LEARNER_POLICY;
+  const int red_blocks = queue_grad_reduce(h, Ln, ps.rows, n, ps.Din);
+  if (red_blocks < 0) return red_blocks;
+
+  if (ps.loss == GS_LOSS_AWR) {
+    GsTrainAwrStatArgs W{};
+    W.term0 = Ln.term0; W.term1 = Ln.term1; W.lp_new = Ln.lp_new; W.logp = ro.logp_recorded ? ro.logp.p : nullptr; W.idx = batch->indices; W.capped = Ln.clipped;
+    W.blocksum = Ln.blocksum; W.stats = Ln.stats; W.N = ob.N; W.n = n; W.blocks = red_blocks; W.ent_coef = cfg.ent_coef;
+    hipLaunchKernelGGL(gs_k_train_stats_awr, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, W);
+  } else {                                   // (an expectile critic: a critic's sum of term0)
+    GsTrainStatArgs S{};
+    S.term0 = Ln.term0; S.term1 = Ln.term1; S.lp_new = Ln.lp_new; S.logp = ro.logp; S.idx = batch->indices; S.clipped = Ln.clipped;
+    S.blocksum = Ln.blocksum; S.stats = Ln.stats; S.N = ob.N; S.n = n; S.blocks = red_blocks; S.policy = policy; S.ent_coef = cfg.ent_coef;
+    hipLaunchKernelGGL(gs_k_train_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, S);
+  }
+  HIPCHK(h, hipGetLastError());
+
+  if ((rc = queue_adam(h, Ln))) return rc;
+  Ln.steps += 1; Ln.n_last = n;
+  return publish(h, h->stream, Ln.ev, consumer_stream);
+}
+
+}  // extern "C"
+
+// ---- gs_learner_step from its checks through the backward-data pass (handle.h): what the step and gs_learner_fisher_accumulate
+// (abi_anchor.hip) share.  `who`: the entry's name, for the messages; `extra`: a check of the caller's that runs behind the step's own
+// and before anything is launched (NULL: none).  Leaves Ln.n_last at 0: the step sets it once every launch is queued ----
+int gsi::learner_backprop(gs_handle* h, const char* who, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, int (*extra)(gs_handle*, int32_t),
+                          LearnerPass& ps) {
+  if (!net_ok(net)) return fail(h, GS_E_INVALID, "%s: unknown net %d", who, net);
+  if (n <= 0 || n > (1 << 24)) return fail(h, GS_E_INVALID, "%s: n = %d outside 1 .. 2^24", who, n);
   gs_handle::Learner& Ln = h->learner[net];
   Installed I{};
-  if (!Ln.live || !installed(h, net, I)) return fail(h, GS_E_STATE, "gs_learner_step: no learner for %s (gs_learner_create after the network was installed)", net_name(net));
+  if (!Ln.live || !installed(h, net, I)) return fail(h, GS_E_STATE, "%s: no learner for %s (gs_learner_create after the network was installed)", who, net_name(net));
   const gs_handle::OnPolicyBatches& ob = h->opb;
   const gs_handle::Rollout& ro = h->ro;
   int rc = GS_OK;
-  if ((rc = check_batches(h, "gs_learner_step"))) return rc;
-  if ((rc = check_norm(h, "gs_learner_step", net, I))) return rc;
+  if ((rc = check_batches(h, who))) return rc;
+  if ((rc = check_norm(h, who, net, I))) return rc;
   const int D = h->obs_dim;
   const bool policy = net == GS_LEARNER_POLICY, qnet = net_is_q(net);
   // what the head regresses on or weights with: a field of the batch, or (a Q learner, GS_SIGNAL_Q) an array of gs_rollout_evaluate_q
@@ -257,12 +307,13 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   // (a Q learner under GS_Q_TARGET_POLICY regresses on gs_rollout_evaluate_q_next's target: DESIGN.md section 25)
   const bool policy_target = qnet && h->qn.target_source == GS_Q_TARGET_POLICY;
   if (policy_target && !q_next_current(h))
-    return fail(h, GS_E_STATE, "gs_learner_step: gs_rollout_evaluate_q_next has not run on the last rollout (%s reads its td_target under GS_Q_TARGET_POLICY)", net_name(net));
-  if (gathered && !policy_target && !q_current(h)) return fail(h, GS_E_STATE, "gs_learner_step: gs_rollout_evaluate_q has not run on the last rollout (%s reads its arrays)", net_name(net));
+    return fail(h, GS_E_STATE, "%s: gs_rollout_evaluate_q_next has not run on the last rollout (%s reads its td_target under GS_Q_TARGET_POLICY)", who, net_name(net));
+  if (gathered && !policy_target && !q_current(h)) return fail(h, GS_E_STATE, "%s: gs_rollout_evaluate_q has not run on the last rollout (%s reads its arrays)", who, net_name(net));
   const int loss = Ln.loss.kind;
-  if (policy && loss == GS_LOSS_DEFAULT && !ro.logp_recorded) return fail(h, GS_E_STATE, "gs_learner_step: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)");
+  if (policy && loss == GS_LOSS_DEFAULT && !ro.logp_recorded) return fail(h, GS_E_STATE, "%s: the last rollout recorded no log-probabilities (a stochastic GS_POLICY_MLP rollout does)", who);
   if (!batch->observations || (!gathered && !target) || ((policy || gathered) && !batch->indices))
-    return fail(h, GS_E_INVALID, "gs_learner_step: the batch lacks %s", !batch->observations ? "observations" : (!gathered && !target) ? (policy ? "advantages" : "returns") : "indices");
+    return fail(h, GS_E_INVALID, "%s: the batch lacks %s", who, !batch->observations ? "observations" : (!gathered && !target) ? (policy ? "advantages" : "returns") : "indices");
+  if (extra && (rc = extra(h, net))) return rc;
   GS_ENTER(h);
   const GsTrainNet& N = Ln.net;
   gs_handle::TrainScratch& tr = h->tr;
@@ -328,26 +379,11 @@ int gs_learner_step(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batc
   HIPCHK(h, hipGetLastError());
 
   if ((rc = queue_bwd_data(h, N, tr.acts, tr.deltas, n))) return rc;
-  const int red_blocks = queue_grad_reduce(h, Ln, rows, n, Din);
-  if (red_blocks < 0) return red_blocks;
-
-  if (loss == GS_LOSS_AWR) {
-    GsTrainAwrStatArgs W{};
-    W.term0 = Ln.term0; W.term1 = Ln.term1; W.lp_new = Ln.lp_new; W.logp = ro.logp_recorded ? ro.logp.p : nullptr; W.idx = batch->indices; W.capped = Ln.clipped;
-    W.blocksum = Ln.blocksum; W.stats = Ln.stats; W.N = ob.N; W.n = n; W.blocks = red_blocks; W.ent_coef = cfg.ent_coef;
-    hipLaunchKernelGGL(gs_k_train_stats_awr, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, W);
-  } else {                                   // (an expectile critic: a critic's sum of term0)
-    GsTrainStatArgs S{};
-    S.term0 = Ln.term0; S.term1 = Ln.term1; S.lp_new = Ln.lp_new; S.logp = ro.logp; S.idx = batch->indices; S.clipped = Ln.clipped;
-    S.blocksum = Ln.blocksum; S.stats = Ln.stats; S.N = ob.N; S.n = n; S.blocks = red_blocks; S.policy = policy; S.ent_coef = cfg.ent_coef;
-    hipLaunchKernelGGL(gs_k_train_stats, dim3(1), dim3(GS_TR_STAT_THREADS), 0, h->stream, S);
-  }
-  HIPCHK(h, hipGetLastError());
-
-  if ((rc = queue_adam(h, Ln))) return rc;
-  Ln.steps += 1; Ln.n_last = n;
-  return publish(h, h->stream, Ln.ev, consumer_stream);
+  ps.rows = rows; ps.Din = Din; ps.loss = loss;
+  return GS_OK;
 }
+
+extern "C" {
 
 int gs_learner_stats(gs_handle* h, int32_t net, gs_learner_stats_out* out) {
   if (!h || !out) return fail(h, GS_E_INVALID, "handle / out is NULL");

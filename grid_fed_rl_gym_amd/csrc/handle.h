@@ -211,6 +211,20 @@ struct gs_handle : GsPlan {
     DevBuf<double> lp_new, ratio, term0, term1, stats, blocksum; DevBuf<int32_t> clipped; int n_last = 0;
     hipEvent_t ev = nullptr;
     int signal = GS_SIGNAL_BATCH;      // gs_learner_set_signal; reset like `loss`
+    // parameter anchors (abi_anchor.hip), all made on first use by the gs_learner_anchor_* / gs_learner_fisher_*
+    // entries and gone with the learner (learner_drop): prox [P] the PROX centre (have_prox), importance / centre [P] the EWC slot
+    // (tasks commits merged), pending [P] the open or last task's Fisher sum over `samples` samples (open: between begin and commit),
+    // sums [3][red blocks] what gs_k_train_anchor leaves for gs_learner_anchor_stats.  mu / lambda: the coefficients the next step
+    // reads; stepped: a step ran with one of them non-zero, under step_mu / step_lambda.
+    struct GS_HIDDEN Anchor {
+      DevBuf<float> prox, importance, centre; DevBuf<double> pending, sums;
+      bool have_prox = false, open = false, stepped = false;
+      double mu = 0.0, lambda = 0.0, step_mu = 0.0, step_lambda = 0.0;
+      int64_t tasks = 0, samples = 0;
+      void drop_prox() { prox.release(); have_prox = false; mu = 0.0; }
+      void drop_ewc() { importance.release(); centre.release(); pending.release(); open = false; tasks = 0; samples = 0; lambda = 0.0; }
+      void release() { drop_prox(); drop_ewc(); sums.release(); stepped = false; step_mu = step_lambda = 0.0; }
+    } an;
   } learner[GS_LEARNER_COUNT];
   // (qsa [n][obs_dim + A], qy [n]: the Q learner's input rows and targets, and the Q-based signals; abi_learner.hip)
   struct GS_HIDDEN TrainScratch { DevBuf<float> acts, deltas, partial, qsa, qy; } tr;
@@ -520,6 +534,21 @@ void learner_release(gs_handle* h);
 const char* net_name(int net);
 struct Installed { const GsPolicyLayerF32* L; const int32_t* dims; int n_layers, activation; const std::vector<double>* norm; const DevBuf<char>* blob; };
 bool installed(const gs_handle* h, int net, Installed& I);
+
+// the argument block of gs_k_train_grad / gs_k_train_grad_sq over h->tr's passes on the input rows `obs` [n][D]; returns the launch's
+// workgroups along x (its y: gs_tr_segments(n))
+int train_grad_args(gs_handle* h, const GsTrainNet& N, const float* obs, int n, int D, GsTrainGradArgs& G);
+// gs_learner_step from its checks through the backward-data pass, shared with gs_learner_fisher_accumulate: the gather (where the net
+// has one), the forward pass, the head of the learner's loss and the backward-data pass on `batch`, h->tr holding the passes.  `who`
+// names the entry in the messages; `extra` (NULL: none) is a check of the caller's, run behind the step's own and before any launch.
+// ps: the input rows [n][Din] the weight gradient reads, and the loss (GS_LOSS_*) the head ran
+struct LearnerPass { const float* rows; int Din, loss; };
+int learner_backprop(gs_handle* h, const char* who, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, int (*extra)(gs_handle*, int32_t),
+                     LearnerPass& ps);
+
+// ---- the terms on the parameters (abi_anchor.hip): gs_k_train_anchor on Ln's reduced gradient under Ln.an's
+// coefficients, queued on the handle's stream behind gs_k_train_reduce (queue_grad_reduce of abi_learner.hip) ----
+int anchor_queue(gs_handle* h, gs_handle::Learner& Ln);
 
 // ---- owner of the Q networks, their targets and their arrays over the rollout (abi_q.hip) ----
 void q_release(gs_handle* h);              // everything

@@ -12,6 +12,7 @@
 #include "q_next.h"
 #include "pathwise.h"
 #include "conservative.h"
+#include "anchor.h"
 #include "refresh.h"
 #include "rollout_load.h"
 #include "rollout_window.h"
@@ -98,6 +99,10 @@ __global__ void gs_k_cql_rows(GsCqlRowsArgs R);
 __global__ void gs_k_cql_lse(GsCqlLseArgs L);
 __global__ void gs_k_cql_head(GsCqlHeadArgs H);
 __global__ void gs_k_cql_stats(GsCqlStatArgs S);
+__global__ void gs_k_train_anchor(GsAnchorArgs A);
+__global__ void gs_k_train_grad_sq(GsTrainGradArgs P);
+__global__ void gs_k_fisher_accumulate(GsFisherAccArgs A);
+__global__ void gs_k_fisher_commit(GsFisherCommitArgs C);
 __global__ void gs_k_refresh_terms(GsRefreshTermsArgs G);
 __global__ void gs_k_refresh_rows(GsRefreshRowsArgs G);
 __global__ void gs_k_refresh_td_policy(GsRefreshTdPolicyArgs G);

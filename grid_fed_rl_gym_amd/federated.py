@@ -4,6 +4,8 @@ and its own rollouts -- average their networks where they lie.  ``FederatedLearn
 the global parameters, clips them, averages them by weight, adds Gaussian noise and writes the result into every client's master
 parameters and packed images: no weight crosses the host and Adam's moments and step counts survive the round.
 
+``round(prox_mu=...)`` adds FedProx's proximal term to the clients' local steps.
+
 What it restates of the reference: ``FedAvgAggregator.aggregate`` (federated/core.py: the mean weighted by ``num_samples``),
 ``FederatedOfflineRL._train_round`` (aggregate, hand the global model back to EVERY client), ``DifferentialPrivacy`` (privacy.py:
 norm clipping and the Gaussian mechanism) and ``SecureAsyncAggregator._filter_byzantine_updates`` (async_coordinator.py:159-219).
@@ -195,15 +197,31 @@ class FederatedLearners:
         self._check(self._lib.gs_fed_set_global(f, ptr))
 
     def aggregate(self, net, participants, weights, clip_norm=0.0, noise_std=0.0, server_lr=1.0, seed=0, round=0, reset_moments=False,
-                  struct_size=None) -> None:
-        """``gs_fed_aggregate`` as it is (asynchronous): what ``round`` calls per network."""
+                  struct_size=None, prox_mu=None) -> None:
+        """``gs_fed_aggregate`` as it is (asynchronous): what ``round`` calls per network.  ``prox_mu``: see ``round``."""
         _, f = self._fed(net)
+        prox_mu = self._prox_mu(prox_mu)
         part = [int(p) for p in participants]
         idx = (C.c_int32 * max(len(part), 1))(*part)
         w = (C.c_double * max(len(part), 1))(*[float(x) for x in weights])
         r = _lib.gs_fed_round(C.sizeof(_lib.gs_fed_round) if struct_size is None else int(struct_size), len(part), idx, w, float(clip_norm),
                               float(noise_std), float(server_lr), int(seed) & 0xFFFFFFFFFFFFFFFF, int(round) & _M32, int(bool(reset_moments)))
         self._check(self._lib.gs_fed_aggregate(f, C.byref(r)))
+        if prox_mu is not None:
+            # (the round has written the global model into every client, and every client's stream waits for it: the copy of a
+            # client's own parameters IS the global model)
+            for l in self.learners:
+                l.anchor_here(net)
+                l.set_anchor(net, prox_mu=prox_mu)
+
+    @staticmethod
+    def _prox_mu(prox_mu) -> Optional[float]:
+        if prox_mu is None:
+            return None
+        prox_mu = float(prox_mu)
+        if not math.isfinite(prox_mu) or prox_mu < 0.0:
+            raise ValueError(f"FederatedLearners: prox_mu = {prox_mu} must be finite and >= 0")
+        return prox_mu
 
     def stats(self, net="policy") -> dict:
         """The last round's ``participants``-ordered ``norms``, ``clip_scales`` (c_k) and ``coefficients`` (a_k), ``noise_std``,
@@ -216,12 +234,15 @@ class FederatedLearners:
                     noise_std=float(o.noise_std), round=int(o.round), rounds=int(o.rounds), n=n)
 
     def round(self, weights=None, participants=None, clip_norm=0.0, noise_std=0.0, server_lr=1.0, seed=0, reset_moments=False,
-              byzantine_tolerance=0) -> Dict[str, dict]:
+              byzantine_tolerance=0, prox_mu=None) -> Dict[str, dict]:
         """One federated round of every network.  ``weights``: one per participant (``num_samples``; equal by default);
         ``participants``: client indices (all by default); ``clip_norm`` / ``noise_std``: the clip of every update's norm and the
         Gaussian noise on the result (0: off); ``byzantine_tolerance`` > 0: ``measure`` and ``filter_outliers_np`` first, the
         dropped clients neither count nor weigh (they still receive the global model).  The round counter, which the noise is
-        drawn on, advances by itself.  Returns per network the ``stats`` with ``participants`` (who was averaged) and ``filtered``
+        drawn on, advances by itself.  ``prox_mu`` (FedProx): with a value, once the global model is in the
+        clients, every client's learner of that network takes its own parameters -- the global model -- as its PROX centre
+        (``anchor_here``) and ``set_anchor(prox_mu=...)``: the local steps until the next round are pulled back by
+        ``prox_mu (w - g)``; None leaves the clients' anchors alone.  Returns per network the ``stats`` with ``participants`` (who was averaged) and ``filtered``
         (client indices the filter dropped)."""
         part = self._participants(participants)
         w = [1.0] * len(part) if weights is None else [float(x) for x in weights]
@@ -232,6 +253,7 @@ class FederatedLearners:
         for k, x in dict(clip_norm=clip_norm, noise_std=noise_std, server_lr=server_lr).items():
             if not math.isfinite(float(x)) or float(x) < 0.0:
                 raise ValueError(f"FederatedLearners.round: {k} = {x} must be finite and >= 0")
+        prox_mu = self._prox_mu(prox_mu)
         if int(byzantine_tolerance) < 0:
             raise ValueError("FederatedLearners.round: byzantine_tolerance must be >= 0")
         plans = {}
@@ -248,7 +270,7 @@ class FederatedLearners:
         out = {}
         for net in self.nets:
             keep, kw, dropped = plans[net]
-            self.aggregate(net, keep, kw, clip_norm, noise_std, server_lr, seed, self._rounds, reset_moments)
+            self.aggregate(net, keep, kw, clip_norm, noise_std, server_lr, seed, self._rounds, reset_moments, prox_mu=prox_mu)
         for net in self.nets:
             keep, kw, dropped = plans[net]
             out[net] = dict(self.stats(net), participants=list(keep), filtered=dropped)

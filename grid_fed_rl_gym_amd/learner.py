@@ -4,7 +4,7 @@ network, one clipped-surrogate (PPO) or critic update on a minibatch of ``OnPoli
 pass, a deterministic gradient reduction and Adam, which also rewrites the image the rollout and critic kernels read: the next
 ``rollout_device(policy="mlp")`` acts with the updated policy and no weight crosses the host.
 
-``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np``, ``pathwise_grad_np`` (with ``pathwise_noise_np``), ``cql_grad_np`` (with ``cql_uniform_np`` and ``cql_noise_np``) and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against.
+``ppo_grad_np``, ``value_grad_np``, ``awr_grad_np``, ``expectile_grad_np``, ``pathwise_grad_np`` (with ``pathwise_noise_np``), ``cql_grad_np`` (with ``cql_uniform_np`` and ``cql_noise_np``) and ``adam_np`` restate the arithmetic in NumPy -- what the kernels are tested against; ``anchor_term_np``, ``fisher_np`` and ``ewc_merge_np`` restate the parameter anchors.
 """
 from __future__ import annotations
 
@@ -76,6 +76,7 @@ def _with_backprop(result: Dict[str, Any], exact: bool, acts, deltas) -> Dict[st
     what rounding those terms can cost"""
     if exact:
         result["backprop"] = dict(acts=acts, deltas=deltas)
+    result["passes"] = dict(acts=acts, deltas=deltas, exact=bool(exact))      # (in the evaluation's own precision: what ``fisher_np`` squares)
     return result
 
 
@@ -182,9 +183,11 @@ def awr_grad_np(policy_layers, obs_n, actions, adv, temperature: float, weight_m
     terms = w * lp
     surrogate, entropy = math.fsum(terms) / n, math.fsum(ent) / n
     kl = float("nan") if lp_old is None else math.fsum(np.asarray(lp_old, dtype=np.float64).reshape(n) - lp) / n
-    return dict(grads=_backward(rounded, acts, ghead, activation), log_probs_new=lp, weights=w, capped=found.astype(np.int32),
-                loss_terms=terms, entropy_terms=ent, log_std_outside=~inside, loss=-surrogate - ent_coef * entropy,
-                surrogate=surrogate, entropy=entropy, approx_kl=kl, clip_fraction=float(np.count_nonzero(found)) / n)
+    deltas: list = []
+    out = dict(grads=_backward(rounded, acts, ghead, activation, deltas), log_probs_new=lp, weights=w, capped=found.astype(np.int32),
+               loss_terms=terms, entropy_terms=ent, log_std_outside=~inside, loss=-surrogate - ent_coef * entropy,
+               surrogate=surrogate, entropy=entropy, approx_kl=kl, clip_fraction=float(np.count_nonzero(found)) / n)
+    return _with_backprop(out, exact, acts, deltas)
 
 
 def expectile_grad_np(value_layers, obs_n, returns, expectile: float, exact: bool = False, activation: str = "relu") -> Dict[str, Any]:
@@ -200,7 +203,9 @@ def expectile_grad_np(value_layers, obs_n, returns, expectile: float, exact: boo
     ghead = (q * ((2.0 * d) / n))[:, None]
     ghead = ghead if exact else ghead.astype(np.float32)
     terms = q * (d * d)
-    return dict(grads=_backward(rounded, acts, ghead, activation), values=v, below=d < 0.0, loss_terms=terms, loss=math.fsum(terms) / n)
+    deltas: list = []
+    out = dict(grads=_backward(rounded, acts, ghead, activation, deltas), values=v, below=d < 0.0, loss_terms=terms, loss=math.fsum(terms) / n)
+    return _with_backprop(out, exact, acts, deltas)
 
 
 def pathwise_noise_np(seed: int, draw: int, n: int, A: int, tag: int = _lib.PATHWISE_NOISE_TAG) -> np.ndarray:
@@ -536,6 +541,77 @@ def adam_np(p, g, m, v, t: int, cfg, grad_norm: float):
     return p, m, v
 
 
+def anchor_term_np(g, w, prox=None, mu: float = 0.0, importance=None, centre=None, lam: float = 0.0) -> np.ndarray:
+    """The terms on the parameters in float32, operation by operation as ``gs_k_train_anchor`` performs them (include/gridstep.h
+    "parameter anchors"): ``g`` the reduced gradient of the loss and ``w`` the master parameters, arrays of one shape; ``mu`` != 0:
+    ``g = g + mu * (w - prox)``; ``lam`` != 0: ``g = g + lam * (importance * (w - centre))``; the coefficients rounded once to
+    float32.  Returns the total gradient, what ``grad_norm``, the clip and Adam see."""
+    f = np.float32
+    g, w = np.asarray(g, dtype=f), np.asarray(w, dtype=f)
+    if f(mu) != f(0.0):
+        g = g + f(mu) * (w - np.asarray(prox, dtype=f))
+    if f(lam) != f(0.0):
+        g = g + f(lam) * (np.asarray(importance, dtype=f) * (w - np.asarray(centre, dtype=f)))
+    return g
+
+
+def anchor_penalty_terms_np(w, prox=None, importance=None, centre=None) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+    """The float64 terms ``gs_k_train_anchor`` sums for ``gs_learner_anchor_stats``: ``d d`` with d the FLOAT32 difference w - prox,
+    and ``A (d d)`` with d the float32 difference w - centre (None for a slot that is not given).  ``penalty_prox = mu / 2`` times
+    the sum of the first, ``penalty_ewc = lambda / 2`` times the sum of the second."""
+    f = np.float32
+    w = np.asarray(w, dtype=f)
+    tp = te = None
+    if prox is not None:
+        d = (w - np.asarray(prox, dtype=f)).astype(np.float64)
+        tp = d * d
+    if importance is not None:
+        d = (w - np.asarray(centre, dtype=f)).astype(np.float64)
+        te = np.asarray(importance, dtype=f).astype(np.float64) * (d * d)
+    return tp, te
+
+
+def fisher_np(result: Dict[str, Any], n: int, exact: bool = False) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """The per-sample (empirical) Fisher diagonal of a minibatch, SUMMED over its samples, as ``gs_learner_fisher_accumulate`` adds
+    it to the pending sum: [(FW_l, Fb_l)] with ``FW_l = sum_i ((n delta_l[i])^2)^T (a_l[i])^2`` and ``Fb_l = sum_i (n delta_l[i])^2``
+    from the ``passes`` a ``*_grad_np`` result carries (``acts`` and ``deltas`` in the evaluation's own precision: evaluate it with the same ``exact``);
+    ``n``: the minibatch size the head divided by.  ``n delta`` is d l_i / d(pre-activation) of the per-sample terms l_i of
+    L = (1/n) sum l_i, so every entry is sum_i (d l_i / d theta)^2.  Float64 when ``exact``; float32 products and sums otherwise."""
+    work = np.float64 if exact else np.float32
+    if "passes" not in result or result["passes"]["exact"] != bool(exact):
+        raise ValueError(f"fisher_np: evaluate the restatement with exact={bool(exact)} (its result carries the passes in that precision)")
+    acts, deltas = result["passes"]["acts"], result["passes"]["deltas"]
+    out = []
+    for l, d in enumerate(deltas):
+        t = work(n) * np.asarray(d).astype(work)
+        A = t * t
+        a = np.asarray(acts[l]).astype(work)
+        out.append((A.T @ (a * a), A.sum(axis=0)))
+    return out
+
+
+def fisher_importance_np(pending, samples: int, min_importance: float = 1e-3) -> np.ndarray:
+    """``F = max(float32(pending / samples), float32(min_importance))`` of ``gs_learner_fisher_commit`` (float32)."""
+    f = np.float32
+    return np.maximum((np.asarray(pending, dtype=np.float64) / float(samples)).astype(f), f(min_importance))
+
+
+def ewc_merge_np(A, c, F, w, decay: float = 1.0, exact: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """The merge of ``gs_learner_fisher_commit``: the consolidated importance ``A`` and centre ``c`` (None: the slot is empty) take a
+    task of importance ``F`` whose optimum is ``w``: ``A' = decay A + F``, ``c' = ((decay A) c + F w) / A'`` (``w`` where ``A'`` is 0),
+    per parameter in float64 on the float32 values, each rounded once to float32.  The first merge gives (F, w).  ``exact``: float64
+    in and out, nothing rounded to float32 -- the recursion whose ``A (p - c)`` is ``sum_k decay^(K - 1 - k) F_k (p - p_k)``."""
+    f = np.float64 if exact else np.float32
+    F64, w64 = np.asarray(F, dtype=f).astype(np.float64), np.asarray(w, dtype=f).astype(np.float64)
+    if A is None:
+        return F64.astype(f), w64.astype(f)
+    dA = float(decay) * np.asarray(A, dtype=f).astype(np.float64)
+    An = dA + F64
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cn = np.where(An != 0.0, (dA * np.asarray(c, dtype=f).astype(np.float64) + F64 * w64) / An, w64)
+    return An.astype(f), cn.astype(f)
+
+
 def split_parameters(flat, dims: Sequence[int]) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """(W, b) lists from a flat array in torch order (W_0 row-major [out, in], b_0, W_1, ...) for the widths ``dims``."""
     flat = np.asarray(flat)
@@ -591,6 +667,10 @@ class DeviceLearner:
     (``conservative_stochastic=False``: ``tanh(mean)``).  It needs ``q_loss="mse"`` and a learner for the policy on the handle (of
     this or of another ``DeviceLearner``), which it reads and does not step.  The uniform candidates of a step are
     ``cql_uniform_np(conservative_seed, draw, n, A)`` and its noise ``cql_noise_np(...)`` with ``draw`` = that twin's steps taken.
+
+    Parameter anchors: ``anchor_here`` / ``set_anchor(prox_mu=)`` add FedProx's proximal term to every later
+    step of a network, ``consolidate`` / ``set_anchor(ewc_lambda=)`` elastic weight consolidation on the per-sample Fisher diagonal
+    of the network's own loss; both are off until asked for and act on the reduced gradient on the device.
 
     ``step(batch)``: one ``gs_learner_step`` per network on a dict of ``OnPolicyBatches.epoch`` (prepared with float32 and the
     networks' own observation normalisation).  After a step the ``MLPPolicy`` / ``MLPValue`` objects the networks were installed
@@ -976,3 +1056,65 @@ class DeviceLearner:
         "expectile" ``loss_terms`` holds q (v - ret)^2."""
         k = self._id(net)
         return self.env.handle.learner_view(k, stream)
+
+    # -- parameter anchors (DESIGN.md section 31) ----------------------------------------------------------------------------------
+    def anchor_here(self, net="policy", params=None) -> None:
+        """The PROX centre of ``net`` (``gs_learner_anchor_here``): ``params`` (flat float32 in torch order), or by default a device
+        copy of the learner's current master parameters -- after a federated round, the global model."""
+        self.env.handle.learner_anchor_here(self._id(net), params)
+
+    def set_anchor(self, net="policy", prox_mu: Optional[float] = None, ewc_lambda: Optional[float] = None) -> None:
+        """The coefficients of the terms on ``net``'s parameters from its next step (``gs_learner_anchor_set``): FedProx's
+        ``prox_mu / 2 |w - a|^2`` (it needs ``anchor_here`` first) and EWC's ``ewc_lambda / 2 sum A (w - c)^2`` (it needs a
+        ``consolidate`` first).  What is not given stays as it is; 0 turns a term off, and with both at 0 a step is, launch for
+        launch and bit for bit, a step of a learner without anchors."""
+        k = self._id(net)
+        now = self.env.handle.learner_anchor_get(k)
+        cfg = dict(prox_mu=now["prox_mu"] if prox_mu is None else float(prox_mu), ewc_lambda=now["ewc_lambda"] if ewc_lambda is None else float(ewc_lambda))
+        for key, x in cfg.items():
+            if not math.isfinite(x) or x < 0.0:
+                raise ValueError(f"DeviceLearner.set_anchor: {key} = {x} must be finite and >= 0")
+        self.env.handle.learner_anchor_set(k, _lib.anchor_config(**cfg))
+
+    def anchor(self, net="policy") -> dict:
+        """``prox_mu`` and ``ewc_lambda`` of ``net`` in force (``gs_learner_anchor_get``)."""
+        return self.env.handle.learner_anchor_get(self._id(net))
+
+    def consolidate(self, net, batches, min_importance: float = 1e-3, decay: float = 1.0, stream=None) -> int:
+        """The end of a task for ``net`` (elastic weight consolidation): the per-sample Fisher diagonal of ``net``'s own loss over the
+        minibatches of the iterable ``batches`` (dicts as ``step`` takes them; ``gs_learner_fisher_begin`` / ``_accumulate``), then
+        ``gs_learner_fisher_commit``: ``F = max(mean, min_importance)`` is merged into the consolidated importance with the CURRENT
+        parameters as the task's optimum (``decay`` 1: the sum over tasks; below 1: online EWC).  No parameter, moment or statistic
+        changes.  Returns the number of samples."""
+        k = self._id(net)
+        if (k == _lib.GS_LEARNER_POLICY and self._pathwise is not None) or (k >= _lib.GS_LEARNER_Q and self._conservative is not None):
+            raise ValueError("DeviceLearner.consolidate: the pathwise and the conservative step couple the samples of a batch; no per-sample Fisher is offered for them")
+        min_importance, decay = float(min_importance), float(decay)
+        if not math.isfinite(min_importance) or min_importance < 0.0:
+            raise ValueError(f"DeviceLearner.consolidate: min_importance = {min_importance} must be finite and >= 0")
+        if not 0.0 < decay <= 1.0:
+            raise ValueError(f"DeviceLearner.consolidate: decay = {decay} must lie in (0, 1]")
+        h = self.env.handle
+        h.learner_fisher_begin(k)
+        samples = 0
+        for batch in batches:
+            n = int(batch["observations"].shape[0])
+            h.learner_fisher_accumulate(k, batch, n, stream)
+            samples += n
+        h.learner_fisher_commit(k, _lib.fisher_config(min_importance, decay))
+        return samples
+
+    def clear_anchor(self, net="policy", which: str = "both") -> None:
+        """Drops the "prox" slot, the "ewc" slot or "both" of ``net``; a cleared slot's coefficient becomes 0."""
+        self.env.handle.learner_anchor_clear(self._id(net), which)
+
+    def anchor_stats(self, net="policy") -> dict:
+        """Of ``net``'s last step with a non-zero coefficient (waits for it): ``penalty_prox``, ``penalty_ewc`` (at the parameters
+        before Adam), ``grad_norm_loss`` (the norm before the terms; ``stats(net)["grad_norm"]`` is the total gradient's), the
+        step's ``prox_mu`` / ``ewc_lambda``, ``tasks`` and ``fisher_samples``."""
+        return self.env.handle.learner_anchor_stats(self._id(net))
+
+    def anchor_arrays(self, net="policy", want=_lib.ANCHOR_ARRAYS) -> dict:
+        """Flat host copies in torch order of ``prox``, ``ewc_importance``, ``ewc_centre`` (float32) and ``fisher_pending`` (float64,
+        the open or last task's sum over ``fisher_samples`` samples)."""
+        return self.env.handle.learner_anchor_download(self._id(net), want)

@@ -1467,6 +1467,93 @@ int gs_fed_aggregate(gs_fed* f, const gs_fed_round* r);
 int gs_fed_stats(gs_fed* f, gs_fed_stats_out* out);
 int gs_fed_download(gs_fed* f, float* global_params);
 
+/* ---- parameter anchors: FedProx's proximal term and elastic weight consolidation on a Fisher diagonal ----
+ * Two terms on the PARAMETERS of a learner (net: GS_LEARNER_*, the learner's own ids), added to the reduced gradient of every step
+ * -- gs_learner_step, gs_learner_step_pathwise and gs_learner_step_conservative alike -- before the statistics and Adam:
+ *     PROX:  L += mu / 2 * sum_p (w_p - a_p)^2                 a: the PROX centre, float32 [P] in torch order
+ *     EWC:   L += lambda / 2 * sum_p A_p (w_p - c_p)^2         A: the consolidated importance, c: the consolidated centre, float32 [P]
+ * Both coefficients are 0 after gs_learner_create, and while both are 0 no launch, buffer or bit of a step differs from a learner
+ * that never heard of anchors.  Nothing is allocated until an entry below is called.  Additive to ABI 2.
+ *
+ * The term (gs_k_train_anchor, queued right behind the gradient's reduction, only when a coefficient is non-zero).  Per parameter,
+ * all float32, every operation rounded, nothing contracted, in this order (w: the master parameter, g: the reduced gradient):
+ *     mu != 0:      g = g + mu * (w - a)
+ *     lambda != 0:  g = g + lambda * (A * (w - c))
+ * with mu = float32(prox_mu) and lambda = float32(ewc_lambda), the host's doubles rounded once.  The result replaces the gradient:
+ * grad_norm, the norm clip, Adam and gs_learner_download's grads see the TOTAL gradient, as torch.nn.utils.clip_grad_norm_ behind
+ * (loss + penalty).backward() does.  A difference of zero adds +0: the step right after gs_learner_anchor_here(NULL) has the
+ * gradient of a step without the term, bit for bit.  The gradient norm's per-workgroup sums are recomputed on the new gradient in
+ * the tree of the reduction (four per thread in order, a butterfly over 256 threads); three more per-workgroup float64 sums in the
+ * same tree keep sum g_loss^2 (the gradient before the terms), sum d^2 with d = w - a, and sum A (d d) with d = w - c (d the
+ * float32 difference the gradient used; the squares and products in float64, each rounded).
+ *
+ * gs_learner_anchor_here sets the PROX centre: params_host == NULL: a device copy of the learner's current master parameters
+ * (queued behind its steps); otherwise P floats in torch order taken from the host.  It does not change prox_mu.
+ * gs_learner_anchor_set / _get: the coefficients, read by the next step (a queued step keeps the ones it was queued with).  Both
+ * must be finite and >= 0 (GS_E_INVALID; gs_learner_anchor_check holds these rules on the host alone, as gs_cost_config_check).
+ * prox_mu > 0 without a PROX centre and ewc_lambda > 0 before the first gs_learner_fisher_commit are GS_E_STATE.
+ *
+ * The Fisher diagonal of a task.  gs_learner_fisher_begin zeroes the pending sum (float64 [P]) and the sample count.
+ * gs_learner_fisher_accumulate has exactly the preconditions and argument rules of gs_learner_step for that net under its current
+ * loss (GS_LOSS_*) and signal; without a begin since the last commit or clear it is GS_E_STATE.  It runs gs_learner_step's
+ * gather (where the net has one), forward pass, head and backward-data pass, then
+ *     pending[p] += sum_i (d l_i / d theta_p)^2        over the n samples, l_i the per-sample terms of L = (1/n) sum_i l_i
+ * computed as the weight-gradient product on squared operands: per layer sum_i ((float)n delta_i)^2 (a_i)^2 on the float32 matrix
+ * cores with the geometry, chains and join order of the step's weight gradient ((float)n delta undoes the 1/n the heads put into
+ * delta; the bias: sum_i ((float)n delta_i)^2), one partial per segment of rows_per_segment rows, the partials added in ascending
+ * segment order in float32, the result widened and added to pending.  This is the per-sample (empirical) Fisher diagonal on the
+ * learner's OWN loss -- not the square of a whole batch's gradient, which equals it at n = 1 only.  It changes no master
+ * parameter, image, m, v, step count, statistic or grads; the per-sample arrays of gs_learner_view become those of this pass (the
+ * clip or cap flags the Fisher was taken under among them).  The pathwise and conservative steps couple the samples of a batch and are not offered.
+ * gs_learner_fisher_commit ends the task with the CURRENT master parameters w as its optimum:
+ *     F   = max((float)(pending / samples), (float)min_importance)                      min_importance finite and >= 0
+ *     A'  = decay A + F                                                                 decay in (0, 1]: 1 sums the tasks, < 1 is online EWC
+ *     c'  = ((decay A) c + F w) / A'                                                    (w where A' is 0)
+ * per parameter in float64, each rounded once to float32; the first commit gives A = F, c = w.  Zero samples or no begin is
+ * GS_E_STATE.  The pending sum and its count stay readable until the next begin.  Because sum_k F_k (p - p_k) = A (p - c) in
+ * real arithmetic (decay 1), the GRADIENT is that of the sum over tasks of F_k / 2 (p - p_k)^2 for any number of tasks at the cost
+ * of two arrays; the penalty VALUE differs from that sum by a constant that does not depend on p.
+ *
+ * gs_learner_anchor_clear: which = GS_ANCHOR_PROX, GS_ANCHOR_EWC or both; a cleared slot loses its arrays, its coefficient
+ * becomes 0 (GS_ANCHOR_EWC also ends an open task and zeroes the task count).
+ * gs_learner_anchor_stats (waits): of the last step taken with a non-zero coefficient (GS_E_STATE before one):
+ *     penalty_prox = prox_mu / 2 * sum (w - a)^2,  penalty_ewc = ewc_lambda / 2 * sum A (w - c)^2   at the parameters BEFORE Adam,
+ *     the workgroups' sums added on the host in ascending order; grad_norm_loss = the norm before the terms, the workgroups' sums
+ *     added in the order of gs_learner_stats' grad_norm: by bits what gs_learner_stats would have reported without the terms;
+ *     tasks = commits merged into the EWC slot, fisher_samples = the samples of the pending sum.
+ * gs_learner_anchor_download: host copies, float32 [P] (prox, ewc_importance, ewc_centre) and float64 [P] (fisher_pending); any
+ * pointer may be NULL; a slot that holds nothing is GS_E_STATE when asked for.
+ * Lifetime: gs_learner_create and installing the network again drop everything here, as they drop the learner.  Every check runs
+ * before anything is launched: a refused call changes nothing.  An unknown net or a wrong struct_size is GS_E_INVALID, a net
+ * without a live learner GS_E_STATE. */
+enum { GS_ANCHOR_PROX = 1, GS_ANCHOR_EWC = 2 };
+typedef struct gs_learner_anchor_config {
+  int32_t struct_size;             /* = sizeof(gs_learner_anchor_config) */
+  int32_t reserved;
+  double prox_mu, ewc_lambda;
+} gs_learner_anchor_config;
+typedef struct gs_fisher_config {
+  int32_t struct_size;             /* = sizeof(gs_fisher_config) */
+  int32_t reserved;
+  double min_importance;           /* the reference's importance_threshold (1e-3 there) */
+  double decay;                    /* (0, 1] */
+} gs_fisher_config;
+typedef struct gs_learner_anchor_stats_out {
+  double penalty_prox, penalty_ewc, grad_norm_loss;
+  double prox_mu, ewc_lambda;      /* the coefficients of that step */
+  int64_t tasks, fisher_samples;
+} gs_learner_anchor_stats_out;
+int gs_learner_anchor_check(const gs_learner_anchor_config* cfg);
+int gs_learner_anchor_here(gs_handle* h, int32_t net, const float* params_host);
+int gs_learner_anchor_set(gs_handle* h, int32_t net, const gs_learner_anchor_config* cfg);
+int gs_learner_anchor_get(gs_handle* h, int32_t net, gs_learner_anchor_config* out);
+int gs_learner_fisher_begin(gs_handle* h, int32_t net);
+int gs_learner_fisher_accumulate(gs_handle* h, int32_t net, const gs_onpolicy_batch_out* batch, int32_t n, void* consumer_stream);
+int gs_learner_fisher_commit(gs_handle* h, int32_t net, const gs_fisher_config* cfg);
+int gs_learner_anchor_clear(gs_handle* h, int32_t net, int32_t which);
+int gs_learner_anchor_stats(gs_handle* h, int32_t net, gs_learner_anchor_stats_out* out);
+int gs_learner_anchor_download(gs_handle* h, int32_t net, float* prox, float* ewc_importance, float* ewc_centre, double* fisher_pending);
+
 /* ---- checkpoint / resume: [B][state_dim] float64 blob ------------
  * layout per instance: time, step, constraint_violations, total_losses, episode_reward,
  * frequency, irradiance, wind, temperature, cloud, seed_lo, seed_hi,
